@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark: rays/s integrated by the HIP occupancy path (BASELINE.json configs[1]) + roofline.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else the
+line can carry (CPU baseline, other_configs, first_pass, moving_sensor, the device-copy ceiling, at N > 1 the deviation
+from sequential integration).  `--dump-outputs DIR` writes what the timed steps computed to DIR/*.npy (dump_outputs).
 
 One "step" = one GpuMap::integrateRays pass over one 1 M-ray synthetic lidar batch (C1) whose rays are already
 resident in HBM when the timed region starts.  At N > 1 -- launched by torch.distributed.run, one rank per GPU, or,
@@ -145,6 +149,54 @@ def load_traffic_profile(kind, build_id):
     return {"doc": doc, "note": "profiles/%s (library build %s)" % (name, build_id)}
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: all files of all ranks together stay below this
+DUMP_SEED = 0x0D0E5EED    # fixed, so every build samples the same regions out of the same key list
+
+
+def dump_outputs(out_dir, map_, gm, st, rank, world, layer="occupancy"):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step -- the map's voxels, brought to the
+    host by syncVoxels() -- as .npy files in float32 / float64 (at N > 1 every rank writes its own map, prefix rank<r>_):
+      region_keys        float64 (R, 3)      every region of the map, sorted
+      region_summary     float64 (R, 3)      per region: voxels with a finite value, their sum, their sum of squares
+      <layer>_sample     float32 (S, V)      the layer's blocks of S regions drawn with DUMP_SEED from the sorted keys,
+                                             non-finite values (+inf = unobserved) written as 0
+      <layer>_sample_state float32 (S, V)    per voxel of the sample: 0 finite, 1 +inf, 2 -inf, 3 NaN
+      <layer>_sample_keys float64 (S, 3)     (S = every region when they fit in DUMP_BYTES, V = voxels per region)
+      batch_stats        float64 (4,)        rays_integrated, voxel_visits, regions_resident, ray_region_segments
+    Every value written is finite."""
+    os.makedirs(out_dir, exist_ok=True)
+    gm.syncVoxels()
+    keys = sorted(k for k, c in map_.chunks.items() if layer in c)
+    blocks = [map_.chunks[k][layer] for k in keys]
+    key_arr = np.array(keys, dtype=np.float64).reshape(-1, 3)
+    summary = np.zeros((len(keys), 3), dtype=np.float64)
+    for i, b in enumerate(blocks):
+        v = b[np.isfinite(b)].astype(np.float64)
+        summary[i] = (v.size, v.sum(), np.dot(v, v))
+    block_bytes = 4 * map_.regionVoxelVolume()
+    room = DUMP_BYTES // world - 2 * key_arr.nbytes - summary.nbytes - 4096
+    n_sample = int(max(0, min(len(keys), room // (2 * block_bytes + 24))))   # values + state per region
+    if n_sample < len(keys):
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(len(keys), size=n_sample, replace=False))
+    else:
+        pick = np.arange(len(keys))
+    sample = np.stack([blocks[i] for i in pick]).astype(np.float32) if len(pick) else \
+        np.zeros((0, map_.regionVoxelVolume()), dtype=np.float32)
+    state = np.zeros(sample.shape, dtype=np.float32)
+    state[np.isposinf(sample)] = 1.0
+    state[np.isneginf(sample)] = 2.0
+    state[np.isnan(sample)] = 3.0
+    sample[state != 0.0] = 0.0
+    prefix = "rank%d_" % rank if world > 1 else ""
+    stats = np.array([st["rays_integrated"], st["voxel_visits"], st["regions_resident"], st["ray_region_segments"]],
+                     dtype=np.float64)
+    for name, arr in (("region_keys", key_arr), ("region_summary", summary), (layer + "_sample", sample),
+                      (layer + "_sample_state", state), (layer + "_sample_keys", key_arr[pick]),
+                      ("batch_stats", stats)):
+        assert np.isfinite(arr).all(), name
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -159,7 +211,15 @@ def main():
     ap.add_argument("--multi-gpu-mode", choices=("partitioned", "replica-merge"), default="partitioned",
                     help="N > 1: partitioned map with routed rays (exact; default) or replicated maps reconciled by the "
                          "additive delta all-reduce (approximate where clamps engage)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the CPU baseline, the other configs "
+                         "(other_configs, first_pass, moving_sensor), the device-copy ceiling and, at N > 1, the "
+                         "deviation from sequential integration.  Without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the map after the last step) to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_relaunch_ranks(args.gpus))
@@ -337,25 +397,28 @@ def main():
         traffic_lower = tj["doc"]["kernels"]["k_region_walk"]["bytes_lower"]
         batch_traffic = tj["doc"]["batch_bytes_upper"]
         batch_traffic_lower = tj["doc"]["batch_bytes_lower"]
-    # Measured ceiling next to the nominal peak: a device-to-device copy of 1 GiB (read + write).
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, map_, gm, st, rank, world)
+    # Measured ceiling next to the nominal peak: a device-to-device copy of 1 GiB (read + write), a run of its own.
     copy_gbps = None
-    try:
-        nbytes = 1 << 30
-        ca, cb = L._vp(), L._vp()
-        L.check(L.lib.ohmhip_buffer_create(C.byref(ca), nbytes, 3), "buffer_create")
-        L.check(L.lib.ohmhip_buffer_create(C.byref(cb), nbytes, 3), "buffer_create")
-        L.check(L.lib.ohmhip_buffer_copy(cb, 0, ca, 0, nbytes, None, None, None), "buffer_copy")
-        L.check(L.lib.ohmhip_device_synchronize(), "device_synchronize")
-        reps = 5
-        t1 = time.perf_counter()
-        for _ in range(reps):
+    if args.full:
+        try:
+            nbytes = 1 << 30
+            ca, cb = L._vp(), L._vp()
+            L.check(L.lib.ohmhip_buffer_create(C.byref(ca), nbytes, 3), "buffer_create")
+            L.check(L.lib.ohmhip_buffer_create(C.byref(cb), nbytes, 3), "buffer_create")
             L.check(L.lib.ohmhip_buffer_copy(cb, 0, ca, 0, nbytes, None, None, None), "buffer_copy")
-        L.check(L.lib.ohmhip_device_synchronize(), "device_synchronize")
-        copy_gbps = 2.0 * nbytes * reps / (time.perf_counter() - t1) / 1e9
-        L.lib.ohmhip_buffer_destroy(ca)
-        L.lib.ohmhip_buffer_destroy(cb)
-    except Exception:
-        copy_gbps = None
+            L.check(L.lib.ohmhip_device_synchronize(), "device_synchronize")
+            reps = 5
+            t1 = time.perf_counter()
+            for _ in range(reps):
+                L.check(L.lib.ohmhip_buffer_copy(cb, 0, ca, 0, nbytes, None, None, None), "buffer_copy")
+            L.check(L.lib.ohmhip_device_synchronize(), "device_synchronize")
+            copy_gbps = 2.0 * nbytes * reps / (time.perf_counter() - t1) / 1e9
+            L.lib.ohmhip_buffer_destroy(ca)
+            L.lib.ohmhip_buffer_destroy(cb)
+        except Exception:
+            copy_gbps = None
     t_walk = float(np.mean(walk_ms)) * 1e-3
     t_dev = float(np.mean(total_ms)) * 1e-3
     achieved = b_alg / t_walk / 1e9
@@ -428,7 +491,7 @@ def main():
                         "note": merge_note,
                         "rule": "merged = clamp(base + sum_r (x_r - base)); exact where no clamp engaged between ranks; "
                                 "regions pending on one rank only stay on that rank (shared base untouched)"}
-    if partitioned and not args.no_deviation:
+    if partitioned and args.full and not args.no_deviation:
         # Untimed: the partitioned map against SEQUENTIAL integration.  Fresh maps: one partitioned step (collective), and
         # every rank integrates the shards of all ranks, in rank order, into one map of its own -- the HIP path, bit exact
         # against the CPU mapper (tests/test_gpu_full_configs.py) -- and compares the regions of its territory bit for
@@ -472,7 +535,7 @@ def main():
             dg.close()
         except Exception as exc:
             out["multi_gpu"]["deviation"] = {"error": repr(exc)}
-    if world > 1 and merge_state["merger"] is not None and not args.no_deviation:
+    if world > 1 and merge_state["merger"] is not None and args.full and not args.no_deviation:
         # Untimed: how far the replica merge is from SEQUENTIAL integration ("must be stated with results").
         # Fresh maps: every rank integrates its shard ONCE and the replicas merge (collective); rank 0 also integrates
         # the shards of all ranks one after the other into one map -- the HIP path, which is bit exact against the CPU
@@ -501,7 +564,7 @@ def main():
         except Exception as exc:
             if rank == 0 and "merge" in out:
                 out["merge"]["deviation"] = {"error": repr(exc)}
-    if world == 1 and not args.no_extra:
+    if world == 1 and args.full and not args.no_extra:
         # Secondary figures (not the headline `value`): C2 GpuNdtMap (1 M rays) and C3 GpuTsdfMap (its full 4 M rays in one
         # call), same harness, each with its own roofline block.  Algorithmic bytes per SURVEY.md 8d:
         #   NDT : 40 B per miss visit (4 + 4 occupancy, 8 mean, 24 covariance) + 72 B per sample + 44 B per ray
@@ -1006,7 +1069,7 @@ def main():
                                     "pipeline_frac": mv["roofline"]["pipeline_frac"],
                                     "kernel_frac": mv["roofline"]["frac"],
                                     "note": "the C1 sweep from an origin advancing 0.41 m per batch, batches back to back"}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(rays, resolution, min(args.cpu_sample, n_rays),
                                            all_cores=not args.no_cpu_all_cores)
     elif rank == 0:

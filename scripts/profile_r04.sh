@@ -12,6 +12,7 @@ python scripts/traffic_json.py gpurun_out/prof_r04_tsdf "python scripts/profile_
 timeout 300 scripts/valu_probe > gpurun_out/r04_valu_probe.txt 2>&1
 # the traffic JSONs have to sit in profiles/ for bench.py to quote them: this run's copies (same build id)
 cp gpurun_out/r04_traffic.json gpurun_out/r04_traffic_c2_ndt.json gpurun_out/r04_traffic_c3_tsdf.json profiles/
-timeout 900 python bench.py > gpurun_out/r04_bench_default.json 2> gpurun_out/r04_bench_default.err
-tail -c 400 gpurun_out/r04_bench_default.err
+# the full bench line (secondary figures included) and its log, in $TMPDIR
+timeout 900 python bench.py --full > "$TMPDIR/r04_bench_default.json" 2> "$TMPDIR/r04_bench_default.err"
+tail -c 400 "$TMPDIR/r04_bench_default.err"
 head -30 gpurun_out/prof_r04final/summary.txt

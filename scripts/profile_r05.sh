@@ -15,7 +15,8 @@ python scripts/timeline.py gpurun_out/prof_r05_tsdf 1 > gpurun_out/prof_r05_tsdf
 python scripts/traffic_json.py gpurun_out/prof_r05_tsdf "python scripts/profile_modes.py tsdf 3" > gpurun_out/r05_traffic_c3_tsdf.json
 timeout 120 scripts/probes/event_probe > gpurun_out/r05_event_probe.txt 2>&1
 cp gpurun_out/r05_traffic.json gpurun_out/r05_traffic_c2_ndt.json gpurun_out/r05_traffic_c3_tsdf.json profiles/
-timeout 1200 python bench.py > gpurun_out/r05_bench_default.json 2> gpurun_out/r05_bench_default.err
-tail -c 400 gpurun_out/r05_bench_default.err
+# the full bench line (secondary figures included) and its log, in $TMPDIR
+timeout 1200 python bench.py --full > "$TMPDIR/r05_bench_default.json" 2> "$TMPDIR/r05_bench_default.err"
+tail -c 400 "$TMPDIR/r05_bench_default.err"
 head -30 gpurun_out/prof_r05final/summary.txt
 head -30 gpurun_out/prof_r05final/timeline.txt

@@ -14,7 +14,8 @@ bash scripts/profile_modes.sh r06 tsdf 3 > gpurun_out/prof_r06_tsdf_stdout.txt 2
 python scripts/timeline.py gpurun_out/prof_r06_tsdf 1 > gpurun_out/prof_r06_tsdf/timeline.txt 2>&1
 python scripts/traffic_json.py gpurun_out/prof_r06_tsdf "python scripts/profile_modes.py tsdf 3" > gpurun_out/r06_traffic_c3_tsdf.json
 cp gpurun_out/r06_traffic.json gpurun_out/r06_traffic_c2_ndt.json gpurun_out/r06_traffic_c3_tsdf.json profiles/
-timeout 1200 python bench.py > gpurun_out/r06_bench_default.json 2> gpurun_out/r06_bench_default.err
-tail -c 400 gpurun_out/r06_bench_default.err
+# the full bench line (secondary figures included) and its log, in $TMPDIR
+timeout 1200 python bench.py --full > "$TMPDIR/r06_bench_default.json" 2> "$TMPDIR/r06_bench_default.err"
+tail -c 400 "$TMPDIR/r06_bench_default.err"
 head -30 gpurun_out/prof_r06final/summary.txt
 head -30 gpurun_out/prof_r06final/timeline.txt

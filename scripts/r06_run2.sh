@@ -20,8 +20,8 @@ for round in 1 2; do
 done 2>&1 | tee gpurun_out/r06/run2_ab.txt
 OHMHIP_DEBUG_FLAGS=64 OHMHIP_DEBUG_TRACE=/tmp/walk_trace.txt timeout 120 python bench.py --steps 6 --warmup 3 --no-cpu --no-extra > /dev/null 2>&1
 python scripts/analyse_trace.py /tmp/walk_trace.txt > gpurun_out/r06/run2_walk_trace.txt 2>&1; cat gpurun_out/r06/run2_walk_trace.txt | head -22
-timeout 600 python bench.py --no-cpu > gpurun_out/r06/run2_bench_full.json 2> gpurun_out/r06/run2_bench_full.err; python - <<'PY'
-import json
-d = json.loads(open('gpurun_out/r06/run2_bench_full.json').read().strip().splitlines()[-1])
+timeout 600 python bench.py --full --no-cpu > "$TMPDIR/run2_bench_full.json" 2> "$TMPDIR/run2_bench_full.err"; python - <<'PY'
+import json, os
+d = json.loads(open(os.path.join(os.environ['TMPDIR'], 'run2_bench_full.json')).read().strip().splitlines()[-1])
 print('full: ms_per_step', d['ms_per_step'], 'first_pass', d.get('first_pass', {}).get('ms_per_step'), 'moving', d.get('moving_sensor', {}).get('ms_per_step'))
 PY

@@ -1,8 +1,11 @@
-"""CPU: the committed default bench line (profiles/r05_bench_default.json, produced by `python bench.py` on an MI355X in
-the same gpurun call as profiles/r05_profile_final.txt and profiles/r05_traffic.json: scripts/profile_r05.sh) carries every
-field the bench contract names, with consistent arithmetic."""
+"""CPU: the committed full bench line (profiles/r05_bench_default.json, produced by `python bench.py` -- today's
+`python bench.py --full` -- on an MI355X in the same GPU session as profiles/r05_profile_final.txt and
+profiles/r05_traffic.json: scripts/profile_r05.sh) carries every field the bench contract names, with consistent
+arithmetic.  Marked gpu: what a plain run prints and what --dump-outputs writes."""
 import json
 import os
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -100,3 +103,60 @@ def test_gpus_n_without_a_launcher_environment_starts_n_ranks():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["ranks"] == 2 and line["backend"] == "gloo"
     assert line["value"] is None and "no HIP device" in line["error"]
+
+
+def test_steps_must_be_positive():
+    """`--steps` sets the number of timed steps, and `ms_per_step` divides by it: zero steps is refused up front."""
+    import subprocess
+    import sys
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True,
+                         text=True, timeout=120)
+    assert res.returncode == 2 and "--steps must be >= 1" in res.stderr, (res.returncode, res.stderr[-2000:])
+
+
+def _plain_bench(out_dir):
+    import subprocess
+    import sys
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--rays", "200000", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_what_they_computed(gpu, tmp_path):
+    """A plain run carries the headline fields and nothing that needs runs of its own (those are --full's); with
+    --dump-outputs it writes the map after the last step, float32 / float64 only, within 64 MB, identical for identical
+    arguments."""
+    import numpy as np
+    lines = [_plain_bench(tmp_path / "a"), _plain_bench(tmp_path / "b")]
+    for line in lines:
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["higher_is_better"] is True
+        assert line["unit"] == "rays/s" and line["dtype"] == "f64" and line["metric"] == "rays/sec integrated (occupancy)"
+        assert abs(line["value"] - 200000 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-6
+        assert line["cpu_baseline"] is None and "other_configs" not in line
+        assert line["roofline"]["peak_measured_copy"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"region_keys.npy", "region_summary.npy", "occupancy_sample.npy", "occupancy_sample_state.npy",
+            "occupancy_sample_keys.npy", "batch_stats.npy"} <= set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64_000_000
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        assert np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+    keys = np.load(tmp_path / "a" / "region_keys.npy")
+    assert keys.shape == (lines[0]["config"]["regions"], 3)
+    summary = np.load(tmp_path / "a" / "region_summary.npy")
+    assert summary.shape == (keys.shape[0], 3) and summary[:, 0].sum() > 0
+    sample = np.load(tmp_path / "a" / "occupancy_sample.npy")
+    state = np.load(tmp_path / "a" / "occupancy_sample_state.npy")
+    sample_keys = np.load(tmp_path / "a" / "occupancy_sample_keys.npy")
+    assert sample.shape == state.shape == (sample_keys.shape[0], 32 ** 3) and sample.shape[0] > 0
+    assert set(map(tuple, sample_keys.tolist())) <= set(map(tuple, keys.tolist()))
+    # unobserved voxels (+inf in the map) are state 1 with value 0; every other voxel is finite (state 0)
+    assert set(np.unique(state).tolist()) <= {0.0, 1.0} and (state == 1.0).any() and (state == 0.0).any()
+    assert (sample[state != 0.0] == 0.0).all()

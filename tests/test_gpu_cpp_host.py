@@ -18,6 +18,7 @@ from parity import assert_parity, compare_maps
 pytestmark = pytest.mark.gpu
 
 DRIVER = os.path.join(os.path.dirname(ohm_amd.LIB_PATH), "gpumap_driver")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ID_TO_NAME = {v[0]: k for k, v in LAYERS.items()}
 
 
@@ -190,8 +191,9 @@ def test_gputil_hip_backend_through_the_reference_headers(gpu):
     """ohm_amd/host/ref_adaptor/gputil_hip: gputil::Device / Queue / Event as the REFERENCE's headers declare them,
     implemented over the C ABI.  The check program is compiled (in the build container, where the reference checkout
     is) against those headers in place and runs here: device enumeration and selection, queue creation, event
-    marking, reference counting, waits and callbacks."""
-    binary = os.path.join(os.path.dirname(DRIVER), "gputil_hip_check")
-    assert os.path.exists(binary), "gputil_hip_check missing: run __graft_entry__.build() where /root/reference exists"
+    marking, reference counting, waits and callbacks.  Being built from reference sources, it lies in oracle/_ref/."""
+    binary = os.path.join(ROOT, "oracle", "_ref", "gputil_hip_check")
+    assert os.path.exists(binary), \
+        "oracle/_ref/gputil_hip_check missing: run __graft_entry__.build() with the reference checkout"
     res = subprocess.run([binary], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0 and "GPUTIL_HIP_OK" in res.stdout, (res.returncode, res.stdout, res.stderr)

@@ -35,7 +35,7 @@ def test_two_rank_rccl_partitioned_map(gpu):
         env.pop(k, None)
     for mode in ("partitioned", "replica-merge"):
         res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup",
-                              "1", "--rays", "200000", "--multi-gpu-mode", mode], env=env, capture_output=True,
+                              "1", "--rays", "200000", "--multi-gpu-mode", mode, "--full"], env=env, capture_output=True,
                              text=True, timeout=900)
         assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
         line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])

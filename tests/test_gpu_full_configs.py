@@ -259,7 +259,7 @@ def _run_bench_gpus_2(extra_args=()):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--rays", "200000"] + list(extra_args), env=env, capture_output=True, text=True, timeout=900)
+                          "--rays", "200000", "--full"] + list(extra_args), env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-4000:])
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
