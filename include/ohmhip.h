@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-/* CORE ABI.  The header has grown to 86 entry points over six rounds; a reference-side binding of ohm::GpuMap /
+/* CORE ABI.  The header has grown to 88 entry points over six rounds; a reference-side binding of ohm::GpuMap /
  * GpuNdtMap / GpuTsdfMap / GpuCache needs FIFTEEN of them.  The list below is exact: it is every ohmhip_* call made by
  * ohm_amd/host/ref_adaptor/private/HipBindingCore.cpp, the compiled and GPU-tested logic of the Level-2 adaptor
  * (INTEGRATION.md), and tests/test_cabi.py keeps the two in step.
@@ -429,6 +429,33 @@ int ohmhip_map_remove_regions(ohmhip_map_t map, const int16_t *keys_xyz, size_t 
  * ohmgpu/GpuKey.h:37-46); counts_out[i] is the line's total voxel count.  Host pointers; synchronous. */
 int ohmhip_map_line_keys(ohmhip_map_t map, const double *lines, size_t line_count, uint32_t max_keys_per_line,
                          void *keys_out, uint32_t *counts_out);
+
+/* RaysQuery / RaysQueryGpu (ohm/RaysQuery.{h,cpp}, ohmgpu/RaysQueryGpu.{h,cpp}; reference kernel raysQuery,
+ * ohmgpu/gpu/RaysQuery.cl:193): for each ray (origin, end point: 6 doubles) of `element_count` points -- an odd trailing
+ * point is not a ray, as in ohmhip_map_integrate_rays -- the CPU query of ohm/RaysQuery.cpp:102-203 as written, bit for
+ * bit: the map's own ray filter (OHMHIP_FILTER_*, map->rayFilter(), :118), then walkSegmentKeys with flags 0 (start and
+ * end voxel visited, fp64, ohm/LineWalk.h:112-129), stopping after the first voxel whose value is > threshold_value
+ * (strict: the reference's GPU kernel uses >=, RaysQuery.cl:111).  Per ray: ranges[i] = float(exit range) of the last
+ * voxel that is not occupied, widened to double (RaysQuery::ranges()); unobserved_volumes[i] = the sum of
+ * volume_coefficient * (exit^3 - enter^3) over the unobserved (+inf) voxels, in walk order; terminal_types[i] =
+ * ohm::OccupancyType of the last visited voxel (kNull -2, kUnobserved -1, kFree 0, kOccupied 1); terminal_keys (nullable)
+ * = its key (Query::intersectedVoxels()) in the 10-byte GpuKey layout of ohmhip_map_line_keys, in the caller's region
+ * coordinates.  A filtered ray reports 0, 0, kNull, Key::kNull.  Reference behaviour kept: the CPU declares the terminal
+ * type and key outside its ray loop (:116-117), so a ray that passes the filter but visits no voxel (a null start or end
+ * key) repeats the type and key of the last preceding ray that did (kNull / Key::kNull before any).
+ * The query observes the map as ohmhip_map_read_regions would -- collected rays launched, an asynchronous launch settled,
+ * regions of the host store (spill to host) included -- and changes nothing of it: voxels, dirty set, residency, use
+ * stamps, ohmhip_map_cache_stats; it uses buffers of its own.  OHMHIP_ERR_UNSUPPORTED for a map without the occupancy
+ * layer (the CPU query refuses it: valid_layers) and for a map with region ownership / a partition (a rank holds only its
+ * territory); OHMHIP_ERR_INVALID_ARG for null arrays, checked before any device work.  Host pointers; synchronous. */
+int ohmhip_map_rays_query(ohmhip_map_t map, const double *rays, size_t element_count, double volume_coefficient,
+                          double *ranges, double *unobserved_volumes, int8_t *terminal_types, void *terminal_keys);
+/* ohmhip_map_rays_query on DEVICE arrays (e.g. the output of ohmhip_transform_samples): enqueued on the map's stream,
+ * ohmhip_map_sync is the fence.  The rays must stay valid, and the outputs unread, until then. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_rays_query_device(ohmhip_map_t map, const double *d_rays, size_t element_count,
+                                                     double volume_coefficient, double *d_ranges,
+                                                     double *d_unobserved_volumes, int8_t *d_terminal_types,
+                                                     void *d_terminal_keys);
 
 /* GpuTransformSamples::transform (ohmgpu/GpuTransformSamples.h:75-79, .cpp:97-210; kernel transformTimestampedPoints,
  * ohmgpu/gpu/TransformSamples.cl:94-228): sensor-frame samples with time stamps + a timestamped trajectory (translations

@@ -6,6 +6,7 @@
 #include "occupancy_kernels.h"
 #include "replay_kernels.h"
 #include "traversal_kernels.h"
+#include "query_kernels.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -390,6 +391,12 @@ try
   m->group_heads.release();
   m->stop_a.release();
   m->stop_b.release();
+  for (DevBuf *b : { &m->query.rays, &m->query.ranges, &m->query.volumes, &m->query.types, &m->query.keys,
+                     &m->query.walked, &m->query.last_walked, &m->query.scan_temp, &m->query.cursor,
+                     &m->query.spill_keys, &m->query.spill_blocks })
+  {
+    b->release();
+  }
   m->merge_slots.release();
   m->merge_keys_dev.release();
   m->merge_delta.release();
@@ -1118,6 +1125,172 @@ try
   }
   cleanup();
   return status;
+}
+OHMHIP_ABI_CATCH
+
+}  // extern "C"
+
+namespace
+{
+/// What both query entry points check before any device work (OHMHIP_ERR_INVALID_ARG / OHMHIP_ERR_UNSUPPORTED).
+int raysQueryRefusal(ohmhip_map_t m, const void *rays, size_t element_count, const void *ranges,
+                     const void *unobserved_volumes, const void *terminal_types)
+{
+  const size_t n = element_count / 2;
+  if (!m || (n && (!rays || !ranges || !unobserved_volumes || !terminal_types)) || n > size_t(0x7fffffff))
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  if (!m->layers[OHMHIP_LID_OCCUPANCY])
+  {
+    return OHMHIP_ERR_UNSUPPORTED;  // the CPU query refuses maps without the layer too (valid_layers)
+  }
+  if (m->mc.owner_world > 1u)
+  {
+    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
+  }
+  return OHMHIP_OK;
+}
+
+/// The query on device arrays, enqueued on the map's stream.  The map is observed as ohmhip_map_read_regions would
+/// observe it: collected rays launched and an asynchronous launch settled first (the caller's OHMHIP_SETTLE), regions
+/// of the host store included.  It changes nothing of the map: no voxel, dirty bit, residency, use stamp or counter.
+int raysQueryDevice(ohmhip_map_t m, const double *d_rays, uint32_t n, double coef, double *d_ranges, double *d_volumes,
+                    int8_t *d_types, GpuKeyOut *d_keys)
+{
+  hipStream_t s = m->stream;
+  ohmhip_map_s::QueryState &qs = m->query;
+  RaysQueryArgs a;
+  a.mc = m->mc;
+  a.rt = regionTable(m);
+  a.spill = QuerySpillTable{ nullptr, nullptr, 0 };
+  if (!m->spilled.empty())
+  {
+    // Regions in the host store answer from their pinned records (device visible), without re-admission.  The table is
+    // rebuilt per call: the store changes with every batch that evicts or re-admits.  (Evictions copy on the copy
+    // stream; the previous query may still read the table being replaced.)
+    OHMHIP_CHECK(hipStreamSynchronize(m->copy_stream));
+    OHMHIP_CHECK(hipStreamSynchronize(s));
+    uint32_t cap = 16;
+    while (cap < 2 * m->spilled.size())
+    {
+      cap <<= 1;
+    }
+    std::vector<unsigned long long> keys(cap, 0ull);
+    std::vector<const float *> blocks(cap, nullptr);
+    for (const auto &entry : m->spilled)
+    {
+      uint32_t idx = hashRegionKey(entry.first, cap - 1);
+      while (keys[idx] != 0)
+      {
+        idx = (idx + 1) & (cap - 1);
+      }
+      keys[idx] = entry.first;
+      blocks[idx] = reinterpret_cast<const float *>(entry.second.record + m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
+    }
+    OHMHIP_CHECK(qs.spill_keys.ensure(sizeof(unsigned long long) * cap, false, s));
+    OHMHIP_CHECK(qs.spill_blocks.ensure(sizeof(const float *) * cap, false, s));
+    OHMHIP_CHECK(hipMemcpy(qs.spill_keys.ptr, keys.data(), sizeof(unsigned long long) * cap, hipMemcpyHostToDevice));
+    OHMHIP_CHECK(hipMemcpy(qs.spill_blocks.ptr, blocks.data(), sizeof(const float *) * cap, hipMemcpyHostToDevice));
+    a.spill = QuerySpillTable{ static_cast<const unsigned long long *>(qs.spill_keys.ptr),
+                               static_cast<const float *const *>(qs.spill_blocks.ptr), cap - 1 };
+  }
+  if (n == 0)
+  {
+    return OHMHIP_OK;
+  }
+  OHMHIP_CHECK(qs.walked.ensure(sizeof(int32_t) * n, false, s));
+  OHMHIP_CHECK(qs.last_walked.ensure(sizeof(int32_t) * n, false, s));
+  OHMHIP_CHECK(qs.cursor.ensure(sizeof(uint32_t), false, s));
+  size_t scan_bytes = 0;
+  int32_t *walked = static_cast<int32_t *>(qs.walked.ptr);
+  int32_t *last_walked = static_cast<int32_t *>(qs.last_walked.ptr);
+  OHMHIP_CHECK(rocprim::inclusive_scan(nullptr, scan_bytes, walked, last_walked, size_t(n), rocprim::maximum<int32_t>(), s));
+  OHMHIP_CHECK(qs.scan_temp.ensure(scan_bytes, false, s));
+  a.occupancy = static_cast<const float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
+  a.rays = d_rays;
+  a.n_rays = n;
+  a.coef = coef;
+  a.ranges = d_ranges;
+  a.volumes = d_volumes;
+  a.types = d_types;
+  a.keys = d_keys;
+  a.walked = walked;
+  a.ray_cursor = static_cast<uint32_t *>(qs.cursor.ptr);
+  // OHMHIP_RAYS_QUERY_REFILL=1: the lane-refill variant (measured against one lane per ray)
+  const char *env = std::getenv("OHMHIP_RAYS_QUERY_REFILL");
+  const bool refill = env && std::atoi(env) != 0;
+  if (refill)
+  {
+    OHMHIP_CHECK(hipMemsetAsync(a.ray_cursor, 0, sizeof(uint32_t), s));
+    const uint32_t blocks = std::min<uint32_t>((n + 255) / 256, 2048u);
+    hipLaunchKernelGGL(k_rays_query<true>, dim3(blocks), dim3(256), 0, s, a);
+  }
+  else
+  {
+    hipLaunchKernelGGL(k_rays_query<false>, dim3((n + 255) / 256), dim3(256), 0, s, a);
+  }
+  OHMHIP_CHECK(hipGetLastError());
+  OHMHIP_CHECK(rocprim::inclusive_scan(qs.scan_temp.ptr, scan_bytes, walked, last_walked, size_t(n),
+                                       rocprim::maximum<int32_t>(), s));
+  hipLaunchKernelGGL(k_rays_query_carry, dim3((n + 255) / 256), dim3(256), 0, s, d_types, d_keys,
+                     static_cast<const int32_t *>(last_walked), n);
+  return hipGetLastError();
+}
+}  // namespace
+
+extern "C" {
+
+int ohmhip_map_rays_query(ohmhip_map_t m, const double *rays, size_t element_count, double volume_coefficient,
+                          double *ranges, double *unobserved_volumes, int8_t *terminal_types, void *terminal_keys)
+try
+{
+  OHMHIP_CHECK(raysQueryRefusal(m, rays, element_count, ranges, unobserved_volumes, terminal_types));
+  OHMHIP_SETTLE(m);
+  const uint32_t n = uint32_t(element_count / 2);
+  hipStream_t s = m->stream;
+  ohmhip_map_s::QueryState &qs = m->query;
+  if (n)
+  {
+    OHMHIP_CHECK(qs.rays.ensure(sizeof(double) * 6 * n, false, s));
+    OHMHIP_CHECK(qs.ranges.ensure(sizeof(double) * n, false, s));
+    OHMHIP_CHECK(qs.volumes.ensure(sizeof(double) * n, false, s));
+    OHMHIP_CHECK(qs.types.ensure(n, false, s));
+    if (terminal_keys)
+    {
+      OHMHIP_CHECK(qs.keys.ensure(sizeof(GpuKeyOut) * n, false, s));
+    }
+    OHMHIP_CHECK(hipMemcpyAsync(qs.rays.ptr, rays, sizeof(double) * 6 * n, hipMemcpyHostToDevice, s));
+  }
+  double *d_ranges = static_cast<double *>(qs.ranges.ptr);
+  double *d_volumes = static_cast<double *>(qs.volumes.ptr);
+  int8_t *d_types = static_cast<int8_t *>(qs.types.ptr);
+  GpuKeyOut *d_keys = terminal_keys ? static_cast<GpuKeyOut *>(qs.keys.ptr) : nullptr;
+  OHMHIP_CHECK(raysQueryDevice(m, static_cast<const double *>(qs.rays.ptr), n, volume_coefficient, d_ranges, d_volumes,
+                               d_types, d_keys));
+  if (n)
+  {
+    OHMHIP_CHECK(hipMemcpyAsync(ranges, d_ranges, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    OHMHIP_CHECK(hipMemcpyAsync(unobserved_volumes, d_volumes, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    OHMHIP_CHECK(hipMemcpyAsync(terminal_types, d_types, n, hipMemcpyDeviceToHost, s));
+    if (terminal_keys)
+    {
+      OHMHIP_CHECK(hipMemcpyAsync(terminal_keys, d_keys, sizeof(GpuKeyOut) * n, hipMemcpyDeviceToHost, s));
+    }
+  }
+  return hipStreamSynchronize(s);
+}
+OHMHIP_ABI_CATCH
+
+int ohmhip_map_rays_query_device(ohmhip_map_t m, const double *d_rays, size_t element_count, double volume_coefficient,
+                                 double *d_ranges, double *d_unobserved_volumes, int8_t *d_terminal_types,
+                                 void *d_terminal_keys)
+try
+{
+  OHMHIP_CHECK(raysQueryRefusal(m, d_rays, element_count, d_ranges, d_unobserved_volumes, d_terminal_types));
+  OHMHIP_SETTLE(m);
+  return raysQueryDevice(m, d_rays, uint32_t(element_count / 2), volume_coefficient, d_ranges, d_unobserved_volumes,
+                         d_terminal_types, static_cast<GpuKeyOut *>(d_terminal_keys));
 }
 OHMHIP_ABI_CATCH
 

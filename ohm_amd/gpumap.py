@@ -35,6 +35,14 @@ class RayFlag(enum.IntFlag):
     kRfReverseWalk = 1 << 8
 
 
+class OccupancyType(enum.IntEnum):
+    """ohm::OccupancyType (ohm/OccupancyType.h:14-24): the terminal state RaysQuery reports per ray."""
+    kNull = -2
+    kUnobserved = -1
+    kFree = 0
+    kOccupied = 1
+
+
 class NdtMode(enum.IntEnum):
     """ohm/NdtMode.h"""
     kNone = 0
@@ -579,6 +587,36 @@ class GpuMap(RayMapper):
         voxels = keys[:, :, 6:9]
         return regions, voxels, counts
 
+    def raysQuery(self, rays, volume_coefficient=1.0):
+        """RaysQuery on the device (ohmhip_map_rays_query; ohm/RaysQuery.cpp:102-203, bit for bit): rays are (2N, 3)
+        float64 origin / end point pairs (an odd trailing point is not a ray).  Returns (ranges f64, unobserved volumes
+        f64, terminal types i8 (OccupancyType), terminal voxel regions (N, 3) int16, local keys (N, 3) uint8).  The map's
+        current parameters (threshold, built-in ray filter) apply; the map is read, never changed."""
+        self._push_config_if_changed()
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 3)
+        n = rays.shape[0] // 2
+        ranges = np.zeros(n, dtype=np.float64)
+        volumes = np.zeros(n, dtype=np.float64)
+        types = np.zeros(n, dtype=np.int8)
+        keys = np.zeros((n, 10), dtype=np.uint8)
+        L.check(L.lib.ohmhip_map_rays_query(self._handle, rays.ctypes.data, rays.shape[0], float(volume_coefficient),
+                                            ranges.ctypes.data, volumes.ctypes.data, types.ctypes.data,
+                                            keys.ctypes.data), "raysQuery")
+        return ranges, volumes, types, keys[:, :6].copy().view(np.int16).reshape(n, 3), keys[:, 6:9].copy()
+
+    def raysQueryDevice(self, d_rays, element_count, d_ranges, d_volumes, d_types, d_keys=None,
+                        volume_coefficient=1.0, sync=True):
+        """raysQuery on device memory (ohmhip_map_rays_query_device), for rays already in HBM: raw device pointers
+        (ohmhip_buffer_ptr of a library buffer, a torch tensor's data_ptr(), ...) to element_count dvec3 and to the
+        outputs -- n = element_count // 2 doubles (ranges, volumes), n int8 (types), n 10-byte GpuKey records (keys,
+        optional).  The rays must be complete when the call is made (synchronise the stream that produced them).  The
+        query runs on the map's stream: with sync=False the outputs are valid after wait()."""
+        self._push_config_if_changed()
+        L.check(L.lib.ohmhip_map_rays_query_device(self._handle, d_rays, int(element_count), float(volume_coefficient),
+                                                   d_ranges, d_volumes, d_types, d_keys), "raysQueryDevice")
+        if sync:
+            self.wait()
+
     def _upload_existing(self):
         """gpumap::enableGpu + GpuLayerCache::upload for regions the CPU map already holds."""
         self.uploadRegions()
@@ -830,3 +868,91 @@ def device_info(device=0):
     L.check(L.lib.ohmhip_device_get_info(device, C.byref(info)), "device_get_info")
     return {"name": info.name.decode(), "arch": info.arch.decode(), "total_memory": info.total_memory,
             "compute_units": info.compute_units, "lds_bytes_per_block": info.lds_bytes_per_block}
+
+
+class RaysQueryGpu:
+    """ohm::RaysQueryGpu (ohmgpu/RaysQueryGpu.h; interface of ohm/RaysQuery.h + ohm/Query.h:51-121): for each ray, how far
+    it sees into the map (range to the first occupied voxel), the unobserved volume it crosses, the state and key of the
+    voxel it ends in -- evaluated on the device against the resident map (GpuMap.raysQuery), bit-identical to the CPU
+    query.  Given the GpuMap that holds the device handle."""
+
+    kQfGpuEvaluate = 1 << 2  # ohm/QueryFlag.h:42
+
+    def __init__(self, gpu_map, query_flags=0):
+        self._gpu_map = gpu_map
+        self._query_flags = int(query_flags) | self.kQfGpuEvaluate
+        self._volume_coefficient = 1.0
+        self._rays = np.zeros((0, 3), dtype=np.float64)
+        self.reset()
+
+    def queryFlags(self):
+        return self._query_flags
+
+    def setQueryFlags(self, flags):
+        self._query_flags = int(flags) | self.kQfGpuEvaluate
+
+    def setVolumeCoefficient(self, coefficient):
+        self._volume_coefficient = float(coefficient)
+
+    def volumeCoefficient(self):
+        return self._volume_coefficient
+
+    def setRays(self, rays):
+        """(2N, 3) origin / end point pairs (an odd trailing point is dropped)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 3)
+        self._rays = rays[:rays.shape[0] & ~1].copy()
+
+    def addRays(self, rays):
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 3)
+        self._rays = np.concatenate([self._rays, rays[:rays.shape[0] & ~1]])
+
+    def addRay(self, origin, end_point):
+        self.addRays(np.array([origin, end_point], dtype=np.float64))
+
+    def clearRays(self):
+        self._rays = np.zeros((0, 3), dtype=np.float64)
+
+    def rays(self):
+        return self._rays
+
+    def numberOfRays(self):
+        return self._rays.shape[0] // 2
+
+    def reset(self, hard_reset=True):
+        """Drops the results; hard_reset also drops the rays (ohm/RaysQuery.cpp onReset)."""
+        if hard_reset:
+            self.clearRays()
+        self._ranges = np.zeros(0, dtype=np.float64)
+        self._volumes = np.zeros(0, dtype=np.float64)
+        self._types = np.zeros(0, dtype=np.int8)
+        self._regions = np.zeros((0, 3), dtype=np.int16)
+        self._locals = np.zeros((0, 3), dtype=np.uint8)
+
+    def execute(self):
+        self.reset(False)
+        (self._ranges, self._volumes, self._types, self._regions,
+         self._locals) = self._gpu_map.raysQuery(self._rays, self._volume_coefficient)
+        return True
+
+    def executeAsync(self):
+        """The device call is synchronous: the asynchronous forms complete at once (ohm/Query.h:103-121)."""
+        return self.execute()
+
+    def wait(self, timeout_ms=0xffffffff):
+        return True
+
+    def numberOfResults(self):
+        return int(self._ranges.shape[0])
+
+    def ranges(self):
+        return self._ranges
+
+    def unobservedVolumes(self):
+        return self._volumes
+
+    def terminalOccupancyTypes(self):
+        return self._types
+
+    def intersectedVoxels(self):
+        """(regions (N, 3) int16, local keys (N, 3) uint8): each ray's terminal voxel."""
+        return self._regions, self._locals

@@ -736,6 +736,9 @@ public:
   }
 
   ohmhip_map_t handle() const { return handle_; }
+  /// Push the map's current parameters (threshold, built-in ray filter, ...) to the device, as a batch would: what a
+  /// query of the map (RaysQueryGpu) calls first.  @return false when the device refuses them.
+  bool syncConfig() { return pushConfigIfChanged(); }
 
 protected:
   using ConfigHook = void (*)(ohmhip_map_config &, void *);
@@ -1151,6 +1154,116 @@ private:
   std::vector<dvec3> rays_;
   std::vector<size_t> result_indices_, result_counts_;
   std::vector<Key> intersected_voxels_;
+};
+
+/// ohm::OccupancyType (ohm/OccupancyType.h:14-24).
+enum OccupancyType : int
+{
+  kNull = -2,
+  kUnobserved = -1,
+  kFree = 0,
+  kOccupied = 1
+};
+
+/// ohm::QueryFlag::kQfGpuEvaluate (ohm/QueryFlag.h:42).
+constexpr unsigned kQfGpuEvaluate = 1u << 2u;
+
+/// ohm::RaysQueryGpu (ohmgpu/RaysQueryGpu.h; the interface of ohm/RaysQuery.h + ohm/Query.h:51-121): for each ray, the
+/// range to the first occupied voxel, the unobserved volume crossed, and the state and key of the voxel the ray ends in
+/// -- evaluated on the device against the resident map (ohmhip_map_rays_query), bit-identical to the CPU query
+/// (ohm/RaysQuery.cpp:102-203).  The map's current parameters apply; the map is read, never changed.
+class RaysQueryGpu
+{
+public:
+  explicit RaysQueryGpu(GpuMap &gpu_map, unsigned query_flags = 0)
+    : gpu_map_(&gpu_map)
+    , query_flags_(query_flags | kQfGpuEvaluate)
+  {}
+  void setGpuMap(GpuMap *gpu_map) { gpu_map_ = gpu_map; }
+  unsigned queryFlags() const { return query_flags_; }
+  void setQueryFlags(unsigned flags) { query_flags_ = flags | kQfGpuEvaluate; }
+
+  void setVolumeCoefficient(double coefficient) { volume_coefficient_ = coefficient; }
+  double volumeCoefficient() const { return volume_coefficient_; }
+
+  /// Origin / end point pairs; @p element_count is twice the number of rays (an odd trailing point is dropped).
+  void setRays(const dvec3 *rays, size_t element_count)
+  {
+    rays_.assign(rays, rays + (element_count & ~size_t(1)));
+  }
+  void addRays(const dvec3 *rays, size_t element_count)
+  {
+    rays_.insert(rays_.end(), rays, rays + (element_count & ~size_t(1)));
+  }
+  void addRay(const dvec3 &origin, const dvec3 &end_point)
+  {
+    rays_.push_back(origin);
+    rays_.push_back(end_point);
+  }
+  void clearRays() { rays_.clear(); }
+  const dvec3 *rays() const { return rays_.data(); }
+  size_t numberOfRays() const { return rays_.size() / 2; }
+
+  size_t numberOfResults() const { return ranges_.size(); }
+  const double *ranges() const { return ranges_.data(); }
+  const double *unobservedVolumes() const { return volumes_.data(); }
+  const OccupancyType *terminalOccupancyTypes() const { return types_.data(); }
+  const Key *intersectedVoxels() const { return keys_.data(); }
+
+  /// Synchronous query (ohm/Query.h:93).  @return true on success.
+  bool execute()
+  {
+    reset(false);
+    if (!gpu_map_ || !gpu_map_->gpuOk() || !gpu_map_->syncConfig())
+    {
+      return false;
+    }
+    const size_t n = rays_.size() / 2;
+    std::vector<int8_t> types(n);
+    std::vector<unsigned char> records(n * 10u);
+    ranges_.resize(n);
+    volumes_.resize(n);
+    if (ohmhip_map_rays_query(gpu_map_->handle(), reinterpret_cast<const double *>(rays_.data()), rays_.size(),
+                              volume_coefficient_, ranges_.data(), volumes_.data(), types.data(),
+                              records.data()) != OHMHIP_OK)
+    {
+      reset(false);
+      return false;
+    }
+    types_.resize(n);
+    keys_.resize(n);
+    for (size_t i = 0; i < n; ++i)
+    {
+      types_[i] = OccupancyType(types[i]);
+      std::memcpy(keys_[i].region, records.data() + i * 10u, 6);
+      std::memcpy(keys_[i].local, records.data() + i * 10u + 6, 3);
+    }
+    return true;
+  }
+  /// The device call is synchronous: the asynchronous forms complete at once (ohm/Query.h:103-121).
+  bool executeAsync() { return execute(); }
+  bool wait(unsigned /*timeout_ms*/ = ~0u) { return true; }
+  /// Drops the results; @p hard_reset also drops the rays (ohm/RaysQuery.cpp onReset).
+  void reset(bool hard_reset = true)
+  {
+    ranges_.clear();
+    volumes_.clear();
+    types_.clear();
+    keys_.clear();
+    if (hard_reset)
+    {
+      rays_.clear();
+    }
+  }
+
+private:
+  GpuMap *gpu_map_ = nullptr;
+  unsigned query_flags_ = kQfGpuEvaluate;
+  double volume_coefficient_ = 1.0;
+  std::vector<dvec3> rays_;
+  std::vector<double> ranges_, volumes_;
+  std::vector<OccupancyType> types_;
+  std::vector<Key> keys_;
 };
 
 /// Not in the reference (ohm is single device): the RCCL communicator the library owns (include/ohmhip.h, ohmhip_comm_*).

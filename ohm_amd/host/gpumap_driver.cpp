@@ -3,7 +3,7 @@
 // (tests/ohmtestgpu/GpuMapTest.cpp:68-205), syncs, and dumps every region layer for the Python parity test to check
 // against the CPU oracle.  Links libohmhip.so only; built with plain g++ (no hipcc, no glm).
 //
-//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|...> <resolution> <batch_rays> <rays.bin> <out.bin>
+//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|...> <resolution> <batch_rays> <rays.bin> <out.bin>
 //   occdev: the sample points (odd entries) go through ohm::GpuTransformSamples with a static identity trajectory and
 //   are integrated straight from the device buffer (all rays then start at the origin).
 //   rays.bin: u64 n_points, then n_points * 3 doubles.  out.bin: u64 regions, per region i16[3] key, then per enabled
@@ -135,6 +135,48 @@ int main(int argc, char **argv)
       {
         std::fwrite(query.intersectedVoxels()[k].region, sizeof(int16_t), 3, out);
         std::fwrite(query.intersectedVoxels()[k].local, sizeof(uint8_t), 3, out);
+      }
+      std::fclose(out);
+      return 0;
+    }
+
+    if (mode == "raysquery")
+    {
+      // ohm::RaysQueryGpu: the first half of the rays builds the map (ohm::GpuMap::integrateRays), the second half is
+      // the query (addRay / executeAsync / wait).  out.bin = u64 rays, then per ray f64 range, f64 unobserved volume,
+      // i32 terminal type, i16[3] region, u8[3] local.
+      ohm::OccupancyMap query_map(resolution);
+      ohm::GpuMap query_gpu_map(&query_map, true);
+      const size_t build_points = (rays.size() / 2) & ~size_t(1);
+      if (build_points && query_gpu_map.integrateRays(rays.data(), build_points) != build_points)
+      {
+        return 8;
+      }
+      ohm::RaysQueryGpu query(query_gpu_map);
+      for (size_t i = build_points; i + 1 < rays.size(); i += 2)
+      {
+        query.addRay(rays[i], rays[i + 1]);
+      }
+      if (!(query.queryFlags() & ohm::kQfGpuEvaluate) || !query.executeAsync() || !query.wait() ||
+          query.numberOfResults() != query.numberOfRays())
+      {
+        return 8;
+      }
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      const uint64_t n = query.numberOfResults();
+      std::fwrite(&n, sizeof(n), 1, out);
+      for (uint64_t i = 0; i < n; ++i)
+      {
+        const int32_t type = query.terminalOccupancyTypes()[i];
+        std::fwrite(&query.ranges()[i], sizeof(double), 1, out);
+        std::fwrite(&query.unobservedVolumes()[i], sizeof(double), 1, out);
+        std::fwrite(&type, sizeof(type), 1, out);
+        std::fwrite(query.intersectedVoxels()[i].region, sizeof(int16_t), 3, out);
+        std::fwrite(query.intersectedVoxels()[i].local, sizeof(uint8_t), 3, out);
       }
       std::fclose(out);
       return 0;
