@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-/* CORE ABI.  The header has grown to 88 entry points over six rounds; a reference-side binding of ohm::GpuMap /
+/* CORE ABI.  The header has grown to 91 entry points over six rounds; a reference-side binding of ohm::GpuMap /
  * GpuNdtMap / GpuTsdfMap / GpuCache needs FIFTEEN of them.  The list below is exact: it is every ohmhip_* call made by
  * ohm_amd/host/ref_adaptor/private/HipBindingCore.cpp, the compiled and GPU-tested logic of the Level-2 adaptor
  * (INTEGRATION.md), and tests/test_cabi.py keeps the two in step.
@@ -456,6 +456,52 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_rays_query_device(ohmhip_map_t map, const dou
                                                      double volume_coefficient, double *d_ranges,
                                                      double *d_unobserved_volumes, int8_t *d_terminal_types,
                                                      void *d_terminal_keys);
+
+/* ClearanceProcess / LineQueryGpu (ohmgpu/ClearanceProcess.{h,cpp}, ohmgpu/LineQueryGpu.{h,cpp}): the clearance of a voxel
+ * v is the CPU's calculateNearestNeighbour(v, map, h, unknown_as_occupied, ignore_self = false, search_radius,
+ * axis_scaling, report_unscaled) (ohm/private/VoxelAlgorithms.cpp:22-98) as written, bit for bit -- not the
+ * reference's approximate GPU flood fill (gpu/RoiRangeFill.cl).  h = int(ceil(double(search_radius) / resolution)) on
+ * every axis (calculateVoxelSearchHalfExtents, :16).  A voxel is a candidate when its region exists and value != +inf
+ * && value >= threshold_value (isOccupied, ohm/VoxelOccupancy.h:161: `>=`, unlike the rays query's `>`), or, with
+ * OHMHIP_QF_UNKNOWN_AS_OCCUPIED, when it is unobserved (+inf) or in no region (isUnobservedOrNull).  v itself a
+ * candidate: 0.  Otherwise the neighbours moveKey(v, x, y, z) for x, y, z in [-h, h] (the region key adds in int16 and
+ * wraps, ohm/private/OccupancyMapDetail.cpp:27-93), all fp32 with rounding after every operation:
+ * c(k) = float(voxelCentreLocal(k)) (fp64 in the order of OccupancyMap::voxelCentre, ohm/OccupancyMap.h:757-777);
+ * sep = c(n) - c(v); r2 = (sep.x*sep.x + sep.y*sep.y) + sep.z*sep.z; s = sep * axis_scaling per component; s2 the same
+ * dot product of s; r2 = s2 unless OHMHIP_QF_REPORT_UNSCALED; a candidate counts when search_radius == 0 ||
+ * r2 <= search_radius * search_radius and is taken when s2 is smaller than the best so far -- strictly, so ties go to
+ * the earliest in the CPU's scan order (z outermost, x innermost; the device selects by (s2, scan index)).  Result:
+ * sqrtf(r2 of the one taken), -1 when none.
+ * The map is observed as ohmhip_map_rays_query observes it -- collected rays launched, an asynchronous launch settled,
+ * resident tiles through the region hash, regions of the host store from their pinned records without re-admission,
+ * tiled regions in the caller's region coordinates -- and nothing of it changes: voxels, dirty set, residency, use
+ * stamps, ohmhip_map_cache_stats.  No clearance layer is kept: results go to the caller's memory, as the reference's
+ * RoiRangeFill::finishRegion downloads each region's block.  OHMHIP_ERR_UNSUPPORTED for a map without the occupancy
+ * layer, a map with region ownership or a partition, and h > 127; OHMHIP_ERR_INVALID_ARG, before any device work, for
+ * null arrays, a negative or non-finite search_radius and a zero or non-finite axis_scaling component. */
+#define OHMHIP_QF_UNKNOWN_AS_OCCUPIED (1u << 0) /* ohm::kQfUnknownAsOccupied (ohm/QueryFlag.h:38) */
+#define OHMHIP_QF_REPORT_UNSCALED (1u << 4)     /* ohm::kQfReportUnscaledResults (:50); other QueryFlag bits ignored */
+typedef struct ohmhip_clearance_params
+{
+  float search_radius;
+  float axis_scaling[3];
+  unsigned flags; /* OHMHIP_QF_* */
+} ohmhip_clearance_params;
+
+/* ClearanceProcess::calculateForExtents per region: every voxel of each listed region (present in the map or not),
+ * MapChunk order x + y*dx + z*dx*dy, one float per voxel -- dsts[i] as in ohmhip_map_read_regions.  Host pointers;
+ * synchronous. */
+int ohmhip_map_clearance_regions(ohmhip_map_t map, const int16_t *keys_xyz, size_t count,
+                                 const ohmhip_clearance_params *params, float *const *dsts);
+/* The same into one device array of count * region_voxels floats, enqueued on the map's stream (keys_xyz is a host
+ * array of count regions); ohmhip_map_sync is the fence. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_clearance_regions_device(ohmhip_map_t map, const int16_t *keys_xyz, size_t count,
+                                                            const ohmhip_clearance_params *params, float *d_out);
+/* Clearance of arbitrary voxels given as 10-byte GpuKey records (the layout ohmhip_map_line_keys writes), one float
+ * each.  A key whose local coordinates lie outside the region dimensions: OHMHIP_ERR_INVALID_ARG.  Host pointers;
+ * synchronous. */
+int ohmhip_map_clearance_keys(ohmhip_map_t map, const void *keys, size_t count, const ohmhip_clearance_params *params,
+                              float *out);
 
 /* GpuTransformSamples::transform (ohmgpu/GpuTransformSamples.h:75-79, .cpp:97-210; kernel transformTimestampedPoints,
  * ohmgpu/gpu/TransformSamples.cl:94-228): sensor-frame samples with time stamps + a timestamped trajectory (translations

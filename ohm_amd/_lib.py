@@ -43,6 +43,11 @@ class DeviceInfo(C.Structure):
                 ("unified_memory", C.c_int)]
 
 
+class ClearanceParams(C.Structure):
+    """ohmhip_clearance_params"""
+    _fields_ = [("search_radius", C.c_float), ("axis_scaling", C.c_float * 3), ("flags", C.c_uint)]
+
+
 class MapConfig(C.Structure):
     _fields_ = [("resolution", C.c_double), ("region_dim", C.c_int * 3), ("origin", C.c_double * 3),
                 ("layers", C.c_uint), ("mode", C.c_int), ("hit_value", C.c_float), ("miss_value", C.c_float),
@@ -146,6 +151,9 @@ _sigs = {
     "ohmhip_map_line_keys": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp]),
     "ohmhip_map_rays_query": (C.c_int, [_vp, _vp, C.c_size_t, C.c_double, _vp, _vp, _vp, _vp]),
     "ohmhip_map_rays_query_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_double, _vp, _vp, _vp, _vp]),
+    "ohmhip_map_clearance_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
+    "ohmhip_map_clearance_regions_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
+    "ohmhip_map_clearance_keys": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
     "ohmhip_map_device_layer_ptr": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "ohmhip_map_region_slot": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "ohmhip_map_ensure_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

@@ -226,12 +226,14 @@ struct ohmhip_map_s
   size_t readmit_period_at = 0;
   DevBuf copy_jobs;  ///< job list of k_copy_jobs (spill to host, compaction)
   DevBuf stop_a, stop_b;  ///< kRfStopOnFirstOccupied: per-ray stop positions (current / candidate)
-  /// ohmhip_map_rays_query (query_kernels.h): buffers of its own, so a query never touches a batch's staging.
+  /// ohmhip_map_rays_query (query_kernels.h) and the clearance queries (clearance_kernels.h): buffers of their own, so a
+  /// query never touches a batch's staging.
   struct QueryState
   {
     DevBuf rays, ranges, volumes, types, keys;   ///< host-pointer calls: device copies of the caller's arrays
     DevBuf walked, last_walked, scan_temp, cursor;
     DevBuf spill_keys, spill_blocks;             ///< table of the host store's regions (spill to host)
+    DevBuf clear_regions, clear_keys, clear_out, clear_mask;  ///< clearance queries (clearance_kernels.h)
   } query;
   uint32_t *d_event_count = nullptr;  ///< per parity: [0] deferred event count, [1] walk kernel chunk cursor, [2] replay group count, [3] stop iteration flag
   uint32_t walk_workgroups = 256;     ///< persistent walk workgroups: one per CU

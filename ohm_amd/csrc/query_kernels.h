@@ -70,7 +70,9 @@ __device__ inline GpuKeyOut queryNullKey()
 }
 
 /// The occupancy block of tile (tx, ty, tz): resident slot, then the host store; null when the map has no such tile.
-__device__ inline const float *queryTileBlock(const RaysQueryArgs &a, int tx, int ty, int tz)
+/// Args: any argument block with mc, rt, spill and occupancy (RaysQueryArgs, ClearanceArgs).
+template <typename Args>
+__device__ inline const float *queryTileBlock(const Args &a, int tx, int ty, int tz)
 {
   // (a region the reference addresses whose tile coordinates leave the packed key's 16-bit fields cannot be in the
   // map: the key must not wrap onto another tile)

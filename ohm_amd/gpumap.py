@@ -43,6 +43,38 @@ class OccupancyType(enum.IntEnum):
     kOccupied = 1
 
 
+class QueryFlag(enum.IntFlag):
+    """ohm::QueryFlag (ohm/QueryFlag.h:35-60), bit for bit."""
+    kQfZero = 0
+    kQfUnknownAsOccupied = 1 << 0
+    kQfNearestResult = 1 << 1
+    kQfGpuEvaluate = 1 << 2
+    kQfNoCache = 1 << 3
+    kQfReportUnscaledResults = 1 << 4
+    kQfSpecialised = 1 << 16
+
+
+def _clearance_params(search_radius, flags, axis_scaling):
+    p = L.ClearanceParams()
+    p.search_radius = float(search_radius)
+    for i, v in enumerate(axis_scaling):
+        p.axis_scaling[i] = float(v)
+    p.flags = int(flags) & 0xffffffff
+    return p
+
+
+def _key_records(keys):
+    """10-byte GpuKey records (N, 10) uint8 from such records or from a (regions (N, 3), locals (N, 3)) pair."""
+    if isinstance(keys, tuple):
+        regions = np.ascontiguousarray(keys[0], dtype=np.int16).reshape(-1, 3)
+        locals_ = np.asarray(keys[1], dtype=np.uint8).reshape(-1, 3)
+        rec = np.zeros((regions.shape[0], 10), dtype=np.uint8)
+        rec[:, :6] = regions.view(np.uint8).reshape(-1, 6)
+        rec[:, 6:9] = locals_
+        return rec
+    return np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 10)
+
+
 class NdtMode(enum.IntEnum):
     """ohm/NdtMode.h"""
     kNone = 0
@@ -604,6 +636,49 @@ class GpuMap(RayMapper):
                                             keys.ctypes.data), "raysQuery")
         return ranges, volumes, types, keys[:, :6].copy().view(np.int16).reshape(n, 3), keys[:, 6:9].copy()
 
+    def clearanceRegions(self, keys, search_radius, flags=0, axis_scaling=(1.0, 1.0, 1.0)):
+        """Clearance of every voxel of each region in keys ((N, 3) int16, present in the map or not) on the device
+        (ohmhip_map_clearance_regions; calculateNearestNeighbour, ohm/private/VoxelAlgorithms.cpp:22-98, bit for bit):
+        (N, dz, dy, dx) float32, the distance to the nearest obstructing voxel within search_radius, 0 for an
+        obstructing voxel, -1 when none.  flags: QueryFlag.kQfUnknownAsOccupied, kQfReportUnscaledResults (others are
+        ignored).  The map is read, never changed."""
+        self._push_config_if_changed()
+        keys = np.ascontiguousarray(keys, dtype=np.int16).reshape(-1, 3)
+        n = keys.shape[0]
+        dx, dy, dz = self._map.region_voxel_dimensions
+        out = np.zeros((n, dz, dy, dx), dtype=np.float32)
+        dsts = (C.c_void_p * max(n, 1))(*[out[i].ctypes.data for i in range(n)])
+        L.check(L.lib.ohmhip_map_clearance_regions(self._handle, keys.ctypes.data, n,
+                                                   C.byref(_clearance_params(search_radius, flags, axis_scaling)),
+                                                   dsts), "clearanceRegions")
+        return out
+
+    def clearanceRegionsDevice(self, keys, d_out, search_radius, flags=0, axis_scaling=(1.0, 1.0, 1.0), sync=True):
+        """clearanceRegions into device memory (ohmhip_map_clearance_regions_device): d_out is a raw device pointer to
+        N * region voxels float32 (a torch tensor's data_ptr(), ...), written on the map's stream; with sync=False the
+        values are valid after wait()."""
+        self._push_config_if_changed()
+        keys = np.ascontiguousarray(keys, dtype=np.int16).reshape(-1, 3)
+        L.check(L.lib.ohmhip_map_clearance_regions_device(self._handle, keys.ctypes.data, keys.shape[0],
+                                                          C.byref(_clearance_params(search_radius, flags,
+                                                                                    axis_scaling)), d_out),
+                "clearanceRegionsDevice")
+        if sync:
+            self.wait()
+
+    def clearanceKeys(self, keys, search_radius, flags=0, axis_scaling=(1.0, 1.0, 1.0)):
+        """The clearance of arbitrary voxels (ohmhip_map_clearance_keys): keys are (N, 10) GpuKey records, as lineKeys
+        returns them, or a (regions (N, 3), locals (N, 3)) pair.  Returns (N,) float32, the values clearanceRegions
+        gives those voxels."""
+        self._push_config_if_changed()
+        rec = _key_records(keys)
+        n = rec.shape[0]
+        out = np.zeros(n, dtype=np.float32)
+        L.check(L.lib.ohmhip_map_clearance_keys(self._handle, rec.ctypes.data, n,
+                                                C.byref(_clearance_params(search_radius, flags, axis_scaling)),
+                                                out.ctypes.data), "clearanceKeys")
+        return out
+
     def raysQueryDevice(self, d_rays, element_count, d_ranges, d_volumes, d_types, d_keys=None,
                         volume_coefficient=1.0, sync=True):
         """raysQuery on device memory (ohmhip_map_rays_query_device), for rays already in HBM: raw device pointers
@@ -956,3 +1031,195 @@ class RaysQueryGpu:
     def intersectedVoxels(self):
         """(regions (N, 3) int16, local keys (N, 3) uint8): each ray's terminal voxel."""
         return self._regions, self._locals
+
+
+def _region_coord(value, origin, region_dim):
+    """pointToRegionCoord (ohm/MapCoord.h:85-93) into the int16 of glm::i16vec3 (MapRegion, ohm/MapRegion.cpp:32-37)."""
+    c = int(math.floor((float(value) - float(origin)) / region_dim + 0.5))
+    return (c + 32768) % 65536 - 32768
+
+
+class ClearanceProcess:
+    """ohm::ClearanceProcess (ohmgpu/ClearanceProcess.h): the clearance of every voxel of a set of regions -- the distance
+    to the nearest obstructing voxel within the search radius, per calculateNearestNeighbour (ohm/private/
+    VoxelAlgorithms.cpp:22-98) -- evaluated exactly on the device (GpuMap.clearanceRegions), not by the reference's
+    approximate flood fill.  The results are kept here per region (there is no clearance layer in the device map).
+    Not provided: update() (the incremental dirty-region pass), stamp-based skipping (force=False recomputes) and
+    serialisation."""
+
+    kQfInstantiateUnknown = int(QueryFlag.kQfSpecialised) << 0  # ohmgpu/ClearanceProcess.h
+
+    def __init__(self, search_radius=0.0, query_flags=0):
+        self._search_radius = float(search_radius)
+        self._query_flags = int(query_flags)
+        self._axis_scaling = (1.0, 1.0, 1.0)
+        self._results = {}
+        self._region_dim = None
+
+    def searchRadius(self):
+        return self._search_radius
+
+    def setSearchRadius(self, radius):
+        self._search_radius = float(radius)
+
+    def queryFlags(self):
+        return self._query_flags
+
+    def setQueryFlags(self, flags):
+        self._query_flags = int(flags)
+
+    def axisScaling(self):
+        return self._axis_scaling
+
+    def setAxisScaling(self, scaling):
+        self._axis_scaling = tuple(float(v) for v in scaling)
+
+    def reset(self):
+        self._results = {}
+
+    def calculateForExtents(self, gpu_map, min_extents, max_extents, force=True):
+        """ClearanceProcess::calculateForExtents (ohmgpu/ClearanceProcess.cpp:474-510): every region from
+        regionKey(min_extents) to regionKey(max_extents) that exists in the map -- every one with kQfInstantiateUnknown,
+        without creating it on the device.  force=False recomputes too (no stamps).  Returns the regions computed."""
+        m = gpu_map.map()
+        rdim = [m.region_voxel_dimensions[i] * m.resolution for i in range(3)]
+        lo = [_region_coord(min_extents[i], m.origin[i], rdim[i]) for i in range(3)]
+        hi = [_region_coord(max_extents[i], m.origin[i], rdim[i]) for i in range(3)]
+        if self._query_flags & self.kQfInstantiateUnknown:
+            keys = [(x, y, z) for z in range(lo[2], hi[2] + 1) for y in range(lo[1], hi[1] + 1)
+                    for x in range(lo[0], hi[0] + 1)]
+        else:
+            present = set(tuple(int(v) for v in k) for k in gpu_map.regionKeys())
+            keys = [(x, y, z) for z in range(lo[2], hi[2] + 1) for y in range(lo[1], hi[1] + 1)
+                    for x in range(lo[0], hi[0] + 1) if (x, y, z) in present]
+        self._region_dim = tuple(m.region_voxel_dimensions)
+        if keys:
+            out = gpu_map.clearanceRegions(np.array(keys, dtype=np.int16), self._search_radius, self._query_flags,
+                                           self._axis_scaling)
+            for key, block in zip(keys, out):
+                self._results[key] = block
+        return keys
+
+    def regionClearance(self, region_key):
+        """(dz, dy, dx) float32 of a computed region, None otherwise."""
+        return self._results.get(tuple(int(v) for v in region_key))
+
+    def voxelClearance(self, key):
+        """The clearance of one voxel, key = (region key, local key), of a computed region; None otherwise."""
+        region_key, local_key = key
+        block = self.regionClearance(region_key)
+        if block is None:
+            return None
+        return float(block[int(local_key[2]), int(local_key[1]), int(local_key[0])])
+
+
+class LineQueryGpu:
+    """ohm::LineQueryGpu (ohmgpu/LineQueryGpu.{h,cpp}; interface of ohm/LineQuery.h): the voxels a line segment passes
+    through and the clearance of each -- how close the path passes to an obstacle.  Composed of the device line walk
+    (GpuMap.lineKeys, calculateSegmentKeys' keys) and the device clearance of those keys (GpuMap.clearanceKeys), with
+    LineQueryGpu::onExecute's post-processing: a voxel outside every region of the map, or with no obstruction within
+    the search radius (-1), reports defaultRange(); kQfUnknownAsOccupied is passed on to the clearance (and nothing
+    else: the reference's GPU query ignores kQfReportUnscaledResults).  With kQfNearestResult only the voxel of the
+    smallest range is kept, chosen as the GPU query chooses it: the first voxel, then any later one with range >= 0 and
+    (range < closest or closest < 0).  The CPU LineQuery selects differently -- `range * range < closest`
+    (ohm/LineQuery.cpp:75-84), so a default range of -1 counts as 1 there -- and is not what this class follows."""
+
+    def __init__(self, gpu_map, start_point=(0.0, 0.0, 0.0), end_point=(0.0, 0.0, 0.0), search_radius=0.0,
+                 query_flags=0):
+        self._gpu_map = gpu_map
+        self._start = tuple(float(v) for v in start_point)
+        self._end = tuple(float(v) for v in end_point)
+        self._search_radius = float(search_radius)
+        self._query_flags = int(query_flags) | int(QueryFlag.kQfGpuEvaluate)
+        self._default_range = -1.0
+        self._axis_scaling = (1.0, 1.0, 1.0)
+        self.reset()
+
+    def startPoint(self):
+        return self._start
+
+    def setStartPoint(self, point):
+        self._start = tuple(float(v) for v in point)
+
+    def endPoint(self):
+        return self._end
+
+    def setEndPoint(self, point):
+        self._end = tuple(float(v) for v in point)
+
+    def searchRadius(self):
+        return self._search_radius
+
+    def setSearchRadius(self, radius):
+        self._search_radius = float(radius)
+
+    def defaultRange(self):
+        return self._default_range
+
+    def setDefaultRange(self, value):
+        self._default_range = float(np.float32(value))
+
+    def axisScaling(self):
+        return self._axis_scaling
+
+    def setAxisScaling(self, scaling):
+        self._axis_scaling = tuple(float(v) for v in scaling)
+
+    def queryFlags(self):
+        return self._query_flags
+
+    def setQueryFlags(self, flags):
+        self._query_flags = int(flags) | int(QueryFlag.kQfGpuEvaluate)
+
+    def reset(self, hard_reset=True):
+        self._regions = np.zeros((0, 3), dtype=np.int16)
+        self._locals = np.zeros((0, 3), dtype=np.uint8)
+        self._ranges = np.zeros(0, dtype=np.float32)
+        self._number_of_results = 0
+
+    def execute(self):
+        self.reset(False)
+        gm = self._gpu_map
+        res = gm.map().resolution
+        start = np.array(self._start, dtype=np.float64)
+        end = np.array(self._end, dtype=np.float64)
+        length = float(np.linalg.norm(end - start))
+        max_keys = int(math.ceil(length / res * math.sqrt(3.0))) + 4
+        regions, voxels, counts = gm.lineKeys(np.array([start, end]), max_keys_per_line=max_keys)
+        n = int(min(int(counts[0]), max_keys))
+        regions = np.ascontiguousarray(regions[0, :n])
+        locals_ = np.ascontiguousarray(voxels[0, :n])
+        flags = int(QueryFlag.kQfUnknownAsOccupied) if self._query_flags & QueryFlag.kQfUnknownAsOccupied else 0
+        ranges = gm.clearanceKeys((regions, locals_), self._search_radius, flags, self._axis_scaling)
+        present = set(tuple(int(v) for v in k) for k in gm.regionKeys())
+        known = np.array([tuple(int(v) for v in r) in present for r in regions], dtype=bool)
+        ranges = np.where(known & (ranges >= 0), ranges, np.float32(self._default_range)).astype(np.float32)
+        if (self._query_flags & QueryFlag.kQfNearestResult) and n:
+            closest_index, closest = 0, np.float32(-1.0)
+            for i in range(n):
+                r = ranges[i]
+                if i == 0 or (r >= 0 and (r < closest or closest < 0)):
+                    closest_index, closest = i, r
+            regions = regions[closest_index:closest_index + 1]
+            locals_ = locals_[closest_index:closest_index + 1]
+            ranges = ranges[closest_index:closest_index + 1]
+        self._regions, self._locals, self._ranges = regions.copy(), locals_.copy(), ranges.copy()
+        self._number_of_results = int(ranges.shape[0])
+        return True
+
+    def executeAsync(self):
+        """The device calls are synchronous: the asynchronous forms complete at once (ohm/Query.h:103-121)."""
+        return self.execute()
+
+    def wait(self, timeout_ms=0xffffffff):
+        return True
+
+    def numberOfResults(self):
+        return self._number_of_results
+
+    def intersectedVoxels(self):
+        """(regions (K, 3) int16, local keys (K, 3) uint8) in walk order (one with kQfNearestResult)."""
+        return self._regions, self._locals
+
+    def ranges(self):
+        return self._ranges

@@ -1266,6 +1266,280 @@ private:
   std::vector<Key> keys_;
 };
 
+/// The other ohm::QueryFlag bits (ohm/QueryFlag.h:35-60).
+constexpr unsigned kQfUnknownAsOccupied = 1u << 0u;
+constexpr unsigned kQfNearestResult = 1u << 1u;
+constexpr unsigned kQfNoCache = 1u << 3u;
+constexpr unsigned kQfReportUnscaledResults = 1u << 4u;
+constexpr unsigned kQfSpecialised = 1u << 16u;
+
+/// ohm::ClearanceProcess (ohmgpu/ClearanceProcess.h): the clearance of every voxel of a set of regions -- the distance
+/// to the nearest obstructing voxel within the search radius, per calculateNearestNeighbour (ohm/private/
+/// VoxelAlgorithms.cpp:22-98), evaluated exactly on the device (ohmhip_map_clearance_regions), not by the reference's
+/// approximate flood fill.  Results are kept here per region: the device map has no clearance layer.  Not provided:
+/// update() (incremental dirty-region processing), stamp-based skipping (force = false recomputes), serialisation.
+class ClearanceProcess
+{
+public:
+  enum : unsigned
+  {
+    kQfInstantiateUnknown = kQfSpecialised << 0u
+  };
+  using RegionKey = std::array<int16_t, 3>;
+
+  ClearanceProcess() = default;
+  ClearanceProcess(float search_radius, unsigned query_flags)
+    : search_radius_(search_radius)
+    , query_flags_(query_flags)
+  {}
+
+  float searchRadius() const { return search_radius_; }
+  void setSearchRadius(float range) { search_radius_ = range; }
+  unsigned queryFlags() const { return query_flags_; }
+  void setQueryFlags(unsigned flags) { query_flags_ = flags; }
+  const float *axisScaling() const { return axis_scaling_; }
+  void setAxisScaling(float x, float y, float z)
+  {
+    axis_scaling_[0] = x;
+    axis_scaling_[1] = y;
+    axis_scaling_[2] = z;
+  }
+  void reset() { results_.clear(); }
+
+  /// ClearanceProcess::calculateForExtents (ohmgpu/ClearanceProcess.cpp:474-510): the regions from regionKey(min) to
+  /// regionKey(max) that exist in the map, or all of them with kQfInstantiateUnknown (not created on the device).
+  /// @return false when the device refuses the query.
+  bool calculateForExtents(GpuMap &gpu_map, const dvec3 &min_extents, const dvec3 &max_extents, bool force = true)
+  {
+    (void)force;  // no stamps: every call recomputes
+    if (!gpu_map.gpuOk() || !gpu_map.syncConfig())
+    {
+      return false;
+    }
+    const OccupancyMap &m = gpu_map.map();
+    const double lo[3] = { min_extents.x, min_extents.y, min_extents.z };
+    const double hi[3] = { max_extents.x, max_extents.y, max_extents.z };
+    int r0[3], r1[3];
+    for (int a = 0; a < 3; ++a)
+    {
+      const double rdim = m.regionVoxelDimensions()[a] * m.resolution();
+      r0[a] = int16_t(int(std::floor((lo[a] - m.origin()[a]) / rdim + 0.5)));  // pointToRegionCoord, ohm/MapCoord.h:85
+      r1[a] = int16_t(int(std::floor((hi[a] - m.origin()[a]) / rdim + 0.5)));
+    }
+    std::vector<RegionKey> present;
+    if (!(query_flags_ & kQfInstantiateUnknown))
+    {
+      size_t n = 0;
+      if (ohmhip_map_regions(gpu_map.handle(), nullptr, 0, &n) != OHMHIP_OK)
+      {
+        return false;
+      }
+      present.resize(n);
+      if (n && ohmhip_map_regions(gpu_map.handle(), present.front().data(), n, &n) != OHMHIP_OK)
+      {
+        return false;
+      }
+      std::sort(present.begin(), present.end());
+    }
+    std::vector<int16_t> keys;
+    for (int z = r0[2]; z <= r1[2]; ++z)
+    {
+      for (int y = r0[1]; y <= r1[1]; ++y)
+      {
+        for (int x = r0[0]; x <= r1[0]; ++x)
+        {
+          const RegionKey key = { int16_t(x), int16_t(y), int16_t(z) };
+          if ((query_flags_ & kQfInstantiateUnknown) || std::binary_search(present.begin(), present.end(), key))
+          {
+            keys.insert(keys.end(), key.begin(), key.end());
+          }
+        }
+      }
+    }
+    const size_t count = keys.size() / 3;
+    const size_t voxels = m.regionVoxelVolume();
+    std::vector<std::vector<float>> blocks(count, std::vector<float>(voxels));
+    std::vector<float *> dsts(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+      dsts[i] = blocks[i].data();
+    }
+    if (ohmhip_map_clearance_regions(gpu_map.handle(), keys.data(), count, params(), dsts.data()) != OHMHIP_OK)
+    {
+      return false;
+    }
+    for (size_t i = 0; i < count; ++i)
+    {
+      results_[RegionKey{ keys[3 * i], keys[3 * i + 1], keys[3 * i + 2] }] = std::move(blocks[i]);
+    }
+    return true;
+  }
+
+  /// The clearance block of a computed region (MapChunk order), null otherwise.
+  const float *regionClearance(const RegionKey &region_key) const
+  {
+    const auto it = results_.find(region_key);
+    return it == results_.end() ? nullptr : it->second.data();
+  }
+  /// The clearance of one voxel of a computed region.  @return false when its region was not computed.
+  bool voxelClearance(const Key &key, const int *region_dim, float *value) const
+  {
+    const float *block = regionClearance(RegionKey{ key.region[0], key.region[1], key.region[2] });
+    if (!block)
+    {
+      return false;
+    }
+    *value = block[key.local[0] + key.local[1] * region_dim[0] + key.local[2] * region_dim[0] * region_dim[1]];
+    return true;
+  }
+
+private:
+  const ohmhip_clearance_params *params()
+  {
+    params_.search_radius = search_radius_;
+    for (int a = 0; a < 3; ++a)
+    {
+      params_.axis_scaling[a] = axis_scaling_[a];
+    }
+    params_.flags = query_flags_;
+    return &params_;
+  }
+
+  float search_radius_ = 0.0f;
+  unsigned query_flags_ = 0;
+  float axis_scaling_[3] = { 1.0f, 1.0f, 1.0f };
+  ohmhip_clearance_params params_{};
+  std::map<RegionKey, std::vector<float>> results_;
+};
+
+/// ohm::LineQueryGpu (ohmgpu/LineQueryGpu.{h,cpp}; interface of ohm/LineQuery.h): the voxels a segment passes through
+/// (calculateSegmentKeys, device walk: ohmhip_map_line_keys) and the clearance of each (ohmhip_map_clearance_keys),
+/// with LineQueryGpu::onExecute's post-processing: a voxel in no region of the map, or unobstructed within the radius
+/// (-1), reports defaultRange(); only kQfUnknownAsOccupied is passed to the clearance.  kQfNearestResult keeps the
+/// first voxel, then any later one with range >= 0 && (range < closest || closest < 0) -- the GPU query's rule; the CPU
+/// LineQuery compares range * range < closest (ohm/LineQuery.cpp:75-84) and is not followed.
+class LineQueryGpu
+{
+public:
+  LineQueryGpu(GpuMap &gpu_map, const dvec3 &start_point, const dvec3 &end_point, float search_radius,
+               unsigned query_flags = 0)
+    : gpu_map_(&gpu_map)
+    , start_(start_point)
+    , end_(end_point)
+    , search_radius_(search_radius)
+    , query_flags_(query_flags | kQfGpuEvaluate)
+  {}
+
+  void setStartPoint(const dvec3 &p) { start_ = p; }
+  void setEndPoint(const dvec3 &p) { end_ = p; }
+  float searchRadius() const { return search_radius_; }
+  void setSearchRadius(float r) { search_radius_ = r; }
+  float defaultRange() const { return default_range_; }
+  void setDefaultRange(float range) { default_range_ = range; }
+  unsigned queryFlags() const { return query_flags_; }
+  void setQueryFlags(unsigned flags) { query_flags_ = flags | kQfGpuEvaluate; }
+  void setAxisScaling(float x, float y, float z)
+  {
+    axis_scaling_[0] = x;
+    axis_scaling_[1] = y;
+    axis_scaling_[2] = z;
+  }
+
+  size_t numberOfResults() const { return ranges_.size(); }
+  const Key *intersectedVoxels() const { return keys_.data(); }
+  const float *ranges() const { return ranges_.data(); }
+
+  /// Synchronous query (ohm/Query.h:93).  @return true on success.
+  bool execute()
+  {
+    reset();
+    if (!gpu_map_ || !gpu_map_->gpuOk() || !gpu_map_->syncConfig())
+    {
+      return false;
+    }
+    const double line[6] = { start_.x, start_.y, start_.z, end_.x, end_.y, end_.z };
+    const double dx = end_.x - start_.x, dy = end_.y - start_.y, dz = end_.z - start_.z;
+    const double len = std::sqrt(dx * dx + dy * dy + dz * dz);
+    const uint32_t max_keys = uint32_t(std::ceil(len / gpu_map_->map().resolution() * std::sqrt(3.0))) + 4u;
+    std::vector<unsigned char> records(size_t(max_keys) * 10u);
+    uint32_t count = 0;
+    if (ohmhip_map_line_keys(gpu_map_->handle(), line, 1, max_keys, records.data(), &count) != OHMHIP_OK)
+    {
+      return false;
+    }
+    const size_t n = std::min<size_t>(count, max_keys);
+    std::vector<float> ranges(n);
+    ohmhip_clearance_params p{};
+    p.search_radius = search_radius_;
+    for (int a = 0; a < 3; ++a)
+    {
+      p.axis_scaling[a] = axis_scaling_[a];
+    }
+    p.flags = query_flags_ & kQfUnknownAsOccupied;
+    if (n && ohmhip_map_clearance_keys(gpu_map_->handle(), records.data(), n, &p, ranges.data()) != OHMHIP_OK)
+    {
+      return false;
+    }
+    size_t n_regions = 0;
+    if (ohmhip_map_regions(gpu_map_->handle(), nullptr, 0, &n_regions) != OHMHIP_OK)
+    {
+      return false;
+    }
+    std::vector<std::array<int16_t, 3>> present(n_regions);
+    if (n_regions && ohmhip_map_regions(gpu_map_->handle(), present.front().data(), n_regions, &n_regions) != OHMHIP_OK)
+    {
+      return false;
+    }
+    std::sort(present.begin(), present.end());
+    keys_.resize(n);
+    ranges_.resize(n);
+    size_t closest_index = 0;
+    float closest = -1.0f;
+    for (size_t i = 0; i < n; ++i)
+    {
+      std::memcpy(keys_[i].region, records.data() + i * 10u, 6);
+      std::memcpy(keys_[i].local, records.data() + i * 10u + 6, 3);
+      const std::array<int16_t, 3> rk = { keys_[i].region[0], keys_[i].region[1], keys_[i].region[2] };
+      float range = ranges[i];
+      if (!std::binary_search(present.begin(), present.end(), rk) || range < 0)
+      {
+        range = default_range_;
+      }
+      ranges_[i] = range;
+      if (i == 0 || (range >= 0 && (range < closest || closest < 0)))
+      {
+        closest_index = i;
+        closest = range;
+      }
+    }
+    if ((query_flags_ & kQfNearestResult) && n)
+    {
+      keys_[0] = keys_[closest_index];
+      ranges_[0] = ranges_[closest_index];
+      keys_.resize(1);
+      ranges_.resize(1);
+    }
+    return true;
+  }
+  bool executeAsync() { return execute(); }
+  bool wait(unsigned /*timeout_ms*/ = ~0u) { return true; }
+  void reset()
+  {
+    keys_.clear();
+    ranges_.clear();
+  }
+
+private:
+  GpuMap *gpu_map_ = nullptr;
+  dvec3 start_, end_;
+  float search_radius_ = 0.0f;
+  float default_range_ = -1.0f;
+  float axis_scaling_[3] = { 1.0f, 1.0f, 1.0f };
+  unsigned query_flags_ = kQfGpuEvaluate;
+  std::vector<Key> keys_;
+  std::vector<float> ranges_;
+};
+
 /// Not in the reference (ohm is single device): the RCCL communicator the library owns (include/ohmhip.h, ohmhip_comm_*).
 /// Rank 0 makes the id (uniqueId) and the host program carries its 128 bytes to the other ranks over whatever it has
 /// (MPI, a socket, a file); every rank then constructs its communicator -- a collective call.

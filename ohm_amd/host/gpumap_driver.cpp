@@ -3,7 +3,8 @@
 // (tests/ohmtestgpu/GpuMapTest.cpp:68-205), syncs, and dumps every region layer for the Python parity test to check
 // against the CPU oracle.  Links libohmhip.so only; built with plain g++ (no hipcc, no glm).
 //
-//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|...> <resolution> <batch_rays> <rays.bin> <out.bin>
+//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|linequery|...> <resolution> <batch_rays>
+//                 <rays.bin> <out.bin> [search radius] [query flags]
 //   occdev: the sample points (odd entries) go through ohm::GpuTransformSamples with a static identity trajectory and
 //   are integrated straight from the device buffer (all rays then start at the origin).
 //   rays.bin: u64 n_points, then n_points * 3 doubles.  out.bin: u64 regions, per region i16[3] key, then per enabled
@@ -135,6 +136,94 @@ int main(int argc, char **argv)
       {
         std::fwrite(query.intersectedVoxels()[k].region, sizeof(int16_t), 3, out);
         std::fwrite(query.intersectedVoxels()[k].local, sizeof(uint8_t), 3, out);
+      }
+      std::fclose(out);
+      return 0;
+    }
+
+    if (mode == "clearance" || mode == "linequery")
+    {
+      // [argv 6: search radius (default 0.5), argv 7: query flags (default 0)]
+      // clearance: every ray builds the map; ohm::ClearanceProcess over the extents of all the rays' points.
+      //   out.bin = u64 regions, then per region i16[3] key and region voxels f32, in ascending key order.
+      // linequery: the last <batch_rays> rays are query lines, each an ohm::LineQueryGpu; the rays before them build
+      //   the map.  out.bin = u64 lines, then per line u32 results and per result i16[3] region, u8[3]
+      //   local, f32 range.
+      const float radius = argc > 6 ? float(std::atof(argv[6])) : 0.5f;
+      const unsigned flags = argc > 7 ? unsigned(std::strtoul(argv[7], nullptr, 0)) : 0u;
+      ohm::OccupancyMap query_map(resolution);
+      ohm::GpuMap query_gpu_map(&query_map, true);
+      const size_t query_points = mode == "clearance" ? 0 : std::min(2 * batch_rays, rays.size() & ~size_t(1));
+      const size_t build_points = (rays.size() & ~size_t(1)) - query_points;
+      if (build_points && query_gpu_map.integrateRays(rays.data(), build_points) != build_points)
+      {
+        return 8;
+      }
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      if (mode == "clearance")
+      {
+        ohm::dvec3 lo = rays[0], hi = rays[0];
+        for (size_t i = 1; i < build_points; ++i)
+        {
+          lo.x = std::min(lo.x, rays[i].x);
+          lo.y = std::min(lo.y, rays[i].y);
+          lo.z = std::min(lo.z, rays[i].z);
+          hi.x = std::max(hi.x, rays[i].x);
+          hi.y = std::max(hi.y, rays[i].y);
+          hi.z = std::max(hi.z, rays[i].z);
+        }
+        ohm::ClearanceProcess clearance(radius, flags | ohm::kQfGpuEvaluate);
+        if (!clearance.calculateForExtents(query_gpu_map, lo, hi))
+        {
+          std::fclose(out);
+          return 8;
+        }
+        size_t n = 0;
+        ohmhip_map_regions(query_gpu_map.handle(), nullptr, 0, &n);
+        std::vector<std::array<int16_t, 3>> keys(n);
+        if (n)
+        {
+          ohmhip_map_regions(query_gpu_map.handle(), keys.front().data(), n, &n);
+        }
+        std::sort(keys.begin(), keys.end());
+        const uint64_t count = keys.size();
+        std::fwrite(&count, sizeof(count), 1, out);
+        for (const auto &key : keys)
+        {
+          const float *block = clearance.regionClearance(key);
+          if (!block)
+          {
+            std::fclose(out);
+            return 8;
+          }
+          std::fwrite(key.data(), sizeof(int16_t), 3, out);
+          std::fwrite(block, sizeof(float), query_map.regionVoxelVolume(), out);
+        }
+        std::fclose(out);
+        return 0;
+      }
+      const uint64_t lines = (rays.size() - build_points) / 2;
+      std::fwrite(&lines, sizeof(lines), 1, out);
+      for (size_t i = build_points; i + 1 < rays.size(); i += 2)
+      {
+        ohm::LineQueryGpu query(query_gpu_map, rays[i], rays[i + 1], radius, flags);
+        if (!(query.queryFlags() & ohm::kQfGpuEvaluate) || !query.executeAsync() || !query.wait())
+        {
+          std::fclose(out);
+          return 8;
+        }
+        const uint32_t n = uint32_t(query.numberOfResults());
+        std::fwrite(&n, sizeof(n), 1, out);
+        for (uint32_t k = 0; k < n; ++k)
+        {
+          std::fwrite(query.intersectedVoxels()[k].region, sizeof(int16_t), 3, out);
+          std::fwrite(query.intersectedVoxels()[k].local, sizeof(uint8_t), 3, out);
+          std::fwrite(&query.ranges()[k], sizeof(float), 1, out);
+        }
       }
       std::fclose(out);
       return 0;
