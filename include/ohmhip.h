@@ -133,7 +133,8 @@ enum ohmhip_layer_id
   OHMHIP_LID_INTENSITY = 6,  /* IntensityMeanCov {float, float}          */
   OHMHIP_LID_HIT_MISS = 7,   /* HitMissCount {u32, u32}                  */
   OHMHIP_LID_TSDF = 8,       /* VoxelTsdf {float weight, float distance} ohm/VoxelTsdfCompute.h:20-24 */
-  OHMHIP_LID_COUNT = 9
+  OHMHIP_LID_CLEARANCE = 9,  /* float, clear -1; written by ohmhip_map_clearance_update* ohm/DefaultLayer.cpp:174-193 */
+  OHMHIP_LID_COUNT = 10
 };
 #define OHMHIP_LAYER_BIT(id) (1u << (id))
 
@@ -475,10 +476,11 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_rays_query_device(ohmhip_map_t map, const dou
  * The map is observed as ohmhip_map_rays_query observes it -- collected rays launched, an asynchronous launch settled,
  * resident tiles through the region hash, regions of the host store from their pinned records without re-admission,
  * tiled regions in the caller's region coordinates -- and nothing of it changes: voxels, dirty set, residency, use
- * stamps, ohmhip_map_cache_stats.  No clearance layer is kept: results go to the caller's memory, as the reference's
- * RoiRangeFill::finishRegion downloads each region's block.  OHMHIP_ERR_UNSUPPORTED for a map without the occupancy
- * layer, a map with region ownership or a partition, and h > 127; OHMHIP_ERR_INVALID_ARG, before any device work, for
- * null arrays, a negative or non-finite search_radius and a zero or non-finite axis_scaling component. */
+ * stamps, ohmhip_map_cache_stats.  Results go to the caller's memory, as the reference's RoiRangeFill::finishRegion
+ * downloads each region's block (ohmhip_map_clearance_update below keeps the map's own clearance layer).
+ * OHMHIP_ERR_UNSUPPORTED for a map without the occupancy layer, a map with region ownership or a partition, and h > 127;
+ * OHMHIP_ERR_INVALID_ARG, before any device work, for null arrays, a negative or non-finite search_radius and a zero or
+ * non-finite axis_scaling component. */
 #define OHMHIP_QF_UNKNOWN_AS_OCCUPIED (1u << 0) /* ohm::kQfUnknownAsOccupied (ohm/QueryFlag.h:38) */
 #define OHMHIP_QF_REPORT_UNSCALED (1u << 4)     /* ohm::kQfReportUnscaledResults (:50); other QueryFlag bits ignored */
 typedef struct ohmhip_clearance_params
@@ -502,6 +504,34 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_clearance_regions_device(ohmhip_map_t map, co
  * synchronous. */
 int ohmhip_map_clearance_keys(ohmhip_map_t map, const void *keys, size_t count, const ohmhip_clearance_params *params,
                               float *out);
+
+/* The clearance layer (OHMHIP_LID_CLEARANCE: a map gets it only with OHMHIP_LAYER_BIT(9) at ohmhip_map_create; float,
+ * cleared to -1; integration never writes it) kept current, as ClearanceProcess::update keeps it in the reference
+ * (ohmgpu/ClearanceProcess.cpp:418-470, 519-623).  Values are those of ohmhip_map_clearance_regions, bit for bit.
+ * h = ceil(search_radius / resolution); D_a = ceil(h / region_dim_a).  A region present in the map (resident or in the
+ * host store) is STALE for params when it was never written with them (new, last written with other parameters, or
+ * its clearance layer written by the host), or when the occupancy of a region within D_a of it on every axis (keys
+ * wrap in int16) changed, or such a region was removed (ohmhip_map_remove_regions), after it was last written.
+ * Occupancy changes: integrated batches, ohmhip_map_write_regions of the occupancy layer, ohmhip_map_mark_dirty and the
+ * replica merge -- conservatively: a batch that touches a region changes it.  Eviction and re-admission are not
+ * changes.  (The reference pads by one region, the same as D = 1 while h <= region_dim, and misses dependencies beyond;
+ * this does not.)  Stale regions are processed in ascending (z, y, x) signed key order.  The map is observed as the
+ * clearance queries observe it; an update re-admits and evicts nothing, changes no use stamp or cache counter, writes
+ * the new values of host-store regions into their records and gives each processed region the sync mark (not the merge
+ * mark).  Tiles of a tiled region that hold no data are not created: they keep reading -1.  OHMHIP_ERR_UNSUPPORTED as
+ * for the clearance queries, and for a map without the clearance layer; OHMHIP_ERR_INVALID_ARG, before any device
+ * work, for null arrays and the parameters ohmhip_map_clearance_regions refuses.  Host pointers; synchronous. */
+/* Stale regions for params, in processing order. *count = total; at most capacity written. */
+int ohmhip_map_clearance_stale_regions(ohmhip_map_t map, const ohmhip_clearance_params *params, int16_t *keys_xyz,
+                                       size_t capacity, size_t *count);
+/* ClearanceProcess::update: bring up to max_regions (0 = all) stale regions up to date, the first in processing order.
+ * processed / remaining (optional): regions written, stale regions left. */
+int ohmhip_map_clearance_update(ohmhip_map_t map, const ohmhip_clearance_params *params, size_t max_regions,
+                                size_t *processed, size_t *remaining);
+/* calculateForExtents / updateRegion(force): the listed regions present in the map (absent ones are skipped, never
+ * created); force = 0 skips up-to-date ones.  processed (optional): regions written. */
+int ohmhip_map_clearance_update_regions(ohmhip_map_t map, const int16_t *keys_xyz, size_t count,
+                                        const ohmhip_clearance_params *params, int force, size_t *processed);
 
 /* GpuTransformSamples::transform (ohmgpu/GpuTransformSamples.h:75-79, .cpp:97-210; kernel transformTimestampedPoints,
  * ohmgpu/gpu/TransformSamples.cl:94-228): sensor-frame samples with time stamps + a timestamped trajectory (translations

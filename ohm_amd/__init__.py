@@ -6,4 +6,5 @@ is the thin host-side mirror of the reference's interface used by the tests and 
 from ._lib import OhmHipError, LIB_PATH, EXPORTED_SYMBOLS  # noqa: F401
 from .gpumap import (GpuMap, GpuNdtMap, GpuTransformSamples, GpuTsdfMap, LineKeysQueryGpu, NdtMode, OccupancyMap, RayFlag,  # noqa: F401
                      OccupancyType, RaysQueryGpu, RayMapper, LAYERS, QueryFlag, ClearanceProcess, LineQueryGpu,
+                     MappingProcessResult, Mapper,
                      device_count, device_info, probability_to_value, value_to_probability)

@@ -32,7 +32,7 @@ ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_CAPACITY, ERR_UNSUPPORTED, ERR_NOT_FOUND, ER
 MERGE_SHARED_ONLY, MERGE_FULL_UNION = 0, 1
 
 (LID_OCCUPANCY, LID_MEAN, LID_COVARIANCE, LID_TRAVERSAL, LID_TOUCH_TIME, LID_INCIDENT, LID_INTENSITY, LID_HIT_MISS,
- LID_TSDF, LID_COUNT) = range(10)
+ LID_TSDF, LID_CLEARANCE, LID_COUNT) = range(11)
 MODE_OCCUPANCY, MODE_NDT_OM, MODE_NDT_TM, MODE_TSDF = range(4)
 FILTER_NONE, FILTER_GOOD, FILTER_CLIP = range(3)
 
@@ -154,6 +154,9 @@ _sigs = {
     "ohmhip_map_clearance_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
     "ohmhip_map_clearance_regions_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
     "ohmhip_map_clearance_keys": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
+    "ohmhip_map_clearance_stale_regions": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ohmhip_map_clearance_update": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "ohmhip_map_clearance_update_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_int, C.POINTER(C.c_size_t)]),
     "ohmhip_map_device_layer_ptr": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "ohmhip_map_region_slot": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "ohmhip_map_ensure_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

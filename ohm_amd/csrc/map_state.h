@@ -7,7 +7,14 @@
 
 namespace
 {
-const size_t kLayerBytes[OHMHIP_LID_COUNT] = { 4, 8, 24, 4, 4, 4, 8, 8, 8 };
+const size_t kLayerBytes[OHMHIP_LID_COUNT] = { 4, 8, 24, 4, 4, 4, 8, 8, 8, 4 };
+
+/// The 32-bit word a cleared voxel of layer l holds (ohm/DefaultLayer.cpp: occupancy +inf, clearance -1.0f), or 0 when
+/// the layer clears to zero bytes.
+inline uint32_t layerClearWord(int l)
+{
+  return (l == OHMHIP_LID_OCCUPANCY) ? 0x7f800000u : (l == OHMHIP_LID_CLEARANCE) ? 0xbf800000u : 0u;
+}
 
 struct DevBuf
 {
@@ -54,6 +61,7 @@ struct DevBuf
 constexpr uint32_t kTimingRing = 32;
 constexpr uint32_t kDirtySync = 1u;   ///< d_dirty bit: modified since the last syncVoxels() (ohmhip_map_clear_dirty)
 constexpr uint32_t kDirtyMerge = 2u;  ///< d_dirty bit: modified since the last replica merge (merge_impl.h)
+constexpr uint32_t kDirtyClearance = 4u;  ///< d_dirty bit: occupancy modified since the last clearance fold (clearance_update.h)
 
 /// A few host threads that stay around for the life of a map: staging a large host ray block into pinned memory is a
 /// memcpy one core cannot do at PCIe speed, and starting threads per call costs as much as the copy of a small batch.
@@ -235,6 +243,24 @@ struct ohmhip_map_s
     DevBuf spill_keys, spill_blocks;             ///< table of the host store's regions (spill to host)
     DevBuf clear_regions, clear_keys, clear_out, clear_mask;  ///< clearance queries (clearance_kernels.h)
   } query;
+  /// The clearance layer's bookkeeping (clearance_update.h), by the caller's region key -- so it needs no care when a
+  /// region changes slot, leaves the pool or comes back.  An update folds the kDirtyClearance bits into `changed` at a
+  /// new epoch; a region is up to date for parameter set P when it was written with P (`params`, 1 + index into
+  /// `param_sets`; 0: never, or its layer was written by the host) at an epoch no change in its neighbourhood exceeds.
+  /// Changes the host makes between updates (uploads, removals) take the epoch of the next fold.
+  struct ClearanceLayerState
+  {
+    struct Region
+    {
+      uint32_t changed = 0;  ///< epoch of the last occupancy change or removal
+      uint32_t written = 0;  ///< epoch the layer was last computed at
+      uint32_t params = 0;
+    };
+    std::unordered_map<uint64_t, Region> regions;
+    uint32_t epoch = 0;
+    std::vector<ohmhip_clearance_params> param_sets;
+    DevBuf table_keys, table_changed, present, written, stale;
+  } clearance_layer;
   uint32_t *d_event_count = nullptr;  ///< per parity: [0] deferred event count, [1] walk kernel chunk cursor, [2] replay group count, [3] stop iteration flag
   uint32_t walk_workgroups = 256;     ///< persistent walk workgroups: one per CU
   /// Regions / tiles of at most 4 096 voxels (16^3) are walked by the WalkHalf shape of k_region_walk: 512-thread workgroups with
@@ -364,6 +390,40 @@ struct ohmhip_map_s
   double wb_host_ms = 0;  ///< OHMHIP_DEBUG_FLAGS & 512: host time spent scheduling write-backs
   double spill_ms[6] = { 0, 0, 0, 0, 0, 0 };  ///< OHMHIP_DEBUG_FLAGS & 512: evict select / copy / compact, readmit copy, failed attempts, store growth
 };
+
+/// The caller's region key of a pool key (a tile key of a tiled map: tiling_impl.h).
+inline uint64_t callerRegionKey(const ohmhip_map_s *m, uint64_t key)
+{
+  if (m->mc.tile_split[1] <= 1 && m->mc.tile_split[2] <= 1)
+  {
+    return key;
+  }
+  int16_t k[3];
+  unpackRegionKey(key, k);
+  return packRegionKey(k[0], floorDiv(k[1], m->mc.tile_split[1]), floorDiv(k[2], m->mc.tile_split[2]));
+}
+
+/// The host changed the occupancy of (or removed) the region of pool key `key`: its neighbourhood's clearance is stale.
+inline void clearanceMarkChanged(ohmhip_map_s *m, uint64_t key)
+{
+  if (m->layers[OHMHIP_LID_CLEARANCE])
+  {
+    m->clearance_layer.regions[callerRegionKey(m, key)].changed = m->clearance_layer.epoch + 1u;
+  }
+}
+
+/// The host wrote the clearance layer of (or removed) the region of pool key `key`: it is no longer a computed result.
+inline void clearanceMarkUnwritten(ohmhip_map_s *m, uint64_t key)
+{
+  if (m->layers[OHMHIP_LID_CLEARANCE])
+  {
+    const auto it = m->clearance_layer.regions.find(callerRegionKey(m, key));
+    if (it != m->clearance_layer.regions.end())
+    {
+      it->second.params = 0;
+    }
+  }
+}
 
 // Background write-back of the spill path (writeback_impl.h).
 namespace

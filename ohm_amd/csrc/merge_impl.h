@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(256)
   if (threadIdx.x == 0)
   {
     // the merged tile differs from what the host last saw; it IS the new base
-    dirty[slots[blockIdx.x]] = (dirty[slots[blockIdx.x]] | kDirtySync) & ~kDirtyMerge;
+    dirty[slots[blockIdx.x]] = (dirty[slots[blockIdx.x]] | kDirtySync | kDirtyClearance) & ~kDirtyMerge;
   }
 }
 

@@ -1058,9 +1058,9 @@ __global__ void __launch_bounds__(1024)
       emit(s_big[q][0], s_big[q][1], s_big[q][2], cnt, nchk, per, c);
     }
   }
-  // "Modified" flags (bit 0: since the last syncVoxels(), bit 1: since the last replica merge): only by a batch the
-  // host is going to run -- one it rejects (pool / chunk list exhausted) is rolled back and must leave no trace here
-  // (the header promises a failing batch leaves the map as it was).
+  // "Modified" flags (bit 0: since the last syncVoxels(), bit 1: since the last replica merge, bit 2: since the last
+  // clearance fold): only by a batch the host is going to run -- one it rejects (pool / chunk list exhausted) is rolled
+  // back and must leave no trace here (the header promises a failing batch leaves the map as it was).
   if (!(bs.info->error & (kErrSlotsFull | kErrHashFull)) && *rt.n_slots <= rt.slot_capacity && s_chk_base <= chunk_capacity)
   {
     for (uint32_t i = tid; i < n; i += 1024)
@@ -1068,7 +1068,7 @@ __global__ void __launch_bounds__(1024)
       const uint32_t slot = rt.vals[bs.touched[i]];
       if (slot < rt.slot_capacity)
       {
-        bs.dirty[slot] |= 3u;
+        bs.dirty[slot] |= 7u;  // kDirtySync | kDirtyMerge | kDirtyClearance (map_state.h)
       }
     }
   }

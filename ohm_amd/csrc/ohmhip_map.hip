@@ -1033,7 +1033,8 @@ try
     OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * count, false, m->stream));
     OHMHIP_CHECK(hipMemcpyAsync(m->merge_slots.ptr, slots, sizeof(uint32_t) * count, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, m->stream, m->d_dirty,
-                       static_cast<const uint32_t *>(m->merge_slots.ptr), count, kDirtySync | kDirtyMerge);
+                       static_cast<const uint32_t *>(m->merge_slots.ptr), count,
+                       kDirtySync | kDirtyMerge | kDirtyClearance);
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   return hipGetLastError();
@@ -1529,6 +1530,7 @@ try
     releaseStoreRecord(m, entry.second.record);
   }
   m->spilled.clear();
+  m->clearance_layer.regions.clear();
   return allocPool(m, m->slot_capacity, 0);
 }
 OHMHIP_ABI_CATCH
@@ -1538,3 +1540,4 @@ OHMHIP_ABI_CATCH
 #include "merge_impl.h"
 #include "partition_impl.h"
 #include "tiling_impl.h"
+#include "clearance_update.h"

@@ -200,14 +200,15 @@ int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
       }
       char *tail = static_cast<char *>(new_layers[l]) + stride * keep;
       const size_t tail_bytes = stride * (capacity - keep);
-      if (l == OHMHIP_LID_OCCUPANCY)
+      if (layerClearWord(l) != 0u)
       {
-        // Occupancy clears to +inf == unobserved (ohm/DefaultLayer.cpp:87-91, ohm/VoxelOccupancy.h:42-45).
+        // Occupancy clears to +inf == unobserved (ohm/DefaultLayer.cpp:87-91, ohm/VoxelOccupancy.h:42-45), clearance
+        // to -1 (:174-193).
         const size_t count = tail_bytes / 4;
         if (count)
         {
-          hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(tail), 0x7f800000u,
-                             count);
+          hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(tail),
+                             layerClearWord(l), count);
         }
       }
       else if (tail_bytes)

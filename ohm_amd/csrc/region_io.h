@@ -432,6 +432,19 @@ try
     }
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   }
+  // (an occupancy upload makes the neighbourhood's clearance stale; a clearance upload makes the region's own)
+  for (size_t i = 0; i < count && (layer_id == OHMHIP_LID_OCCUPANCY || layer_id == OHMHIP_LID_CLEARANCE); ++i)
+  {
+    const uint64_t key = packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]);
+    if (layer_id == OHMHIP_LID_OCCUPANCY)
+    {
+      clearanceMarkChanged(m, key);
+    }
+    else
+    {
+      clearanceMarkUnwritten(m, key);
+    }
+  }
   return OHMHIP_OK;
 }
 OHMHIP_ABI_CATCH
@@ -510,6 +523,21 @@ try
   if (tiledBoundary(m))
   {
     return tiledRemoveRegions(m, keys_xyz, count, removed);
+  }
+  if (m->layers[OHMHIP_LID_CLEARANCE])
+  {
+    // (a removal makes the neighbourhood's clearance stale)
+    OHMHIP_CHECK(hipStreamSynchronize(m->stream));
+    OHMHIP_CHECK(refreshHostRegionTable(m));
+    for (size_t i = 0; i < count; ++i)
+    {
+      const uint64_t key = packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]);
+      if (m->region_slots.count(key) || m->spilled.count(key))
+      {
+        clearanceMarkChanged(m, key);
+        clearanceMarkUnwritten(m, key);
+      }
+    }
   }
   // Regions held in the host store (spill to host) are simply forgotten.
   size_t forgotten = 0;

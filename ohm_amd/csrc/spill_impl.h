@@ -101,9 +101,9 @@ static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t
     }
     const size_t stride = rv * kLayerBytes[l];
     char *tail = static_cast<char *>(m->layers[l]) + stride * new_n;
-    if (l == OHMHIP_LID_OCCUPANCY)
+    if (layerClearWord(l) != 0u)
     {
-      hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(tail), 0x7f800000u,
+      hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(tail), layerClearWord(l),
                          stride * k / 4);
     }
     else
@@ -397,7 +397,8 @@ int queueReadmission(ohmhip_map_t m, const std::vector<std::pair<uint32_t, ohmhi
   const size_t rv = size_t(m->mc.region_voxels);
   const ohmhip_map_s::HostStore &st = m->store;
   const bool keep_mask = m->config.mode != OHMHIP_MODE_OCCUPANCY;
-  std::vector<uint32_t> dirty_slots[4];
+  constexpr uint32_t kDirtyBits = kDirtySync | kDirtyMerge | kDirtyClearance;
+  std::vector<uint32_t> dirty_slots[kDirtyBits + 1];
   std::vector<uint32_t> use_pairs;  // (slot, stamp of the region's last use before it left the pool)
   use_pairs.reserve(back.size() * 2);
   std::vector<CopyJob> jobs;
@@ -433,7 +434,7 @@ int queueReadmission(ohmhip_map_t m, const std::vector<std::pair<uint32_t, ohmhi
       jobs.push_back(CopyJob{ record + st.mask_offset, reinterpret_cast<char *>(m->d_hit_mask) + st.mask_bytes * slot,
                               st.mask_bytes });
     }
-    dirty_slots[entry.second.dirty & (kDirtySync | kDirtyMerge)].push_back(slot);
+    dirty_slots[entry.second.dirty & kDirtyBits].push_back(slot);
   }
   OHMHIP_CHECK(launchCopyJobs(m, jobs, m->copy_stream));
   // The use history comes back with the content: the slot's "use before the gap" is the region's last use before it
@@ -443,12 +444,16 @@ int queueReadmission(ohmhip_map_t m, const std::vector<std::pair<uint32_t, ohmhi
   hipLaunchKernelGGL(k_set_prev_use, dim3(64), dim3(256), 0, m->copy_stream, m->d_last_use,
                      static_cast<const uint32_t *>(m->use_scratch.ptr), back.size());
   // (k_plan may be OR-ing this batch's bits into the same words: atomic ORs, from a persistent index scratch)
-  size_t n_index = dirty_slots[1].size() + dirty_slots[2].size() + dirty_slots[3].size();
+  size_t n_index = 0;
+  for (uint32_t bits = 1; bits <= kDirtyBits; ++bits)
+  {
+    n_index += dirty_slots[bits].size();
+  }
   if (n_index)
   {
     OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * n_index, false, m->copy_stream));
     uint32_t *d_index = static_cast<uint32_t *>(m->merge_slots.ptr);
-    for (uint32_t bits = 1; bits < 4; ++bits)
+    for (uint32_t bits = 1; bits <= kDirtyBits; ++bits)
     {
       if (dirty_slots[bits].empty())
       {

@@ -114,13 +114,13 @@ void regionsOfTiles(const MapConst &mc, const std::vector<int16_t> &tiles, std::
 
 void fillLayerClear(int layer_id, void *dst, size_t voxels)
 {
-  // ohm/DefaultLayer.cpp:87-91: occupancy clears to +inf, every other layer to zero bytes
-  if (layer_id == OHMHIP_LID_OCCUPANCY)
+  // ohm/DefaultLayer.cpp:87-91, 174-193: occupancy clears to +inf, clearance to -1, every other layer to zero bytes
+  if (layerClearWord(layer_id) != 0u)
   {
     uint32_t *p = static_cast<uint32_t *>(dst);
     for (size_t i = 0; i < voxels; ++i)
     {
-      p[i] = 0x7f800000u;
+      p[i] = layerClearWord(layer_id);
     }
   }
   else

@@ -15,6 +15,7 @@ The C++14 mirror of the same classes lives in ohm_amd/host/ (header-only, over t
 import ctypes as C
 import enum
 import math
+import time
 
 import numpy as np
 
@@ -52,6 +53,12 @@ class QueryFlag(enum.IntFlag):
     kQfNoCache = 1 << 3
     kQfReportUnscaledResults = 1 << 4
     kQfSpecialised = 1 << 16
+
+
+class MappingProcessResult(enum.IntEnum):
+    """ohm::MappingProcessResult (ohm/MappingProcess.h:18-24)."""
+    kMprUpToDate = 0
+    kMprProgressing = 1
 
 
 def _clearance_params(search_radius, flags, axis_scaling):
@@ -93,6 +100,7 @@ LAYERS = {
     "intensity": (L.LID_INTENSITY, np.float32, 2),
     "hit_miss_count": (L.LID_HIT_MISS, np.uint32, 2),
     "tsdf": (L.LID_TSDF, np.float32, 2),
+    "clearance": (L.LID_CLEARANCE, np.float32, 1),
 }
 
 
@@ -220,6 +228,7 @@ class GpuMap(RayMapper):
         for name in map_.layers:
             layer_bits |= 1 << LAYERS[name][0]
         cfg.layers = layer_bits
+        self._layer_bits = layer_bits
         cfg.mode = self._mode
         self._fill_map_values(cfg)
         cfg.gpu_mem_size = int(gpu_mem_size)
@@ -679,6 +688,48 @@ class GpuMap(RayMapper):
                                                 out.ctypes.data), "clearanceKeys")
         return out
 
+    def hasLayer(self, name):
+        """Whether the device map was created with layer `name` (LAYERS)."""
+        return bool(self._layer_bits & (1 << LAYERS[name][0]))
+
+    def clearanceStaleRegions(self, search_radius, flags=0, axis_scaling=(1.0, 1.0, 1.0)):
+        """The regions whose clearance layer is stale for these parameters, (N, 3) int16 in processing order
+        (ascending z, y, x): ohmhip_map_clearance_stale_regions."""
+        self._push_config_if_changed()
+        params = _clearance_params(search_radius, flags, axis_scaling)
+        n = C.c_size_t(0)
+        L.check(L.lib.ohmhip_map_clearance_stale_regions(self._handle, C.byref(params), None, 0, C.byref(n)),
+                "clearanceStaleRegions")
+        keys = np.zeros((n.value, 3), dtype=np.int16)
+        if n.value:
+            L.check(L.lib.ohmhip_map_clearance_stale_regions(self._handle, C.byref(params), keys.ctypes.data, n.value,
+                                                             C.byref(n)), "clearanceStaleRegions")
+        return keys[:n.value]
+
+    def clearanceUpdate(self, search_radius, flags=0, axis_scaling=(1.0, 1.0, 1.0), max_regions=0):
+        """Bring up to max_regions (0: all) stale regions' clearance layer up to date (ohmhip_map_clearance_update).
+        Returns (processed, remaining)."""
+        self._push_config_if_changed()
+        processed, remaining = C.c_size_t(0), C.c_size_t(0)
+        L.check(L.lib.ohmhip_map_clearance_update(self._handle, C.byref(_clearance_params(search_radius, flags,
+                                                                                          axis_scaling)),
+                                                  int(max_regions), C.byref(processed), C.byref(remaining)),
+                "clearanceUpdate")
+        return int(processed.value), int(remaining.value)
+
+    def clearanceUpdateRegions(self, keys, search_radius, flags=0, axis_scaling=(1.0, 1.0, 1.0), force=True):
+        """Write the clearance layer of the listed regions that are present in the map -- all of them with force, the
+        stale ones otherwise (ohmhip_map_clearance_update_regions).  Returns how many were written."""
+        self._push_config_if_changed()
+        keys = np.ascontiguousarray(keys, dtype=np.int16).reshape(-1, 3)
+        processed = C.c_size_t(0)
+        L.check(L.lib.ohmhip_map_clearance_update_regions(self._handle, keys.ctypes.data, keys.shape[0],
+                                                          C.byref(_clearance_params(search_radius, flags,
+                                                                                    axis_scaling)),
+                                                          1 if force else 0, C.byref(processed)),
+                "clearanceUpdateRegions")
+        return int(processed.value)
+
     def raysQueryDevice(self, d_rays, element_count, d_ranges, d_volumes, d_types, d_keys=None,
                         volume_coefficient=1.0, sync=True):
         """raysQuery on device memory (ohmhip_map_rays_query_device), for rays already in HBM: raw device pointers
@@ -1043,8 +1094,10 @@ class ClearanceProcess:
     """ohm::ClearanceProcess (ohmgpu/ClearanceProcess.h): the clearance of every voxel of a set of regions -- the distance
     to the nearest obstructing voxel within the search radius, per calculateNearestNeighbour (ohm/private/
     VoxelAlgorithms.cpp:22-98) -- evaluated exactly on the device (GpuMap.clearanceRegions), not by the reference's
-    approximate flood fill.  The results are kept here per region (there is no clearance layer in the device map).
-    Not provided: update() (the incremental dirty-region pass), stamp-based skipping (force=False recomputes) and
+    approximate flood fill.  The results of calculateForExtents are kept here per region.  On a map created with the
+    clearance layer (ensureClearanceLayer before the GpuMap is made) the process also keeps that layer current:
+    update() recomputes the regions whose neighbourhood changed since they were last written (ohmhip_map_clearance_update),
+    and calculateForExtents writes the layer too, skipping up-to-date regions unless forced.  Not provided:
     serialisation."""
 
     kQfInstantiateUnknown = int(QueryFlag.kQfSpecialised) << 0  # ohmgpu/ClearanceProcess.h
@@ -1077,10 +1130,37 @@ class ClearanceProcess:
     def reset(self):
         self._results = {}
 
+    @staticmethod
+    def ensureClearanceLayer(map_):
+        """ClearanceProcess::ensureClearanceLayer (ohm/DefaultLayer.cpp:174-193): add the clearance layer (float,
+        cleared to -1) to an OccupancyMap before its GpuMap is created.  A live GpuMap cannot gain a layer: given one
+        without it, this raises."""
+        if isinstance(map_, GpuMap):
+            if not map_.hasLayer("clearance"):
+                raise RuntimeError("ensureClearanceLayer: the device map was created without the clearance layer; "
+                                   "add it to the OccupancyMap before creating the GpuMap")
+            return
+        map_.addLayer("clearance")
+
+    def update(self, gpu_map, time_slice=0.0, max_regions=0):
+        """ClearanceProcess::update (ohmgpu/ClearanceProcess.cpp:418-470): recompute the clearance layer of stale
+        regions, in ascending (z, y, x) key order, max_regions (0: all) per device call -- until time_slice seconds have
+        passed, or until nothing is stale when time_slice <= 0.  Returns a MappingProcessResult."""
+        self.ensureClearanceLayer(gpu_map)
+        start = time.perf_counter()
+        while True:
+            _, remaining = gpu_map.clearanceUpdate(self._search_radius, self._query_flags, self._axis_scaling,
+                                                   max_regions)
+            if remaining == 0:
+                return MappingProcessResult.kMprUpToDate
+            if time_slice > 0 and time.perf_counter() - start >= time_slice:
+                return MappingProcessResult.kMprProgressing
+
     def calculateForExtents(self, gpu_map, min_extents, max_extents, force=True):
         """ClearanceProcess::calculateForExtents (ohmgpu/ClearanceProcess.cpp:474-510): every region from
         regionKey(min_extents) to regionKey(max_extents) that exists in the map -- every one with kQfInstantiateUnknown,
-        without creating it on the device.  force=False recomputes too (no stamps).  Returns the regions computed."""
+        without creating it on the device.  Returns the regions computed.  With the clearance layer, the layer of the
+        regions present in the map is written as well: every one with force, the stale ones otherwise."""
         m = gpu_map.map()
         rdim = [m.region_voxel_dimensions[i] * m.resolution for i in range(3)]
         lo = [_region_coord(min_extents[i], m.origin[i], rdim[i]) for i in range(3)]
@@ -1098,6 +1178,9 @@ class ClearanceProcess:
                                            self._axis_scaling)
             for key, block in zip(keys, out):
                 self._results[key] = block
+            if gpu_map.hasLayer("clearance"):
+                gpu_map.clearanceUpdateRegions(np.array(keys, dtype=np.int16), self._search_radius, self._query_flags,
+                                               self._axis_scaling, force=force)
         return keys
 
     def regionClearance(self, region_key):
@@ -1111,6 +1194,44 @@ class ClearanceProcess:
         if block is None:
             return None
         return float(block[int(local_key[2]), int(local_key[1]), int(local_key[0])])
+
+
+class Mapper:
+    """ohm::Mapper (ohm/Mapper.h): runs its mapping processes (a ClearanceProcess) over one GpuMap between
+    integrateRays batches."""
+
+    def __init__(self, gpu_map=None):
+        self._map = gpu_map
+        self._processes = []
+
+    def setMap(self, gpu_map):
+        self._map = gpu_map
+
+    def map(self):
+        return self._map
+
+    def addProcess(self, process):
+        self._processes.append(process)
+
+    def processes(self):
+        return list(self._processes)
+
+    def update(self, time_slice=0.0, max_regions=0):
+        """Mapper::update: each process in turn shares time_slice seconds (<= 0: run each until it is up to date).
+        Returns kMprUpToDate when every process is."""
+        start = time.perf_counter()
+        result = MappingProcessResult.kMprUpToDate
+        if self._map is None:
+            return result
+        for process in self._processes:
+            left = 0.0
+            if time_slice > 0:
+                left = time_slice - (time.perf_counter() - start)
+                if left <= 0:
+                    return MappingProcessResult.kMprProgressing
+            if process.update(self._map, left, max_regions) != MappingProcessResult.kMprUpToDate:
+                result = MappingProcessResult.kMprProgressing
+        return result
 
 
 class LineQueryGpu:

@@ -19,11 +19,13 @@
 
 #include <algorithm>
 #include <array>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -1278,6 +1280,13 @@ constexpr unsigned kQfSpecialised = 1u << 16u;
 /// VoxelAlgorithms.cpp:22-98), evaluated exactly on the device (ohmhip_map_clearance_regions), not by the reference's
 /// approximate flood fill.  Results are kept here per region: the device map has no clearance layer.  Not provided:
 /// update() (incremental dirty-region processing), stamp-based skipping (force = false recomputes), serialisation.
+/// ohm::MappingProcessResult (ohm/MappingProcess.h:18-24).
+enum MappingProcessResult : int
+{
+  kMprUpToDate = 0,
+  kMprProgressing = 1
+};
+
 class ClearanceProcess
 {
 public:
@@ -1306,12 +1315,48 @@ public:
   }
   void reset() { results_.clear(); }
 
+  /// ClearanceProcess::ensureClearanceLayer (ohm/DefaultLayer.cpp:174-193): add the clearance layer to the map before
+  /// its GpuMap is created (a live device map cannot gain a layer).
+  static void ensureClearanceLayer(OccupancyMap &map) { map.addLayer(OHMHIP_LID_CLEARANCE); }
+
+  /// ClearanceProcess::update (ohmgpu/ClearanceProcess.cpp:418-470): recompute the clearance layer of stale regions in
+  /// ascending (z, y, x) key order, max_regions (0: all) per device call, until time_slice seconds have passed or --
+  /// time_slice <= 0 -- nothing is stale (ohmhip_map_clearance_update).
+  /// @return kMprUpToDate / kMprProgressing, or a negative OHMHIP_ERR_* status.
+  int update(GpuMap &gpu_map, double time_slice = 0.0, size_t max_regions = 0)
+  {
+    if (!gpu_map.gpuOk() || !gpu_map.syncConfig())
+    {
+      return OHMHIP_ERR_INVALID_ARG;
+    }
+    const auto start = std::chrono::steady_clock::now();
+    for (;;)
+    {
+      size_t processed = 0, remaining = 0;
+      const int status = ohmhip_map_clearance_update(gpu_map.handle(), params(), max_regions, &processed, &remaining);
+      if (status != OHMHIP_OK)
+      {
+        return status;
+      }
+      if (remaining == 0)
+      {
+        return kMprUpToDate;
+      }
+      if (time_slice > 0 &&
+          std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count() >= time_slice)
+      {
+        return kMprProgressing;
+      }
+    }
+  }
+
   /// ClearanceProcess::calculateForExtents (ohmgpu/ClearanceProcess.cpp:474-510): the regions from regionKey(min) to
-  /// regionKey(max) that exist in the map, or all of them with kQfInstantiateUnknown (not created on the device).
+  /// regionKey(max) that exist in the map, or all of them with kQfInstantiateUnknown (not created on the device).  On a
+  /// map with the clearance layer, the layer of those present is written too: all of them with force, the stale ones
+  /// otherwise.
   /// @return false when the device refuses the query.
   bool calculateForExtents(GpuMap &gpu_map, const dvec3 &min_extents, const dvec3 &max_extents, bool force = true)
   {
-    (void)force;  // no stamps: every call recomputes
     if (!gpu_map.gpuOk() || !gpu_map.syncConfig())
     {
       return false;
@@ -1372,6 +1417,12 @@ public:
     {
       results_[RegionKey{ keys[3 * i], keys[3 * i + 1], keys[3 * i + 2] }] = std::move(blocks[i]);
     }
+    if (m.hasLayer(OHMHIP_LID_CLEARANCE) &&
+        ohmhip_map_clearance_update_regions(gpu_map.handle(), keys.data(), count, params(), force ? 1 : 0, nullptr) !=
+          OHMHIP_OK)
+    {
+      return false;
+    }
     return true;
   }
 
@@ -1418,6 +1469,55 @@ private:
 /// (-1), reports defaultRange(); only kQfUnknownAsOccupied is passed to the clearance.  kQfNearestResult keeps the
 /// first voxel, then any later one with range >= 0 && (range < closest || closest < 0) -- the GPU query's rule; the CPU
 /// LineQuery compares range * range < closest (ohm/LineQuery.cpp:75-84) and is not followed.
+/// ohm::Mapper (ohm/Mapper.h): runs its processes (ClearanceProcess) over one GpuMap between integrateRays batches.
+class Mapper
+{
+public:
+  explicit Mapper(GpuMap *gpu_map = nullptr)
+    : map_(gpu_map)
+  {}
+  void setMap(GpuMap *gpu_map) { map_ = gpu_map; }
+  GpuMap *map() const { return map_; }
+  /// Takes ownership, as the reference's Mapper does.
+  void addProcess(ClearanceProcess *process) { processes_.emplace_back(process); }
+  size_t processCount() const { return processes_.size(); }
+
+  /// Mapper::update: each process in turn shares time_slice seconds (<= 0: each runs until it is up to date).
+  /// @return kMprUpToDate when every process is, kMprProgressing, or a negative OHMHIP_ERR_* status.
+  int update(double time_slice = 0.0, size_t max_regions = 0)
+  {
+    if (!map_)
+    {
+      return kMprUpToDate;
+    }
+    const auto start = std::chrono::steady_clock::now();
+    int result = kMprUpToDate;
+    for (auto &process : processes_)
+    {
+      double left = 0.0;
+      if (time_slice > 0)
+      {
+        left = time_slice - std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        if (left <= 0)
+        {
+          return kMprProgressing;
+        }
+      }
+      const int status = process->update(*map_, left, max_regions);
+      if (status < 0)
+      {
+        return status;
+      }
+      result = (status == kMprUpToDate) ? result : int(kMprProgressing);
+    }
+    return result;
+  }
+
+private:
+  GpuMap *map_;
+  std::vector<std::unique_ptr<ClearanceProcess>> processes_;
+};
+
 class LineQueryGpu
 {
 public:

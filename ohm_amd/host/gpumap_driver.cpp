@@ -3,7 +3,7 @@
 // (tests/ohmtestgpu/GpuMapTest.cpp:68-205), syncs, and dumps every region layer for the Python parity test to check
 // against the CPU oracle.  Links libohmhip.so only; built with plain g++ (no hipcc, no glm).
 //
-//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|linequery|...> <resolution> <batch_rays>
+//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|...> <resolution> <batch_rays>
 //                 <rays.bin> <out.bin> [search radius] [query flags]
 //   occdev: the sample points (odd entries) go through ohm::GpuTransformSamples with a static identity trajectory and
 //   are integrated straight from the device buffer (all rays then start at the origin).
@@ -136,6 +136,60 @@ int main(int argc, char **argv)
       {
         std::fwrite(query.intersectedVoxels()[k].region, sizeof(int16_t), 3, out);
         std::fwrite(query.intersectedVoxels()[k].local, sizeof(uint8_t), 3, out);
+      }
+      std::fclose(out);
+      return 0;
+    }
+
+    if (mode == "clearanceupdate")
+    {
+      // [argv 6: search radius, argv 7: query flags, argv 8: region budget of the updates between batches (default 2),
+      //  argv 9: region dimension (default 32)]
+      // ohm::Mapper with an ohm::ClearanceProcess: batches of <batch_rays> rays, a budgeted update after each, a full
+      // update at the end.  out.bin = u64 regions, then per region i16[3] key and the clearance layer (region voxels
+      // f32), in ascending key order.
+      const float radius = argc > 6 ? float(std::atof(argv[6])) : 0.5f;
+      const unsigned flags = argc > 7 ? unsigned(std::strtoul(argv[7], nullptr, 0)) : 0u;
+      const size_t budget = argc > 8 ? size_t(std::atoll(argv[8])) : 2u;
+      const int dim = argc > 9 ? std::atoi(argv[9]) : 32;
+      ohm::OccupancyMap update_map(resolution, dim, dim, dim);
+      ohm::ClearanceProcess::ensureClearanceLayer(update_map);
+      ohm::GpuMap update_gpu_map(&update_map, true);
+      ohm::Mapper mapper(&update_gpu_map);
+      mapper.addProcess(new ohm::ClearanceProcess(radius, flags | ohm::kQfGpuEvaluate));
+      const size_t points = rays.size() & ~size_t(1);
+      const size_t step = std::max<size_t>(2, 2 * batch_rays);
+      for (size_t i = 0; i < points; i += step)
+      {
+        const size_t n = std::min(step, points - i);
+        if (update_gpu_map.integrateRays(rays.data() + i, n) != n || mapper.update(1e-9, budget) < 0)
+        {
+          return 8;
+        }
+      }
+      if (mapper.update(0.0) != ohm::kMprUpToDate)
+      {
+        return 8;
+      }
+      update_gpu_map.syncVoxels();
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      std::vector<std::array<int16_t, 3>> keys;
+      for (const auto &entry : update_map.chunks())
+      {
+        keys.push_back(entry.second.region);
+      }
+      std::sort(keys.begin(), keys.end());
+      const uint64_t count = keys.size();
+      std::fwrite(&count, sizeof(count), 1, out);
+      for (const auto &key : keys)
+      {
+        const auto &block = update_map.chunks().find(key)->second.voxel_blocks[OHMHIP_LID_CLEARANCE];
+        std::fwrite(key.data(), sizeof(int16_t), 3, out);
+        std::fwrite(block.data(), 1, block.size(), out);
       }
       std::fclose(out);
       return 0;
