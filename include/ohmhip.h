@@ -533,6 +533,105 @@ int ohmhip_map_clearance_update(ohmhip_map_t map, const ohmhip_clearance_params 
 int ohmhip_map_clearance_update_regions(ohmhip_map_t map, const int16_t *keys_xyz, size_t count,
                                         const ohmhip_clearance_params *params, int force, size_t *processed);
 
+/* HEIGHTMAP.  The planar heightmap of ohm::Heightmap::buildHeightmap (ohmheightmap/Heightmap.cpp:335-412, HeightmapMode::
+ * kPlanar, the class default: private/HeightmapDetail.h:68) computed on the device against the resident map, equal to
+ * the CPU algorithm as written for every cell and every field.  The reference is CPU only.  In its order:
+ *  1 EXTENTS (Heightmap.cpp:349-365).  calculateExtents of the source map (ohm/OccupancyMap.cpp:397-459): over the regions
+ *    present -- resident or in the host store -- region.centre -+ 0.5 * regionSpatialResolution per axis in fp64, where
+ *    region.centre = coord * regionSpatialResolution WITHOUT the map origin (ohm/MapRegion.cpp:32-43); an axis with
+ *    cull_max - cull_min > 0 takes the cull box's min / max instead; min_ext_key / max_ext_key = voxelKey(min / max).
+ *    The upper corner of the last region is a point of the next region: the walked range is one voxel wider than the
+ *    data.  An empty map (or a null extents / reference key) builds nothing: *populated = 0, the arrays untouched.
+ *  2 WALK (PlaneWalker.cpp:24-52).  (a, b, up) = heightmapAxisIndices(up_axis) (HeightmapUtil.cpp:86-116: X up (1, 2, 0),
+ *    Y up (0, 2, 1), Z up (0, 1, 2); the negative axes the same indices with up = -e).  The plane is voxelKey(
+ *    reference_pos)'s up coordinate clamped into [min_ext_key, max_ext_key].  Columns are visited with a innermost: the
+ *    WALK INDEX of a column is ib * na + ia.
+ *  3 SUPPORTING VOXEL (private/HeightmapOperations.cpp:186-419).  findNearestSupportingVoxel with kIgnoreVirtualAbove, plus
+ *    kVirtualSurfaces / kPromoteVirtualBelow from the flags, never kBiasAbove; voxel_floor / voxel_ceiling =
+ *    pointToRegionCoord(floor / ceiling, resolution) (0: unlimited); clearance_voxel_count_permissive = max(1,
+ *    pointToRegionCoord(min_clearance, resolution) - 1).  findNearestSupportingVoxel2 as written: vertical_range =
+ *    rangeBetween(seed, limit)[up] + 1, the step direction from ITS sign, the limit applied, then ++vertical_range for
+ *    the downward search only; offsets 0 (up) / 1 (down) at i = 0 and i + 1 after; the upward search reads the seed only
+ *    for last_unobserved and starts one voxel on; a voxel of a region that does not exist reads +inf and the walk then
+ *    leaves that region in one step (:321-328: to local 0 of the next region going up the key, to the last voxel of the
+ *    previous one going down), i advancing by as much; occupied is value >= threshold && value != +inf, free is value <
+ *    threshold; upward the first unobserved -> free transition records the unobserved voxel, downward every free ->
+ *    unobserved transition records the unobserved voxel (the last stands).  Then the selection ladder of :367-418.
+ *  4 GROUND (findGround, :422-512).  From the candidate in the direction of up while the key is within [min_ext_key,
+ *    max_ext_key] on the up axis; kNull (no region) and kUnobserved are both "unobserved" for the virtual transition and
+ *    neither sets observed_above; heights are fp64 dot(position, up), position = voxelCentreGlobal(key), plus
+ *    subVoxelToLocalCoord(mean.coord, resolution) for OCCUPIED voxels when the source has the mean layer and
+ *    OHMHIP_HM_IGNORE_VOXEL_MEAN is off (a never written coord of 0 decodes too: ohm/VoxelMeanCompute.h:112 tests a
+ *    constant); clearance test column_clearance_height - column_height >= min_clearance in fp64.  clearance and
+ *    observed_above are reported as they stand when the loop ends, also when it runs out of range.
+ *  5 CELL (Heightmap.cpp:619-671, addSurfaceVoxel :703-835).  ground_key = the ground found, else the walk key; its type is
+ *    forced to kNull when there was no candidate; a cell is written for kOccupied, and for kFree with virtual surfaces
+ *    on.  Position: the mean position for occupied, the centre for free.  src_height = dot(up, pos); pos[up] = 0; hm_key
+ *    = voxelKey(pos) IN THE HEIGHTMAP'S OWN GEOMETRY (grid_resolution, regions of region_size voxels with 1 on the up
+ *    axis, origin) with the up axis' region and local zeroed.  Occupancy +1.0f (surface) / -1.0f (virtual surface);
+ *    HeightmapVoxel (24 bytes, ohmheightmap/HeightmapVoxel.h:68-97): height = float(src_height - dot(voxelCentreGlobal(
+ *    hm_key), up)), clearance = float(ground clearance), normal 0, layer 0 (kHvlBaseLayer), flags = 1 (kHvfObservedAbove)
+ *    or 0, contributing_samples = min(mean.count, 0xffff) of the ground voxel -- free ones too -- when the source's mean
+ *    layer is in use, else 0; heightmap mean (when in use): coord = subVoxelCoord(pos - voxelCentreGlobal(hm_key),
+ *    grid_resolution), count = 1.
+ *  6 COLLISIONS.  Planar mode overwrites: of the source columns landing in one heightmap cell the one with the LARGEST
+ *    walk index stands.  *populated counts every write, overwritten or not; *cells the cells that hold a value.
+ * Results: the heightmap's three layers as dense mb x ma arrays (a fastest) over the cell range extents.first_cell ..:
+ * voxelKey of the heightmap for voxelCentreGlobal(min_ext_key) - resolution / 2 and voxelCentreGlobal(max_ext_key) +
+ * resolution / 2 on a and b.  Cells nobody wrote hold +inf / zeros, as a cleared chunk does.  source_column (optional):
+ * the walk index of the column that wrote the cell, 0xffffffff for none.
+ * NOT PROVIDED: the flood-fill modes (kSimpleFill, kLayeredFill*: their visiting order depends on earlier results) and
+ * with them the virtual-surface filter; blur, mesh, serialisation.  mode != 0: OHMHIP_ERR_UNSUPPORTED.  Surface normals
+ * from an NDT map's covariance are left 0: the reference derives them with an eigen solver chosen at compile time
+ * (Eigen, or 20 rounds of glm::qr_decompose, ohm/CovarianceVoxel.cpp:49-144), so there is no single answer to be
+ * exact against.
+ * The map is observed as the clearance queries observe it -- collected rays launched, an asynchronous launch settled,
+ * regions of the host store from their pinned records, tiled regions in the caller's coordinates -- and nothing of it
+ * changes.  OHMHIP_ERR_UNSUPPORTED also for a map without the occupancy layer and for a map with region ownership or a
+ * partition; OHMHIP_ERR_INVALID_ARG, before any device work, for null arrays, a non-finite or non-positive
+ * grid_resolution, negative or non-finite floor / ceiling / min_clearance and up_axis outside -3 .. 2;
+ * OHMHIP_ERR_CAPACITY when ma * mb or na * nb exceeds 2^31. */
+#define OHMHIP_HM_GENERATE_VIRTUAL_SURFACE (1u << 0) /* Heightmap::setGenerateVirtualSurface */
+#define OHMHIP_HM_PROMOTE_VIRTUAL_BELOW (1u << 1)    /* Heightmap::setPromoteVirtualBelow */
+#define OHMHIP_HM_IGNORE_VOXEL_MEAN (1u << 2)        /* Heightmap::setIgnoreVoxelMean */
+typedef struct ohmhip_heightmap_params
+{
+  double reference_pos[3];
+  double cull_min[3], cull_max[3]; /* an axis with max - min <= 0 is not culled */
+  double grid_resolution;          /* heightmap geometry */
+  double origin[3];
+  uint8_t region_size;             /* 0 = 128 (Heightmap::kDefaultRegionSize) */
+  int8_t up_axis;                  /* ohm::UpAxis: -3 (kNegZ) .. 2 (kZ) */
+  uint8_t mode;                    /* 0 = planar; others OHMHIP_ERR_UNSUPPORTED */
+  double floor, ceiling, min_clearance;
+  unsigned flags;                  /* OHMHIP_HM_* */
+} ohmhip_heightmap_params;
+typedef struct ohmhip_heightmap_extents
+{
+  int16_t min_region[3]; /* min_ext_key, 10-byte GpuKey layout */
+  uint8_t min_local[4];
+  int16_t max_region[3]; /* max_ext_key */
+  uint8_t max_local[4];
+  uint32_t na, nb;       /* source columns walked */
+  int16_t first_region[2]; /* first heightmap cell: region and local index on a and b */
+  uint8_t first_local[2];
+  uint8_t use_mean;      /* the heightmap carries a mean layer (source has one and it is not ignored) */
+  uint8_t populated;     /* 0: empty map, nothing to build (every count 0) */
+  uint32_t ma, mb;       /* cells of the dense result grid */
+} ohmhip_heightmap_extents;
+int ohmhip_map_heightmap_extents(ohmhip_map_t map, const ohmhip_heightmap_params *params,
+                                 ohmhip_heightmap_extents *extents);
+/* Builds the heightmap into host arrays of ma * mb cells (sizes from ohmhip_map_heightmap_extents of the same map state):
+ * occupancy float, voxels24 24-byte HeightmapVoxel, mean8 (nullable) VoxelMean {u32 coord, u32 count} -- zeros when the
+ * heightmap has no mean layer --, source_column (nullable).  Synchronous. */
+int ohmhip_map_heightmap(ohmhip_map_t map, const ohmhip_heightmap_params *params, float *occupancy, void *voxels24,
+                         void *mean8, uint32_t *source_column, uint64_t *populated, uint64_t *cells);
+/* The same into DEVICE arrays, enqueued on the map's stream; ohmhip_map_sync is the fence.  d_counts (nullable): two
+ * uint64 on the device, populated and cells. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_heightmap_device(ohmhip_map_t map, const ohmhip_heightmap_params *params,
+                                                    float *d_occupancy, void *d_voxels24, void *d_mean8,
+                                                    uint32_t *d_source_column, uint64_t *d_counts);
+
 /* GpuTransformSamples::transform (ohmgpu/GpuTransformSamples.h:75-79, .cpp:97-210; kernel transformTimestampedPoints,
  * ohmgpu/gpu/TransformSamples.cl:94-228): sensor-frame samples with time stamps + a timestamped trajectory (translations
  * xyz, rotations as quaternions x,y,z,w) -> world-frame ray pairs (sensor origin, sample), 6 doubles per valid sample,

@@ -8,3 +8,4 @@ from .gpumap import (GpuMap, GpuNdtMap, GpuTransformSamples, GpuTsdfMap, LineKey
                      OccupancyType, RaysQueryGpu, RayMapper, LAYERS, QueryFlag, ClearanceProcess, LineQueryGpu,
                      MappingProcessResult, Mapper,
                      device_count, device_info, probability_to_value, value_to_probability)
+from .heightmap import Heightmap, HeightmapMode, HeightmapVoxelType, UpAxis, HEIGHTMAP_VOXEL_DTYPE  # noqa: F401

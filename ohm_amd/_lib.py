@@ -48,6 +48,25 @@ class ClearanceParams(C.Structure):
     _fields_ = [("search_radius", C.c_float), ("axis_scaling", C.c_float * 3), ("flags", C.c_uint)]
 
 
+class HeightmapParams(C.Structure):
+    """ohmhip_heightmap_params"""
+    _fields_ = [("reference_pos", C.c_double * 3), ("cull_min", C.c_double * 3), ("cull_max", C.c_double * 3),
+                ("grid_resolution", C.c_double), ("origin", C.c_double * 3), ("region_size", C.c_uint8),
+                ("up_axis", C.c_int8), ("mode", C.c_uint8), ("floor", C.c_double), ("ceiling", C.c_double),
+                ("min_clearance", C.c_double), ("flags", C.c_uint)]
+
+
+class HeightmapExtents(C.Structure):
+    """ohmhip_heightmap_extents"""
+    _fields_ = [("min_region", C.c_int16 * 3), ("min_local", C.c_uint8 * 4), ("max_region", C.c_int16 * 3),
+                ("max_local", C.c_uint8 * 4), ("na", C.c_uint32), ("nb", C.c_uint32), ("first_region", C.c_int16 * 2),
+                ("first_local", C.c_uint8 * 2), ("use_mean", C.c_uint8), ("populated", C.c_uint8), ("ma", C.c_uint32),
+                ("mb", C.c_uint32)]
+
+
+HM_GENERATE_VIRTUAL_SURFACE, HM_PROMOTE_VIRTUAL_BELOW, HM_IGNORE_VOXEL_MEAN = 1, 2, 4
+
+
 class MapConfig(C.Structure):
     _fields_ = [("resolution", C.c_double), ("region_dim", C.c_int * 3), ("origin", C.c_double * 3),
                 ("layers", C.c_uint), ("mode", C.c_int), ("hit_value", C.c_float), ("miss_value", C.c_float),
@@ -157,6 +176,10 @@ _sigs = {
     "ohmhip_map_clearance_stale_regions": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ohmhip_map_clearance_update": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "ohmhip_map_clearance_update_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_int, C.POINTER(C.c_size_t)]),
+    "ohmhip_map_heightmap_extents": (C.c_int, [_vp, C.POINTER(HeightmapParams), C.POINTER(HeightmapExtents)]),
+    "ohmhip_map_heightmap": (C.c_int, [_vp, C.POINTER(HeightmapParams), _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]),
+    "ohmhip_map_heightmap_device": (C.c_int, [_vp, C.POINTER(HeightmapParams), _vp, _vp, _vp, _vp, _vp]),
     "ohmhip_map_device_layer_ptr": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "ohmhip_map_region_slot": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "ohmhip_map_ensure_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

@@ -1,0 +1,374 @@
+// heightmap_impl.h -- host side of the planar heightmap (heightmap_kernels.h): argument checks, rule 1 (extents) and
+// the dense result grid in fp64 on the host, then the two kernels on the map's stream.  Included at the end of
+// ohmhip_map.hip's translation unit.
+#ifndef OHMHIP_HEIGHTMAP_IMPL_H
+#define OHMHIP_HEIGHTMAP_IMPL_H
+
+namespace
+{
+/// ohm/MapCoord.h:85-93
+inline int hmHostRegionCoord(double coord, double resolution)
+{
+  const double v = std::floor(coord / resolution + 0.5);
+  return (v >= -2147483648.0 && v < 2147483648.0) ? int(v) : int(0x80000000u);
+}
+
+/// ohm/MapCoord.h:45-80
+inline int hmHostRegionVoxel(double coord, double voxel_resolution, double region_resolution)
+{
+  const double epsilon = double(1e-6f);
+  if (-epsilon <= coord && coord < 0)
+  {
+    coord = 0;
+  }
+  else if (coord >= region_resolution && coord - epsilon < region_resolution)
+  {
+    coord -= epsilon;
+  }
+  const double v = std::floor(coord / voxel_resolution);
+  return (v >= -2147483648.0 && v < 2147483648.0) ? int(v) : int(0x80000000u);
+}
+
+/// OccupancyMap::voxelKey (ohm/OccupancyMap.cpp:859-886 -> ohm/MapRegion.cpp:32-69) on the host: false for Key::kNull.
+inline bool hmHostVoxelKey(const MapConst &mc, const double p[3], int region[3], int local[3])
+{
+  bool ok = true;
+  for (int a = 0; a < 3; ++a)
+  {
+    const int coord = hmHostRegionCoord(p[a] - mc.origin[a], mc.region_dim[a]);
+    ok = ok && coord >= -32768 && coord <= 32767;
+    const double centre = coord * mc.region_dim[a];
+    const double region_min = centre - 0.5 * mc.region_dim[a];
+    const double pl = p[a] - mc.origin[a] - region_min;
+    const int q = hmHostRegionVoxel(pl, mc.resolution, mc.region_dim[a]);
+    ok = ok && 0 <= q && q < mc.kdim[a];
+    region[a] = coord;
+    local[a] = q;
+  }
+  return ok;
+}
+
+/// ohm/OccupancyMap.h:757-778 (one axis)
+inline double hmHostCentre(const MapConst &mc, int a, int region, int local)
+{
+  double v = double(float(region));
+  v *= mc.region_dim[a];
+  v -= 0.5 * mc.region_dim[a];
+  v += mc.origin[a];
+  v += double(local) * mc.resolution;
+  v += 0.5 * mc.resolution;
+  return v;
+}
+
+/// What every heightmap entry point checks before any device work.
+int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p)
+{
+  if (!p)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(p->grid_resolution) || !(p->grid_resolution > 0.0) || p->up_axis < -3 || p->up_axis > 2)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  for (const double v : { p->floor, p->ceiling, p->min_clearance })
+  {
+    if (!std::isfinite(v) || v < 0.0)
+    {
+      return OHMHIP_ERR_INVALID_ARG;
+    }
+  }
+  if (p->mode != 0)
+  {
+    return OHMHIP_ERR_UNSUPPORTED;  // the flood-fill modes
+  }
+  if (!m)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  if (!m->layers[OHMHIP_LID_OCCUPANCY])
+  {
+    return OHMHIP_ERR_UNSUPPORTED;
+  }
+  if (m->mc.owner_world > 1u || m->mc.owner_table)
+  {
+    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
+  }
+  return OHMHIP_OK;
+}
+
+/// Rules 1 and 2 and the dense grid, on the host in fp64: fills the geometry fields of `a` and `e`.  The map is settled
+/// by the caller.  e.populated == 0: nothing to build.
+int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, HeightmapArgs &a, ohmhip_heightmap_extents &e)
+{
+  std::memset(&e, 0, sizeof(e));
+  a = HeightmapArgs{};
+  const MapConst &mc = m->mc;
+  a.mc = mc;
+  const int up_axis = int(p->up_axis);
+  const int up = (up_axis >= 0) ? up_axis : -up_axis - 1;
+  a.up = up;
+  a.a = (up == 0) ? 1 : 0;
+  a.b = (up == 2) ? 1 : 2;
+  a.up_positive = up_axis >= 0;
+  a.use_mean = m->layers[OHMHIP_LID_MEAN] && !(p->flags & OHMHIP_HM_IGNORE_VOXEL_MEAN);
+  e.use_mean = uint8_t(a.use_mean);
+  a.generate_virtual = (p->flags & OHMHIP_HM_GENERATE_VIRTUAL_SURFACE) ? 1 : 0;
+  a.flags = (a.generate_virtual ? kHmVirtualSurfaces : 0u) |
+            ((p->flags & OHMHIP_HM_PROMOTE_VIRTUAL_BELOW) ? kHmPromoteVirtualBelow : 0u);
+  a.voxel_floor = hmHostRegionCoord(p->floor, mc.resolution);
+  a.voxel_ceiling = hmHostRegionCoord(p->ceiling, mc.resolution);
+  a.clearance_permissive = std::max(1, hmHostRegionCoord(p->min_clearance, mc.resolution) - 1);
+  a.min_clearance = p->min_clearance;
+
+  // rule 1: the regions present, in the caller's coordinates (resident and host store)
+  size_t n_regions = 0;
+  OHMHIP_CHECK(ohmhip_map_region_count(m, &n_regions));
+  if (n_regions == 0)
+  {
+    return OHMHIP_OK;
+  }
+  std::vector<int16_t> keys(3 * n_regions);
+  size_t listed = 0;
+  OHMHIP_CHECK(ohmhip_map_regions(m, keys.data(), n_regions, &listed));
+  n_regions = std::min(n_regions, listed);
+  double lo[3], hi[3];
+  for (int c = 0; c < 3; ++c)
+  {
+    lo[c] = std::numeric_limits<double>::max();
+    hi[c] = -std::numeric_limits<double>::max();
+  }
+  for (size_t i = 0; i < n_regions; ++i)
+  {
+    for (int c = 0; c < 3; ++c)
+    {
+      const double centre = int(keys[3 * i + c]) * mc.region_dim[c];  // MapRegion::centre: no origin
+      lo[c] = std::min(lo[c], centre - 0.5 * mc.region_dim[c]);
+      hi[c] = std::max(hi[c], centre + 0.5 * mc.region_dim[c]);
+    }
+  }
+  for (int c = 0; c < 3; ++c)
+  {
+    if (p->cull_max[c] - p->cull_min[c] > 0)
+    {
+      lo[c] = p->cull_min[c];
+      hi[c] = p->cull_max[c];
+    }
+  }
+  int rmin[3], lmin[3], rmax[3], lmax[3], rref[3], lref[3];
+  if (!hmHostVoxelKey(mc, lo, rmin, lmin) || !hmHostVoxelKey(mc, hi, rmax, lmax) ||
+      !hmHostVoxelKey(mc, p->reference_pos, rref, lref))
+  {
+    return OHMHIP_OK;  // a null key: the reference walks nothing
+  }
+  for (int c = 0; c < 3; ++c)
+  {
+    a.min_g[c] = rmin[c] * mc.kdim[c] + lmin[c];
+    a.max_g[c] = rmax[c] * mc.kdim[c] + lmax[c];
+    e.min_region[c] = int16_t(rmin[c]);
+    e.min_local[c] = uint8_t(lmin[c]);
+    e.max_region[c] = int16_t(rmax[c]);
+    e.max_local[c] = uint8_t(lmax[c]);
+  }
+  // rule 2
+  a.plane = std::min(std::max(rref[up] * mc.kdim[up] + lref[up], a.min_g[up]), a.max_g[up]);
+  const long long na = (long long)a.max_g[a.a] - a.min_g[a.a] + 1;
+  const long long nb = (long long)a.max_g[a.b] - a.min_g[a.b] + 1;
+  if (na <= 0 || nb <= 0)
+  {
+    return OHMHIP_OK;
+  }
+  if (na * nb > (1ll << 31))
+  {
+    return OHMHIP_ERR_CAPACITY;
+  }
+  // the heightmap's own geometry (Heightmap.cpp:124-142)
+  const int region_size = p->region_size ? int(p->region_size) : 128;
+  a.hm = MapConst{};
+  a.hm.resolution = p->grid_resolution;
+  for (int c = 0; c < 3; ++c)
+  {
+    a.hm.kdim[c] = a.hm.dim[c] = (c == up) ? 1 : region_size;
+    a.hm.region_dim[c] = a.hm.kdim[c] * p->grid_resolution;  // ohm/OccupancyMap.cpp:200-202
+    a.hm.origin[c] = p->origin[c];
+    a.hm.tile_split[c] = 1;
+  }
+  a.hm.region_voxels = a.hm.dim[0] * a.hm.dim[1] * a.hm.dim[2];
+  double c_lo[3], c_hi[3];
+  for (int c = 0; c < 3; ++c)
+  {
+    c_lo[c] = hmHostCentre(mc, c, rmin[c], lmin[c]) - 0.5 * mc.resolution;
+    c_hi[c] = hmHostCentre(mc, c, rmax[c], lmax[c]) + 0.5 * mc.resolution;
+  }
+  c_lo[up] = c_hi[up] = 0.0;
+  int hr0[3], hl0[3], hr1[3], hl1[3];
+  if (!hmHostVoxelKey(a.hm, c_lo, hr0, hl0) || !hmHostVoxelKey(a.hm, c_hi, hr1, hl1))
+  {
+    return OHMHIP_ERR_CAPACITY;  // the heightmap's keys cannot address the source's extents
+  }
+  a.cell0_a = hr0[a.a] * region_size + hl0[a.a];
+  a.cell0_b = hr0[a.b] * region_size + hl0[a.b];
+  const long long ma = (long long)(hr1[a.a] * region_size + hl1[a.a]) - a.cell0_a + 1;
+  const long long mb = (long long)(hr1[a.b] * region_size + hl1[a.b]) - a.cell0_b + 1;
+  if (ma <= 0 || mb <= 0 || ma * mb > (1ll << 31))
+  {
+    return OHMHIP_ERR_CAPACITY;
+  }
+  a.na = int(na);
+  a.nb = int(nb);
+  a.ma = int(ma);
+  a.mb = int(mb);
+  e.na = uint32_t(na);
+  e.nb = uint32_t(nb);
+  e.ma = uint32_t(ma);
+  e.mb = uint32_t(mb);
+  e.first_region[0] = int16_t(hr0[a.a]);
+  e.first_region[1] = int16_t(hr0[a.b]);
+  e.first_local[0] = uint8_t(hl0[a.a]);
+  e.first_local[1] = uint8_t(hl0[a.b]);
+  e.populated = 1;
+  return OHMHIP_OK;
+}
+
+/// The two kernels on the map's stream, results into device arrays.  d_counts: 4 uint64 of the query's own.
+int heightmapDevice(ohmhip_map_t m, HeightmapArgs &a, float *d_occ, void *d_vox, void *d_mean, uint32_t *d_col)
+{
+  hipStream_t s = m->stream;
+  ohmhip_map_s::QueryState &qs = m->query;
+  a.rt = regionTable(m);
+  a.occupancy = static_cast<const float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
+  a.mean = a.use_mean ? static_cast<const uint2 *>(m->layers[OHMHIP_LID_MEAN]) : nullptr;
+  a.spill_mean_delta =
+    (long long)(m->store.layer_offset[OHMHIP_LID_MEAN]) - (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
+  OHMHIP_CHECK(querySpillTable(m, a.spill));
+  const size_t columns = size_t(a.na) * size_t(a.nb);
+  const size_t cells = size_t(a.ma) * size_t(a.mb);
+  OHMHIP_CHECK(qs.hm_winner.ensure(sizeof(int) * cells, false, s));
+  OHMHIP_CHECK(qs.hm_rec_occ.ensure(sizeof(float) * columns, false, s));
+  OHMHIP_CHECK(qs.hm_rec_vox.ensure(sizeof(uint32_t) * kHmVoxelWords * columns, false, s));
+  OHMHIP_CHECK(qs.hm_rec_mean.ensure(sizeof(uint2) * columns, false, s));
+  OHMHIP_CHECK(qs.hm_counts.ensure(sizeof(unsigned long long) * 4, false, s));
+  a.winner = static_cast<int *>(qs.hm_winner.ptr);
+  a.rec_occ = static_cast<float *>(qs.hm_rec_occ.ptr);
+  a.rec_vox = static_cast<uint32_t *>(qs.hm_rec_vox.ptr);
+  a.rec_mean = static_cast<uint2 *>(qs.hm_rec_mean.ptr);
+  a.counts = static_cast<unsigned long long *>(qs.hm_counts.ptr);
+  const char *env = std::getenv("OHMHIP_HEIGHTMAP_COUNT");  // development: count the voxels inspected (counts[3])
+  a.count_inspected = (env && std::atoi(env) != 0) ? 1 : 0;
+  a.out_occ = d_occ;
+  a.out_vox = static_cast<uint32_t *>(d_vox);
+  a.out_mean = static_cast<uint2 *>(d_mean);
+  a.out_col = d_col;
+  OHMHIP_CHECK(hipMemsetAsync(a.winner, 0xff, sizeof(int) * cells, s));
+  OHMHIP_CHECK(hipMemsetAsync(a.counts, 0, sizeof(unsigned long long) * 4, s));
+  hipLaunchKernelGGL(k_heightmap_columns, dim3(uint32_t((a.na + 63) / 64), uint32_t((a.nb + 3) / 4)), dim3(256), 0, s,
+                     a);
+  OHMHIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_heightmap_cells, dim3(uint32_t((cells + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+}  // namespace
+
+extern "C" {
+
+int ohmhip_map_heightmap_extents(ohmhip_map_t m, const ohmhip_heightmap_params *params, ohmhip_heightmap_extents *extents)
+try
+{
+  if (!extents)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  OHMHIP_CHECK(heightmapRefusal(m, params));
+  OHMHIP_SETTLE(m);
+  HeightmapArgs a;
+  return heightmapGeometry(m, params, a, *extents);
+}
+OHMHIP_ABI_CATCH
+
+int ohmhip_map_heightmap(ohmhip_map_t m, const ohmhip_heightmap_params *params, float *occupancy, void *voxels24,
+                         void *mean8, uint32_t *source_column, uint64_t *populated, uint64_t *cells)
+try
+{
+  if (!occupancy || !voxels24 || !populated || !cells)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  OHMHIP_CHECK(heightmapRefusal(m, params));
+  OHMHIP_SETTLE(m);
+  HeightmapArgs a;
+  ohmhip_heightmap_extents e;
+  OHMHIP_CHECK(heightmapGeometry(m, params, a, e));
+  *populated = 0;
+  *cells = 0;
+  if (!e.populated)
+  {
+    return OHMHIP_OK;
+  }
+  hipStream_t s = m->stream;
+  ohmhip_map_s::QueryState &qs = m->query;
+  const size_t n = size_t(a.ma) * size_t(a.mb);
+  OHMHIP_CHECK(qs.hm_out_occ.ensure(sizeof(float) * n, false, s));
+  OHMHIP_CHECK(qs.hm_out_vox.ensure(24 * n, false, s));
+  if (mean8)
+  {
+    OHMHIP_CHECK(qs.hm_out_mean.ensure(8 * n, false, s));
+  }
+  if (source_column)
+  {
+    OHMHIP_CHECK(qs.hm_out_col.ensure(sizeof(uint32_t) * n, false, s));
+  }
+  OHMHIP_CHECK(heightmapDevice(m, a, static_cast<float *>(qs.hm_out_occ.ptr), qs.hm_out_vox.ptr,
+                               mean8 ? qs.hm_out_mean.ptr : nullptr,
+                               source_column ? static_cast<uint32_t *>(qs.hm_out_col.ptr) : nullptr));
+  OHMHIP_CHECK(hipMemcpyAsync(occupancy, qs.hm_out_occ.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+  OHMHIP_CHECK(hipMemcpyAsync(voxels24, qs.hm_out_vox.ptr, 24 * n, hipMemcpyDeviceToHost, s));
+  if (mean8)
+  {
+    OHMHIP_CHECK(hipMemcpyAsync(mean8, qs.hm_out_mean.ptr, 8 * n, hipMemcpyDeviceToHost, s));
+  }
+  if (source_column)
+  {
+    OHMHIP_CHECK(hipMemcpyAsync(source_column, qs.hm_out_col.ptr, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+  }
+  unsigned long long counts[4] = { 0, 0, 0, 0 };
+  OHMHIP_CHECK(hipMemcpyAsync(counts, a.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
+  OHMHIP_CHECK(hipStreamSynchronize(s));
+  *populated = counts[0];
+  *cells = counts[1];
+  if (a.count_inspected)
+  {
+    std::fprintf(stderr, "ohmhip heightmap: %llu voxels inspected, %d x %d columns\n", counts[3], a.na, a.nb);
+  }
+  return counts[2] ? OHMHIP_ERR_INTERNAL : OHMHIP_OK;  // (a column's cell outside the grid: cannot happen)
+}
+OHMHIP_ABI_CATCH
+
+int ohmhip_map_heightmap_device(ohmhip_map_t m, const ohmhip_heightmap_params *params, float *d_occupancy,
+                                void *d_voxels24, void *d_mean8, uint32_t *d_source_column, uint64_t *d_counts)
+try
+{
+  if (!d_occupancy || !d_voxels24)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  OHMHIP_CHECK(heightmapRefusal(m, params));
+  OHMHIP_SETTLE(m);
+  HeightmapArgs a;
+  ohmhip_heightmap_extents e;
+  OHMHIP_CHECK(heightmapGeometry(m, params, a, e));
+  if (!e.populated)
+  {
+    return d_counts ? int(hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), m->stream)) : OHMHIP_OK;
+  }
+  OHMHIP_CHECK(heightmapDevice(m, a, d_occupancy, d_voxels24, d_mean8, d_source_column));
+  if (d_counts)
+  {
+    OHMHIP_CHECK(hipMemcpyAsync(d_counts, a.counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice, m->stream));
+  }
+  return OHMHIP_OK;
+}
+OHMHIP_ABI_CATCH
+
+}  // extern "C"
+
+#endif  // OHMHIP_HEIGHTMAP_IMPL_H

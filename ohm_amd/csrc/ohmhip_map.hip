@@ -8,6 +8,7 @@
 #include "traversal_kernels.h"
 #include "query_kernels.h"
 #include "clearance_kernels.h"
+#include "heightmap_kernels.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -394,7 +395,9 @@ try
   m->stop_b.release();
   for (DevBuf *b : { &m->query.rays, &m->query.ranges, &m->query.volumes, &m->query.types, &m->query.keys,
                      &m->query.walked, &m->query.last_walked, &m->query.scan_temp, &m->query.cursor,
-                     &m->query.spill_keys, &m->query.spill_blocks })
+                     &m->query.spill_keys, &m->query.spill_blocks, &m->query.hm_winner, &m->query.hm_rec_occ,
+                     &m->query.hm_rec_vox, &m->query.hm_rec_mean, &m->query.hm_counts, &m->query.hm_out_occ,
+                     &m->query.hm_out_vox, &m->query.hm_out_mean, &m->query.hm_out_col })
   {
     b->release();
   }
@@ -1541,3 +1544,4 @@ OHMHIP_ABI_CATCH
 #include "partition_impl.h"
 #include "tiling_impl.h"
 #include "clearance_update.h"
+#include "heightmap_impl.h"

@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <string>
@@ -81,6 +82,8 @@ public:
     kClippedEnd = 2u
   };
   Aabb(const dvec3 &min_ext, const dvec3 &max_ext) : corners_{ min_ext, max_ext } {}
+  const dvec3 &minExtents() const { return corners_[0]; }
+  const dvec3 &maxExtents() const { return corners_[1]; }
   /// ohm/Aabb.h:301-312 with epsilon 0: closed box.
   bool contains(const dvec3 &p) const
   {
@@ -1776,6 +1779,259 @@ private:
   std::vector<uint32_t> send_counts_, recv_counts_;
   uint64_t recv_batch_[3] = { 0, 0, 0 };  ///< launch count of the batch reading each receive buffer (0: none)
   size_t rays_received_ = 0;
+  int last_status_ = OHMHIP_OK;
+};
+
+/// ohm::UpAxis (ohmheightmap/UpAxis.h)
+enum class UpAxis : int
+{
+  kNegZ = -3,
+  kNegY = -2,
+  kNegX = -1,
+  kX = 0,
+  kY = 1,
+  kZ = 2
+};
+
+/// ohm::HeightmapVoxelType (ohmheightmap/HeightmapVoxelType.h)
+enum class HeightmapVoxelType : uint8_t
+{
+  kUnknown = 0,
+  kVacant,
+  kSurface,
+  kVirtualSurface
+};
+
+/// ohm::HeightmapMode (ohmheightmap/HeightmapMode.h); only kPlanar is built on the device.
+enum class HeightmapMode : int
+{
+  kPlanar = 0,
+  kSimpleFill,
+  kLayeredFillUnordered,
+  kLayeredFill
+};
+
+/// ohm::HeightmapVoxel (ohmheightmap/HeightmapVoxel.h:68-97)
+struct alignas(8) HeightmapVoxel
+{
+  float height;
+  float clearance;
+  float normal_x, normal_y, normal_z;
+  uint8_t layer;
+  uint8_t flags;  ///< kHvfObservedAbove = 1
+  uint16_t contributing_samples;
+};
+static_assert(sizeof(HeightmapVoxel) == 24, "HeightmapVoxel is 24 bytes");
+
+/// ohm::VoxelMean (ohm/VoxelMean.h)
+struct VoxelMean
+{
+  uint32_t coord;
+  uint32_t count;
+};
+
+/// ohm::Heightmap (ohmheightmap/Heightmap.h) in planar mode, built on the device from the resident map of a GpuMap
+/// (ohmhip_map_heightmap: include/ohmhip.h, "HEIGHTMAP"), equal to the CPU algorithm for every cell and field.  Only the
+/// results cross to the host: the heightmap's layers as dense arrays of heightmapCellsA() x heightmapCellsB() cells, a
+/// fastest, over the cell range the source's extents cover (extents()).
+class Heightmap
+{
+public:
+  static constexpr unsigned kDefaultRegionSize = 128;
+
+  Heightmap(double grid_resolution, double min_clearance, UpAxis up_axis = UpAxis::kZ, unsigned region_size = 0)
+    : grid_resolution_(grid_resolution)
+    , min_clearance_(min_clearance)
+    , up_axis_(up_axis)
+    , region_size_(region_size ? region_size : kDefaultRegionSize)
+  {}
+
+  void setOccupancyMap(GpuMap *gpu_map) { gpu_map_ = gpu_map; }
+  GpuMap *occupancyMap() const { return gpu_map_; }
+
+  void setCeiling(double ceiling) { ceiling_ = ceiling; }
+  double ceiling() const { return ceiling_; }
+  void setFloor(double floor) { floor_ = floor; }
+  double floor() const { return floor_; }
+  void setMinClearance(double clearance) { min_clearance_ = clearance; }
+  double minClearance() const { return min_clearance_; }
+  void setIgnoreVoxelMean(bool ignore) { ignore_voxel_mean_ = ignore; }
+  bool ignoreVoxelMean() const { return ignore_voxel_mean_; }
+  void setGenerateVirtualSurface(bool enable) { generate_virtual_surface_ = enable; }
+  bool generateVirtualSurface() const { return generate_virtual_surface_; }
+  void setPromoteVirtualBelow(bool enable) { promote_virtual_below_ = enable; }
+  bool promoteVirtualBelow() const { return promote_virtual_below_; }
+  void setMode(HeightmapMode mode) { mode_ = mode; }
+  HeightmapMode mode() const { return mode_; }
+  /// The origin of the heightmap's own OccupancyMap (heightmap().setOrigin() in the reference).
+  void setHeightmapOrigin(const dvec3 &origin) { origin_ = origin; }
+  const dvec3 &heightmapOrigin() const { return origin_; }
+  double gridResolution() const { return grid_resolution_; }
+  UpAxis upAxis() const { return up_axis_; }
+  int upAxisIndex() const { return int(up_axis_) >= 0 ? int(up_axis_) : -int(up_axis_) - 1; }
+  /// heightmapAxisIndices (ohmheightmap/HeightmapUtil.cpp:86-116)
+  int surfaceAxisIndexA() const { return upAxisIndex() == 0 ? 1 : 0; }
+  int surfaceAxisIndexB() const { return upAxisIndex() == 2 ? 1 : 2; }
+  dvec3 upAxisNormal() const
+  {
+    double n[3] = { 0.0, 0.0, 0.0 };
+    n[upAxisIndex()] = int(up_axis_) >= 0 ? 1.0 : -1.0;
+    return dvec3{ n[0], n[1], n[2] };
+  }
+
+  /// Heightmap::buildHeightmap (ohmheightmap/Heightmap.cpp:335-412).  @return true when any cell was populated.
+  bool buildHeightmap(const dvec3 &reference_pos, const Aabb &cull_to = Aabb(dvec3{ 0, 0, 0 }, dvec3{ 0, 0, 0 }))
+  {
+    occupancy_.clear();
+    voxels_.clear();
+    mean_.clear();
+    populated_ = cells_ = 0;
+    extents_ = ohmhip_heightmap_extents{};
+    if (!gpu_map_ || !gpu_map_->gpuOk() || !gpu_map_->syncConfig())
+    {
+      return false;
+    }
+    ohmhip_heightmap_params p{};
+    const double ref[3] = { reference_pos.x, reference_pos.y, reference_pos.z };
+    const double lo[3] = { cull_to.minExtents().x, cull_to.minExtents().y, cull_to.minExtents().z };
+    const double hi[3] = { cull_to.maxExtents().x, cull_to.maxExtents().y, cull_to.maxExtents().z };
+    const double origin[3] = { origin_.x, origin_.y, origin_.z };
+    for (int i = 0; i < 3; ++i)
+    {
+      p.reference_pos[i] = ref[i];
+      p.cull_min[i] = lo[i];
+      p.cull_max[i] = hi[i];
+      p.origin[i] = origin[i];
+    }
+    p.grid_resolution = grid_resolution_;
+    p.region_size = uint8_t(region_size_ == kDefaultRegionSize ? 0 : region_size_);
+    p.up_axis = int8_t(up_axis_);
+    p.mode = uint8_t(mode_);
+    p.floor = floor_;
+    p.ceiling = ceiling_;
+    p.min_clearance = min_clearance_;
+    p.flags = (generate_virtual_surface_ ? OHMHIP_HM_GENERATE_VIRTUAL_SURFACE : 0u) |
+              (promote_virtual_below_ ? OHMHIP_HM_PROMOTE_VIRTUAL_BELOW : 0u) |
+              (ignore_voxel_mean_ ? OHMHIP_HM_IGNORE_VOXEL_MEAN : 0u);
+    last_status_ = ohmhip_map_heightmap_extents(gpu_map_->handle(), &p, &extents_);
+    if (last_status_ != OHMHIP_OK || !extents_.populated)
+    {
+      return false;
+    }
+    const size_t n = size_t(extents_.ma) * size_t(extents_.mb);
+    occupancy_.resize(n);
+    voxels_.resize(n);
+    if (extents_.use_mean)
+    {
+      mean_.resize(n);
+    }
+    uint64_t populated = 0, cells = 0;
+    last_status_ = ohmhip_map_heightmap(gpu_map_->handle(), &p, occupancy_.data(), voxels_.data(),
+                                        extents_.use_mean ? mean_.data() : nullptr, nullptr, &populated, &cells);
+    if (last_status_ != OHMHIP_OK)
+    {
+      occupancy_.clear();
+      voxels_.clear();
+      mean_.clear();
+      return false;
+    }
+    populated_ = populated;
+    cells_ = cells;
+    return populated != 0;
+  }
+
+  int lastStatus() const { return last_status_; }
+  const ohmhip_heightmap_extents &extents() const { return extents_; }
+  size_t heightmapCellsA() const { return extents_.ma; }
+  size_t heightmapCellsB() const { return extents_.mb; }
+  uint64_t populatedCount() const { return populated_; }
+  uint64_t cellCount() const { return cells_; }
+  /// Dense [cellsB][cellsA] layers: occupancy (+1 surface, -1 virtual surface, +inf nothing), HeightmapVoxel, VoxelMean
+  /// (empty when the heightmap has no mean layer).
+  const std::vector<float> &occupancy() const { return occupancy_; }
+  const std::vector<HeightmapVoxel> &heightmapVoxels() const { return voxels_; }
+  const std::vector<VoxelMean> &voxelMeans() const { return mean_; }
+
+  /// voxelCentreGlobal of the heightmap's own OccupancyMap (ohm/OccupancyMap.h:757-778).
+  dvec3 voxelCentreGlobal(const Key &key) const
+  {
+    const double origin[3] = { origin_.x, origin_.y, origin_.z };
+    double c[3];
+    for (int i = 0; i < 3; ++i)
+    {
+      const double region_dim = (i == upAxisIndex() ? 1.0 : double(region_size_)) * grid_resolution_;
+      double v = double(float(key.region[i]));
+      v *= region_dim;
+      v -= 0.5 * region_dim;
+      v += origin[i];
+      v += double(key.local[i]) * grid_resolution_;
+      v += 0.5 * grid_resolution_;
+      c[i] = v;
+    }
+    return dvec3{ c[0], c[1], c[2] };
+  }
+
+  /// Heightmap::getHeightmapVoxelInfo (ohmheightmap/Heightmap.cpp:415-461) for a key of the heightmap.
+  HeightmapVoxelType getHeightmapVoxelInfo(const Key &key, dvec3 *pos, HeightmapVoxel *voxel_info = nullptr) const
+  {
+    if (!extents_.populated || occupancy_.empty())
+    {
+      return HeightmapVoxelType::kUnknown;
+    }
+    const int a = surfaceAxisIndexA(), b = surfaceAxisIndexB();
+    const long ca = (long(key.region[a]) - extents_.first_region[0]) * long(region_size_) + key.local[a] - extents_.first_local[0];
+    const long cb = (long(key.region[b]) - extents_.first_region[1]) * long(region_size_) + key.local[b] - extents_.first_local[1];
+    if (ca < 0 || cb < 0 || ca >= long(extents_.ma) || cb >= long(extents_.mb))
+    {
+      return HeightmapVoxelType::kUnknown;
+    }
+    Key flat = key;
+    flat.region[upAxisIndex()] = 0;
+    flat.local[upAxisIndex()] = 0;
+    const dvec3 centre = voxelCentreGlobal(flat);
+    const size_t cell = size_t(cb) * extents_.ma + size_t(ca);
+    const float occupancy = occupancy_[cell];
+    if (pos)
+    {
+      *pos = centre;
+    }
+    if (occupancy == std::numeric_limits<float>::infinity())
+    {
+      return HeightmapVoxelType::kUnknown;
+    }
+    const HeightmapVoxel &info = voxels_[cell];
+    if (pos)
+    {
+      const dvec3 up = upAxisNormal();
+      *pos = dvec3{ centre.x + up.x * double(info.height), centre.y + up.y * double(info.height),
+                    centre.z + up.z * double(info.height) };
+    }
+    if (voxel_info)
+    {
+      *voxel_info = info;
+    }
+    if (occupancy == 0)
+    {
+      return HeightmapVoxelType::kVacant;
+    }
+    return occupancy > 0 ? HeightmapVoxelType::kSurface : HeightmapVoxelType::kVirtualSurface;
+  }
+
+private:
+  GpuMap *gpu_map_ = nullptr;
+  double grid_resolution_;
+  double min_clearance_;
+  UpAxis up_axis_;
+  unsigned region_size_;
+  double ceiling_ = 0, floor_ = 0;
+  bool ignore_voxel_mean_ = false, generate_virtual_surface_ = false, promote_virtual_below_ = false;
+  HeightmapMode mode_ = HeightmapMode::kPlanar;
+  dvec3 origin_{ 0, 0, 0 };
+  ohmhip_heightmap_extents extents_{};
+  std::vector<float> occupancy_;
+  std::vector<HeightmapVoxel> voxels_;
+  std::vector<VoxelMean> mean_;
+  uint64_t populated_ = 0, cells_ = 0;
   int last_status_ = OHMHIP_OK;
 };
 

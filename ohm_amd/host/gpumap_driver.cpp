@@ -3,7 +3,7 @@
 // (tests/ohmtestgpu/GpuMapTest.cpp:68-205), syncs, and dumps every region layer for the Python parity test to check
 // against the CPU oracle.  Links libohmhip.so only; built with plain g++ (no hipcc, no glm).
 //
-//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|...> <resolution> <batch_rays>
+//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|heightmap|...> <resolution> <batch_rays>
 //                 <rays.bin> <out.bin> [search radius] [query flags]
 //   occdev: the sample points (odd entries) go through ohm::GpuTransformSamples with a static identity trajectory and
 //   are integrated straight from the device buffer (all rays then start at the origin).
@@ -279,6 +279,51 @@ int main(int argc, char **argv)
           std::fwrite(&query.ranges()[k], sizeof(float), 1, out);
         }
       }
+      std::fclose(out);
+      return 0;
+    }
+
+    if (mode == "heightmap")
+    {
+      // ohm::Heightmap: the map (occupancy + mean) is built by ohm::GpuMap::integrateRays in batches, still collected by
+      // batch coalescing when the heightmap is asked for; [search radius] is min_clearance, [query flags] bit 0 turns
+      // virtual surfaces on.  Reference position (0, 0, 0), +Z up, grid resolution = the map's.  out.bin = u32 ma, u32
+      // mb, u64 populated, u64 cells, u8 has mean, then the occupancy, HeightmapVoxel and (if any) VoxelMean arrays.
+      ohm::OccupancyMap hm_map(resolution);
+      hm_map.addLayer(OHMHIP_LID_MEAN);
+      ohm::GpuMap hm_gpu_map(&hm_map, true);
+      const size_t step = std::max<size_t>(2, batch_rays * 2);
+      for (size_t at = 0; at + 1 < rays.size(); at += step)
+      {
+        const size_t count = std::min(step, (rays.size() - at) & ~size_t(1));
+        if (hm_gpu_map.integrateRays(rays.data() + at, count) != count)
+        {
+          return 8;
+        }
+      }
+      ohm::Heightmap heightmap(resolution, argc > 6 ? std::atof(argv[6]) : 0.0, ohm::UpAxis::kZ);
+      heightmap.setOccupancyMap(&hm_gpu_map);
+      heightmap.setGenerateVirtualSurface(argc > 7 && (std::atoi(argv[7]) & 1));
+      if (!heightmap.buildHeightmap(ohm::dvec3{ 0.0, 0.0, 0.0 }))
+      {
+        return 8;
+      }
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      const uint32_t ma = uint32_t(heightmap.heightmapCellsA()), mb = uint32_t(heightmap.heightmapCellsB());
+      const uint64_t populated = heightmap.populatedCount(), cells = heightmap.cellCount();
+      const uint8_t has_mean = heightmap.voxelMeans().empty() ? 0 : 1;
+      std::fwrite(&ma, sizeof(ma), 1, out);
+      std::fwrite(&mb, sizeof(mb), 1, out);
+      std::fwrite(&populated, sizeof(populated), 1, out);
+      std::fwrite(&cells, sizeof(cells), 1, out);
+      std::fwrite(&has_mean, 1, 1, out);
+      std::fwrite(heightmap.occupancy().data(), sizeof(float), heightmap.occupancy().size(), out);
+      std::fwrite(heightmap.heightmapVoxels().data(), sizeof(ohm::HeightmapVoxel), heightmap.heightmapVoxels().size(), out);
+      std::fwrite(heightmap.voxelMeans().data(), sizeof(ohm::VoxelMean), heightmap.voxelMeans().size(), out);
       std::fclose(out);
       return 0;
     }
