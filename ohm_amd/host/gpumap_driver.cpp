@@ -3,10 +3,13 @@
 // (tests/ohmtestgpu/GpuMapTest.cpp:68-205), syncs, and dumps every region layer for the Python parity test to check
 // against the CPU oracle.  Links libohmhip.so only; built with plain g++ (no hipcc, no glm).
 //
-//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|heightmap|...> <resolution> <batch_rays>
+//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|heightmap|transform|...> <resolution> <batch_rays>
 //                 <rays.bin> <out.bin> [search radius] [query flags]
 //   occdev: the sample points (odd entries) go through ohm::GpuTransformSamples with a static identity trajectory and
 //   are integrated straight from the device buffer (all rays then start at the origin).
+//   transform: <rays.bin> is a trajectory-and-samples file instead and <out.bin> receives the ray buffer of
+//   ohm::GpuTransformSamples::transform (layouts at the mode below); <resolution> and <batch_rays> are not used.
+//   filter:<clipbounded|cliptobounds|clipray|goodray>: host only, one record per ray (layout at the mode below).
 //   rays.bin: u64 n_points, then n_points * 3 doubles.  out.bin: u64 regions, per region i16[3] key, then per enabled
 //   layer (ascending id): u32 layer id, u64 bytes, payload.
 #include "OhmGpuMap.h"
@@ -20,7 +23,7 @@ int main(int argc, char **argv)
 {
   if (argc < 6)
   {
-    std::fprintf(stderr, "usage: %s <occ|occmean|occdev|occcoalesce|occowner|occclipbox|ndt|tsdf> <resolution> <batch_rays> <rays.bin> <out.bin>\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <occ|occmean|occdev|occcoalesce|occowner|occclipbox|ndt|tsdf|transform|...> <resolution> <batch_rays> <rays.bin | transform input> <out.bin>\n", argv[0]);
     return 2;
   }
   const std::string mode = argv[1];
@@ -31,17 +34,23 @@ int main(int argc, char **argv)
     // Host only (no device): run one of the stock ray filters of OhmGpuMap.h over the rays and write, per ray,
     // accepted (1 byte), filter flags (1 byte), start and end (6 doubles).  Box (-1,-1,-1)..(2,2,2), length = resolution.
     FILE *in = std::fopen(argv[4], "rb");
-    uint64_t n_points = 0;
-    if (!in || std::fread(&n_points, sizeof(n_points), 1, in) != 1)
+    if (!in)
     {
       return 4;
     }
-    std::vector<ohm::dvec3> rays(n_points);
-    if (std::fread(rays.data(), sizeof(ohm::dvec3), n_points, in) != n_points)
+    uint64_t n_points = 0;
+    std::vector<ohm::dvec3> rays;
+    bool read_ok = std::fread(&n_points, sizeof(n_points), 1, in) == 1;
+    if (read_ok)
     {
-      return 4;
+      rays.resize(n_points);
+      read_ok = std::fread(rays.data(), sizeof(ohm::dvec3), n_points, in) == n_points;
     }
     std::fclose(in);
+    if (!read_ok)
+    {
+      return 4;
+    }
     const ohm::Aabb box(ohm::dvec3{ -1.0, -1.0, -1.0 }, ohm::dvec3{ 2.0, 2.0, 2.0 });
     FILE *out = std::fopen(argv[5], "wb");
     if (!out)
@@ -88,6 +97,89 @@ int main(int argc, char **argv)
       std::fprintf(stderr, "no HIP device\n");
       return 3;
     }
+    if (mode == "transform")
+    {
+      // ohm::GpuTransformSamples::transform on a trajectory and samples from the input file, the output buffer to the
+      // output file (resolution and batch size are not used).  in: u64 transforms, u64 points, f64 max_range, then
+      // times[transforms], translations (dvec3 each), rotations (dquat x, y, z, w each), sample times[points], local
+      // samples (dvec3 each).  out: u64 elements (2 x valid samples), then elements x (x, y, z) read back from the buffer.
+      FILE *tin = std::fopen(argv[4], "rb");
+      if (!tin)
+      {
+        return 4;
+      }
+      uint64_t counts[2] = { 0, 0 };
+      double max_range = 0;
+      if (std::fread(counts, sizeof(uint64_t), 2, tin) != 2 || std::fread(&max_range, sizeof(double), 1, tin) != 1)
+      {
+        std::fclose(tin);
+        return 4;
+      }
+      const size_t transform_count = size_t(counts[0]), point_count = size_t(counts[1]);
+      // The file is read as plain doubles and every struct is filled member by member, so that the order in which dvec3
+      // and dquat declare their members matters: the mirror casts these arrays back to double pointers.
+      std::vector<double> times(transform_count), sample_times(point_count);
+      std::vector<double> raw_translations(3 * transform_count), raw_rotations(4 * transform_count);
+      std::vector<double> raw_samples(3 * point_count);
+      const auto read_doubles = [tin](std::vector<double> &to) {
+        return std::fread(to.data(), sizeof(double), to.size(), tin) == to.size();
+      };
+      const bool read_ok = read_doubles(times) && read_doubles(raw_translations) && read_doubles(raw_rotations) &&
+                           read_doubles(sample_times) && read_doubles(raw_samples);
+      std::fclose(tin);
+      if (!read_ok)
+      {
+        return 4;
+      }
+      std::vector<ohm::dvec3> translations(transform_count), samples(point_count);
+      std::vector<ohm::dquat> rotations(transform_count);
+      for (size_t i = 0; i < transform_count; ++i)
+      {
+        translations[i].x = raw_translations[3 * i + 0];
+        translations[i].y = raw_translations[3 * i + 1];
+        translations[i].z = raw_translations[3 * i + 2];
+        rotations[i].x = raw_rotations[4 * i + 0];
+        rotations[i].y = raw_rotations[4 * i + 1];
+        rotations[i].z = raw_rotations[4 * i + 2];
+        rotations[i].w = raw_rotations[4 * i + 3];
+      }
+      for (size_t i = 0; i < point_count; ++i)
+      {
+        samples[i].x = raw_samples[3 * i + 0];
+        samples[i].y = raw_samples[3 * i + 1];
+        samples[i].z = raw_samples[3 * i + 2];
+      }
+      gputil::Device device;
+      gputil::Queue queue = device.defaultQueue();
+      ohm::GpuTransformSamples transform(device);
+      gputil::Buffer device_rays;
+      const uint64_t elements =
+        transform.transform(times.data(), translations.data(), rotations.data(), unsigned(transform_count),
+                            sample_times.data(), samples.data(), unsigned(point_count), queue, device_rays, max_range);
+      if (transform.lastStatus() != OHMHIP_OK)
+      {
+        return 8;
+      }
+      std::vector<ohm::dvec3> world(elements);
+      if (elements)
+      {
+        device_rays.read(world.data(), sizeof(ohm::dvec3) * elements);
+      }
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      std::fwrite(&elements, sizeof(elements), 1, out);
+      for (uint64_t i = 0; i < elements; ++i)
+      {
+        const double xyz[3] = { world[i].x, world[i].y, world[i].z };
+        std::fwrite(xyz, sizeof(double), 3, out);
+      }
+      std::fclose(out);
+      return 0;
+    }
+
     FILE *in = std::fopen(argv[4], "rb");
     if (!in)
     {

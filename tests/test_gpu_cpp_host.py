@@ -120,6 +120,40 @@ def test_cpp_transform_samples_feeds_device_integration(gpu):
     assert_parity(stats)
 
 
+def test_cpp_transform_samples_general_trajectory(gpu):
+    """ohm::GpuTransformSamples::transform with dvec3 / dquat arrays on a general 3-D trajectory (driver mode
+    `transform`) against the Python binding on the same input: it is the same library call, so the output buffers are
+    bit-identical -- unless the mirror's reinterpret casts get a member order or a stride wrong, which the identity
+    trajectory of the test above cannot show.  The driver fills every dvec3 / dquat member by name from the plain
+    doubles of the file and writes the output from .x, .y, .z, so the order of the members is part of what is tested."""
+    import transform_cases as TC
+    from ohm_amd import GpuTransformSamples
+    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
+    for name in ("general_small_stamps", "general_big_stamps"):
+        for case in dict(TC.families())[name]:
+            ts = GpuTransformSamples()
+            _, count = ts.transform(case["times"], case["translations"], case["rotations"], case["sample_times"],
+                                    case["local"], case["max_range"])
+            expect = ts.read(count)
+            ts.close()
+            with tempfile.TemporaryDirectory() as tmp:
+                ip, op = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+                with open(ip, "wb") as f:
+                    f.write(struct.pack("<QQd", case["times"].shape[0], case["local"].shape[0], case["max_range"]))
+                    for key in ("times", "translations", "rotations", "sample_times", "local"):
+                        f.write(np.ascontiguousarray(case[key], dtype="<f8").tobytes())
+                res = subprocess.run([DRIVER, "transform", "0.1", "0", ip, op], capture_output=True, text=True,
+                                     timeout=300)
+                assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
+                data = open(op, "rb").read()
+            (elements,) = struct.unpack_from("<Q", data, 0)
+            assert elements == count > 0 and len(data) == 8 + 24 * elements
+            got = np.frombuffer(data, dtype="<f8", offset=8).reshape(-1, 3)
+            nan = np.isnan(expect)  # bit patterns, any NaN compared by position only
+            assert np.array_equal(nan, np.isnan(got))
+            assert np.array_equal(got.view(np.uint64)[~nan], expect.view(np.uint64)[~nan])
+
+
 def test_cpp_batch_coalescing_and_region_ownership(gpu):
     from ohm_amd import distributed as D
     rays = synth.rays_c1(n=20000, max_range=12.0)
