@@ -29,37 +29,52 @@ def _floor_div(a, b):
     return a // b  # Python ints: floor division
 
 
-def voxel_of(p_units):
-    """Global voxel coordinate of a lattice point (map origin 0): plain floor."""
-    return tuple(_floor_div(c, SUB) for c in p_units)
+def _dims(region):
+    """Region dimensions per axis (voxels, even): an int means a cube."""
+    return (region, region, region) if isinstance(region, int) else tuple(region)
 
 
-def key_of(voxel):
+def voxel_of(p_units, sub=SUB, origin_units=(0, 0, 0)):
+    """Global voxel coordinate of a lattice point, counted from the map origin (itself on the lattice): plain floor."""
+    return tuple(_floor_div(c - o, sub) for c, o in zip(p_units, origin_units))
+
+
+def key_of(voxel, region=REGION):
     """(region key, local key) of a global voxel coordinate, region (0,0,0) centred on the origin as in ohm
-    (ohm/MapCoord.h:45-93: region = floor(p / R + 0.5)): global voxel v lies in region floor((v + 16) / 32)."""
-    half = REGION // 2
-    region = tuple(_floor_div(v + half, REGION) for v in voxel)
-    local = tuple(v + half - REGION * r for v, r in zip(voxel, region))
-    return region, local
+    (ohm/MapCoord.h:45-93: region = floor(p / R + 0.5)): global voxel v lies in region floor((v + R / 2) / R), R even
+    (the default: floor((v + 16) / 32))."""
+    dims = _dims(region)
+    region_key = tuple(_floor_div(v + r // 2, r) for v, r in zip(voxel, dims))
+    local = tuple(v + r // 2 - r * k for v, r, k in zip(voxel, dims, region_key))
+    return region_key, local
 
 
 class Undecidable(Exception):
     """The ray asks fp64 for a comparison it cannot be trusted with (see the module docstring)."""
 
 
-def walk(start_units, end_units, rel_gap=1e-9):
+def walk(start_units, end_units, rel_gap=1e-9, sub=SUB, region=REGION, origin_units=(0, 0, 0), trace=None):
     """Exact voxel sequence [(region, local), ...] of the segment start -> end, both given in lattice units, with the
-    reference's default flags (start voxel and end voxel included).  Raises Undecidable for rays outside the contract."""
+    reference's default flags (start voxel and end voxel included).  Raises Undecidable for rays outside the contract.
+    `sub` is the lattice density (units per voxel), `region` the region dimensions (an int or one per axis, even) and
+    `origin_units` a lattice-aligned map origin.
+
+    With `trace` a list, every decision that has a runner-up appends a record (axis, other, num, den, voxel, stepped):
+    the chosen axis leads the next smallest finite exit time, that of `other`, by num / den of ray parameter u (exact
+    integers, num == 0: a structural tie), taken in the voxel `voxel` (global, from the origin) after `stepped` steps per
+    axis.  smallest_gap() reduces a trace.  Consecutive exit times are all compared this way, so every pair of exit
+    times along the ray is at least as far apart as the smallest recorded gap, or tied."""
+    SUB = sub  # (shadows the module default)
     s, e = tuple(start_units), tuple(end_units)
     d = tuple(b - a for a, b in zip(s, e))
-    v0, v1 = voxel_of(s), voxel_of(e)
+    v0, v1 = voxel_of(s, sub, origin_units), voxel_of(e, sub, origin_units)
     remaining = [b - a for a, b in zip(v0, v1)]
     sign = [1 if c < 0 else 0 for c in d]                 # as the reference: dir < 0
     step_dir = [-2 * sg + 1 for sg in sign]
     # distance (lattice units) from the start point to the first wall in the direction of travel
     x = []
     for a in range(3):
-        lo = v0[a] * SUB
+        lo = v0[a] * SUB + origin_units[a]
         x.append((s[a] - lo) if sign[a] else (lo + SUB - s[a]))
     absd = [abs(c) for c in d]
     stepped = [0, 0, 0]
@@ -91,15 +106,28 @@ def walk(start_units, end_units, rel_gap=1e-9):
         axis = 0
         axis = axis if less(axis, 1) else 1
         axis = axis if less(axis, 2) else 2
+        if trace is not None:
+            ta, best = time(axis), None
+            for b in range(3):
+                tb = time(b)
+                if b == axis or tb is None or ta is None:
+                    continue
+                num, den = tb[0] * ta[1] - ta[0] * tb[1], ta[1] * tb[1]
+                if best is None or num * best[2] < best[1] * den:
+                    best = (b, num, den)
+            if best is not None:
+                trace.append((axis, best[0], best[1], best[2], tuple(cur), tuple(abs(c) for c in stepped)))
         return axis
 
     cur = list(v0)
     out = []
     limit = sum((1 << a) for a in range(3) if remaining[a] == 0)
+    if limit == 7:
+        return [key_of(v1, region)]
     axis = select()
     guard = 0
     while limit < 7 and tuple(cur) != v1:
-        out.append(key_of(tuple(cur)))
+        out.append(key_of(tuple(cur), region))
         cur[axis] += step_dir[axis]
         remaining[axis] -= step_dir[axis]
         stepped[axis] += step_dir[axis]
@@ -109,15 +137,28 @@ def walk(start_units, end_units, rel_gap=1e-9):
         guard += 1
         if guard > 100000:
             raise AssertionError("exact walk does not terminate")
-    out.append(key_of(v1))
+    out.append(key_of(v1, region))
     return out
 
 
-def generate(count, seed=20260927, resolution=0.125):
+def smallest_gap(trace, skip=None):
+    """Smallest non-tie gap of a walk's trace as (num, den, index), in ray parameter u; None without one.  `skip` leaves
+    one record out (the comparison a generated ray is built around)."""
+    best = None
+    for i, (_, _, num, den, _, _) in enumerate(trace):
+        if num == 0 or i == skip:
+            continue
+        if best is None or num * best[1] < best[0] * den:
+            best = (num, den, i)
+    return best
+
+
+def generate(count, seed=20260927, resolution=0.125, sub=SUB, region=REGION):
     """Tie-rich lattice rays: [(start_xyz float, end_xyz float, expected keys)], and how many candidates were discarded
     as undecidable.  Families: axis-aligned, plane and space diagonals through centres / corners / generic offsets
     (structural ties), 2:1 and 3:1 slopes and random lattice segments at generic offsets, zero components, negative
-    directions, origins near region boundaries so the walks cross regions."""
+    directions, origins near region boundaries so the walks cross regions (those of the default 32^3 regions)."""
+    SUB = sub  # (shadows the module default)
     rng = random.Random(seed)
     unit = resolution / SUB
     rays, discarded, tried = [], 0, 0
@@ -153,7 +194,7 @@ def generate(count, seed=20260927, resolution=0.125):
         if s == e:
             continue
         try:
-            keys = walk(s, e)
+            keys = walk(s, e, sub=sub, region=region)
         except Undecidable:
             discarded += 1
             continue
