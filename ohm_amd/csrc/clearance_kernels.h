@@ -35,12 +35,8 @@ constexpr int kClearanceMaxH = 127;              ///< largest half extent at all
 constexpr int kClearanceMaxTileBlocks = 1024;    ///< LDS table of the tiles a staged window touches
 constexpr uint32_t kClearanceNone = 0xffffffffu;
 
-struct ClearanceArgs
+struct ClearanceArgs : MapReadView
 {
-  MapConst mc;
-  RegionTable rt;
-  QuerySpillTable spill;
-  const float *occupancy;  ///< pool layer: [slot][tile voxel]
   int h;                   ///< voxel search half extent, every axis (calculateVoxelSearchHalfExtents)
   float radius;            ///< search_radius (0: no radius test)
   float scale[3];          ///< axis_scaling

@@ -6,60 +6,6 @@
 
 namespace
 {
-/// ohm/MapCoord.h:85-93
-inline int hmHostRegionCoord(double coord, double resolution)
-{
-  const double v = std::floor(coord / resolution + 0.5);
-  return (v >= -2147483648.0 && v < 2147483648.0) ? int(v) : int(0x80000000u);
-}
-
-/// ohm/MapCoord.h:45-80
-inline int hmHostRegionVoxel(double coord, double voxel_resolution, double region_resolution)
-{
-  const double epsilon = double(1e-6f);
-  if (-epsilon <= coord && coord < 0)
-  {
-    coord = 0;
-  }
-  else if (coord >= region_resolution && coord - epsilon < region_resolution)
-  {
-    coord -= epsilon;
-  }
-  const double v = std::floor(coord / voxel_resolution);
-  return (v >= -2147483648.0 && v < 2147483648.0) ? int(v) : int(0x80000000u);
-}
-
-/// OccupancyMap::voxelKey (ohm/OccupancyMap.cpp:859-886 -> ohm/MapRegion.cpp:32-69) on the host: false for Key::kNull.
-inline bool hmHostVoxelKey(const MapConst &mc, const double p[3], int region[3], int local[3])
-{
-  bool ok = true;
-  for (int a = 0; a < 3; ++a)
-  {
-    const int coord = hmHostRegionCoord(p[a] - mc.origin[a], mc.region_dim[a]);
-    ok = ok && coord >= -32768 && coord <= 32767;
-    const double centre = coord * mc.region_dim[a];
-    const double region_min = centre - 0.5 * mc.region_dim[a];
-    const double pl = p[a] - mc.origin[a] - region_min;
-    const int q = hmHostRegionVoxel(pl, mc.resolution, mc.region_dim[a]);
-    ok = ok && 0 <= q && q < mc.kdim[a];
-    region[a] = coord;
-    local[a] = q;
-  }
-  return ok;
-}
-
-/// ohm/OccupancyMap.h:757-778 (one axis)
-inline double hmHostCentre(const MapConst &mc, int a, int region, int local)
-{
-  double v = double(float(region));
-  v *= mc.region_dim[a];
-  v -= 0.5 * mc.region_dim[a];
-  v += mc.origin[a];
-  v += double(local) * mc.resolution;
-  v += 0.5 * mc.resolution;
-  return v;
-}
-
 /// What every heightmap entry point checks before any device work.
 int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p)
 {
@@ -116,9 +62,9 @@ int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, Heightma
   a.generate_virtual = (p->flags & OHMHIP_HM_GENERATE_VIRTUAL_SURFACE) ? 1 : 0;
   a.flags = (a.generate_virtual ? kHmVirtualSurfaces : 0u) |
             ((p->flags & OHMHIP_HM_PROMOTE_VIRTUAL_BELOW) ? kHmPromoteVirtualBelow : 0u);
-  a.voxel_floor = hmHostRegionCoord(p->floor, mc.resolution);
-  a.voxel_ceiling = hmHostRegionCoord(p->ceiling, mc.resolution);
-  a.clearance_permissive = std::max(1, hmHostRegionCoord(p->min_clearance, mc.resolution) - 1);
+  a.voxel_floor = pointToRegionCoord(p->floor, mc.resolution);
+  a.voxel_ceiling = pointToRegionCoord(p->ceiling, mc.resolution);
+  a.clearance_permissive = std::max(1, pointToRegionCoord(p->min_clearance, mc.resolution) - 1);
   a.min_clearance = p->min_clearance;
 
   // rule 1: the regions present, in the caller's coordinates (resident and host store)
@@ -155,9 +101,11 @@ int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, Heightma
       hi[c] = p->cull_max[c];
     }
   }
+  // OccupancyMap::voxelKey, the reference's key maths with no tile range: the keys are the caller's
+  MapConst kc = mc;
+  kc.tile_split[0] = kc.tile_split[1] = kc.tile_split[2] = 1;
   int rmin[3], lmin[3], rmax[3], lmax[3], rref[3], lref[3];
-  if (!hmHostVoxelKey(mc, lo, rmin, lmin) || !hmHostVoxelKey(mc, hi, rmax, lmax) ||
-      !hmHostVoxelKey(mc, p->reference_pos, rref, lref))
+  if (!voxelKey(kc, lo, rmin, lmin) || !voxelKey(kc, hi, rmax, lmax) || !voxelKey(kc, p->reference_pos, rref, lref))
   {
     return OHMHIP_OK;  // a null key: the reference walks nothing
   }
@@ -197,12 +145,12 @@ int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, Heightma
   double c_lo[3], c_hi[3];
   for (int c = 0; c < 3; ++c)
   {
-    c_lo[c] = hmHostCentre(mc, c, rmin[c], lmin[c]) - 0.5 * mc.resolution;
-    c_hi[c] = hmHostCentre(mc, c, rmax[c], lmax[c]) + 0.5 * mc.resolution;
+    c_lo[c] = voxelCentreAxis(mc, c, rmin[c], lmin[c]) - 0.5 * mc.resolution;
+    c_hi[c] = voxelCentreAxis(mc, c, rmax[c], lmax[c]) + 0.5 * mc.resolution;
   }
   c_lo[up] = c_hi[up] = 0.0;
   int hr0[3], hl0[3], hr1[3], hl1[3];
-  if (!hmHostVoxelKey(a.hm, c_lo, hr0, hl0) || !hmHostVoxelKey(a.hm, c_hi, hr1, hl1))
+  if (!voxelKey(a.hm, c_lo, hr0, hl0) || !voxelKey(a.hm, c_hi, hr1, hl1))
   {
     return OHMHIP_ERR_CAPACITY;  // the heightmap's keys cannot address the source's extents
   }
@@ -235,12 +183,10 @@ int heightmapDevice(ohmhip_map_t m, HeightmapArgs &a, float *d_occ, void *d_vox,
 {
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
-  a.rt = regionTable(m);
-  a.occupancy = static_cast<const float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
+  OHMHIP_CHECK(mapReadView(m, a));
   a.mean = a.use_mean ? static_cast<const uint2 *>(m->layers[OHMHIP_LID_MEAN]) : nullptr;
   a.spill_mean_delta =
     (long long)(m->store.layer_offset[OHMHIP_LID_MEAN]) - (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
-  OHMHIP_CHECK(querySpillTable(m, a.spill));
   const size_t columns = size_t(a.na) * size_t(a.nb);
   const size_t cells = size_t(a.ma) * size_t(a.mb);
   OHMHIP_CHECK(qs.hm_winner.ensure(sizeof(int) * cells, false, s));

@@ -41,13 +41,9 @@ enum : unsigned
 constexpr int kHmNoCell = -1;
 constexpr uint32_t kHmVoxelWords = 6;  ///< HeightmapVoxel: 24 bytes
 
-struct HeightmapArgs
+struct HeightmapArgs : MapReadView  ///< the source map
 {
-  MapConst mc;  ///< source map
   MapConst hm;  ///< heightmap geometry: resolution, region_dim, origin, kdim (1 on the up axis), tile_split 1
-  RegionTable rt;
-  QuerySpillTable spill;
-  const float *occupancy;     ///< pool layer: [slot][tile voxel]
   const uint2 *mean;          ///< pool layer or null
   long long spill_mean_delta; ///< bytes from a stored region's occupancy block to its mean block
   int use_mean;               ///< source has the mean layer and ignore_voxel_mean is off
@@ -86,57 +82,28 @@ struct HmCursor
   uint32_t inspected;
 };
 
+/// The occupancy and mean blocks of tile (tx, ty, tz); false (and nulls) when the map has no such tile.
 __device__ inline bool hmTile(const HeightmapArgs &a, int tx, int ty, int tz, const float *&occ, const uint2 *&mean)
 {
-  occ = nullptr;
+  const FoundTile t = mapFindTile(a, tx, ty, tz);
+  if (t.slot != kSlotUnassigned)
+  {
+    occ = a.occupancy + size_t(t.slot) * size_t(a.mc.region_voxels);
+    mean = (a.use_mean && a.mean) ? a.mean + size_t(t.slot) * size_t(a.mc.region_voxels) : nullptr;
+    return true;
+  }
+  occ = t.stored;
   mean = nullptr;
-  if (tx < -32768 || tx > 32767 || ty < -32768 || ty > 32767 || tz < -32768 || tz > 32767)
+  if (!occ)
   {
     return false;
   }
-  const uint64_t key = packRegionKey(tx, ty, tz);
-  const uint32_t h = regionFind(a.rt, key);
-  if (h != 0xffffffffu)
-  {
-    const uint32_t slot = a.rt.vals[h];
-    if (slot < a.rt.slot_capacity)
-    {
-      occ = a.occupancy + size_t(slot) * size_t(a.mc.region_voxels);
-      mean = (a.use_mean && a.mean) ? a.mean + size_t(slot) * size_t(a.mc.region_voxels) : nullptr;
-      return true;
-    }
-  }
-  if (a.spill.keys)
-  {
-    uint32_t idx = hashRegionKey(key, a.spill.mask);
-    for (uint32_t probe = 0; probe <= a.spill.mask; ++probe)
-    {
-      const unsigned long long k = a.spill.keys[idx];
-      if (k == key)
-      {
-        occ = a.spill.blocks[idx];
-        mean = a.use_mean ? reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(occ) + a.spill_mean_delta)
-                          : nullptr;
-        return true;
-      }
-      if (k == 0)
-      {
-        break;
-      }
-      idx = (idx + 1) & a.spill.mask;
-    }
-  }
-  return false;
+  mean = a.use_mean ? reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(occ) + a.spill_mean_delta) : nullptr;
+  return true;
 }
 
-/// Component `idx` of a 3-vector / writing it, with selects: a run-time index into a local array would put the array
-/// into scratch memory.
-template <typename T>
-__device__ inline T hmPick(const T v[3], int idx)
-{
-  return (idx == 0) ? v[0] : ((idx == 1) ? v[1] : v[2]);
-}
-
+/// Writing component `idx` of a 3-vector with selects (reading it: sel3): a run-time index into a local array would put
+/// the array into scratch memory.
 template <typename T>
 __device__ inline void hmPut(T v[3], int idx, T value)
 {
@@ -230,7 +197,7 @@ __device__ inline int hmSearch(const HeightmapArgs &a, HmCursor &c, const int se
   const bool allow_virtual = (a.flags & kHmVirtualSurfaces) != 0;
   const int up = a.up;
   const float inf = __int_as_float(0x7f800000);
-  const int seed_up = hmPick(seed, up);
+  const int seed_up = sel3(up, seed);
   int vertical_range = (to_up - seed_up) + 1;  // rangeBetween(from, to)[up] + 1
   const int step = (vertical_range >= 0) ? 1 : -1;
   vertical_range = (vertical_range >= 0) ? vertical_range : -vertical_range;
@@ -304,7 +271,7 @@ __device__ inline int hmSearch(const HeightmapArgs &a, HmCursor &c, const int se
 /// kIgnoreVirtualAbove.  Returns false when there is no candidate.
 __device__ inline bool hmSupportingVoxel(const HeightmapArgs &a, HmCursor &c, const int seed[3], int &candidate)
 {
-  const int min_up = hmPick(a.min_g, a.up), max_up = hmPick(a.max_g, a.up);
+  const int min_up = sel3(a.up, a.min_g), max_up = sel3(a.up, a.max_g);
   const int down_to = a.up_positive ? min_up : max_up;
   const int up_to = a.up_positive ? max_up : min_up;
   int below = 0, above = 0;
@@ -397,10 +364,10 @@ __global__ void __launch_bounds__(256) k_heightmap_columns(HeightmapArgs a)
     double up_vec[3] = { 0.0, 0.0, 0.0 };
     hmPut(up_vec, up, a.up_positive ? 1.0 : -1.0);
     int walk[3] = { 0, 0, 0 };
-    hmPut(walk, a.a, hmPick(a.min_g, a.a) + ia);
-    hmPut(walk, a.b, hmPick(a.min_g, a.b) + ib);
+    hmPut(walk, a.a, sel3(a.a, a.min_g) + ia);
+    hmPut(walk, a.b, sel3(a.b, a.min_g) + ib);
     hmPut(walk, up, a.plane);
-    const int min_up = hmPick(a.min_g, up), max_up = hmPick(a.max_g, up);
+    const int min_up = sel3(up, a.min_g), max_up = sel3(up, a.max_g);
     int candidate = 0;
     const bool have_candidate = hmSupportingVoxel(a, c, walk, candidate);
 
@@ -472,8 +439,8 @@ __global__ void __launch_bounds__(256) k_heightmap_columns(HeightmapArgs a)
       const bool ok = voxelKey(a.hm, pos, hr, hl);
       hmPut(hr, up, 0);
       hmPut(hl, up, 0);
-      const int ca = hmPick(hr, a.a) * hmPick(a.hm.kdim, a.a) + hmPick(hl, a.a) - a.cell0_a;
-      const int cb = hmPick(hr, a.b) * hmPick(a.hm.kdim, a.b) + hmPick(hl, a.b) - a.cell0_b;
+      const int ca = sel3(a.a, hr) * sel3(a.a, a.hm.kdim) + sel3(a.a, hl) - a.cell0_a;
+      const int cb = sel3(a.b, hr) * sel3(a.b, a.hm.kdim) + sel3(a.b, hl) - a.cell0_b;
       if (ok && ca >= 0 && ca < a.ma && cb >= 0 && cb < a.mb)
       {
         double centre[3];

@@ -239,7 +239,7 @@ struct ohmhip_map_s
   struct QueryState
   {
     DevBuf rays, ranges, volumes, types, keys;   ///< host-pointer calls: device copies of the caller's arrays
-    DevBuf walked, last_walked, scan_temp, cursor;
+    DevBuf walked, last_walked, scan_temp;
     DevBuf spill_keys, spill_blocks;             ///< table of the host store's regions (spill to host)
     DevBuf clear_regions, clear_keys, clear_out, clear_mask;  ///< clearance queries (clearance_kernels.h)
     /// heightmap (heightmap_kernels.h): per-cell winner, per-column records, counters; device copies of the host arrays

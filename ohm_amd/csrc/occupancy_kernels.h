@@ -1831,50 +1831,6 @@ __device__ inline uint32_t waitTile(uint32_t old)
   return old;
 }
 
-/// Local voxel coordinates of voxel index `vi` of a region.
-__device__ inline void voxelLocal(const MapConst &mc, uint32_t vi, int &lx, int &ly, int &lz)
-{
-  const uint32_t dx = uint32_t(mc.dim[0]);
-  const uint32_t dxy = dx * uint32_t(mc.dim[1]);
-  lz = int(vi / dxy);
-  const uint32_t r = vi - uint32_t(lz) * dxy;
-  ly = int(r / dx);
-  lx = int(r - uint32_t(ly) * dx);
-}
-
-/// Steps a ray has taken along each axis when it stands in voxel `vi` of region (rx, ry, rz): the walk moves
-/// monotonically away from the start voxel on every axis.
-__device__ inline void stepsAtVoxel(const MapConst &mc, const RayWalk &rw, int rx, int ry, int rz, uint32_t vi, int &k0,
-                                    int &k1, int &k2)
-{
-  int lx, ly, lz;
-  voxelLocal(mc, vi, lx, ly, lz);
-  k0 = abs(rx * mc.dim[0] + lx - rw.g0[0]);
-  k1 = abs(ry * mc.dim[1] + ly - rw.g0[1]);
-  k2 = abs(rz * mc.dim[2] + lz - rw.g0[2]);
-}
-
-/// time_next of one axis after k steps along it (ohm/LineWalkCompute.h:299-301, :375-378).
-__device__ inline double timeNext(double init, double delta, int k, int total)
-{
-  return (k < total) ? ((k == 0) ? init : init + delta * double(k)) : dInf();
-}
-
-/// The exact decision of the reference walk for a ray standing in voxel `vi` of region (rx, ry, rz): the axis of the
-/// next step.  walkSelectNextAxis (ohm/LineWalkCompute.h:282-289): smallest time_next, ties go to the higher axis.
-__device__ inline int exactNextAxis(const MapConst &mc, const RayWalk &rw, int rx, int ry, int rz, uint32_t vi)
-{
-  int k0, k1, k2;
-  stepsAtVoxel(mc, rw, rx, ry, rz, vi, k0, k1, k2);
-  const double t0 = timeNext(rw.init[0], rw.delta[0], k0, rw.total[0]);
-  const double t1 = timeNext(rw.init[1], rw.delta[1], k1, rw.total[1]);
-  const double t2 = timeNext(rw.init[2], rw.delta[2], k2, rw.total[2]);
-  const bool m01 = t0 < t1;
-  const double t01 = m01 ? t0 : t1;
-  const bool m2 = t01 < t2;
-  return m2 ? (m01 ? 0 : 1) : 2;
-}
-
 /// Kernel parameters of k_region_walk (one struct keeps the template instantiations readable).
 struct WalkArgs
 {

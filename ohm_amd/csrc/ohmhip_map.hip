@@ -394,7 +394,7 @@ try
   m->stop_a.release();
   m->stop_b.release();
   for (DevBuf *b : { &m->query.rays, &m->query.ranges, &m->query.volumes, &m->query.types, &m->query.keys,
-                     &m->query.walked, &m->query.last_walked, &m->query.scan_temp, &m->query.cursor,
+                     &m->query.walked, &m->query.last_walked, &m->query.scan_temp,
                      &m->query.spill_keys, &m->query.spill_blocks, &m->query.hm_winner, &m->query.hm_rec_occ,
                      &m->query.hm_rec_vox, &m->query.hm_rec_mean, &m->query.hm_counts, &m->query.hm_out_occ,
                      &m->query.hm_out_vox, &m->query.hm_out_mean, &m->query.hm_out_col })
@@ -1137,12 +1137,16 @@ OHMHIP_ABI_CATCH
 
 namespace
 {
-/// The table of the host store's regions the query kernels read (QuerySpillTable; empty without spill to host).
-int querySpillTable(ohmhip_map_t m, QuerySpillTable &spill)
+/// The map as the read-only kernels see it (MapReadView): configuration, region hash, occupancy layer and the table of
+/// the host store's regions (QuerySpillTable; empty without spill to host).
+int mapReadView(ohmhip_map_t m, MapReadView &view)
 {
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
-  spill = QuerySpillTable{ nullptr, nullptr, 0 };
+  view.mc = m->mc;
+  view.rt = regionTable(m);
+  view.occupancy = static_cast<const float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
+  view.spill = QuerySpillTable{ nullptr, nullptr, 0 };
   if (!m->spilled.empty())
   {
     // Regions in the host store answer from their pinned records (device visible), without re-admission.  The table is
@@ -1171,8 +1175,8 @@ int querySpillTable(ohmhip_map_t m, QuerySpillTable &spill)
     OHMHIP_CHECK(qs.spill_blocks.ensure(sizeof(const float *) * cap, false, s));
     OHMHIP_CHECK(hipMemcpy(qs.spill_keys.ptr, keys.data(), sizeof(unsigned long long) * cap, hipMemcpyHostToDevice));
     OHMHIP_CHECK(hipMemcpy(qs.spill_blocks.ptr, blocks.data(), sizeof(const float *) * cap, hipMemcpyHostToDevice));
-    spill = QuerySpillTable{ static_cast<const unsigned long long *>(qs.spill_keys.ptr),
-                             static_cast<const float *const *>(qs.spill_blocks.ptr), cap - 1 };
+    view.spill = QuerySpillTable{ static_cast<const unsigned long long *>(qs.spill_keys.ptr),
+                                  static_cast<const float *const *>(qs.spill_blocks.ptr), cap - 1 };
   }
   return OHMHIP_OK;
 }
@@ -1206,22 +1210,18 @@ int raysQueryDevice(ohmhip_map_t m, const double *d_rays, uint32_t n, double coe
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
   RaysQueryArgs a;
-  a.mc = m->mc;
-  a.rt = regionTable(m);
-  OHMHIP_CHECK(querySpillTable(m, a.spill));
+  OHMHIP_CHECK(mapReadView(m, a));
   if (n == 0)
   {
     return OHMHIP_OK;
   }
   OHMHIP_CHECK(qs.walked.ensure(sizeof(int32_t) * n, false, s));
   OHMHIP_CHECK(qs.last_walked.ensure(sizeof(int32_t) * n, false, s));
-  OHMHIP_CHECK(qs.cursor.ensure(sizeof(uint32_t), false, s));
   size_t scan_bytes = 0;
   int32_t *walked = static_cast<int32_t *>(qs.walked.ptr);
   int32_t *last_walked = static_cast<int32_t *>(qs.last_walked.ptr);
   OHMHIP_CHECK(rocprim::inclusive_scan(nullptr, scan_bytes, walked, last_walked, size_t(n), rocprim::maximum<int32_t>(), s));
   OHMHIP_CHECK(qs.scan_temp.ensure(scan_bytes, false, s));
-  a.occupancy = static_cast<const float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
   a.rays = d_rays;
   a.n_rays = n;
   a.coef = coef;
@@ -1230,20 +1230,7 @@ int raysQueryDevice(ohmhip_map_t m, const double *d_rays, uint32_t n, double coe
   a.types = d_types;
   a.keys = d_keys;
   a.walked = walked;
-  a.ray_cursor = static_cast<uint32_t *>(qs.cursor.ptr);
-  // OHMHIP_RAYS_QUERY_REFILL=1: the lane-refill variant (measured against one lane per ray)
-  const char *env = std::getenv("OHMHIP_RAYS_QUERY_REFILL");
-  const bool refill = env && std::atoi(env) != 0;
-  if (refill)
-  {
-    OHMHIP_CHECK(hipMemsetAsync(a.ray_cursor, 0, sizeof(uint32_t), s));
-    const uint32_t blocks = std::min<uint32_t>((n + 255) / 256, 2048u);
-    hipLaunchKernelGGL(k_rays_query<true>, dim3(blocks), dim3(256), 0, s, a);
-  }
-  else
-  {
-    hipLaunchKernelGGL(k_rays_query<false>, dim3((n + 255) / 256), dim3(256), 0, s, a);
-  }
+  hipLaunchKernelGGL(k_rays_query, dim3((n + 255) / 256), dim3(256), 0, s, a);
   OHMHIP_CHECK(hipGetLastError());
   OHMHIP_CHECK(rocprim::inclusive_scan(qs.scan_temp.ptr, scan_bytes, walked, last_walked, size_t(n),
                                        rocprim::maximum<int32_t>(), s));
@@ -1369,9 +1356,7 @@ int clearanceRegionsDevice(ohmhip_map_t m, ClearanceArgs &a, const int16_t *keys
   {
     return OHMHIP_OK;
   }
-  a.rt = regionTable(m);
-  a.occupancy = static_cast<const float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
-  OHMHIP_CHECK(querySpillTable(m, a.spill));
+  OHMHIP_CHECK(mapReadView(m, a));
   OHMHIP_CHECK(qs.clear_regions.ensure(sizeof(int16_t) * 3 * count, false, s));
   OHMHIP_CHECK(hipMemcpyAsync(qs.clear_regions.ptr, keys_xyz, sizeof(int16_t) * 3 * count, hipMemcpyHostToDevice, s));
   const int16_t *d_regions = static_cast<const int16_t *>(qs.clear_regions.ptr);
@@ -1499,9 +1484,7 @@ try
   }
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
-  a.rt = regionTable(m);
-  a.occupancy = static_cast<const float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
-  OHMHIP_CHECK(querySpillTable(m, a.spill));
+  OHMHIP_CHECK(mapReadView(m, a));
   OHMHIP_CHECK(qs.clear_keys.ensure(sizeof(GpuKeyOut) * count, false, s));
   OHMHIP_CHECK(qs.clear_out.ensure(sizeof(float) * count, false, s));
   OHMHIP_CHECK(hipMemcpyAsync(qs.clear_keys.ptr, keys, sizeof(GpuKeyOut) * count, hipMemcpyHostToDevice, s));

@@ -1,5 +1,7 @@
-// query_kernels.h -- RaysQueryGpu: read-only ray casts against the device-resident occupancy layer.
+// query_kernels.h -- the read side of the device-resident map: what every reader shares (MapReadView, mapFindTile, the
+// caller's GpuKeyOut), LineKeysQueryGpu and RaysQueryGpu, read-only ray casts against the occupancy layer.
 //
+//   k_line_keys         1 lane / line    the keys of every voxel on a line, in walk order
 //   k_rays_query        1 lane / ray     the CPU query's walk (ohm/RaysQuery.cpp:102-203 onExecute) over the pool
 //   k_rays_query_carry  1 lane / ray     the terminal type / key of rays that visit no voxel (see below)
 //
@@ -18,7 +20,6 @@
 #define OHMHIP_QUERY_KERNELS_H
 
 #include "occupancy_kernels.h"
-#include "replay_kernels.h"
 
 namespace ohmhip
 {
@@ -41,25 +42,100 @@ struct QuerySpillTable
   uint32_t mask;
 };
 
-struct RaysQueryArgs
+/// What a read-only kernel needs to find a voxel of the map: filled by mapReadView() on the host.
+struct MapReadView
 {
   MapConst mc;
   RegionTable rt;
   QuerySpillTable spill;
   const float *occupancy;  ///< pool layer: [slot][tile voxel]
-  const double *rays;      ///< [n_rays][6] origin, end point
-  uint32_t n_rays;
-  double coef;             ///< RaysQuery::volumeCoefficient()
-  double *ranges;
-  double *volumes;
-  int8_t *types;
-  GpuKeyOut *keys;         ///< null: not requested
-  int32_t *walked;         ///< [n_rays] the ray's index when it visited a voxel, -1 otherwise (max-scanned afterwards)
-  uint32_t *ray_cursor;    ///< refill variant: rays handed out beyond the first grid (zero at launch)
 };
 
-/// Idle lanes of a wave that make the refill variant fetch new rays (one atomic per wave).
-constexpr int kQueryRefillIdle = 16;
+/// Where mapFindTile found a tile: resident in pool slot `slot` (!= kSlotUnassigned), else in the host store with its
+/// occupancy block at `stored`, else (null) the map has no such tile.
+struct FoundTile
+{
+  uint32_t slot;
+  const float *stored;
+};
+
+/// Tile (tx, ty, tz) of the map: the device region hash, then the host store.
+__device__ inline FoundTile mapFindTile(const MapReadView &v, int tx, int ty, int tz)
+{
+  FoundTile t = { kSlotUnassigned, nullptr };
+  // (a region the reference addresses whose tile coordinates leave the packed key's 16-bit fields cannot be in the
+  // map: the key must not wrap onto another tile)
+  if (tx < -32768 || tx > 32767 || ty < -32768 || ty > 32767 || tz < -32768 || tz > 32767)
+  {
+    return t;
+  }
+  const uint64_t key = packRegionKey(tx, ty, tz);
+  const uint32_t h = regionFind(v.rt, key);
+  if (h != 0xffffffffu)
+  {
+    const uint32_t slot = v.rt.vals[h];
+    if (slot < v.rt.slot_capacity)
+    {
+      t.slot = slot;
+      return t;
+    }
+  }
+  if (v.spill.keys)
+  {
+    uint32_t idx = hashRegionKey(key, v.spill.mask);
+    for (uint32_t probe = 0; probe <= v.spill.mask; ++probe)
+    {
+      const unsigned long long k = v.spill.keys[idx];
+      if (k == key)
+      {
+        t.stored = v.spill.blocks[idx];
+        return t;
+      }
+      if (k == 0)
+      {
+        break;
+      }
+      idx = (idx + 1) & v.spill.mask;
+    }
+  }
+  return t;
+}
+
+/// The occupancy block of tile (tx, ty, tz); null when the map has no such tile.
+__device__ inline const float *queryTileBlock(const MapReadView &v, int tx, int ty, int tz)
+{
+  const FoundTile t = mapFindTile(v, tx, ty, tz);
+  return (t.slot != kSlotUnassigned) ? v.occupancy + size_t(t.slot) * size_t(v.mc.region_voxels) : t.stored;
+}
+
+/// GpuKey layout of the reference (ohmgpu/GpuKey.h:37-46): short region[3]; uchar voxel[4].
+struct GpuKeyOut
+{
+  int16_t region[3];
+  uint8_t voxel[4];
+};
+// The reference's record, from its own header compiled in place (tests/golden/ref_vectors.npz: gpukey_layout).
+static_assert(sizeof(GpuKeyOut) == 10 && alignof(GpuKeyOut) == 2 && offsetof(GpuKeyOut, region) == 0 &&
+                offsetof(GpuKeyOut, voxel) == 6,
+              "GpuKeyOut must keep the layout of ohm::GpuKey (ohmgpu/GpuKey.h:37-46)");
+
+/// The caller's key of global voxel (g0, g1, g2): split on the region edge, not the tile edge.
+__device__ inline GpuKeyOut callerKey(const MapConst &mc, int g0, int g1, int g2)
+{
+  int r0, r1, r2, l0, l1, l2;
+  splitGlobal(g0, mc.kdim[0], r0, l0);
+  splitGlobal(g1, mc.kdim[1], r1, l1);
+  splitGlobal(g2, mc.kdim[2], r2, l2);
+  GpuKeyOut k;
+  k.region[0] = int16_t(r0);
+  k.region[1] = int16_t(r1);
+  k.region[2] = int16_t(r2);
+  k.voxel[0] = uint8_t(l0);
+  k.voxel[1] = uint8_t(l1);
+  k.voxel[2] = uint8_t(l2);
+  k.voxel[3] = 0;
+  return k;
+}
 
 __device__ inline GpuKeyOut queryNullKey()
 {
@@ -69,54 +145,73 @@ __device__ inline GpuKeyOut queryNullKey()
   return k;
 }
 
-/// The occupancy block of tile (tx, ty, tz): resident slot, then the host store; null when the map has no such tile.
-/// Args: any argument block with mc, rt, spill and occupancy (RaysQueryArgs, ClearanceArgs).
-template <typename Args>
-__device__ inline const float *queryTileBlock(const Args &a, int tx, int ty, int tz)
+/// LineKeysQueryGpu / `calculateLines` (ohmgpu/gpu/LineKeys.cl:66-100) with the CPU walk's semantics
+/// (ohm/LineWalk.h:112-129 walkSegmentKeys, flags 0: start and end voxel included): one lane per query line writes the
+/// keys of every voxel on the line, in walk order.  counts[i] is the full number of voxels even when it exceeds
+/// max_keys_per_line (only the first max_keys_per_line keys are stored).
+__global__ void __launch_bounds__(256)
+  k_line_keys(MapConst mc, const double *__restrict__ lines, uint32_t n_lines, uint32_t max_keys_per_line,
+              GpuKeyOut *__restrict__ keys_out, uint32_t *__restrict__ counts)
 {
-  // (a region the reference addresses whose tile coordinates leave the packed key's 16-bit fields cannot be in the
-  // map: the key must not wrap onto another tile)
-  if (tx < -32768 || tx > 32767 || ty < -32768 || ty > 32767 || tz < -32768 || tz > 32767)
+  const uint32_t line = blockIdx.x * blockDim.x + threadIdx.x;
+  if (line >= n_lines)
   {
-    return nullptr;
+    return;
   }
-  const uint64_t key = packRegionKey(tx, ty, tz);
-  const uint32_t h = regionFind(a.rt, key);
-  if (h != 0xffffffffu)
+  double start[3], end[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
   {
-    const uint32_t slot = a.rt.vals[h];
-    if (slot < a.rt.slot_capacity)
+    start[a] = lines[size_t(line) * 6 + a];
+    end[a] = lines[size_t(line) * 6 + 3 + a];
+  }
+  MapConst nofilter = mc;
+  nofilter.filter_mode = OHMHIP_FILTER_NONE;
+  nofilter.batch_filter_flags = nullptr;
+  RayWalk rw;
+  setupRay(nofilter, start, end, OHMHIP_RF_END_POINT_AS_FREE, rw, line);
+  if (!(rw.flags & kRwValid))
+  {
+    counts[line] = 0;
+    return;
+  }
+  LaneWalk w;
+  laneStart(w, rw, 0, 0, 0);
+  uint32_t n = 0;
+  GpuKeyOut *out = keys_out + size_t(line) * max_keys_per_line;
+  while (true)
+  {
+    if (n < max_keys_per_line)
     {
-      return a.occupancy + size_t(slot) * size_t(a.mc.region_voxels);
+      out[n] = callerKey(mc, w.g0, w.g1, w.g2);
     }
-  }
-  if (a.spill.keys)
-  {
-    uint32_t idx = hashRegionKey(key, a.spill.mask);
-    for (uint32_t probe = 0; probe <= a.spill.mask; ++probe)
+    ++n;
+    if (laneFinished(w))
     {
-      const unsigned long long k = a.spill.keys[idx];
-      if (k == key)
-      {
-        return a.spill.blocks[idx];
-      }
-      if (k == 0)
-      {
-        break;
-      }
-      idx = (idx + 1) & a.spill.mask;
+      break;
     }
+    laneStep(w);
   }
-  return nullptr;
+  counts[line] = n;
 }
 
-/// One lane's query state: the CPU walk of one ray (k_line_keys' stepping) and the visit lambda's accumulators.
+struct RaysQueryArgs : MapReadView
+{
+  const double *rays;      ///< [n_rays][6] origin, end point
+  uint32_t n_rays;
+  double coef;             ///< RaysQuery::volumeCoefficient()
+  double *ranges;
+  double *volumes;
+  int8_t *types;
+  GpuKeyOut *keys;         ///< null: not requested
+  int32_t *walked;         ///< [n_rays] the ray's index when it visited a voxel, -1 otherwise (max-scanned afterwards)
+};
+
+/// One lane's query state: the CPU walk of one ray and the visit lambda's accumulators.
 struct QueryLane
 {
-  double init0, init1, init2, delta0, delta1, delta2;
-  double t0, t1, t2, k0, k1, k2;
+  LaneWalk w;
   double length, enter, volume;
-  int g0, g1, g2, rem0, rem1, rem2, d0, d1, d2;
   int tx, ty, tz;  ///< tile of `block`
   const float *block;
   float range;
@@ -163,27 +258,8 @@ __device__ inline bool queryStart(const RaysQueryArgs &a, uint32_t ray, QueryLan
     return false;
   }
   q.ray = ray;
-  q.init0 = rw.init[0];
-  q.init1 = rw.init[1];
-  q.init2 = rw.init[2];
-  q.delta0 = rw.delta[0];
-  q.delta1 = rw.delta[1];
-  q.delta2 = rw.delta[2];
+  laneStart(q.w, rw, 0, 0, 0);
   q.length = rw.length;
-  q.d0 = rwDir(rw, 0);
-  q.d1 = rwDir(rw, 1);
-  q.d2 = rwDir(rw, 2);
-  q.g0 = rw.g0[0];
-  q.g1 = rw.g0[1];
-  q.g2 = rw.g0[2];
-  q.rem0 = rw.total[0];
-  q.rem1 = rw.total[1];
-  q.rem2 = rw.total[2];
-  const double inf = dInf();
-  q.k0 = q.k1 = q.k2 = 0;
-  q.t0 = q.rem0 ? q.init0 : inf;
-  q.t1 = q.rem1 ? q.init1 : inf;
-  q.t2 = q.rem2 ? q.init2 : inf;
   q.enter = 0;
   q.volume = 0;
   q.range = 0.0f;
@@ -197,18 +273,15 @@ __device__ inline bool queryStart(const RaysQueryArgs &a, uint32_t ray, QueryLan
 __device__ inline bool queryStep(const RaysQueryArgs &a, QueryLane &q)
 {
   const MapConst &mc = a.mc;
-  const bool last = (q.rem0 | q.rem1 | q.rem2) == 0;
+  const bool last = laneFinished(q.w);
   // exit range: time_next of the axis walkSelectNextAxis picks (ohm/LineWalkCompute.h:282-289), the walk's length at
   // the end voxel
-  const bool c01 = q.t0 < q.t1;
-  const double t01 = c01 ? q.t0 : q.t1;
-  const bool c2 = t01 < q.t2;
-  const double exit = last ? q.length : (c2 ? t01 : q.t2);
+  const double exit = last ? q.length : laneExitTime(q.w);
 
   int tx, lx, ty, ly, tz, lz;
-  splitGlobal(q.g0, mc.dim[0], tx, lx);
-  splitGlobal(q.g1, mc.dim[1], ty, ly);
-  splitGlobal(q.g2, mc.dim[2], tz, lz);
+  splitGlobal(q.w.g0, mc.dim[0], tx, lx);
+  splitGlobal(q.w.g1, mc.dim[1], ty, ly);
+  splitGlobal(q.w.g2, mc.dim[2], tz, lz);
   if (tx != q.tx || ty != q.ty || tz != q.tz)
   {
     q.block = queryTileBlock(a, tx, ty, tz);
@@ -228,114 +301,25 @@ __device__ inline bool queryStep(const RaysQueryArgs &a, QueryLane &q)
 
   if (is_occupied || last)
   {
-    int r0, r1, r2, l0, l1, l2;  // the caller's region key
-    splitGlobal(q.g0, mc.kdim[0], r0, l0);
-    splitGlobal(q.g1, mc.kdim[1], r1, l1);
-    splitGlobal(q.g2, mc.kdim[2], r2, l2);
-    GpuKeyOut key;
-    key.region[0] = int16_t(r0);
-    key.region[1] = int16_t(r1);
-    key.region[2] = int16_t(r2);
-    key.voxel[0] = uint8_t(l0);
-    key.voxel[1] = uint8_t(l1);
-    key.voxel[2] = uint8_t(l2);
-    key.voxel[3] = 0;
-    queryWrite(a, q.ray, q.range, q.volume, q.type, key, true);
+    queryWrite(a, q.ray, q.range, q.volume, q.type, callerKey(mc, q.w.g0, q.w.g1, q.w.g2), true);
     return false;
   }
   q.enter = exit;
-  // ohm/LineWalkCompute.h:291-307 as k_line_keys steps it
-  const double inf = dInf();
-  if (!c2)
-  {
-    q.g2 += q.d2;
-    --q.rem2;
-    q.k2 += 1.0;
-    q.t2 = q.rem2 ? q.init2 + q.delta2 * q.k2 : inf;
-  }
-  else if (c01)
-  {
-    q.g0 += q.d0;
-    --q.rem0;
-    q.k0 += 1.0;
-    q.t0 = q.rem0 ? q.init0 + q.delta0 * q.k0 : inf;
-  }
-  else
-  {
-    q.g1 += q.d1;
-    --q.rem1;
-    q.k1 += 1.0;
-    q.t1 = q.rem1 ? q.init1 + q.delta1 * q.k1 : inf;
-  }
+  laneStep(q.w);
   return true;
 }
 
-/// kRefill = false: one lane per ray, the lane is done when its ray is (a wave waits for its longest ray).
-/// kRefill = true: lanes that finished pick the next ray from a device-wide cursor (one atomic per wave for all of its
-/// idle lanes, once kQueryRefillIdle of them are idle), the walk kernel's lane refill.
-template <bool kRefill>
+/// One lane per ray; the lane is done when its ray is (a wave waits for its longest ray).
 __global__ void __launch_bounds__(256) k_rays_query(RaysQueryArgs a)
 {
-  const uint32_t grid_lanes = gridDim.x * blockDim.x;
-  uint32_t ray = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t ray = blockIdx.x * blockDim.x + threadIdx.x;
   QueryLane q;
-  if (!kRefill)
+  if (ray >= a.n_rays || !queryStart(a, ray, q))
   {
-    if (ray >= a.n_rays || !queryStart(a, ray, q))
-    {
-      return;
-    }
-    while (queryStep(a, q))
-    {
-    }
     return;
   }
-  bool want = ray < a.n_rays;  // the lane holds a ray that is not set up yet
-  bool active = false;
-  bool exhausted = grid_lanes >= a.n_rays;
-  const uint32_t lane = threadIdx.x & 63u;
-  while (true)
+  while (queryStep(a, q))
   {
-    if (want)
-    {
-      want = false;
-      active = queryStart(a, ray, q);
-    }
-    const unsigned long long am = __ballot(active);
-    const int n_idle = 64 - __popcll(am);
-    if (n_idle >= kQueryRefillIdle)
-    {
-      if (exhausted)
-      {
-        if (am == 0)
-        {
-          break;
-        }
-      }
-      else
-      {
-        uint32_t base = 0;
-        if (lane == 0)
-        {
-          base = atomicAdd(a.ray_cursor, uint32_t(n_idle));
-        }
-        base = grid_lanes + __builtin_amdgcn_readfirstlane(base);
-        exhausted = base + uint32_t(n_idle) >= a.n_rays;
-        const unsigned long long idle = ~am;
-        const uint32_t mine =
-          base + __builtin_amdgcn_mbcnt_hi(uint32_t(idle >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(idle), 0u));
-        if (!active && mine < a.n_rays)
-        {
-          ray = mine;
-          want = true;
-        }
-        continue;
-      }
-    }
-    if (active)
-    {
-      active = queryStep(a, q);
-    }
   }
 }
 

@@ -642,24 +642,19 @@ __global__ void __launch_bounds__(256)
     s1 = stepsBefore(rw.init[1], rw.delta[1], 1.0 / rw.delta[1], rw.total[1], 1, 3, t_star);
     s2 = stepsBefore(rw.init[2], rw.delta[2], 1.0 / rw.delta[2], rw.total[2], 2, 3, t_star);
   }
-  const int d0 = rwDir(rw, 0), d1 = rwDir(rw, 1), d2 = rwDir(rw, 2);
-  int g0 = rw.g0[0] + d0 * s0, g1 = rw.g0[1] + d1 * s1, g2 = rw.g0[2] + d2 * s2;
-  int rem0 = rw.total[0] - s0, rem1 = rw.total[1] - s1, rem2 = rw.total[2] - s2;
-  const double inf = dInf();
-  double k0 = double(s0), k1 = double(s1), k2 = double(s2);
-  double t0 = rem0 ? ((s0 == 0) ? rw.init[0] : rw.init[0] + rw.delta[0] * k0) : inf;
-  double t1 = rem1 ? ((s1 == 0) ? rw.init[1] : rw.init[1] + rw.delta[1] * k1) : inf;
-  double t2 = rem2 ? ((s2 == 0) ? rw.init[2] : rw.init[2] + rw.delta[2] * k2) : inf;
+  LaneWalk w;
+  laneStart(w, rw, s0, s1, s2);
   uint64_t cached_key = 0;
   uint32_t cached_slot = kSlotUnassigned;
   const uint32_t mask_words = uint32_t(mc.region_voxels + 31) >> 5;
   while (true)
   {
     int r0, r1, r2, l0, l1, l2;
-    splitGlobal(g0, mc.dim[0], r0, l0);
-    splitGlobal(g1, mc.dim[1], r1, l1);
-    splitGlobal(g2, mc.dim[2], r2, l2);
-    const D3 centre = d3(globalVoxelCentreAxis(mc, 0, g0), globalVoxelCentreAxis(mc, 1, g1), globalVoxelCentreAxis(mc, 2, g2));
+    splitGlobal(w.g0, mc.dim[0], r0, l0);
+    splitGlobal(w.g1, mc.dim[1], r1, l1);
+    splitGlobal(w.g2, mc.dim[2], r2, l2);
+    const D3 centre =
+      d3(globalVoxelCentreAxis(mc, 0, w.g0), globalVoxelCentreAxis(mc, 1, w.g1), globalVoxelCentreAxis(mc, 2, w.g2));
     const float sdf = tsdfComputeDistance(sensor, sample, centre);
     if (sdf < kTsdfFreeMargin * mc.tsdf_trunc)
     {
@@ -682,34 +677,11 @@ __global__ void __launch_bounds__(256)
         }
       }
     }
-    if ((rem0 | rem1 | rem2) == 0)
+    if (laneFinished(w))
     {
       break;
     }
-    const bool c01 = t0 < t1;
-    const double t01 = c01 ? t0 : t1;
-    const bool c2 = t01 < t2;
-    if (!c2)
-    {
-      g2 += d2;
-      --rem2;
-      k2 += 1.0;
-      t2 = rem2 ? rw.init[2] + rw.delta[2] * k2 : inf;
-    }
-    else if (c01)
-    {
-      g0 += d0;
-      --rem0;
-      k0 += 1.0;
-      t0 = rem0 ? rw.init[0] + rw.delta[0] * k0 : inf;
-    }
-    else
-    {
-      g1 += d1;
-      --rem1;
-      k1 += 1.0;
-      t1 = rem1 ? rw.init[1] + rw.delta[1] * k1 : inf;
-    }
+    laneStep(w);
   }
 }
 
@@ -745,107 +717,6 @@ __global__ void __launch_bounds__(256)
     }
     hit_mask[size_t(slot) * mask_words + w] = bits;
   }
-}
-/// GpuKey layout of the reference (ohmgpu/GpuKey.h:37-46): short region[3]; uchar voxel[4].
-struct GpuKeyOut
-{
-  int16_t region[3];
-  uint8_t voxel[4];
-};
-// The reference's record, from its own header compiled in place (tests/golden/ref_vectors.npz: gpukey_layout).
-static_assert(sizeof(GpuKeyOut) == 10 && alignof(GpuKeyOut) == 2 && offsetof(GpuKeyOut, region) == 0 &&
-                offsetof(GpuKeyOut, voxel) == 6,
-              "GpuKeyOut must keep the layout of ohm::GpuKey (ohmgpu/GpuKey.h:37-46)");
-
-/// LineKeysQueryGpu / `calculateLines` (ohmgpu/gpu/LineKeys.cl:66-100) with the CPU walk's semantics
-/// (ohm/LineWalk.h:112-129 walkSegmentKeys, flags 0: start and end voxel included): one lane per query line writes the
-/// keys of every voxel on the line, in walk order.  counts[i] is the full number of voxels even when it exceeds
-/// max_keys_per_line (only the first max_keys_per_line keys are stored).
-__global__ void __launch_bounds__(256)
-  k_line_keys(MapConst mc, const double *__restrict__ lines, uint32_t n_lines, uint32_t max_keys_per_line,
-              GpuKeyOut *__restrict__ keys_out, uint32_t *__restrict__ counts)
-{
-  const uint32_t line = blockIdx.x * blockDim.x + threadIdx.x;
-  if (line >= n_lines)
-  {
-    return;
-  }
-  double start[3], end[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-  {
-    start[a] = lines[size_t(line) * 6 + a];
-    end[a] = lines[size_t(line) * 6 + 3 + a];
-  }
-  MapConst nofilter = mc;
-  nofilter.filter_mode = OHMHIP_FILTER_NONE;
-  nofilter.batch_filter_flags = nullptr;
-  RayWalk rw;
-  setupRay(nofilter, start, end, OHMHIP_RF_END_POINT_AS_FREE, rw, line);
-  if (!(rw.flags & kRwValid))
-  {
-    counts[line] = 0;
-    return;
-  }
-  const int d0 = rwDir(rw, 0), d1 = rwDir(rw, 1), d2 = rwDir(rw, 2);
-  int g0 = rw.g0[0], g1 = rw.g0[1], g2 = rw.g0[2];
-  int rem0 = rw.total[0], rem1 = rw.total[1], rem2 = rw.total[2];
-  const double inf = dInf();
-  double k0 = 0, k1 = 0, k2 = 0;
-  double t0 = rem0 ? rw.init[0] : inf;
-  double t1 = rem1 ? rw.init[1] : inf;
-  double t2 = rem2 ? rw.init[2] : inf;
-  uint32_t n = 0;
-  GpuKeyOut *out = keys_out + size_t(line) * max_keys_per_line;
-  while (true)
-  {
-    if (n < max_keys_per_line)
-    {
-      int r0, r1, r2, l0, l1, l2;  // the caller's region key: region edge, not tile edge
-      splitGlobal(g0, mc.kdim[0], r0, l0);
-      splitGlobal(g1, mc.kdim[1], r1, l1);
-      splitGlobal(g2, mc.kdim[2], r2, l2);
-      GpuKeyOut k;
-      k.region[0] = int16_t(r0);
-      k.region[1] = int16_t(r1);
-      k.region[2] = int16_t(r2);
-      k.voxel[0] = uint8_t(l0);
-      k.voxel[1] = uint8_t(l1);
-      k.voxel[2] = uint8_t(l2);
-      k.voxel[3] = 0;
-      out[n] = k;
-    }
-    ++n;
-    if ((rem0 | rem1 | rem2) == 0)
-    {
-      break;
-    }
-    const bool c01 = t0 < t1;
-    const double t01 = c01 ? t0 : t1;
-    const bool c2 = t01 < t2;
-    if (!c2)
-    {
-      g2 += d2;
-      --rem2;
-      k2 += 1.0;
-      t2 = rem2 ? rw.init[2] + rw.delta[2] * k2 : inf;
-    }
-    else if (c01)
-    {
-      g0 += d0;
-      --rem0;
-      k0 += 1.0;
-      t0 = rem0 ? rw.init[0] + rw.delta[0] * k0 : inf;
-    }
-    else
-    {
-      g1 += d1;
-      --rem1;
-      k1 += 1.0;
-      t1 = rem1 ? rw.init[1] + rw.delta[1] * k1 : inf;
-    }
-  }
-  counts[line] = n;
 }
 }  // namespace ohmhip
 

@@ -1,5 +1,8 @@
-// walk_device.h -- fp64 device maths shared by the gfx950 kernels: voxel keys, voxel centres, line-walk set-up and
-// the closed-form "resume the walk at step (axis, j)" that lets a region workgroup pick a ray up mid-walk.
+// walk_device.h -- fp64 device maths shared by the gfx950 kernels: voxel keys, voxel centres, line-walk set-up, the
+// closed-form "resume the walk at step (axis, j)" that lets a region workgroup pick a ray up mid-walk, the exact
+// next-axis decision (timeNext / nextAxis / exactNextAxis) and LaneWalk, the one voxel-by-voxel walker of the kernels
+// that walk a whole ray in one lane (k_line_keys, k_tsdf_flag, k_rays_query).  The key maths (hostInt ... voxelCentreAxis)
+// is __host__ __device__: the host computes its keys with the very functions the kernels use.
 //
 // Everything here follows the CPU instantiation of the reference's shared compute headers (WalkReal = double) with
 // the same operation order; the library is compiled with -ffp-contract=off so no FMA is formed, and fp64 divide /
@@ -19,19 +22,19 @@ __device__ inline double dInf()
 /// double -> int the way the host the reference runs on does it (x86 cvttsd2si): values outside the int range and
 /// NaN give INT_MIN, where the device conversion would saturate.  Only matters for absurd inputs (points 10^5 km from
 /// the map origin), but those still have to produce the same keys as the CPU mapper.
-__device__ inline int hostInt(double v)
+__host__ __device__ inline int hostInt(double v)
 {
   return (v >= -2147483648.0 && v < 2147483648.0) ? int(v) : int(0x80000000u);
 }
 
 /// ohm/MapCoord.h:85-93
-__device__ inline int pointToRegionCoord(double coord, double resolution)
+__host__ __device__ inline int pointToRegionCoord(double coord, double resolution)
 {
   return hostInt(floor(coord / resolution + 0.5));
 }
 
 /// ohm/MapCoord.h:45-80
-__device__ inline int pointToRegionVoxel(double coord, double voxel_resolution, double region_resolution)
+__host__ __device__ inline int pointToRegionVoxel(double coord, double voxel_resolution, double region_resolution)
 {
   const double epsilon = double(1e-6f);
   if (-epsilon <= coord && coord < 0)
@@ -51,8 +54,8 @@ __device__ inline int pointToRegionVoxel(double coord, double voxel_resolution, 
 /// @param[out] local Local voxel coordinate per axis.
 /// @param[out] beyond_tiles Optional: set when the point is addressable in the reference's sense and only the tile
 ///   coordinates of a map cut into tiles leave the key's range.
-__device__ inline bool voxelKey(const MapConst &mc, const double p[3], int region[3], int local[3],
-                                bool *beyond_tiles = nullptr)
+__host__ __device__ inline bool voxelKey(const MapConst &mc, const double p[3], int region[3], int local[3],
+                                         bool *beyond_tiles = nullptr)
 {
   bool ok = true;
   bool tiles_ok = true;
@@ -83,13 +86,13 @@ __device__ inline bool voxelKey(const MapConst &mc, const double p[3], int regio
 
 /// Key::isNull() is "all three region coordinates == int16 lowest" (ohm/Key.h:206): that one corner region reads as
 /// null -- for the line walk -- even when the point is addressable.
-__device__ inline bool keyIsNull(bool addressable, const int region[3])
+__host__ __device__ inline bool keyIsNull(bool addressable, const int region[3])
 {
   return !addressable || (region[0] == -32768 && region[1] == -32768 && region[2] == -32768);
 }
 
 /// ohm/OccupancyMap.h:757-778 (one axis).
-__device__ inline double voxelCentreAxis(const MapConst &mc, int a, int region, int local)
+__host__ __device__ inline double voxelCentreAxis(const MapConst &mc, int a, int region, int local)
 {
   double v = double(float(region));
   v *= mc.region_dim[a];
@@ -156,12 +159,33 @@ __device__ inline bool stepPrecedes(double tb, int b, double ta, int a)
   return tb < ta || (tb == ta && b > a);
 }
 
+/// time_next of one axis after k steps along it (ohm/LineWalkCompute.h:299-301, :375-378).
+__device__ inline double timeNext(double init, double delta, int k, int total)
+{
+  return (k < total) ? ((k == 0) ? init : init + delta * double(k)) : dInf();
+}
+
+/// walkSelectNextAxis (ohm/LineWalkCompute.h:282-289): the axis with the smallest time_next, ties go to the higher axis.
+__device__ inline int nextAxis(double t0, double t1, double t2)
+{
+  const bool c01 = t0 < t1;
+  const double t01 = c01 ? t0 : t1;
+  const bool c2 = t01 < t2;
+  return c2 ? (c01 ? 0 : 1) : 2;
+}
+
 /// Select one of three per-axis values without indexing an array at run time (run-time indexed locals end up in
 /// scratch memory on gfx950; every per-axis quantity in the kernels is therefore a named scalar).
 template <typename T>
 __device__ inline T sel3(int axis, T v0, T v1, T v2)
 {
   return (axis == 0) ? v0 : ((axis == 1) ? v1 : v2);
+}
+
+template <typename T>
+__device__ inline T sel3(int axis, const T v[3])
+{
+  return (axis == 0) ? v[0] : ((axis == 1) ? v[1] : v[2]);
 }
 
 /// Number of steps already taken along axis b at the moment the j-th step of axis a (time ta) is about to be taken.
@@ -372,6 +396,106 @@ __device__ inline int rwSign(const RayWalk &rw, int a)
 __device__ inline int rwDir(const RayWalk &rw, int a)
 {
   return 1 - 2 * rwSign(rw, a);
+}
+
+/// Local voxel coordinates of voxel index `vi` of a region.
+__device__ inline void voxelLocal(const MapConst &mc, uint32_t vi, int &lx, int &ly, int &lz)
+{
+  const uint32_t dx = uint32_t(mc.dim[0]);
+  const uint32_t dxy = dx * uint32_t(mc.dim[1]);
+  lz = int(vi / dxy);
+  const uint32_t r = vi - uint32_t(lz) * dxy;
+  ly = int(r / dx);
+  lx = int(r - uint32_t(ly) * dx);
+}
+
+/// Steps a ray has taken along each axis when it stands in voxel `vi` of region (rx, ry, rz): the walk moves
+/// monotonically away from the start voxel on every axis.
+__device__ inline void stepsAtVoxel(const MapConst &mc, const RayWalk &rw, int rx, int ry, int rz, uint32_t vi, int &k0,
+                                    int &k1, int &k2)
+{
+  int lx, ly, lz;
+  voxelLocal(mc, vi, lx, ly, lz);
+  k0 = abs(rx * mc.dim[0] + lx - rw.g0[0]);
+  k1 = abs(ry * mc.dim[1] + ly - rw.g0[1]);
+  k2 = abs(rz * mc.dim[2] + lz - rw.g0[2]);
+}
+
+/// The exact decision of the reference walk for a ray standing in voxel `vi` of region (rx, ry, rz): the axis of the
+/// next step.
+__device__ inline int exactNextAxis(const MapConst &mc, const RayWalk &rw, int rx, int ry, int rz, uint32_t vi)
+{
+  int k0, k1, k2;
+  stepsAtVoxel(mc, rw, rx, ry, rz, vi, k0, k1, k2);
+  return nextAxis(timeNext(rw.init[0], rw.delta[0], k0, rw.total[0]), timeNext(rw.init[1], rw.delta[1], k1, rw.total[1]),
+                  timeNext(rw.init[2], rw.delta[2], k2, rw.total[2]));
+}
+
+/// The reference's walk (ohm/LineWalkCompute.h:282-307), voxel by voxel, for the kernels that give a ray a lane of its
+/// own.  Named scalars per axis: see sel3.
+struct LaneWalk
+{
+  double init0, init1, init2, delta0, delta1, delta2;
+  double t0, t1, t2;           ///< time_next
+  double k0, k1, k2;           ///< steps taken (a whole number; kept as the double the step multiplies by)
+  int rem0, rem1, rem2;        ///< steps left
+  int g0, g1, g2;              ///< the current voxel, global coordinates
+  int d0, d1, d2;              ///< step direction
+};
+
+/// The walk of `rw` after s0, s1, s2 steps along the axes (a valid prefix of the walk; zeros: its start voxel).
+__device__ inline void laneStart(LaneWalk &w, const RayWalk &rw, int s0, int s1, int s2)
+{
+  w.init0 = rw.init[0], w.init1 = rw.init[1], w.init2 = rw.init[2];
+  w.delta0 = rw.delta[0], w.delta1 = rw.delta[1], w.delta2 = rw.delta[2];
+  w.rem0 = rw.total[0] - s0, w.rem1 = rw.total[1] - s1, w.rem2 = rw.total[2] - s2;
+  w.d0 = rwDir(rw, 0), w.d1 = rwDir(rw, 1), w.d2 = rwDir(rw, 2);
+  w.k0 = double(s0), w.k1 = double(s1), w.k2 = double(s2);
+  w.g0 = rw.g0[0] + w.d0 * s0, w.g1 = rw.g0[1] + w.d1 * s1, w.g2 = rw.g0[2] + w.d2 * s2;
+  w.t0 = timeNext(w.init0, w.delta0, s0, rw.total[0]);
+  w.t1 = timeNext(w.init1, w.delta1, s1, rw.total[1]);
+  w.t2 = timeNext(w.init2, w.delta2, s2, rw.total[2]);
+}
+
+/// The lane stands in the walk's last voxel.
+__device__ inline bool laneFinished(const LaneWalk &w)
+{
+  return (w.rem0 | w.rem1 | w.rem2) == 0;
+}
+
+/// The time at which the walk leaves the current voxel: the time_next of the axis the next step takes (+inf in the
+/// last voxel).
+__device__ inline double laneExitTime(const LaneWalk &w)
+{
+  const double t01 = (w.t0 < w.t1) ? w.t0 : w.t1;  // (nextAxis' comparisons: the value it selects)
+  return (t01 < w.t2) ? t01 : w.t2;
+}
+
+/// One step along one axis: timeNext() after k >= 1 steps, with k carried as a double (no conversion per step).
+__device__ inline void laneStepAxis(int &g, int d, double &k, int &rem, double &t, double init, double delta)
+{
+  g += d;
+  --rem;
+  k += 1.0;
+  t = rem ? init + delta * k : dInf();
+}
+
+/// One voxel on (not in the last voxel).
+__device__ inline void laneStep(LaneWalk &w)
+{
+  const int axis = nextAxis(w.t0, w.t1, w.t2);
+  if (axis == 2)
+  {
+    laneStepAxis(w.g2, w.d2, w.k2, w.rem2, w.t2, w.init2, w.delta2);
+  }
+  else if (axis == 0)
+  {
+    laneStepAxis(w.g0, w.d0, w.k0, w.rem0, w.t0, w.init0, w.delta0);
+  }
+  else
+  {
+    laneStepAxis(w.g1, w.d1, w.k1, w.rem1, w.t1, w.init1, w.delta1);
+  }
 }
 }  // namespace ohmhip
 

@@ -181,6 +181,26 @@ def test_cull_box(gpu):
     map_, gm = scene()
     check(gm, map_, params(cull_min=(-1.05, -2.0, 0.0), cull_max=(2.55, 1.33, 0.0)), "cull xy")
     check(gm, map_, params(cull_min=(0.0, -2.0, -0.3), cull_max=(0.0, 1.33, 0.6), virtual_surface=True), "cull yz")
+    # A cull box far from the origin of a map whose regions are cut into tiles (64^3: 8 tiles along z; no rays, one
+    # uploaded region).  Region 20000 along z is addressable by the caller's int16 key while its tile coordinates,
+    # 160000..160007, are beyond the packed tile key: the extents are the caller's keys and must not notice.
+    far = OccupancyMap(0.1, (64, 64, 64), layers=("occupancy",))
+    block = np.full(64 ** 3, np.inf, dtype=np.float32)
+    block[0] = np.float32(far.hit_value)
+    far.chunks[(0, 0, 0)] = {"occupancy": block}
+    far_gm = GpuMap(far)
+    far_gm.uploadRegions([(0, 0, 0)])
+    z = 20000 * 6.4
+    p = params(up_axis=1, reference_pos=(1.15, 0.0, z), cull_min=(1.0, -0.2, z - 0.15), cull_max=(1.3, 0.2, z + 0.15))
+    hm, want = check(far_gm, far, p, "far tiled", surface=False)
+    src, e = source_of(far), hm.extents
+    assert want is not None and src.split(want.min_ext)[0][2] == 20000 and want.na > 1 and want.nb > 1
+    assert e.populated == 1
+    assert (tuple(e.min_region), tuple(e.min_local)[:3]) == src.split(want.min_ext)
+    assert (tuple(e.max_region), tuple(e.max_local)[:3]) == src.split(want.max_ext)
+    first = [divmod(c, p.region_size) for c in want.first_cell]
+    assert tuple(e.first_region) == (first[0][0], first[1][0])
+    assert tuple(e.first_local) == (first[0][1], first[1][1])
 
 
 @pytest.mark.parametrize("reference_pos", [(0.0, 0.0, 2.5), (0.0, 0.0, 1.2), (0.0, 0.0, -0.7), (0.0, 0.0, -30.0),

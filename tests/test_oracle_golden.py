@@ -67,7 +67,7 @@ def test_golden_gpukey_layout():
     assert np.array_equal(raw[:, 6:10], G["gpukey_voxels"])
     # the library's own record and the C++ host mirror's declare the same members in the same order
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "ohm_amd", "csrc", "replay_kernels.h")).read()
+    src = open(os.path.join(root, "ohm_amd", "csrc", "query_kernels.h")).read()
     assert "static_assert(sizeof(GpuKeyOut) == 10" in src and "offsetof(GpuKeyOut, voxel) == 6" in src
 
 
