@@ -632,6 +632,76 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_heightmap_device(ohmhip_map_t map, const ohmh
                                                     float *d_occupancy, void *d_voxels24, void *d_mean8,
                                                     uint32_t *d_source_column, uint64_t *d_counts);
 
+/* POINT CLOUDS.  The voxels of the map that pass a test, as points, compacted on the device: what ohmtools::saveCloud,
+ * saveDensityCloud, saveTsdfCloud and saveClearanceCloud (ohmtools/OhmCloud.cpp, driven by ohm2ply) collect on the host
+ * after downloading every layer they read.  Only the points cross to the host.  A point is a position (3 doubles), the
+ * caller's voxel key (10-byte GpuKey layout: int16 region[3], uint8 voxel[4], voxel[3] = 0) and one float value.
+ *  OCCUPANCY (saveCloud, OhmCloud.cpp:453-493).  Passes: isOccupied, v != +inf && v >= threshold (ohm/VoxelOccupancy.h:
+ *    161-164); with OHMHIP_CLOUD_EXPORT_FREE also isFree, v != +inf && v < threshold.  A NaN passes neither.  Position:
+ *    the mean position when the map has the mean layer and OHMHIP_CLOUD_IGNORE_VOXEL_MEAN is off, else voxelCentreGlobal.
+ *    The mean position is positionSafe (ohm/VoxelMean.h:47-54): voxelCentreGlobal(key) + subVoxelToLocalCoord(mean.coord,
+ *    resolution), which decodes a coord of 0 like any other (ohm/VoxelMeanCompute.h:112 tests a constant) -- a free voxel
+ *    exported with the mean layer lands on the decoded position of coord 0, half a voxel below its centre on every axis.  Value: the
+ *    occupancy value.
+ *  DENSITY (the rule saveDensityCloud is documented to apply: ohm/Density.h:34-55, SaveDensityCloudOptions; the function
+ *    as written never sets the key of the voxels it reads, OhmCloud.cpp:524-538, so its output specifies nothing).
+ *    density = count > 0 ? (traversal > 0 ? float(count) / traversal : +inf) : 0 with count the mean layer's sample
+ *    count.  Passes: density >= density_threshold -- with a threshold of 0 every voxel of every region.  Needs the
+ *    traversal and mean layers.  Position: the mean position, or voxelCentreGlobal with IGNORE_VOXEL_MEAN.  Value: the
+ *    density.
+ *  TSDF (saveTsdfCloud, :950-987).  Passes: weight > 0 && fabsf(distance) < surface_distance.  Position: voxelCentreLocal,
+ *    the centre with a map origin of zero (ohm/OccupancyMap.h:757-778, OccupancyMap.cpp:849-852).  Value: the distance.
+ *  CLEARANCE (saveClearanceCloud, :879-947).  Needs the occupancy and clearance layers.  Passes: occupancyType(v) >=
+ *    export_type with unobserved -1, free 0, occupied 1 (ohm/VoxelOccupancy.h:116-128: a NaN is unobserved), and then
+ *    range >= 0, where range is the clearance value, replaced by colour_range when negative.  Position:
+ *    voxelCentreLocal.  Value: the range after the replacement.
+ *  EXTENTS.  With OHMHIP_CLOUD_USE_EXTENTS, in any mode, only regions whose key lies per axis within [regionKey(
+ *    min_extents), regionKey(max_extents)] take part (ohm/OccupancyMap.cpp:746-750, MapRegion.cpp:32-38), with every
+ *    voxel of theirs, as saveClearanceCloud does.
+ *  A map without a layer its mode needs yields 0 points and OHMHIP_OK (the reference returns 0).
+ *  ORDER.  The reference iterates a hash map; this library fixes the order: regions ascending by (rz, ry, rx), voxels
+ *    of a region ascending by MapChunk index x + y * dx + z * dx * dy -- for a region cut into tiles too.  Two calls on
+ *    the same map state return identical bytes.
+ * The map is observed as the heightmap observes it -- collected rays launched, an asynchronous launch settled, regions
+ * of the host store from their pinned records, keys and positions in the caller's region coordinates -- and nothing of
+ * it changes: no voxel, dirty bit, residency, use stamp or cache counter.
+ * *count is always the number of ALL matching voxels; the arrays receive the first min(count, capacity) points.
+ * capacity == 0 (null arrays) only counts.  OHMHIP_ERR_INVALID_ARG, before any device work, for null params, a null
+ * map, a null count, mode > 3, unknown flag bits, a NaN density_threshold / surface_distance / colour_range, non-finite
+ * extents under USE_EXTENTS and capacity > 0 with null positions; OHMHIP_ERR_UNSUPPORTED for a map with region ownership
+ * or a partition (a rank holds only its territory). */
+#define OHMHIP_CLOUD_OCCUPANCY 0
+#define OHMHIP_CLOUD_DENSITY 1
+#define OHMHIP_CLOUD_TSDF 2
+#define OHMHIP_CLOUD_CLEARANCE 3
+#define OHMHIP_CLOUD_EXPORT_FREE (1u << 0)       /* SaveCloudOptions::export_free */
+#define OHMHIP_CLOUD_IGNORE_VOXEL_MEAN (1u << 1) /* SaveCloudOptions::ignore_voxel_mean */
+#define OHMHIP_CLOUD_USE_EXTENTS (1u << 2)
+/* Voxels per unit of device work: a region's block is cut into chunks of this many consecutive voxels (tests place
+ * voxels on its edges). */
+#define OHMHIP_CLOUD_CHUNK_VOXELS 4096
+typedef struct ohmhip_cloud_params
+{
+  double min_extents[3], max_extents[3]; /* USE_EXTENTS */
+  float density_threshold;               /* DENSITY */
+  float surface_distance;                /* TSDF */
+  float colour_range;                    /* CLEARANCE */
+  int32_t export_type;                   /* CLEARANCE: -1 unobserved and up, 0 free and up, 1 occupied */
+  uint32_t flags;                        /* OHMHIP_CLOUD_* flag bits */
+  uint8_t mode;                          /* OHMHIP_CLOUD_OCCUPANCY .. OHMHIP_CLOUD_CLEARANCE */
+} ohmhip_cloud_params;
+/* The number of matching voxels. */
+int ohmhip_map_cloud_count(ohmhip_map_t map, const ohmhip_cloud_params *params, uint64_t *count);
+/* The cloud into host arrays of `capacity` points: positions_xyz 3 doubles each, keys10 (nullable) 10 bytes each,
+ * values (nullable).  Synchronous. */
+int ohmhip_map_cloud(ohmhip_map_t map, const ohmhip_cloud_params *params, uint64_t capacity, double *positions_xyz,
+                     void *keys10, float *values, uint64_t *count);
+/* The same into DEVICE arrays, enqueued on the map's stream; ohmhip_map_sync is the fence.  d_count: one uint64 on the
+ * device. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_cloud_device(ohmhip_map_t map, const ohmhip_cloud_params *params, uint64_t capacity,
+                                                double *d_positions_xyz, void *d_keys10, float *d_values,
+                                                uint64_t *d_count);
+
 /* GpuTransformSamples::transform (ohmgpu/GpuTransformSamples.h:75-79, .cpp:97-210; kernel transformTimestampedPoints,
  * ohmgpu/gpu/TransformSamples.cl:94-228): sensor-frame samples with time stamps + a timestamped trajectory (translations
  * xyz, rotations as quaternions x,y,z,w) -> world-frame ray pairs (sensor origin, sample), 6 doubles per valid sample,

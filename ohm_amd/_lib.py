@@ -67,6 +67,18 @@ class HeightmapExtents(C.Structure):
 HM_GENERATE_VIRTUAL_SURFACE, HM_PROMOTE_VIRTUAL_BELOW, HM_IGNORE_VOXEL_MEAN = 1, 2, 4
 
 
+class CloudParams(C.Structure):
+    """ohmhip_cloud_params"""
+    _fields_ = [("min_extents", C.c_double * 3), ("max_extents", C.c_double * 3), ("density_threshold", C.c_float),
+                ("surface_distance", C.c_float), ("colour_range", C.c_float), ("export_type", C.c_int32),
+                ("flags", C.c_uint32), ("mode", C.c_uint8)]
+
+
+CLOUD_OCCUPANCY, CLOUD_DENSITY, CLOUD_TSDF, CLOUD_CLEARANCE = range(4)
+CLOUD_EXPORT_FREE, CLOUD_IGNORE_VOXEL_MEAN, CLOUD_USE_EXTENTS = 1, 2, 4
+CLOUD_CHUNK_VOXELS = 4096  # OHMHIP_CLOUD_CHUNK_VOXELS
+
+
 class MapConfig(C.Structure):
     _fields_ = [("resolution", C.c_double), ("region_dim", C.c_int * 3), ("origin", C.c_double * 3),
                 ("layers", C.c_uint), ("mode", C.c_int), ("hit_value", C.c_float), ("miss_value", C.c_float),
@@ -180,6 +192,9 @@ _sigs = {
     "ohmhip_map_heightmap": (C.c_int, [_vp, C.POINTER(HeightmapParams), _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]),
     "ohmhip_map_heightmap_device": (C.c_int, [_vp, C.POINTER(HeightmapParams), _vp, _vp, _vp, _vp, _vp]),
+    "ohmhip_map_cloud_count": (C.c_int, [_vp, C.POINTER(CloudParams), C.POINTER(C.c_uint64)]),
+    "ohmhip_map_cloud": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "ohmhip_map_cloud_device": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, _vp]),
     "ohmhip_map_device_layer_ptr": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "ohmhip_map_region_slot": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "ohmhip_map_ensure_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

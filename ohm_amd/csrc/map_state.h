@@ -244,6 +244,8 @@ struct ohmhip_map_s
     DevBuf clear_regions, clear_keys, clear_out, clear_mask;  ///< clearance queries (clearance_kernels.h)
     /// heightmap (heightmap_kernels.h): per-cell winner, per-column records, counters; device copies of the host arrays
     DevBuf hm_winner, hm_rec_occ, hm_rec_vox, hm_rec_mean, hm_counts, hm_out_occ, hm_out_vox, hm_out_mean, hm_out_col;
+    /// point clouds (cloud_kernels.h): the work list, per-wave counts and their scan; device copies of the host arrays
+    DevBuf cloud_chunks, cloud_partials, cloud_offsets, cloud_scan_temp, cloud_pos, cloud_keys, cloud_values;
   } query;
   /// The clearance layer's bookkeeping (clearance_update.h), by the caller's region key -- so it needs no care when a
   /// region changes slot, leaves the pool or comes back.  An update folds the kDirtyClearance bits into `changed` at a

@@ -9,6 +9,7 @@
 #include "query_kernels.h"
 #include "clearance_kernels.h"
 #include "heightmap_kernels.h"
+#include "cloud_kernels.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -397,7 +398,9 @@ try
                      &m->query.walked, &m->query.last_walked, &m->query.scan_temp,
                      &m->query.spill_keys, &m->query.spill_blocks, &m->query.hm_winner, &m->query.hm_rec_occ,
                      &m->query.hm_rec_vox, &m->query.hm_rec_mean, &m->query.hm_counts, &m->query.hm_out_occ,
-                     &m->query.hm_out_vox, &m->query.hm_out_mean, &m->query.hm_out_col })
+                     &m->query.hm_out_vox, &m->query.hm_out_mean, &m->query.hm_out_col, &m->query.cloud_chunks,
+                     &m->query.cloud_partials, &m->query.cloud_offsets, &m->query.cloud_scan_temp, &m->query.cloud_pos,
+                     &m->query.cloud_keys, &m->query.cloud_values })
   {
     b->release();
   }
@@ -1528,3 +1531,4 @@ OHMHIP_ABI_CATCH
 #include "tiling_impl.h"
 #include "clearance_update.h"
 #include "heightmap_impl.h"
+#include "cloud_impl.h"

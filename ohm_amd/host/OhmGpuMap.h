@@ -2035,6 +2035,93 @@ private:
   int last_status_ = OHMHIP_OK;
 };
 
+/// What a point cloud is made of (include/ohmhip.h, "POINT CLOUDS").
+enum class CloudMode : uint8_t
+{
+  kOccupancy = OHMHIP_CLOUD_OCCUPANCY,  ///< ohmtools::saveCloud
+  kDensity = OHMHIP_CLOUD_DENSITY,      ///< ohmtools::saveDensityCloud, by the rule it documents
+  kTsdf = OHMHIP_CLOUD_TSDF,            ///< ohmtools::saveTsdfCloud
+  kClearance = OHMHIP_CLOUD_CLEARANCE   ///< ohmtools::saveClearanceCloud
+};
+
+/// The options of the reference's exporters (SaveCloudOptions, SaveDensityCloudOptions and the arguments of
+/// saveTsdfCloud / saveClearanceCloud) under their names.
+struct CloudOptions
+{
+  CloudMode mode = CloudMode::kOccupancy;
+  bool export_free = false;
+  bool ignore_voxel_mean = false;
+  float density_threshold = 0.0f;
+  float surface_distance = std::numeric_limits<float>::infinity();
+  float colour_range = 0.0f;
+  int export_type = 0;       ///< ohm::OccupancyType: -1 unobserved and up, 0 free and up, 1 occupied
+  bool use_extents = false;  ///< only regions from regionKey(min_extents) to regionKey(max_extents)
+  dvec3 min_extents{ 0, 0, 0 }, max_extents{ 0, 0, 0 };
+};
+
+/// ohm::GpuKey (ohmgpu/GpuKey.h:37-46)
+struct CloudKey
+{
+  int16_t region[3];
+  uint8_t voxel[4];
+};
+static_assert(sizeof(CloudKey) == 10, "CloudKey keeps the 10-byte GpuKey layout");
+
+/// The points of a cloud in the library's fixed order -- regions ascending by (z, y, x), voxels by MapChunk index --
+/// and the number of all matching voxels.
+struct VoxelCloud
+{
+  std::vector<dvec3> positions;
+  std::vector<CloudKey> keys;
+  std::vector<float> values;
+  uint64_t count = 0;
+  int status = OHMHIP_OK;
+};
+
+/// The cloud of `gpu_map`'s device map, compacted on the device: a count call, then arrays of exactly that size.
+inline VoxelCloud extractCloud(GpuMap &gpu_map, const CloudOptions &options = CloudOptions())
+{
+  VoxelCloud cloud;
+  if (!gpu_map.gpuOk() || !gpu_map.syncConfig())
+  {
+    cloud.status = OHMHIP_ERR_INVALID_ARG;
+    return cloud;
+  }
+  ohmhip_cloud_params p{};
+  p.mode = uint8_t(options.mode);
+  p.flags = (options.export_free ? OHMHIP_CLOUD_EXPORT_FREE : 0u) |
+            (options.ignore_voxel_mean ? OHMHIP_CLOUD_IGNORE_VOXEL_MEAN : 0u) |
+            (options.use_extents ? OHMHIP_CLOUD_USE_EXTENTS : 0u);
+  p.density_threshold = options.density_threshold;
+  p.surface_distance = options.surface_distance;
+  p.colour_range = options.colour_range;
+  p.export_type = int32_t(options.export_type);
+  const double lo[3] = { options.min_extents.x, options.min_extents.y, options.min_extents.z };
+  const double hi[3] = { options.max_extents.x, options.max_extents.y, options.max_extents.z };
+  for (int i = 0; i < 3; ++i)
+  {
+    p.min_extents[i] = lo[i];
+    p.max_extents[i] = hi[i];
+  }
+  cloud.status = ohmhip_map_cloud_count(gpu_map.handle(), &p, &cloud.count);
+  if (cloud.status != OHMHIP_OK || cloud.count == 0)
+  {
+    return cloud;
+  }
+  static_assert(sizeof(dvec3) == 3 * sizeof(double), "positions are written as 3 doubles a point");
+  const uint64_t capacity = cloud.count;
+  cloud.positions.resize(size_t(capacity));
+  cloud.keys.resize(size_t(capacity));
+  cloud.values.resize(size_t(capacity));
+  cloud.status = ohmhip_map_cloud(gpu_map.handle(), &p, capacity, &cloud.positions[0].x, cloud.keys.data(),
+                                  cloud.values.data(), &cloud.count);
+  const size_t held = (cloud.status == OHMHIP_OK) ? size_t(std::min(cloud.count, capacity)) : 0;
+  cloud.positions.resize(held);
+  cloud.keys.resize(held);
+  cloud.values.resize(held);
+  return cloud;
+}
+
 /// ohm::configureGpu / gpuDevice (ohmgpu/OhmGpu.h:40-66): select the process-wide device.
 inline int configureGpu(int device_index = 0)
 {

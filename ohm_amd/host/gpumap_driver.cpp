@@ -3,7 +3,7 @@
 // (tests/ohmtestgpu/GpuMapTest.cpp:68-205), syncs, and dumps every region layer for the Python parity test to check
 // against the CPU oracle.  Links libohmhip.so only; built with plain g++ (no hipcc, no glm).
 //
-//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|heightmap|transform|...> <resolution> <batch_rays>
+//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|heightmap|cloud|transform|...> <resolution> <batch_rays>
 //                 <rays.bin> <out.bin> [search radius] [query flags]
 //   occdev: the sample points (odd entries) go through ohm::GpuTransformSamples with a static identity trajectory and
 //   are integrated straight from the device buffer (all rays then start at the origin).
@@ -416,6 +416,45 @@ int main(int argc, char **argv)
       std::fwrite(heightmap.occupancy().data(), sizeof(float), heightmap.occupancy().size(), out);
       std::fwrite(heightmap.heightmapVoxels().data(), sizeof(ohm::HeightmapVoxel), heightmap.heightmapVoxels().size(), out);
       std::fwrite(heightmap.voxelMeans().data(), sizeof(ohm::VoxelMean), heightmap.voxelMeans().size(), out);
+      std::fclose(out);
+      return 0;
+    }
+
+    if (mode == "cloud")
+    {
+      // ohm::extractCloud: the map (occupancy + mean) is built by ohm::GpuMap::integrateRays in batches, still collected
+      // by batch coalescing when the cloud is asked for; [search radius] != 0 exports free voxels too.  out.bin = u64
+      // count, u64 points, then the positions (3 f64 each), the keys (10 bytes each) and the values (f32).
+      ohm::OccupancyMap cloud_map(resolution);
+      cloud_map.addLayer(OHMHIP_LID_MEAN);
+      ohm::GpuMap cloud_gpu_map(&cloud_map, true);
+      const size_t step = std::max<size_t>(2, batch_rays * 2);
+      for (size_t at = 0; at + 1 < rays.size(); at += step)
+      {
+        const size_t count = std::min(step, (rays.size() - at) & ~size_t(1));
+        if (cloud_gpu_map.integrateRays(rays.data() + at, count) != count)
+        {
+          return 8;
+        }
+      }
+      ohm::CloudOptions options;
+      options.export_free = argc > 6 && std::atof(argv[6]) != 0.0;
+      const ohm::VoxelCloud cloud = ohm::extractCloud(cloud_gpu_map, options);
+      if (cloud.status != OHMHIP_OK)
+      {
+        return 8;
+      }
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      const uint64_t points = cloud.positions.size();
+      std::fwrite(&cloud.count, sizeof(cloud.count), 1, out);
+      std::fwrite(&points, sizeof(points), 1, out);
+      std::fwrite(cloud.positions.data(), sizeof(ohm::dvec3), cloud.positions.size(), out);
+      std::fwrite(cloud.keys.data(), sizeof(ohm::CloudKey), cloud.keys.size(), out);
+      std::fwrite(cloud.values.data(), sizeof(float), cloud.values.size(), out);
       std::fclose(out);
       return 0;
     }
