@@ -27,7 +27,7 @@ struct BatchRun
   uint32_t n_rays;
   unsigned ray_flags;
   hipStream_t s, f;
-  hipEvent_t *tev;
+  const Event *tev;
   uint32_t ring;  ///< this batch's entry of the timing ring
   // decided once per call
   uint32_t next_info_index = 0;
@@ -121,13 +121,13 @@ struct BatchRun
       ray_flags = OHMHIP_RF_END_POINT_AS_FREE;
     }
     ray_shift = occupancy_mode ? 0 : kEvRayShift;
-    sec.traversal = tsdf_mode ? nullptr : static_cast<float *>(m->layers[OHMHIP_LID_TRAVERSAL]);
-    sec.touch_time = tsdf_mode ? nullptr : static_cast<uint32_t *>(m->layers[OHMHIP_LID_TOUCH_TIME]);
-    sec.incident = tsdf_mode ? nullptr : static_cast<uint32_t *>(m->layers[OHMHIP_LID_INCIDENT]);
+    sec.traversal = tsdf_mode ? nullptr : static_cast<float *>(m->pool.layers[OHMHIP_LID_TRAVERSAL].get());
+    sec.touch_time = tsdf_mode ? nullptr : static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_TOUCH_TIME].get());
+    sec.incident = tsdf_mode ? nullptr : static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_INCIDENT].get());
     sec.timestamps = d_timestamps;
     sec.time_base = m->first_ray_time;
-    occ_inline = occupancy_mode && !m->layers[OHMHIP_LID_MEAN] && !sec.traversal && !sec.touch_time && !sec.incident &&
-                 !m->layers[OHMHIP_LID_INTENSITY] && !m->layers[OHMHIP_LID_HIT_MISS];
+    occ_inline = occupancy_mode && !m->pool.layers[OHMHIP_LID_MEAN] && !sec.traversal && !sec.touch_time && !sec.incident &&
+                 !m->pool.layers[OHMHIP_LID_INTENSITY] && !m->pool.layers[OHMHIP_LID_HIT_MISS];
 
     for (int p = 0; p < 2; ++p)
     {
@@ -160,14 +160,14 @@ struct BatchRun
     {
       hipExtLaunchKernelGGL(k_ray_bin<kLtabSmall>, dim3(bin_blocks), dim3(bin_threads), 0, s, nullptr, tev[1], 0, m->mc,
                             regionTable(m), batchScratch(m), static_cast<const RayWalk *>(batchWalks(m).ptr), n_rays,
-                            static_cast<Segment *>(m->segments.ptr), seg_capacity, hit_keys, m->d_hit_mask, ray_shift,
+                            static_cast<Segment *>(m->segments.ptr), seg_capacity, hit_keys, m->pool.d_hit_mask.get(), ray_shift,
                             bucket ? 1 : 0, bin_rays_per_block, bin_tab_mask);
     }
     else
     {
       hipExtLaunchKernelGGL(k_ray_bin<kLtabSize>, dim3(bin_blocks), dim3(bin_threads), 0, s, nullptr, tev[1], 0, m->mc,
                             regionTable(m), batchScratch(m), static_cast<const RayWalk *>(batchWalks(m).ptr), n_rays,
-                            static_cast<Segment *>(m->segments.ptr), seg_capacity, hit_keys, m->d_hit_mask, ray_shift,
+                            static_cast<Segment *>(m->segments.ptr), seg_capacity, hit_keys, m->pool.d_hit_mask.get(), ray_shift,
                             bucket ? 1 : 0, bin_rays_per_block, bin_tab_mask);
     }
     mark(1);
@@ -190,7 +190,7 @@ struct BatchRun
     if (need_dense)
     {
       hipExtLaunchKernelGGL((k_sort_region_hits<kSortRegionHits, kSortThreads>), dim3(2 * m->walk_workgroups),
-                            dim3(kSortThreads), 0, s, nullptr, kSortSmallHits ? nullptr : tev[2], 0, regionTable(m),
+                            dim3(kSortThreads), 0, s, nullptr, kSortSmallHits ? nullptr : tev[2].handle, 0, regionTable(m),
                             batchScratch(m), in, out, m->mc.region_voxels, kSortSmallHits);
     }
     if (kSortSmallHits)
@@ -259,7 +259,7 @@ struct BatchRun
     // stamps reach the host with the summary -- a copy queued behind the plan, so there the wait is on an event
     // recorded behind that copy.)
     hipExtLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, f, nullptr, tev[5], 0, regionTable(m), batchScratch(m),
-                          batchChunks(m), m->chunk_capacity, batch_chunk_segments, m->h_info_dev,
+                          batchChunks(m), m->pool.chunk_capacity, batch_chunk_segments, m->h_info.dev,
                           m->d_info + next_info_index, batchEventCount(m), occ_inline ? walkLdsHits() : 0u);
     mark(5);
     m->info_clean = true;
@@ -295,8 +295,8 @@ struct BatchRun
 
   bool exhausted() const
   {
-    return (info.error & (kErrSlotsFull | kErrHashFull)) || info.n_slots > m->slot_capacity ||
-           info.n_chunks > m->chunk_capacity;
+    return (info.error & (kErrSlotsFull | kErrHashFull)) || info.n_slots > m->pool.slot_capacity ||
+           info.n_chunks > m->pool.chunk_capacity;
   }
 
   /// Pool / chunk list exhausted.  Returns an error when the batch fails (the map is as it was before the call) and
@@ -323,7 +323,7 @@ struct BatchRun
         // batch.  (The failed attempt's k_plan stamped the regions this batch touches: they go last.)
         const uint64_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
         const uint64_t allowed =
-          m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->slot_capacity;
+          m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->pool.slot_capacity;
         const uint64_t wanted = uint64_t(info.n_slots);  // committed + the batch's new regions
         // (the one cause integrateRaysDevice answers by presenting the batch in halves: the batch ALONE does not fit)
         m->batch_exceeds_limit = wanted > allowed && wanted - allowed > m->slots_committed;
@@ -449,7 +449,7 @@ struct BatchRun
       if (tsdf_mode)
       {
         hipExtLaunchKernelGGL(k_tsdf_flag, dim3(ray_blocks), dim3(256), 0, s, nullptr, tev[2], 0, m->mc, regionTable(m),
-                              static_cast<const RayWalk *>(batchWalks(m).ptr), d_rays, n_rays, m->d_hit_mask);
+                              static_cast<const RayWalk *>(batchWalks(m).ptr), d_rays, n_rays, m->pool.d_hit_mask.get());
         mark(2);
         m->tev_pre_walk[ring] = 2;
       }
@@ -479,7 +479,7 @@ struct BatchRun
   int walk(int first_attempt = 0)
   {
     // Single-chunk regions are applied by the walk kernel straight from LDS (plain log-odds misses only).
-    direct_occ = (occupancy_mode || mode == OHMHIP_MODE_NDT_OM) ? static_cast<float *>(m->layers[OHMHIP_LID_OCCUPANCY]) :
+    direct_occ = (occupancy_mode || mode == OHMHIP_MODE_NDT_OM) ? static_cast<float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get()) :
                                                                   nullptr;
     direct_segments = (direct_occ || tsdf_mode) ? batch_chunk_segments : 0u;
     n_events = 0;
@@ -497,10 +497,10 @@ struct BatchRun
         wa.chunks = batchChunks(m);
         wa.segments = static_cast<const Segment *>(m->segments.ptr);
         wa.walks = static_cast<const RayWalk *>(batchWalks(m).ptr);
-        wa.slot_keys = m->d_slot_keys;
+        wa.slot_keys = m->pool.d_slot_keys;
         wa.sorted_hits = sorted;
-        wa.hit_mask = m->d_hit_mask;
-        wa.miss_counts = m->d_miss_counts;
+        wa.hit_mask = m->pool.d_hit_mask;
+        wa.miss_counts = m->pool.d_miss_counts;
         wa.interval_counts = static_cast<uint32_t *>(m->interval_counts.ptr);
         wa.events = events;
         wa.event_capacity = event_capacity;
@@ -510,7 +510,7 @@ struct BatchRun
         wa.ray_shift = ray_shift;
         wa.defer_all = occupancy_mode ? 0 : 1;
         wa.occupancy = direct_occ;
-        wa.tsdf = tsdf_mode ? static_cast<float *>(m->layers[OHMHIP_LID_TSDF]) : nullptr;
+        wa.tsdf = tsdf_mode ? static_cast<float *>(m->pool.layers[OHMHIP_LID_TSDF].get()) : nullptr;
         wa.ray_flags = ray_flags;
         const bool trace = (m->debug_flags & (16u | 64u | 128u)) != 0;
         wa.dbg_counters = trace ? m->d_dbg : nullptr;
@@ -532,7 +532,7 @@ struct BatchRun
         const dim3 wblock(m->walk_half ? WalkHalf::kThreads : WalkFull::kThreads);
         const size_t wlds = walkLdsBytes(m->mc, m->chunk_segments, m->walk_half);
         // tev[3] -- the end of the walk phase -- is the stop event of the phase's last kernel.
-        hipEvent_t walk_stop = traversal_pass ? nullptr : tev[3];
+        hipEvent_t walk_stop = traversal_pass ? nullptr : tev[3].handle;
         if (m->walk_half)
         {
           if (special)
@@ -567,8 +567,8 @@ struct BatchRun
           ta.chunks = wa.chunks;
           ta.segments = wa.segments;
           ta.walks = wa.walks;
-          ta.slot_keys = m->d_slot_keys;
-          ta.traversal_acc = m->d_traversal_acc;
+          ta.slot_keys = m->pool.d_slot_keys;
+          ta.traversal_acc = m->pool.d_traversal_acc;
           ta.unit_bits = traversalUnitBits(m->mc.resolution);
           ta.refill_min_idle = 16;  // (8: +8 %, 32: the same, measured on C1)
           ta.chunk_cursor = batchEventCount(m) + 3;  // (k_plan zeroes it; the stop-flag replay that shares the word runs later)
@@ -584,9 +584,9 @@ struct BatchRun
           if (info.max_region_hits > walkLdsHits())
           {
             hipLaunchKernelGGL(k_flagged_events, dim3(4096), dim3(256), 0, s, batchScratch(m), events, event_capacity,
-                               batchEventCount(m), sorted, m->d_miss_counts,
+                               batchEventCount(m), sorted, m->pool.d_miss_counts,
                                static_cast<uint32_t *>(m->interval_counts.ptr), m->mc.region_voxels,
-                               reinterpret_cast<uint32_t *>(m->h_info_dev + 1));
+                               reinterpret_cast<uint32_t *>(m->h_info.dev + 1));
           }
           else
           {
@@ -603,7 +603,7 @@ struct BatchRun
         {
           spec_events = uint32_t(std::min<uint64_t>(event_capacity, uint64_t(m->event_demand) + m->event_demand / 8u + 4096u));
           hipExtLaunchKernelGGL(k_pad_events, dim3(256), dim3(256), 0, s, nullptr, m->ev[5], 0, events, batchEventCount(m),
-                                spec_events, reinterpret_cast<uint32_t *>(m->h_info_dev + 1));
+                                spec_events, reinterpret_cast<uint32_t *>(m->h_info.dev + 1));
           events_speculated = true;
           n_events = spec_events;
           break;
@@ -637,7 +637,7 @@ struct BatchRun
   int recoverEventOverflow()
   {
     hipLaunchKernelGGL(k_clear_counts, dim3(info.n_touched), dim3(256), 0, s, m->mc, regionTable(m), batchScratch(m),
-                       m->d_miss_counts);
+                       m->pool.d_miss_counts);
     const size_t total = size_t(n_rays) + size_t(n_events) + (size_t(n_events) >> 3) + 1024;
     OHMHIP_CHECK(m->hit_keys_a.ensure(sizeof(unsigned long long) * total, false, s));
     OHMHIP_CHECK(m->hit_keys_b.ensure(sizeof(unsigned long long) * total, false, s));
@@ -659,8 +659,8 @@ struct BatchRun
     // sort + apply in C1; the sample replay wants small workgroups and few registers.)
     // (tev[4], the end of the batch, is the stop event of its last kernel: what the set-up pass of the batch after the
     // next waits for before it reuses this batch's scratch copy)
-    float *occ = static_cast<float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
-    uint32_t *mean_layer = static_cast<uint32_t *>(m->layers[OHMHIP_LID_MEAN]);
+    float *occ = static_cast<float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get());
+    uint32_t *mean_layer = static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_MEAN].get());
     uint32_t *intervals = static_cast<uint32_t *>(m->interval_counts.ptr);
     const RayWalk *walks = static_cast<const RayWalk *>(batchWalks(m).ptr);
     if (occ_inline)
@@ -675,13 +675,13 @@ struct BatchRun
       if (hit_blocks + info.n_apply_counts)
       {
         hipLaunchKernelGGL(k_apply_lists, dim3(hit_blocks + info.n_apply_counts * kApplyListParts), dim3(256), 0, s, m->mc,
-                           regionTable(m), batchScratch(m), ray_flags, sorted, intervals, m->d_miss_counts, m->d_hit_mask,
+                           regionTable(m), batchScratch(m), ray_flags, sorted, intervals, m->pool.d_miss_counts, m->pool.d_hit_mask,
                            d_rays, occ, hit_blocks, blocks_per_region, hit_tiles);
       }
       if (info.n_touched)
       {
         hipExtLaunchKernelGGL(k_batch_cleanup, dim3(std::min<uint32_t>(info.n_touched, 4096u)), dim3(256), 0, s, nullptr,
-                              tev[4], 0, m->mc, regionTable(m), batchScratch(m), info.n_touched, m->d_hit_mask);
+                              tev[4], 0, m->mc, regionTable(m), batchScratch(m), info.n_touched, m->pool.d_hit_mask.get());
       }
       else
       {
@@ -694,15 +694,15 @@ struct BatchRun
     // One launch with a workgroup per region that receives samples, and the count application shared by eight
     // workgroups per region, were both measured slower in round 5 -- 1.01 and 0.93 against 0.91 ms per C1 batch: short-lived
     // workgroups that leave after three dependent loads cost more than the idle lanes they replace)
-    hipExtLaunchKernelGGL(k_apply_hits, dim3(ray_blocks), dim3(256), 0, s, nullptr, info.n_touched ? nullptr : tev[4], 0,
-                          m->mc, regionTable(m), batchScratch(m), ray_flags, sorted, intervals, m->d_miss_counts, d_rays,
+    hipExtLaunchKernelGGL(k_apply_hits, dim3(ray_blocks), dim3(256), 0, s, nullptr, info.n_touched ? nullptr : tev[4].handle, 0,
+                          m->mc, regionTable(m), batchScratch(m), ray_flags, sorted, intervals, m->pool.d_miss_counts.get(), d_rays,
                           occ, mean_layer, sec, walks);
     if (info.n_touched)
     {
       hipExtLaunchKernelGGL(k_apply_counts, dim3(info.n_touched), dim3(1024), 0, s, nullptr, tev[4], 0, m->mc,
-                            regionTable(m), batchScratch(m), ray_flags, m->d_miss_counts, m->d_hit_mask, occ, 1,
+                            regionTable(m), batchScratch(m), ray_flags, m->pool.d_miss_counts.get(), m->pool.d_hit_mask.get(), occ, 1,
                             static_cast<uint32_t *>(nullptr), direct_segments, 0, sec.traversal,
-                            sec.traversal ? m->d_traversal_acc : nullptr);
+                            sec.traversal ? m->pool.d_traversal_acc.get() : nullptr);
     }
     batch_end_marked = true;
     return OHMHIP_OK;
@@ -748,17 +748,17 @@ struct BatchRun
       const bool tm = mode == OHMHIP_MODE_NDT_TM;
       hipLaunchKernelGGL(k_replay_ndt, dim3(replay_blocks), dim3(128), 0, s, m->mc, regionTable(m), sorted,
                          uint32_t(total), d_rays, d_intensities,
-                         static_cast<float *>(m->layers[OHMHIP_LID_OCCUPANCY]),
-                         static_cast<uint32_t *>(m->layers[OHMHIP_LID_MEAN]),
-                         static_cast<float *>(m->layers[OHMHIP_LID_COVARIANCE]),
-                         tm ? static_cast<float *>(m->layers[OHMHIP_LID_INTENSITY]) : nullptr,
-                         tm ? static_cast<uint32_t *>(m->layers[OHMHIP_LID_HIT_MISS]) : nullptr, sec,
+                         static_cast<float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get()),
+                         static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_MEAN].get()),
+                         static_cast<float *>(m->pool.layers[OHMHIP_LID_COVARIANCE].get()),
+                         tm ? static_cast<float *>(m->pool.layers[OHMHIP_LID_INTENSITY].get()) : nullptr,
+                         tm ? static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_HIT_MISS].get()) : nullptr, sec,
                          static_cast<const RayWalk *>(batchWalks(m).ptr), replay_heads, n_heads, guard_count, guard_limit);
     }
     else if (tsdf_mode)
     {
       hipLaunchKernelGGL(k_replay_tsdf, dim3(replay_blocks), dim3(128), 0, s, m->mc, regionTable(m), sorted,
-                         uint32_t(total), d_rays, static_cast<float *>(m->layers[OHMHIP_LID_TSDF]), replay_heads, n_heads,
+                         uint32_t(total), d_rays, static_cast<float *>(m->pool.layers[OHMHIP_LID_TSDF].get()), replay_heads, n_heads,
                          guard_count, guard_limit);
     }
     return OHMHIP_OK;
@@ -806,8 +806,8 @@ struct BatchRun
       OHMHIP_CHECK(hipMemsetAsync(stop_next, 0xff, sizeof(uint32_t) * size_t(n_rays), s));
       uint32_t *d_changed = batchEventCount(m) + 3;
       const RayWalk *walks = static_cast<const RayWalk *>(batchWalks(m).ptr);
-      float *occ = static_cast<float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
-      uint32_t *mean_layer = static_cast<uint32_t *>(m->layers[OHMHIP_LID_MEAN]);
+      float *occ = static_cast<float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get());
+      uint32_t *mean_layer = static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_MEAN].get());
       bool settled = false;
       for (uint64_t scan = 0; scan <= uint64_t(n_rays) && !settled; ++scan)
       {
@@ -832,9 +832,9 @@ struct BatchRun
         // (with a traversal layer: the ray lengths the walk summed per voxel -- stopped rays keep adding theirs,
         // ohm/RayMapperOccupancy.cpp:166-173 runs for null updates too -- go into the layer here)
         hipLaunchKernelGGL(k_apply_counts, dim3(info.n_touched), dim3(1024), 0, s, m->mc, regionTable(m),
-                           batchScratch(m), ray_flags, m->d_miss_counts, m->d_hit_mask, occ, 1,
+                           batchScratch(m), ray_flags, m->pool.d_miss_counts, m->pool.d_hit_mask, occ, 1,
                            static_cast<uint32_t *>(nullptr), 0u, 1, sec.traversal,
-                           sec.traversal ? m->d_traversal_acc : static_cast<unsigned long long *>(nullptr));
+                           sec.traversal ? m->pool.d_traversal_acc : static_cast<unsigned long long *>(nullptr));
       }
     }
     else if (ndt_mode)
@@ -843,17 +843,17 @@ struct BatchRun
       if (info.n_touched)
       {
         hipLaunchKernelGGL(k_apply_counts, dim3(info.n_touched), dim3(1024), 0, s, m->mc, regionTable(m),
-                           batchScratch(m), 0u, m->d_miss_counts, m->d_hit_mask,
-                           static_cast<float *>(m->layers[OHMHIP_LID_OCCUPANCY]), 0,
-                           tm ? static_cast<uint32_t *>(m->layers[OHMHIP_LID_HIT_MISS]) : nullptr, direct_segments, 1,
-                           sec.traversal, sec.traversal ? m->d_traversal_acc : nullptr);
+                           batchScratch(m), 0u, m->pool.d_miss_counts, m->pool.d_hit_mask,
+                           static_cast<float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get()), 0,
+                           tm ? static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_HIT_MISS].get()) : nullptr, direct_segments, 1,
+                           sec.traversal, sec.traversal ? m->pool.d_traversal_acc : nullptr);
       }
     }
     else if (info.n_touched)
     {
       hipLaunchKernelGGL(k_apply_counts_tsdf, dim3(info.n_touched * kTsdfApplyParts), dim3(256), 0, s, m->mc, regionTable(m),
-                         batchScratch(m), m->d_miss_counts, m->d_hit_mask,
-                         static_cast<float *>(m->layers[OHMHIP_LID_TSDF]), direct_segments);
+                         batchScratch(m), m->pool.d_miss_counts, m->pool.d_hit_mask,
+                         static_cast<float *>(m->pool.layers[OHMHIP_LID_TSDF].get()), direct_segments);
       hipLaunchKernelGGL(k_batch_reset, dim3((info.n_touched + 255u) / 256u), dim3(256), 0, s, batchScratch(m),
                          info.n_touched);
     }

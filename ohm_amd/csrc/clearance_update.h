@@ -101,7 +101,7 @@ int clearanceFold(ohmhip_map_t m)
   std::vector<uint32_t> dirty(m->slots_committed);
   if (!dirty.empty())
   {
-    OHMHIP_CHECK(hipMemcpy(dirty.data(), m->d_dirty, sizeof(uint32_t) * dirty.size(), hipMemcpyDeviceToHost));
+    OHMHIP_CHECK(hipMemcpy(dirty.data(), m->pool.d_dirty, sizeof(uint32_t) * dirty.size(), hipMemcpyDeviceToHost));
   }
   bool any = false;
   for (size_t i = 0; i < dirty.size(); ++i)
@@ -114,8 +114,8 @@ int clearanceFold(ohmhip_map_t m)
   }
   if (any)
   {
-    hipLaunchKernelGGL(k_and_u32, dim3(256), dim3(256), 0, m->stream, m->d_dirty, ~kDirtyClearance,
-                       size_t(m->slot_capacity));
+    hipLaunchKernelGGL(k_and_u32, dim3(256), dim3(256), 0, m->stream, m->pool.d_dirty, ~kDirtyClearance,
+                       size_t(m->pool.slot_capacity));
     OHMHIP_CHECK(hipGetLastError());
   }
   for (auto &entry : m->spilled)
@@ -234,7 +234,7 @@ int clearanceProcess(ohmhip_map_t m, ClearanceArgs &a, const std::vector<uint64_
   const uint32_t batch = uint32_t(std::max<size_t>(1, std::min<size_t>(count, (size_t(256) << 20) / (sizeof(float) * kvox))));
   OHMHIP_CHECK(m->query.clear_out.ensure(sizeof(float) * kvox * batch, false, s));
   const float *d_out = static_cast<const float *>(m->query.clear_out.ptr);
-  char *layer = static_cast<char *>(m->layers[OHMHIP_LID_CLEARANCE]);
+  char *layer = static_cast<char *>(m->pool.layers[OHMHIP_LID_CLEARANCE].get());
   std::vector<int16_t> keys_xyz(3 * size_t(count));
   for (uint32_t i = 0; i < count; ++i)
   {
@@ -281,7 +281,7 @@ int clearanceProcess(ohmhip_map_t m, ClearanceArgs &a, const std::vector<uint64_
   {
     OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * slots.size(), false, s));
     OHMHIP_CHECK(hipMemcpyAsync(m->merge_slots.ptr, slots.data(), sizeof(uint32_t) * slots.size(), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, s, m->d_dirty, static_cast<const uint32_t *>(m->merge_slots.ptr),
+    hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, s, m->pool.d_dirty, static_cast<const uint32_t *>(m->merge_slots.ptr),
                        slots.size(), kDirtySync);
     OHMHIP_CHECK(hipGetLastError());
   }
@@ -302,7 +302,7 @@ int clearanceUpdateSetup(ohmhip_map_t m, const ohmhip_clearance_params *p, size_
 {
   static const char kAny = 0;
   OHMHIP_CHECK(clearanceSetup(m, keys, count, p, &kAny, a));
-  if (!m->layers[OHMHIP_LID_CLEARANCE])
+  if (!m->pool.layers[OHMHIP_LID_CLEARANCE])
   {
     return OHMHIP_ERR_UNSUPPORTED;
   }

@@ -71,7 +71,7 @@ int cloudWorkList(ohmhip_map_t m, const ohmhip_cloud_params *p, CloudArgs &a, st
   switch (a.mode)
   {
   case OHMHIP_CLOUD_OCCUPANCY:
-    a.use_mean = (m->layers[OHMHIP_LID_MEAN] && !(p->flags & OHMHIP_CLOUD_IGNORE_VOXEL_MEAN)) ? 1 : 0;
+    a.use_mean = (m->pool.layers[OHMHIP_LID_MEAN] && !(p->flags & OHMHIP_CLOUD_IGNORE_VOXEL_MEAN)) ? 1 : 0;
     aux_layer = a.use_mean ? OHMHIP_LID_MEAN : -1;
     break;
   case OHMHIP_CLOUD_DENSITY:
@@ -88,7 +88,7 @@ int cloudWorkList(ohmhip_map_t m, const ohmhip_cloud_params *p, CloudArgs &a, st
     aux_needed = true;
     break;
   }
-  if (!m->layers[sel_layer] || (aux_needed && !m->layers[aux_layer]))
+  if (!m->pool.layers[sel_layer] || (aux_needed && !m->pool.layers[aux_layer]))
   {
     return OHMHIP_OK;  // the reference returns 0 for a map without the layer
   }
@@ -150,7 +150,7 @@ int cloudWorkList(ohmhip_map_t m, const ohmhip_cloud_params *p, CloudArgs &a, st
   const size_t aux_bytes = (aux_layer >= 0) ? kLayerBytes[aux_layer] : 0;
   auto block = [&](const CloudTileSource &s, int layer) -> const char * {
     return (s.slot != kSlotUnassigned) ?
-             static_cast<const char *>(m->layers[layer]) + size_t(s.slot) * tile_voxels * kLayerBytes[layer] :
+             static_cast<const char *>(m->pool.layers[layer].get()) + size_t(s.slot) * tile_voxels * kLayerBytes[layer] :
              s.record + m->store.layer_offset[layer];
   };
   const uint32_t tiles_per_region = uint32_t(split_y * split_z);

@@ -32,7 +32,7 @@ int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->layers[OHMHIP_LID_OCCUPANCY])
+  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
   {
     return OHMHIP_ERR_UNSUPPORTED;
   }
@@ -57,7 +57,7 @@ int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, Heightma
   a.a = (up == 0) ? 1 : 0;
   a.b = (up == 2) ? 1 : 2;
   a.up_positive = up_axis >= 0;
-  a.use_mean = m->layers[OHMHIP_LID_MEAN] && !(p->flags & OHMHIP_HM_IGNORE_VOXEL_MEAN);
+  a.use_mean = m->pool.layers[OHMHIP_LID_MEAN] && !(p->flags & OHMHIP_HM_IGNORE_VOXEL_MEAN);
   e.use_mean = uint8_t(a.use_mean);
   a.generate_virtual = (p->flags & OHMHIP_HM_GENERATE_VIRTUAL_SURFACE) ? 1 : 0;
   a.flags = (a.generate_virtual ? kHmVirtualSurfaces : 0u) |
@@ -184,7 +184,7 @@ int heightmapDevice(ohmhip_map_t m, HeightmapArgs &a, float *d_occ, void *d_vox,
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
   OHMHIP_CHECK(mapReadView(m, a));
-  a.mean = a.use_mean ? static_cast<const uint2 *>(m->layers[OHMHIP_LID_MEAN]) : nullptr;
+  a.mean = a.use_mean ? static_cast<const uint2 *>(m->pool.layers[OHMHIP_LID_MEAN].get()) : nullptr;
   a.spill_mean_delta =
     (long long)(m->store.layer_offset[OHMHIP_LID_MEAN]) - (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
   const size_t columns = size_t(a.na) * size_t(a.nb);

@@ -16,10 +16,28 @@ inline uint32_t layerClearWord(int l)
   return (l == OHMHIP_LID_OCCUPANCY) ? 0x7f800000u : (l == OHMHIP_LID_CLEARANCE) ? 0xbf800000u : 0u;
 }
 
+// Owning types: every device buffer, pinned block, stream and event of the map is a member of one of these, so that
+// releasing it is a property of the member.  All are movable and not copyable.
+
+/// A device buffer that grows on demand (per-batch scratch, query staging).
 struct DevBuf
 {
   void *ptr = nullptr;
   size_t bytes = 0;
+
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr, o.bytes = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept
+  {
+    if (this != &o)
+    {
+      release();
+      ptr = o.ptr, bytes = o.bytes;
+      o.ptr = nullptr, o.bytes = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
 
   int ensure(size_t want, bool zero, hipStream_t stream)
   {
@@ -56,6 +74,122 @@ struct DevBuf
     bytes = 0;
   }
 };
+
+/// One handle with one owner: `Free` releases it when the owner dies or is given another.
+template <typename H, hipError_t (*Free)(H)>
+struct Owned
+{
+  H handle = nullptr;
+
+  Owned() = default;
+  Owned(Owned &&o) noexcept : handle(o.handle) { o.handle = nullptr; }
+  Owned &operator=(Owned &&o) noexcept
+  {
+    if (this != &o)
+    {
+      reset();
+      handle = o.handle;
+      o.handle = nullptr;
+    }
+    return *this;
+  }
+  ~Owned() { reset(); }
+
+  void reset()
+  {
+    if (handle)
+    {
+      (void)Free(handle);
+    }
+    handle = nullptr;
+  }
+};
+
+/// A device allocation of fixed size, read where a `T *` is expected.
+template <typename T>
+struct DevArray : Owned<void *, hipFree>
+{
+  hipError_t alloc(size_t bytes)
+  {
+    reset();
+    return hipMalloc(&handle, bytes);
+  }
+  T *get() const { return static_cast<T *>(handle); }
+  operator T *() const { return get(); }
+};
+
+/// A stream of the map's own.
+struct Stream : Owned<hipStream_t, hipStreamDestroy>
+{
+  hipError_t create()
+  {
+    reset();
+    return hipStreamCreateWithFlags(&handle, hipStreamNonBlocking);
+  }
+  operator hipStream_t() const { return handle; }
+};
+
+/// An event of the map's own.
+struct Event : Owned<hipEvent_t, hipEventDestroy>
+{
+  hipError_t create(unsigned flags = hipEventDefault)
+  {
+    reset();
+    return hipEventCreateWithFlags(&handle, flags);
+  }
+  operator hipEvent_t() const { return handle; }
+};
+
+/// A pinned host block, read where a `T *` is expected.  `dev` is the block's device address when it was allocated
+/// hipHostMallocMapped: an alias of the same memory, not owned.
+template <typename T>
+struct PinnedBuf
+{
+  T *ptr = nullptr;
+  T *dev = nullptr;
+
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf &&o) noexcept : ptr(o.ptr), dev(o.dev) { o.ptr = o.dev = nullptr; }
+  PinnedBuf &operator=(PinnedBuf &&o) noexcept
+  {
+    if (this != &o)
+    {
+      reset();
+      ptr = o.ptr, dev = o.dev;
+      o.ptr = o.dev = nullptr;
+    }
+    return *this;
+  }
+  ~PinnedBuf() { reset(); }
+
+  hipError_t alloc(size_t bytes, unsigned flags)
+  {
+    reset();
+    hipError_t err = hipHostMalloc(reinterpret_cast<void **>(&ptr), bytes, flags);
+    if (err == hipSuccess && (flags & hipHostMallocMapped))
+    {
+      err = hipHostGetDevicePointer(reinterpret_cast<void **>(&dev), ptr, 0);
+    }
+    return err;
+  }
+  void reset()
+  {
+    if (ptr)
+    {
+      (void)hipHostFree(ptr);
+    }
+    ptr = dev = nullptr;
+  }
+  T *get() const { return ptr; }
+  operator T *() const { return ptr; }
+};
+
+template <typename T>
+constexpr bool kMoveOnly = std::is_nothrow_move_constructible<T>::value && std::is_nothrow_move_assignable<T>::value &&
+                           !std::is_copy_constructible<T>::value && !std::is_copy_assignable<T>::value;
+static_assert(kMoveOnly<DevBuf> && kMoveOnly<DevArray<uint32_t>> && kMoveOnly<PinnedBuf<uint32_t>> && kMoveOnly<Stream> &&
+                kMoveOnly<Event>,
+              "the owning types move and do not copy");
 }  // namespace
 
 constexpr uint32_t kTimingRing = 32;
@@ -147,72 +281,80 @@ private:
 
 struct ohmhip_map_s
 {
+  /// Settles what is in flight (the launch thread, every stream), joins the map's threads; then the members release
+  /// themselves in reverse order of declaration -- the streams, declared first, last.
+  ~ohmhip_map_s();
+
   ohmhip_map_config config;
   MapConst mc;
   int device = 0;
-  hipStream_t stream = nullptr;       ///< compute stream
-  hipStream_t copy_stream = nullptr;  ///< side stream for region upload/download
-  hipStream_t wb_stream = nullptr;    ///< background write-back of the spill path (created on first use): its device-to-host
+  Stream stream;       ///< compute stream
+  Stream copy_stream;  ///< side stream for region upload/download
+  Stream wb_stream;    ///< background write-back of the spill path (created on first use): its device-to-host
                                       ///< copies must not delay the re-admissions queued on copy_stream
   /// Stream of a batch's set-up pass (k_ray_setup, k_plan).  It reads the rays and the region table only, and writes
   /// per-batch scratch that exists twice (see `parity`), so the set-up of batch N+1 runs beside the sample sort of batch
   /// N and in the CUs its walk kernel vacates.  It is idle whenever no batch call is in progress: every call waits for
   /// its own plan summary.
-  hipStream_t front_stream = nullptr;
+  Stream front_stream;
   /// Cross-stream ordering uses the STOP EVENTS of the kernels themselves (hipExtLaunchKernelGGL binds an event to the
   /// kernel's own completion signal: free), never a hipEventRecord behind a kernel -- on gfx950 / ROCm 7.2 a record is a
   /// barrier packet that idles the queue for 3-7 us before the next kernel starts (scripts/probes/event_probe.hip,
   /// profiles/r05_event_probe.txt; round 4 paid eight of them per batch).  The events live in the timing ring below.
+  /// (batch_done_event and bin_done_event name events of the timing ring `tev`: aliases, not owned)
   hipEvent_t batch_done_event[2] = { nullptr, nullptr };  ///< per parity: stop event of the last kernel of the batch that last used this scratch copy
   hipEvent_t bin_done_event = nullptr;  ///< stop event of the latest k_ray_bin
   uint32_t parity = 0;  ///< which copy of the doubled per-batch scratch (RayWalk array, per-hash / per-slot counters,
                         ///< chunk list, event counters) the current batch uses
-  hipEvent_t ev[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+  Event ev[8];
   /// Events of the last kTimingRing batches: [1] binned, [2] samples ordered (the kernel before the walk), [3] walked,
   /// [4] batch done, [5] plan done -- all stop events of kernels --, and with `phase_timing` [0] set-up pass starts, [6]
   /// binning starts (records: they cost the batch a few microseconds each).  tev_mask: which of them the batch recorded;
   /// tev_pre_walk: the event that marks the start of the batch's walk phase ([2], or [1] when nothing ran in between).
-  hipEvent_t tev[kTimingRing][7] = {};
+  Event tev[kTimingRing][7];
   uint8_t tev_mask[kTimingRing] = {};
   uint8_t tev_pre_walk[kTimingRing] = {};
   bool phase_timing = false;  ///< ohmhip_map_set_phase_timing / OHMHIP_PHASE_TIMING=1 / OHMHIP_DEBUG_FLAGS & 256
   uint64_t batch_seq = 0;
 
-  uint32_t slot_capacity = 0;
-  uint32_t hash_capacity = 0;
   uint32_t slots_committed = 0;  ///< slots in use after the last successful batch / upload
 
-  void *layers[OHMHIP_LID_COUNT] = {};
-  unsigned long long *d_keys = nullptr;
-  uint32_t *d_vals = nullptr;
-  uint64_t *d_slot_keys = nullptr;
-  uint32_t *d_n_slots = nullptr;
-  // scratch
-  uint32_t *d_hit_count = nullptr, *d_sort_list = nullptr;
-  uint32_t *d_seg_count = nullptr, *d_seg_cursor = nullptr, *d_seg_offset = nullptr, *d_touched_flag = nullptr,
-           *d_touched = nullptr;
-  uint32_t *d_voxel_first_hit = nullptr, *d_hit_begin = nullptr, *d_hit_end = nullptr, *d_dirty = nullptr;
-  /// [2 x slot_capacity] per slot: the stamp of the batch that used the region last, and the stamp of the last use before
-  /// the current run of consecutive batches (0: none) -- what the spill policy predicts a region's next use from
-  /// (touchRegionUse, evictColdRegions); moves with the slot
-  uint32_t *d_last_use = nullptr;
-  BatchInfo *d_info = nullptr;   ///< three summaries used in turn: k_plan of one batch zeroes the next batch's
-  BatchInfo *h_info = nullptr;   ///< pinned, device visible: [0] batch summary (written by k_plan), [1] event count
-  BatchInfo *h_info_dev = nullptr;  ///< device address of h_info
+  /// The region pool: every array allocPool (pool_impl.h) sizes by the pool's capacity.  One value: a pool is built
+  /// beside the one in use and takes its place whole, or is dropped whole.
+  struct RegionPool
+  {
+    uint32_t slot_capacity = 0;
+    uint32_t hash_capacity = 0;
+    uint32_t chunk_capacity = 0;
+    DevArray<void> layers[OHMHIP_LID_COUNT];
+    DevArray<unsigned long long> d_keys;
+    DevArray<uint32_t> d_vals;
+    DevArray<uint64_t> d_slot_keys;
+    // scratch
+    DevArray<uint32_t> d_hit_count, d_sort_list;
+    DevArray<uint32_t> d_seg_count, d_seg_cursor, d_seg_offset, d_touched_flag, d_touched;
+    DevArray<uint32_t> d_voxel_first_hit, d_hit_begin, d_hit_end, d_dirty;
+    /// [2 x slot_capacity] per slot: the stamp of the batch that used the region last, and the stamp of the last use
+    /// before the current run of consecutive batches (0: none) -- what the spill policy predicts a region's next use
+    /// from (touchRegionUse, evictColdRegions); moves with the slot
+    DevArray<uint32_t> d_last_use;
+    DevArray<uint32_t> d_miss_counts;
+    DevArray<uint32_t> d_hit_mask;
+    DevArray<Chunk> d_chunks;
+    /// Replica merge (merge_impl.h): base copy of the occupancy layer (null until ohmhip_map_enable_merge).
+    DevArray<float> d_merge_base;
+    /// Traversal layer only: per-voxel fixed-point sum of a batch's ray lengths (zero between batches).
+    DevArray<unsigned long long> d_traversal_acc;
+  } pool;
+  DevArray<uint32_t> d_n_slots;
+  DevArray<BatchInfo> d_info;   ///< three summaries used in turn: k_plan of one batch zeroes the next batch's
+  PinnedBuf<BatchInfo> h_info;  ///< device visible: [0] batch summary (written by k_plan), [1] event count
   uint32_t info_index = 0;
   bool info_clean = false;       ///< d_info[next index] was zeroed by the previous batch's k_plan
-  uint32_t *d_miss_counts = nullptr;
-  uint32_t *d_hit_mask = nullptr;
-  Chunk *d_chunks = nullptr;
-  uint32_t chunk_capacity = 0;
 
   DevBuf walks_buf[2], hit_keys_a, hit_keys_b, interval_counts, segments, sort_temp, events;
   DevBuf wg_regions[2], wg_region_count[2], group_heads;  // (workgroup region lists: per parity)
-  /// Replica merge (merge_impl.h): base copy of the occupancy layer (null until ohmhip_map_enable_merge) and scratch.
-  float *d_merge_base = nullptr;
   int merge_mode = 0;  ///< OHMHIP_MERGE_SHARED_ONLY / OHMHIP_MERGE_FULL_UNION
-  /// Traversal layer only: per-voxel fixed-point sum of a batch's ray lengths (zero between batches).
-  unsigned long long *d_traversal_acc = nullptr;
   DevBuf merge_slots, merge_keys_dev, merge_delta, merge_observers;
   /// Regions cut into tiles (tiling_impl.h): > 0 while the translation layer calls back into the entry points with tile
   /// keys.
@@ -221,11 +363,10 @@ struct ohmhip_map_s
   /// ohmhip_map_region_owners, device copy behind MapConst::owner_table) and the scratch of ohmhip_map_route_rays.
   struct PartitionState
   {
+    Stream route_stream;  ///< routing runs beside the batches in flight: it reads no map state
     std::vector<unsigned char> table_host;
     DevBuf table_dev, masks, block_counts, totals;
-    uint32_t *h_totals = nullptr;      ///< pinned, device visible: rays per destination of the last routing
-    uint32_t *h_totals_dev = nullptr;
-    hipStream_t route_stream = nullptr;  ///< routing runs beside the batches in flight: it reads no map state
+    PinnedBuf<uint32_t> h_totals;  ///< device visible: rays per destination of the last routing
   } partition;
   DevBuf use_scratch;  ///< (slot, stamp) pairs of re-admitted regions (queueReadmission)
   /// After how many batches the regions re-admitted lately came back (ring of the last 256): their median stands in as
@@ -265,13 +406,13 @@ struct ohmhip_map_s
     std::vector<ohmhip_clearance_params> param_sets;
     DevBuf table_keys, table_changed, present, written, stale;
   } clearance_layer;
-  uint32_t *d_event_count = nullptr;  ///< per parity: [0] deferred event count, [1] walk kernel chunk cursor, [2] replay group count, [3] stop iteration flag
+  DevArray<uint32_t> d_event_count;  ///< per parity: [0] deferred event count, [1] walk kernel chunk cursor, [2] replay group count, [3] stop iteration flag
   uint32_t walk_workgroups = 256;     ///< persistent walk workgroups: one per CU
   /// Regions / tiles of at most 4 096 voxels (16^3) are walked by the WalkHalf shape of k_region_walk: 512-thread workgroups with
   /// half of everything, two per CU (occupancy_kernels.h; OHMHIP_WALK_HALF=0 keeps the full shape for A/B runs).
   bool walk_half = false;
   uint32_t walkSlots() const { return walk_workgroups * (walk_half ? 2u : 1u); }  ///< persistent walk workgroups of a launch
-  unsigned long long *d_dbg = nullptr;  ///< 8 debug counters (OHMHIP_DEBUG_FLAGS & 64)
+  DevArray<unsigned long long> d_dbg;  ///< 8 debug counters (OHMHIP_DEBUG_FLAGS & 64)
   double first_ray_time = -1.0;  ///< OccupancyMap::firstRayTime() (ohm/OccupancyMap.cpp:343-347)
   uint32_t event_demand = 0;
   uint32_t event_limit = 0;  ///< OHMHIP_EVENT_LIMIT (tests): cap of the NDT / TSDF event list's first sizing
@@ -288,7 +429,7 @@ struct ohmhip_map_s
   /// call spends its time; 4096 = one line per batch: segments, chunks, regions, densest region.
   unsigned debug_flags = 0;
   int refill_min_idle = kRefillMinIdle;      ///< tunable (OHMHIP_REFILL_MIN_IDLE)  ///< events the previous batch produced (sizes the next batch's list)
-  void *h_stage = nullptr;  ///< pinned staging for region copies
+  PinnedBuf<void> h_stage;  ///< staging for region copies
   size_t h_stage_bytes = 0;
 
   /// Host-pointer ray batches go through one of two staging slots (pinned host block + device copies), so the host
@@ -296,11 +437,11 @@ struct ohmhip_map_s
   /// batches with the same flags accumulate in the filling slot and run as one device batch.
   struct RaySlot
   {
-    char *h = nullptr;            ///< pinned: capacity x 48 B rays, x 8 B timestamps, x 4 B intensities, x 1 B filter flags
+    PinnedBuf<char> h;            ///< capacity x 48 B rays, x 8 B timestamps, x 4 B intensities, x 1 B filter flags
     size_t capacity = 0;          ///< rays
     DevBuf d_rays, d_times, d_intens, d_fflags;
-    hipEvent_t uploaded = nullptr;  ///< H2D copies done (copy stream)
-    hipEvent_t done = nullptr;      ///< the batch reading the device copies has finished (compute stream)
+    Event uploaded;  ///< H2D copies done (copy stream)
+    Event done;      ///< the batch reading the device copies has finished (compute stream)
     bool in_flight = false;
     bool rays_uploaded = false;     ///< the rays' H2D copies were queued piece by piece while the block was staged
   } ray_slots[2];
@@ -319,9 +460,8 @@ struct ohmhip_map_s
   /// The pending rays were presented through the device-pointer entry point: they sit in the filling slot's DEVICE
   /// buffers already (copied there device to device), the pinned block is not used.
   bool pending_on_device = false;
-  uint32_t *h_passed = nullptr;      ///< pinned, device visible: per-call filter count of a deferred device-pointer batch
-  uint32_t *h_passed_dev = nullptr;
-  hipEvent_t ev_passed = nullptr;
+  PinnedBuf<uint32_t> h_passed;  ///< device visible: per-call filter count of a deferred device-pointer batch
+  Event ev_passed;
   /// Host-pointer batches smaller than this are collected and run as one device batch (0: every host batch is launched
   /// by the call that presents it).  On by default: the reference tools present 4096 rays per call.
   size_t coalesce_min_rays = size_t(1) << 16;
@@ -354,7 +494,7 @@ struct ohmhip_map_s
     size_t layer_offset[OHMHIP_LID_COUNT] = {};
     size_t mask_offset = 0;
     size_t mask_bytes = 0;
-    std::vector<void *> slabs;
+    std::vector<PinnedBuf<void>> slabs;
     std::vector<char *> free_records;
     size_t records_total = 0;
   } store;
@@ -371,15 +511,14 @@ struct ohmhip_map_s
   static constexpr uint32_t kWritebackRing = 4;
   struct WritebackRing
   {
-    void *jobs_host = nullptr;  ///< pinned, device visible: the kernel reads its job list straight from here (no copy call:
-                                ///< a blocking hipMemcpy from pageable memory would stall the batch pipeline)
-    void *jobs_dev = nullptr;
-    size_t capacity = 0;        ///< bytes
-    hipEvent_t done = nullptr;
+    PinnedBuf<void> jobs;  ///< device visible: the kernel reads its job list straight from here (no copy call: a
+                           ///< blocking hipMemcpy from pageable memory would stall the batch pipeline)
+    size_t capacity = 0;   ///< bytes
+    Event done;
     bool used = false;
   } wb_ring[kWritebackRing];
   uint32_t wb_next = 0;
-  uint32_t *h_use = nullptr;     ///< pinned: the resident regions' use stamps as of the latest plan (queueUseStamps)
+  PinnedBuf<uint32_t> h_use;     ///< the resident regions' use stamps as of the latest plan (queueUseStamps)
   size_t h_use_capacity = 0;
   uint32_t h_use_slots = 0;      ///< slots the copy covers
   uint32_t evicted_per_call = 0; ///< regions the latest eviction moved out (sizes the write-back's lead)
@@ -410,7 +549,7 @@ inline uint64_t callerRegionKey(const ohmhip_map_s *m, uint64_t key)
 /// The host changed the occupancy of (or removed) the region of pool key `key`: its neighbourhood's clearance is stale.
 inline void clearanceMarkChanged(ohmhip_map_s *m, uint64_t key)
 {
-  if (m->layers[OHMHIP_LID_CLEARANCE])
+  if (m->pool.layers[OHMHIP_LID_CLEARANCE])
   {
     m->clearance_layer.regions[callerRegionKey(m, key)].changed = m->clearance_layer.epoch + 1u;
   }
@@ -419,7 +558,7 @@ inline void clearanceMarkChanged(ohmhip_map_s *m, uint64_t key)
 /// The host wrote the clearance layer of (or removed) the region of pool key `key`: it is no longer a computed result.
 inline void clearanceMarkUnwritten(ohmhip_map_s *m, uint64_t key)
 {
-  if (m->layers[OHMHIP_LID_CLEARANCE])
+  if (m->pool.layers[OHMHIP_LID_CLEARANCE])
   {
     const auto it = m->clearance_layer.regions.find(callerRegionKey(m, key));
     if (it != m->clearance_layer.regions.end())

@@ -13,8 +13,8 @@ struct ohmhip_comm_s
   ncclComm_t comm = nullptr;
   int world = 1;
   int rank = 0;
-  int64_t *d_words = nullptr;    ///< [world + 2] small words of ohmhip_map_merge_replicas: counts, own count, status pair
-  uint32_t *d_counts = nullptr;  ///< [world + world * world] scratch of ohmhip_comm_exchange_counts (partition_impl.h)
+  DevArray<int64_t> d_words;     ///< [world + 2] small words of ohmhip_map_merge_replicas: counts, own count, status pair
+  DevArray<uint32_t> d_counts;   ///< [world + world * world] scratch of ohmhip_comm_exchange_counts (partition_impl.h)
 };
 
 namespace
@@ -143,13 +143,9 @@ try
   }
   // (the small device words of the collectives are allocated here, with the communicator: an allocation that fails on
   // one rank in the middle of a collective call would leave its peers blocked)
-  if (hipMalloc(&c->d_words, sizeof(int64_t) * size_t(world_size + 2)) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void **>(&c->d_counts), sizeof(uint32_t) * size_t(world_size) * size_t(world_size + 1)) != hipSuccess)
+  if (c->d_words.alloc(sizeof(int64_t) * size_t(world_size + 2)) != hipSuccess ||
+      c->d_counts.alloc(sizeof(uint32_t) * size_t(world_size) * size_t(world_size + 1)) != hipSuccess)
   {
-    if (c->d_words)
-    {
-      (void)hipFree(c->d_words);
-    }
     (void)hipGetLastError();
     (void)ncclCommDestroy(c->comm);
     delete c;
@@ -169,14 +165,6 @@ try
     {
       (void)ncclCommDestroy(comm->comm);
     }
-    if (comm->d_words)
-    {
-      (void)hipFree(comm->d_words);
-    }
-    if (comm->d_counts)
-    {
-      (void)hipFree(comm->d_counts);
-    }
     delete comm;
   }
   return OHMHIP_OK;
@@ -195,11 +183,11 @@ try
   {
     return OHMHIP_ERR_UNSUPPORTED;  // the replica merge exchanges whole regions by slot: one-tile regions only
   }
-  if (m->config.mode != OHMHIP_MODE_OCCUPANCY || !m->layers[OHMHIP_LID_OCCUPANCY])
+  if (m->config.mode != OHMHIP_MODE_OCCUPANCY || !m->pool.layers[OHMHIP_LID_OCCUPANCY])
   {
     return OHMHIP_ERR_UNSUPPORTED;  // NDT / TSDF state is not additive: replicas or region ownership
   }
-  if (m->d_merge_base)
+  if (m->pool.d_merge_base)
   {
     return OHMHIP_OK;
   }
@@ -208,17 +196,17 @@ try
     return OHMHIP_ERR_UNSUPPORTED;  // a merging map keeps a base copy per resident region: not combined with spilling
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
-  const size_t bytes = size_t(m->mc.region_voxels) * sizeof(float) * m->slot_capacity;
-  if (hipMalloc(reinterpret_cast<void **>(&m->d_merge_base), bytes) != hipSuccess)
+  const size_t bytes = size_t(m->mc.region_voxels) * sizeof(float) * m->pool.slot_capacity;
+  if (m->pool.d_merge_base.alloc(bytes) != hipSuccess)
   {
     (void)hipGetLastError();
-    m->d_merge_base = nullptr;
+    m->pool.d_merge_base.reset();
     return OHMHIP_ERR_CAPACITY;
   }
   // What the map holds now is what all replicas are taken to share.
-  OHMHIP_CHECK(hipMemcpyAsync(m->d_merge_base, m->layers[OHMHIP_LID_OCCUPANCY], bytes, hipMemcpyDeviceToDevice,
+  OHMHIP_CHECK(hipMemcpyAsync(m->pool.d_merge_base, m->pool.layers[OHMHIP_LID_OCCUPANCY], bytes, hipMemcpyDeviceToDevice,
                               m->stream));
-  hipLaunchKernelGGL(k_and_u32, dim3(256), dim3(256), 0, m->stream, m->d_dirty, ~kDirtyMerge, size_t(m->slot_capacity));
+  hipLaunchKernelGGL(k_and_u32, dim3(256), dim3(256), 0, m->stream, m->pool.d_dirty, ~kDirtyMerge, size_t(m->pool.slot_capacity));
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   return OHMHIP_OK;
 }
@@ -232,7 +220,7 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->d_merge_base)
+  if (!m->pool.d_merge_base)
   {
     return OHMHIP_ERR_INVALID_ARG;  // ohmhip_map_enable_merge first
   }
@@ -241,7 +229,7 @@ try
   std::vector<uint32_t> dirty(m->slots_committed);
   if (!dirty.empty())
   {
-    OHMHIP_CHECK(hipMemcpy(dirty.data(), m->d_dirty, sizeof(uint32_t) * dirty.size(), hipMemcpyDeviceToHost));
+    OHMHIP_CHECK(hipMemcpy(dirty.data(), m->pool.d_dirty, sizeof(uint32_t) * dirty.size(), hipMemcpyDeviceToHost));
   }
   size_t n = 0;
   for (size_t i = 0; i < dirty.size(); ++i)
@@ -265,7 +253,7 @@ int ohmhip_map_merge_pack(ohmhip_map_t m, const int16_t *keys_xyz, size_t count,
 try
 {
   OHMHIP_SETTLE(m);
-  if (!m || !m->d_merge_base || (count && (!keys_xyz || !d_delta || !d_observers)))
+  if (!m || !m->pool.d_merge_base || (count && (!keys_xyz || !d_delta || !d_observers)))
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
@@ -276,7 +264,7 @@ try
   OHMHIP_CHECK(mergeSlots(m, keys_xyz, count, m->merge_slots));
   hipLaunchKernelGGL(k_merge_pack, dim3(uint32_t(count)), dim3(256), 0, m->stream,
                      static_cast<const uint32_t *>(m->merge_slots.ptr), uint32_t(m->mc.region_voxels),
-                     static_cast<const float *>(m->layers[OHMHIP_LID_OCCUPANCY]), m->d_merge_base, d_delta, d_observers);
+                     static_cast<const float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get()), m->pool.d_merge_base, d_delta, d_observers);
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   return hipGetLastError();
 }
@@ -287,7 +275,7 @@ int ohmhip_map_merge_apply(ohmhip_map_t m, const int16_t *keys_xyz, size_t count
 try
 {
   OHMHIP_SETTLE(m);
-  if (!m || !m->d_merge_base || (count && (!keys_xyz || !d_delta_sum || !d_observer_sum)))
+  if (!m || !m->pool.d_merge_base || (count && (!keys_xyz || !d_delta_sum || !d_observer_sum)))
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
@@ -298,8 +286,8 @@ try
   OHMHIP_CHECK(mergeSlots(m, keys_xyz, count, m->merge_slots));
   hipLaunchKernelGGL(k_merge_apply, dim3(uint32_t(count)), dim3(256), 0, m->stream,
                      static_cast<const uint32_t *>(m->merge_slots.ptr), uint32_t(m->mc.region_voxels),
-                     static_cast<float *>(m->layers[OHMHIP_LID_OCCUPANCY]), m->d_merge_base, d_delta_sum,
-                     d_observer_sum, m->mc.min_value, m->mc.max_value, m->d_dirty);
+                     static_cast<float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get()), m->pool.d_merge_base, d_delta_sum,
+                     d_observer_sum, m->mc.min_value, m->mc.max_value, m->pool.d_dirty);
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   return hipGetLastError();
 }
@@ -309,7 +297,7 @@ int ohmhip_map_merge_finish(ohmhip_map_t m)
 try
 {
   OHMHIP_SETTLE(m);
-  if (!m || !m->d_merge_base)
+  if (!m || !m->pool.d_merge_base)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }

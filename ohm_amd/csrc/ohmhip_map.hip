@@ -37,6 +37,29 @@ using namespace ohmhip;
 #include "batch_run.h"
 #include "pending_rays.h"
 
+ohmhip_map_s::~ohmhip_map_s()
+{
+  (void)settleLaunch(this);  // (a batch still being launched by the map's thread)
+  for (hipStream_t s : { stream.handle, copy_stream.handle, front_stream.handle, wb_stream.handle, partition.route_stream.handle })
+  {
+    if (s)
+    {
+      (void)hipStreamSynchronize(s);
+    }
+  }
+  if (debug_flags & 512u)
+  {
+    std::fprintf(stderr,
+                 "[ohmhip spill] evictions %llu readmissions %llu | ms: select %.1f copy-out %.1f compact %.1f copy-in %.1f "
+                 "store-growth %.1f write-back scheduling (host) %.1f\n",
+                 (unsigned long long)evictions, (unsigned long long)readmissions, spill_ms[0], spill_ms[1], spill_ms[2],
+                 spill_ms[3], spill_ms[5], wb_host_ms);
+  }
+  // (the threads use the pinned blocks and the streams: they go first)
+  launch_thread.reset();
+  stage_pool.reset();
+}
+
 extern "C" {
 
 size_t ohmhip_layer_voxel_bytes(int layer_id)
@@ -96,7 +119,9 @@ try
   {
     return derr ? derr : OHMHIP_ERR_NO_DEVICE;
   }
-  ohmhip_map_t m = new (std::nothrow) ohmhip_map_s;
+  // (a map that is not handed out dies here, half built or not: ~ohmhip_map_s)
+  std::unique_ptr<ohmhip_map_s> owner(new (std::nothrow) ohmhip_map_s);
+  ohmhip_map_t m = owner.get();
   if (!m)
   {
     return OHMHIP_ERR_INTERNAL;
@@ -110,7 +135,6 @@ try
     }
     if (m->config.region_dim[a] > 255)
     {
-      delete m;
       return OHMHIP_ERR_INVALID_ARG;
     }
   }
@@ -143,82 +167,38 @@ try
   }
   applyValueConfig(m);
 
-  int err = OHMHIP_OK;
-  auto fail = [&](int e) {
-    ohmhip_map_destroy(m);
-    return e;
-  };
   if (hipGetDevice(&m->device) != hipSuccess)
   {
-    return fail(OHMHIP_ERR_NO_DEVICE);
+    return OHMHIP_ERR_NO_DEVICE;
   }
-  if ((err = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking)) != 0)
-  {
-    return fail(err);
-  }
-  if ((err = hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking)) != 0)
-  {
-    return fail(err);
-  }
-  if ((err = hipStreamCreateWithFlags(&m->front_stream, hipStreamNonBlocking)) != 0)
-  {
-    return fail(err);
-  }
+  OHMHIP_CHECK(m->stream.create());
+  OHMHIP_CHECK(m->copy_stream.create());
+  OHMHIP_CHECK(m->front_stream.create());
   for (auto &e : m->ev)
   {
-    if ((err = hipEventCreate(&e)) != 0)
-    {
-      return fail(err);
-    }
+    OHMHIP_CHECK(e.create());
   }
   for (auto &set : m->tev)
   {
     for (auto &e : set)
     {
-      if ((err = hipEventCreate(&e)) != 0)
-      {
-        return fail(err);
-      }
+      OHMHIP_CHECK(e.create());
     }
   }
   for (auto &sl : m->ray_slots)
   {
-    if ((err = hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming)) != 0 ||
-        (err = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming)) != 0)
-    {
-      return fail(err);
-    }
+    OHMHIP_CHECK(sl.uploaded.create(hipEventDisableTiming));
+    OHMHIP_CHECK(sl.done.create(hipEventDisableTiming));
   }
-  if ((err = hipMalloc(reinterpret_cast<void **>(&m->d_n_slots), sizeof(uint32_t))) != 0)
-  {
-    return fail(err);
-  }
-  if ((err = hipMalloc(reinterpret_cast<void **>(&m->d_info), 3 * sizeof(BatchInfo))) != 0)
-  {
-    return fail(err);
-  }
-  if ((err = hipMalloc(reinterpret_cast<void **>(&m->d_event_count), 8 * sizeof(uint32_t))) != 0)
-  {
-    return fail(err);
-  }
-  if ((err = hipMalloc(reinterpret_cast<void **>(&m->d_dbg), kDbgWords * sizeof(unsigned long long))) != 0)
-  {
-    return fail(err);
-  }
+  OHMHIP_CHECK(m->d_n_slots.alloc(sizeof(uint32_t)));
+  OHMHIP_CHECK(m->d_info.alloc(3 * sizeof(BatchInfo)));
+  OHMHIP_CHECK(m->d_event_count.alloc(8 * sizeof(uint32_t)));
+  OHMHIP_CHECK(m->d_dbg.alloc(kDbgWords * sizeof(unsigned long long)));
   (void)hipMemset(m->d_dbg, 0, kDbgWords * sizeof(unsigned long long));
-  if ((err = hipHostMalloc(reinterpret_cast<void **>(&m->h_info), 2 * sizeof(BatchInfo),
-                           hipHostMallocMapped | hipHostMallocCoherent)) != 0 ||
-      (err = hipHostGetDevicePointer(reinterpret_cast<void **>(&m->h_info_dev), m->h_info, 0)) != 0)
-  {
-    return fail(err);
-  }
+  OHMHIP_CHECK(m->h_info.alloc(2 * sizeof(BatchInfo), hipHostMallocMapped | hipHostMallocCoherent));
   std::memset(m->h_info, 0, 2 * sizeof(BatchInfo));
-  if ((err = hipHostMalloc(reinterpret_cast<void **>(&m->h_passed), 64, hipHostMallocMapped | hipHostMallocCoherent)) != 0 ||
-      (err = hipHostGetDevicePointer(reinterpret_cast<void **>(&m->h_passed_dev), m->h_passed, 0)) != 0 ||
-      (err = hipEventCreateWithFlags(&m->ev_passed, hipEventDisableTiming)) != 0)
-  {
-    return fail(err);
-  }
+  OHMHIP_CHECK(m->h_passed.alloc(64, hipHostMallocMapped | hipHostMallocCoherent));
+  OHMHIP_CHECK(m->ev_passed.create(hipEventDisableTiming));
 
   uint32_t capacity = m->config.region_capacity;
   if (capacity == 0)
@@ -227,10 +207,7 @@ try
     capacity = uint32_t(std::max<uint64_t>(64, budget / bytesPerRegionAllLayers(m->config, mc.region_voxels)));
   }
   capacity = std::min<uint32_t>(capacity, kMaxRegionSlots);  // 20-bit slot field of the hit key
-  if ((err = allocPool(m, capacity, 0)) != 0)
-  {
-    return fail(err);
-  }
+  OHMHIP_CHECK(allocPool(m, capacity, 0));
   {
     int device = 0, cus = 0;
     if (hipGetDevice(&device) == hipSuccess &&
@@ -301,16 +278,10 @@ try
   const void *const *walk_kernels = m->walk_half ? walk_kernels_half : walk_kernels_full;
   for (int k = 0; k < 3; ++k)
   {
-    if ((err = hipFuncSetAttribute(walk_kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes))) != 0)
-    {
-      return fail(err);
-    }
+    OHMHIP_CHECK(hipFuncSetAttribute(walk_kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
   }
-  if ((err = hipFuncSetAttribute(reinterpret_cast<const void *>(k_region_traversal),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, int(traversalLdsBytes(mc)))) != 0)
-  {
-    return fail(err);
-  }
+  OHMHIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_region_traversal),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, int(traversalLdsBytes(mc))));
   if (const char *env = std::getenv("OHMHIP_DEBUG_FLAGS"))
   {
     m->debug_flags = unsigned(std::atoi(env));
@@ -335,7 +306,7 @@ try
     wa.bs = batchScratch(m);
     wa.n_chunks = 0;
     wa.chunk_cursor = batchEventCount(m) + 1;
-    for (hipStream_t stream : { m->stream, m->front_stream })
+    for (hipStream_t stream : { m->stream.handle, m->front_stream.handle })
     {
       if (m->walk_half)
       {
@@ -345,14 +316,11 @@ try
       {
         hipLaunchKernelGGL((k_region_walk<true, false, WalkFull>), dim3(1), dim3(WalkFull::kThreads), lds_bytes, stream, wa);
       }
-      if ((err = hipMemsetAsync(batchEventCount(m), 0, 2 * sizeof(uint32_t), stream)) != 0 ||
-          (err = hipStreamSynchronize(stream)) != 0)
-      {
-        return fail(err);
-      }
+      OHMHIP_CHECK(hipMemsetAsync(batchEventCount(m), 0, 2 * sizeof(uint32_t), stream));
+      OHMHIP_CHECK(hipStreamSynchronize(stream));
     }
   }
-  *map = m;
+  *map = owner.release();
   return OHMHIP_OK;
 }
 OHMHIP_ABI_CATCH
@@ -360,171 +328,6 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_destroy(ohmhip_map_t m)
 try
 {
-  if (!m)
-  {
-    return OHMHIP_OK;
-  }
-  (void)settleLaunch(m);  // (a batch still being launched by the map's thread)
-  if (m->stream)
-  {
-    (void)hipStreamSynchronize(m->stream);
-  }
-  if (m->copy_stream)
-  {
-    (void)hipStreamSynchronize(m->copy_stream);
-  }
-  if (m->front_stream)
-  {
-    (void)hipStreamSynchronize(m->front_stream);
-  }
-  freePool(m);
-  m->walks_buf[0].release();
-  m->walks_buf[1].release();
-  m->hit_keys_a.release();
-  m->hit_keys_b.release();
-  m->interval_counts.release();
-  m->segments.release();
-  m->sort_temp.release();
-  m->events.release();
-  for (int i = 0; i < 2; ++i)
-  {
-    m->wg_regions[i].release();
-    m->wg_region_count[i].release();
-  }
-  m->group_heads.release();
-  m->stop_a.release();
-  m->stop_b.release();
-  for (DevBuf *b : { &m->query.rays, &m->query.ranges, &m->query.volumes, &m->query.types, &m->query.keys,
-                     &m->query.walked, &m->query.last_walked, &m->query.scan_temp,
-                     &m->query.spill_keys, &m->query.spill_blocks, &m->query.hm_winner, &m->query.hm_rec_occ,
-                     &m->query.hm_rec_vox, &m->query.hm_rec_mean, &m->query.hm_counts, &m->query.hm_out_occ,
-                     &m->query.hm_out_vox, &m->query.hm_out_mean, &m->query.hm_out_col, &m->query.cloud_chunks,
-                     &m->query.cloud_partials, &m->query.cloud_offsets, &m->query.cloud_scan_temp, &m->query.cloud_pos,
-                     &m->query.cloud_keys, &m->query.cloud_values })
-  {
-    b->release();
-  }
-  m->merge_slots.release();
-  m->merge_keys_dev.release();
-  m->merge_delta.release();
-  m->merge_observers.release();
-  if (m->wb_stream)
-  {
-    (void)hipStreamSynchronize(m->wb_stream);
-    (void)hipStreamDestroy(m->wb_stream);
-  }
-  if (m->h_use)
-  {
-    (void)hipHostFree(m->h_use);
-  }
-  for (auto &ring : m->wb_ring)
-  {
-    if (ring.jobs_host)
-    {
-      (void)hipHostFree(ring.jobs_host);
-    }
-    if (ring.done)
-    {
-      (void)hipEventDestroy(ring.done);
-    }
-  }
-  m->partition.table_dev.release();
-  m->partition.masks.release();
-  m->partition.block_counts.release();
-  m->partition.totals.release();
-  if (m->partition.route_stream)
-  {
-    (void)hipStreamDestroy(m->partition.route_stream);
-  }
-  if (m->partition.h_totals)
-  {
-    (void)hipHostFree(m->partition.h_totals);
-  }
-  if (m->d_event_count)
-  {
-    (void)hipFree(m->d_event_count);
-  }
-  if (m->d_n_slots)
-  {
-    (void)hipFree(m->d_n_slots);
-  }
-  if (m->d_info)
-  {
-    (void)hipFree(m->d_info);
-  }
-  if (m->h_info)
-  {
-    (void)hipHostFree(m->h_info);
-  }
-  if (m->h_passed)
-  {
-    (void)hipHostFree(m->h_passed);
-  }
-  if (m->ev_passed)
-  {
-    (void)hipEventDestroy(m->ev_passed);
-  }
-  if (m->h_stage)
-  {
-    (void)hipHostFree(m->h_stage);
-  }
-  if (m->debug_flags & 512u)
-  {
-    std::fprintf(stderr,
-                 "[ohmhip spill] evictions %llu readmissions %llu | ms: select %.1f copy-out %.1f compact %.1f copy-in %.1f "
-                 "store-growth %.1f write-back scheduling (host) %.1f\n",
-                 (unsigned long long)m->evictions, (unsigned long long)m->readmissions, m->spill_ms[0], m->spill_ms[1],
-                 m->spill_ms[2], m->spill_ms[3], m->spill_ms[5], m->wb_host_ms);
-  }
-  freeHostStore(m);
-  for (auto &sl : m->ray_slots)
-  {
-    sl.d_rays.release();
-    sl.d_times.release();
-    sl.d_intens.release();
-    sl.d_fflags.release();
-    if (sl.h)
-    {
-      (void)hipHostFree(sl.h);
-    }
-    if (sl.uploaded)
-    {
-      (void)hipEventDestroy(sl.uploaded);
-    }
-    if (sl.done)
-    {
-      (void)hipEventDestroy(sl.done);
-    }
-  }
-  for (auto &e : m->ev)
-  {
-    if (e)
-    {
-      (void)hipEventDestroy(e);
-    }
-  }
-  for (auto &set : m->tev)
-  {
-    for (auto &e : set)
-    {
-      if (e)
-      {
-        (void)hipEventDestroy(e);
-      }
-    }
-  }
-  if (m->stream)
-  {
-    (void)hipStreamDestroy(m->stream);
-  }
-  if (m->copy_stream)
-  {
-    (void)hipStreamDestroy(m->copy_stream);
-  }
-  if (m->front_stream)
-  {
-    (void)hipStreamDestroy(m->front_stream);
-  }
   delete m;
   return OHMHIP_OK;
 }
@@ -675,7 +478,7 @@ try
     hipEvent_t origin = m->tev[(m->batch_seq - 3) % kTimingRing][0];
     for (uint64_t back = 3; back >= 1; --back)
     {
-      hipEvent_t *tev = m->tev[(m->batch_seq - back) % kTimingRing];
+      const Event *tev = m->tev[(m->batch_seq - back) % kTimingRing];
       std::fprintf(stderr, "[ohmhip timeline] batch -%llu:", (unsigned long long)back);
       for (int k = 0; k < 7; ++k)
       {
@@ -703,7 +506,7 @@ try
     return OHMHIP_ERR_INVALID_ARG;
   }
   const uint32_t ring = uint32_t((m->batch_seq - 1 - batches_back) % kTimingRing);
-  hipEvent_t *tev = m->tev[ring];
+  const Event *tev = m->tev[ring];
   const uint32_t have = m->tev_mask[ring];
   auto has = [&](int k) { return (have >> k) & 1u; };
   ms[0] = ms[1] = ms[2] = ms[3] = 0.0f;
@@ -888,7 +691,7 @@ try
   stats->misses = m->cache_misses;
   stats->full = m->cache_full;
   stats->regions_resident = m->slots_committed;
-  stats->region_capacity = m->slot_capacity;
+  stats->region_capacity = m->pool.slot_capacity;
   stats->bytes_per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
   stats->memory_limit = m->memory_limit;
   stats->evictions = m->evictions;
@@ -929,7 +732,7 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (enable && m->d_merge_base)
+  if (enable && m->pool.d_merge_base)
   {
     return OHMHIP_ERR_UNSUPPORTED;  // replica-merge maps keep a base copy per region: they do not spill
   }
@@ -942,7 +745,7 @@ try
     // leaves spilling off and the coalescing threshold as it was.
     const uint64_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
     const uint64_t pool_regions =
-      m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->slot_capacity;
+      m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->pool.slot_capacity;
     // (what the pool holds + the quarter an eviction moves out while as much again may still be waiting in the store)
     const uint64_t by_count = std::min<uint64_t>(pool_regions + pool_regions / 2 + 64, 16384);
     const uint64_t by_bytes = std::max<uint64_t>((uint64_t(8) << 30) / std::max<uint64_t>(per_region, 1), 64);
@@ -970,7 +773,7 @@ try
     // the middle of a batch (up to half the pool, capped like the store's eager reservation)
     const uint64_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
     const uint64_t pool_regions =
-      m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->slot_capacity;
+      m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->pool.slot_capacity;
     const uint64_t extra = std::min<uint64_t>(pool_regions / 2 + 64, (uint64_t(4) << 30) / std::max<uint64_t>(per_region, 1));
     OHMHIP_CHECK(reserveStoreRecords(m, m->store.free_records.size() + size_t(extra)));
   }
@@ -1026,7 +829,7 @@ try
   }
   for (size_t i = 0; i < count; ++i)
   {
-    if (slots[i] >= m->slot_capacity)
+    if (slots[i] >= m->pool.slot_capacity)
     {
       return OHMHIP_ERR_INVALID_ARG;
     }
@@ -1038,7 +841,7 @@ try
     dropPrecleaned(m);
     OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * count, false, m->stream));
     OHMHIP_CHECK(hipMemcpyAsync(m->merge_slots.ptr, slots, sizeof(uint32_t) * count, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, m->stream, m->d_dirty,
+    hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, m->stream, m->pool.d_dirty,
                        static_cast<const uint32_t *>(m->merge_slots.ptr), count,
                        kDirtySync | kDirtyMerge | kDirtyClearance);
   }
@@ -1100,23 +903,13 @@ try
   OHMHIP_CHECK(settleLaunch(m));  // (the query shares the map's stream and reads its configuration)
   hipStream_t s = m->stream;
   const size_t key_bytes = sizeof(GpuKeyOut) * line_count * size_t(max_keys_per_line);
-  double *d_lines = nullptr;
-  GpuKeyOut *d_keys = nullptr;
-  uint32_t *d_counts = nullptr;
-  int status = OHMHIP_OK;
-  auto cleanup = [&]() {
-    (void)hipFree(d_lines);
-    (void)hipFree(d_keys);
-    (void)hipFree(d_counts);
-  };
-  if ((status = hipMalloc(reinterpret_cast<void **>(&d_lines), sizeof(double) * 6 * line_count)) != 0 ||
-      (status = hipMalloc(reinterpret_cast<void **>(&d_keys), key_bytes)) != 0 ||
-      (status = hipMalloc(reinterpret_cast<void **>(&d_counts), sizeof(uint32_t) * line_count)) != 0)
-  {
-    cleanup();
-    return status;
-  }
-  status = hipMemcpyAsync(d_lines, lines, sizeof(double) * 6 * line_count, hipMemcpyHostToDevice, s);
+  DevArray<double> d_lines;
+  DevArray<GpuKeyOut> d_keys;
+  DevArray<uint32_t> d_counts;
+  OHMHIP_CHECK(d_lines.alloc(sizeof(double) * 6 * line_count));
+  OHMHIP_CHECK(d_keys.alloc(key_bytes));
+  OHMHIP_CHECK(d_counts.alloc(sizeof(uint32_t) * line_count));
+  int status = hipMemcpyAsync(d_lines, lines, sizeof(double) * 6 * line_count, hipMemcpyHostToDevice, s);
   if (!status)
   {
     hipLaunchKernelGGL(k_line_keys, dim3(uint32_t((line_count + 255) / 256)), dim3(256), 0, s, m->mc, d_lines,
@@ -1131,7 +924,6 @@ try
   {
     status = hipStreamSynchronize(s);
   }
-  cleanup();
   return status;
 }
 OHMHIP_ABI_CATCH
@@ -1148,7 +940,7 @@ int mapReadView(ohmhip_map_t m, MapReadView &view)
   ohmhip_map_s::QueryState &qs = m->query;
   view.mc = m->mc;
   view.rt = regionTable(m);
-  view.occupancy = static_cast<const float *>(m->layers[OHMHIP_LID_OCCUPANCY]);
+  view.occupancy = static_cast<const float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get());
   view.spill = QuerySpillTable{ nullptr, nullptr, 0 };
   if (!m->spilled.empty())
   {
@@ -1193,7 +985,7 @@ int raysQueryRefusal(ohmhip_map_t m, const void *rays, size_t element_count, con
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->layers[OHMHIP_LID_OCCUPANCY])
+  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
   {
     return OHMHIP_ERR_UNSUPPORTED;  // the CPU query refuses maps without the layer too (valid_layers)
   }
@@ -1322,7 +1114,7 @@ int clearanceSetup(ohmhip_map_t m, const void *keys, size_t count, const ohmhip_
       return OHMHIP_ERR_INVALID_ARG;
     }
   }
-  if (!m->layers[OHMHIP_LID_OCCUPANCY])
+  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
   {
     return OHMHIP_ERR_UNSUPPORTED;
   }
@@ -1520,7 +1312,7 @@ try
   }
   m->spilled.clear();
   m->clearance_layer.regions.clear();
-  return allocPool(m, m->slot_capacity, 0);
+  return allocPool(m, m->pool.slot_capacity, 0);
 }
 OHMHIP_ABI_CATCH
 

@@ -348,15 +348,13 @@ try
   ohmhip_map_s::PartitionState &ps = m->partition;
   if (!ps.h_totals)
   {
-    OHMHIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ps.h_totals), sizeof(uint32_t) * kRouteMaxWorld + sizeof(uint64_t),
-                               hipHostMallocMapped));
-    OHMHIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&ps.h_totals_dev), ps.h_totals, 0));
+    OHMHIP_CHECK(ps.h_totals.alloc(sizeof(uint32_t) * kRouteMaxWorld + sizeof(uint64_t), hipHostMallocMapped));
   }
   // A stream of its own: routing reads the rays, the map's constants and the territory table -- nothing a batch writes --
   // so the routing of the next batch runs beside the batches still in flight (the call itself stays synchronous).
   if (!ps.route_stream)
   {
-    OHMHIP_CHECK(hipStreamCreateWithFlags(&ps.route_stream, hipStreamNonBlocking));
+    OHMHIP_CHECK(ps.route_stream.create());
   }
   hipStream_t s = ps.route_stream;
   const uint32_t n = uint32_t(ray_count);
@@ -381,7 +379,7 @@ try
                      static_cast<unsigned long long *>(ps.masks.ptr), static_cast<uint32_t *>(ps.block_counts.ptr), world,
                      d_visits);
   hipLaunchKernelGGL(k_route_scan, dim3(world), dim3(1024), 0, s, static_cast<uint32_t *>(ps.block_counts.ptr), blocks,
-                     static_cast<uint32_t *>(ps.totals.ptr), ps.h_totals_dev);
+                     static_cast<uint32_t *>(ps.totals.ptr), ps.h_totals.dev);
   hipLaunchKernelGGL(k_route_scatter, dim3(blocks), dim3(kRouteThreads), 0, s, d_rays, n,
                      static_cast<const unsigned long long *>(ps.masks.ptr), static_cast<const uint32_t *>(ps.block_counts.ptr),
                      static_cast<const uint32_t *>(ps.totals.ptr), world, d_routed, d_routed_index,

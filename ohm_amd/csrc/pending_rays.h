@@ -21,9 +21,7 @@ int growRaySlot(ohmhip_map_t m, ohmhip_map_s::RaySlot &sl, size_t rays)
   }
   ohmhip_map_s::RaySlot grown;
   grown.capacity = std::max<size_t>(rays + rays / 4, 4096);
-  void *block = nullptr;
-  OHMHIP_CHECK(hipHostMalloc(&block, grown.capacity * 61, hipHostMallocDefault));
-  grown.h = static_cast<char *>(block);
+  OHMHIP_CHECK(grown.h.alloc(grown.capacity * 61, hipHostMallocDefault));
   if (m->pending_rays)
   {
     std::memcpy(slotRays(grown), slotRays(sl), m->pending_rays * 48);
@@ -31,11 +29,7 @@ int growRaySlot(ohmhip_map_t m, ohmhip_map_s::RaySlot &sl, size_t rays)
     std::memcpy(slotIntens(grown), slotIntens(sl), m->pending_rays * 4);
     std::memcpy(slotFilterFlags(grown), slotFilterFlags(sl), m->pending_rays);
   }
-  if (sl.h)
-  {
-    OHMHIP_CHECK(hipHostFree(sl.h));
-  }
-  sl.h = grown.h;
+  sl.h = std::move(grown.h);
   sl.capacity = grown.capacity;
   return OHMHIP_OK;
 }

@@ -10,12 +10,12 @@ namespace
 RegionTable regionTable(ohmhip_map_t m)
 {
   RegionTable rt;
-  rt.keys = m->d_keys;
-  rt.vals = m->d_vals;
-  rt.slot_keys = m->d_slot_keys;
+  rt.keys = m->pool.d_keys;
+  rt.vals = m->pool.d_vals;
+  rt.slot_keys = m->pool.d_slot_keys;
   rt.n_slots = m->d_n_slots;
-  rt.hash_mask = m->hash_capacity - 1;
-  rt.slot_capacity = m->slot_capacity;
+  rt.hash_mask = m->pool.hash_capacity - 1;
+  rt.slot_capacity = m->pool.slot_capacity;
   return rt;
 }
 
@@ -23,25 +23,25 @@ BatchScratch batchScratch(ohmhip_map_t m)
 {
   // The counters a batch's set-up pass writes exist twice (allocPool makes the arrays twice as long): batch N+1 sets up
   // in the other half while batch N's walk / apply kernels still read theirs.
-  const size_t h = size_t(m->parity) * m->hash_capacity;
-  const size_t c = size_t(m->parity) * m->slot_capacity;
+  const size_t h = size_t(m->parity) * m->pool.hash_capacity;
+  const size_t c = size_t(m->parity) * m->pool.slot_capacity;
   BatchScratch bs;
-  bs.seg_count = m->d_seg_count + h;
-  bs.seg_cursor = m->d_seg_cursor + h;
-  bs.seg_offset = m->d_seg_offset + h;
-  bs.touched_flag = m->d_touched_flag + h;
-  bs.touched = m->d_touched + h;
-  bs.hit_count = m->d_hit_count + h;
+  bs.seg_count = m->pool.d_seg_count + h;
+  bs.seg_cursor = m->pool.d_seg_cursor + h;
+  bs.seg_offset = m->pool.d_seg_offset + h;
+  bs.touched_flag = m->pool.d_touched_flag + h;
+  bs.touched = m->pool.d_touched + h;
+  bs.hit_count = m->pool.d_hit_count + h;
   // (three lists per parity in one allocation: regions receiving samples, regions whose counts / whose samples the apply
   // kernels still have to process -- k_plan)
-  bs.sort_list = m->d_sort_list + 3 * h;
-  bs.apply_counts_list = bs.sort_list + m->hash_capacity;
-  bs.apply_hits_list = bs.sort_list + 2 * size_t(m->hash_capacity);
-  bs.voxel_first_hit = m->d_voxel_first_hit;
-  bs.hit_begin = m->d_hit_begin + c;
-  bs.hit_end = m->d_hit_end + c;
-  bs.dirty = m->d_dirty;
-  bs.last_use = m->d_last_use;
+  bs.sort_list = m->pool.d_sort_list + 3 * h;
+  bs.apply_counts_list = bs.sort_list + m->pool.hash_capacity;
+  bs.apply_hits_list = bs.sort_list + 2 * size_t(m->pool.hash_capacity);
+  bs.voxel_first_hit = m->pool.d_voxel_first_hit;
+  bs.hit_begin = m->pool.d_hit_begin + c;
+  bs.hit_end = m->pool.d_hit_end + c;
+  bs.dirty = m->pool.d_dirty;
+  bs.last_use = m->pool.d_last_use;
   bs.stamp = uint32_t(m->batch_seq + 1u);
   bs.info = m->d_info + m->info_index;
   bs.wg_regions = static_cast<WgRegion *>(m->wg_regions[m->parity].ptr);
@@ -49,7 +49,7 @@ BatchScratch batchScratch(ohmhip_map_t m)
   return bs;
 }
 
-inline Chunk *batchChunks(ohmhip_map_t m) { return m->d_chunks + size_t(m->parity) * m->chunk_capacity; }
+inline Chunk *batchChunks(ohmhip_map_t m) { return m->pool.d_chunks + size_t(m->parity) * m->pool.chunk_capacity; }
 inline uint32_t *batchEventCount(ohmhip_map_t m) { return m->d_event_count + 4u * m->parity; }
 inline DevBuf &batchWalks(ohmhip_map_t m) { return m->walks_buf[m->parity]; }
 
@@ -102,86 +102,28 @@ size_t bytesPerRegionAllLayers(const ohmhip_map_config &c, int region_voxels)
   return b;
 }
 
-void freePool(ohmhip_map_t m)
-{
-  for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
-  {
-    if (m->layers[l])
-    {
-      (void)hipFree(m->layers[l]);
-      m->layers[l] = nullptr;
-    }
-  }
-  void *ptrs[] = { m->d_keys,       m->d_vals,        m->d_slot_keys, m->d_seg_count, m->d_seg_cursor,
-                   m->d_seg_offset, m->d_touched_flag, m->d_touched,   m->d_voxel_first_hit, m->d_hit_begin, m->d_hit_end,
-                   m->d_dirty,      m->d_miss_counts,  m->d_hit_mask,  m->d_chunks,    m->d_hit_count, m->d_sort_list,
-                   m->d_last_use };
-  for (void *p : ptrs)
-  {
-    if (p)
-    {
-      (void)hipFree(p);
-    }
-  }
-  m->d_keys = nullptr;
-  m->d_vals = nullptr;
-  m->d_slot_keys = nullptr;
-  m->d_seg_count = m->d_seg_cursor = m->d_seg_offset = m->d_touched_flag = m->d_touched = nullptr;
-  m->d_voxel_first_hit = m->d_hit_begin = m->d_hit_end = m->d_dirty = nullptr;
-  m->d_last_use = nullptr;
-  m->d_miss_counts = m->d_hit_mask = nullptr;
-  m->d_chunks = nullptr;
-  m->d_hit_count = m->d_sort_list = nullptr;
-  if (m->d_merge_base)
-  {
-    (void)hipFree(m->d_merge_base);
-    m->d_merge_base = nullptr;
-  }
-  if (m->d_traversal_acc)
-  {
-    (void)hipFree(m->d_traversal_acc);
-    m->d_traversal_acc = nullptr;
-  }
-}
-
 /// (Re)allocate the region pool for `capacity` regions, preserving the first `keep` slots' contents.  Everything new is
 /// allocated before anything old is released: a failed allocation leaves the map exactly as it was.
 int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
 {
   const size_t rv = size_t(m->mc.region_voxels);
-  const uint32_t hash_cap = nextPow2(std::max<uint32_t>(1024u, capacity * 2u));
   hipStream_t s = m->stream;
   if (!m->precleaned.empty() || !m->stale_records.empty())
   {
     OHMHIP_CHECK(drainWriteBack(m));  // background write-back copies read the pool being replaced
   }
 
-  std::vector<void *> fresh;  // released again if any step fails
-  auto alloc = [&](void **p, size_t bytes) -> int {
-    *p = nullptr;
-    const int err = int(hipMalloc(p, std::max<size_t>(bytes, 4)));
-    if (err == 0)
-    {
-      fresh.push_back(*p);
-    }
-    return err;
-  };
-  auto zalloc = [&](void **p, size_t bytes) -> int {
-    OHMHIP_CHECK(alloc(p, bytes));
-    OHMHIP_CHECK(hipMemsetAsync(*p, 0, std::max<size_t>(bytes, 4), s));
+  const ohmhip_map_s::RegionPool &old = m->pool;
+  ohmhip_map_s::RegionPool fresh;  // releases itself if any step fails
+  fresh.slot_capacity = capacity;
+  fresh.hash_capacity = nextPow2(std::max<uint32_t>(1024u, capacity * 2u));
+  fresh.chunk_capacity = capacity + (1u << 16);
+  const size_t hash_cap = fresh.hash_capacity;
+  auto zalloc = [&](auto &array, size_t bytes) -> int {
+    OHMHIP_CHECK(array.alloc(std::max<size_t>(bytes, 4)));
+    OHMHIP_CHECK(hipMemsetAsync(array, 0, std::max<size_t>(bytes, 4), s));
     return OHMHIP_OK;
   };
-  void *new_layers[OHMHIP_LID_COUNT] = {};
-  uint64_t *new_slot_keys = nullptr;
-  uint32_t *new_mask = nullptr, *new_dirty = nullptr, *new_last_use = nullptr;
-  unsigned long long *n_keys = nullptr;
-  uint32_t *n_vals = nullptr, *n_seg_count = nullptr, *n_seg_cursor = nullptr, *n_hit_count = nullptr,
-           *n_sort_list = nullptr, *n_seg_offset = nullptr, *n_touched_flag = nullptr, *n_touched = nullptr,
-           *n_first_hit = nullptr, *n_hit_begin = nullptr, *n_hit_end = nullptr, *n_miss_counts = nullptr;
-  Chunk *n_chunks = nullptr;
-  float *n_merge_base = nullptr;
-  unsigned long long *n_traversal_acc = nullptr;
-  const uint32_t chunk_capacity = capacity + (1u << 16);
   // The per-voxel mask is persistent state for NDT / TSDF (voxels that take the ordered replay path): it moves with
   // the regions it describes.
   const size_t mask_row = ((rv + 31) / 32) * sizeof(uint32_t);
@@ -193,12 +135,12 @@ int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
         continue;
       }
       const size_t stride = rv * kLayerBytes[l];
-      OHMHIP_CHECK(alloc(&new_layers[l], stride * capacity));
-      if (keep && m->layers[l])
+      OHMHIP_CHECK(fresh.layers[l].alloc(std::max<size_t>(stride * capacity, 4)));
+      if (keep && old.layers[l])
       {
-        OHMHIP_CHECK(hipMemcpyAsync(new_layers[l], m->layers[l], stride * keep, hipMemcpyDeviceToDevice, s));
+        OHMHIP_CHECK(hipMemcpyAsync(fresh.layers[l], old.layers[l], stride * keep, hipMemcpyDeviceToDevice, s));
       }
-      char *tail = static_cast<char *>(new_layers[l]) + stride * keep;
+      char *tail = static_cast<char *>(fresh.layers[l].get()) + stride * keep;
       const size_t tail_bytes = stride * (capacity - keep);
       if (layerClearWord(l) != 0u)
       {
@@ -216,58 +158,58 @@ int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
         OHMHIP_CHECK(hipMemsetAsync(tail, 0, tail_bytes, s));
       }
     }
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&new_slot_keys), sizeof(uint64_t) * capacity));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&new_mask), mask_row * capacity));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&new_dirty), sizeof(uint32_t) * capacity));
-    if (keep && m->d_slot_keys)
+    OHMHIP_CHECK(zalloc(fresh.d_slot_keys, sizeof(uint64_t) * capacity));
+    OHMHIP_CHECK(zalloc(fresh.d_hit_mask, mask_row * capacity));
+    OHMHIP_CHECK(zalloc(fresh.d_dirty, sizeof(uint32_t) * capacity));
+    if (keep && old.d_slot_keys)
     {
-      OHMHIP_CHECK(hipMemcpyAsync(new_slot_keys, m->d_slot_keys, sizeof(uint64_t) * keep, hipMemcpyDeviceToDevice, s));
+      OHMHIP_CHECK(hipMemcpyAsync(fresh.d_slot_keys, old.d_slot_keys, sizeof(uint64_t) * keep, hipMemcpyDeviceToDevice, s));
     }
-    if (keep && m->d_hit_mask)
+    if (keep && old.d_hit_mask)
     {
-      OHMHIP_CHECK(hipMemcpyAsync(new_mask, m->d_hit_mask, mask_row * keep, hipMemcpyDeviceToDevice, s));
+      OHMHIP_CHECK(hipMemcpyAsync(fresh.d_hit_mask, old.d_hit_mask, mask_row * keep, hipMemcpyDeviceToDevice, s));
     }
-    if (keep && m->d_dirty)
+    if (keep && old.d_dirty)
     {
-      OHMHIP_CHECK(hipMemcpyAsync(new_dirty, m->d_dirty, sizeof(uint32_t) * keep, hipMemcpyDeviceToDevice, s));
+      OHMHIP_CHECK(hipMemcpyAsync(fresh.d_dirty, old.d_dirty, sizeof(uint32_t) * keep, hipMemcpyDeviceToDevice, s));
     }
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&new_last_use), sizeof(uint32_t) * 2 * capacity));
-    if (keep && m->d_last_use)
+    OHMHIP_CHECK(zalloc(fresh.d_last_use, sizeof(uint32_t) * 2 * capacity));
+    if (keep && old.d_last_use)
     {
-      OHMHIP_CHECK(hipMemcpyAsync(new_last_use, m->d_last_use, sizeof(uint32_t) * 2 * keep, hipMemcpyDeviceToDevice, s));
+      OHMHIP_CHECK(hipMemcpyAsync(fresh.d_last_use, old.d_last_use, sizeof(uint32_t) * 2 * keep, hipMemcpyDeviceToDevice, s));
     }
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_keys), sizeof(unsigned long long) * hash_cap));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_vals), sizeof(uint32_t) * hash_cap));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_seg_count), sizeof(uint32_t) * 2 * hash_cap));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_seg_cursor), sizeof(uint32_t) * 2 * hash_cap));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_hit_count), sizeof(uint32_t) * 2 * hash_cap));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_sort_list), sizeof(uint32_t) * 6 * hash_cap));  // (3 lists x 2 parities)
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_seg_offset), sizeof(uint32_t) * 2 * hash_cap));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_touched_flag), sizeof(uint32_t) * 2 * hash_cap));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_touched), sizeof(uint32_t) * 2 * hash_cap));
+    OHMHIP_CHECK(zalloc(fresh.d_keys, sizeof(unsigned long long) * hash_cap));
+    OHMHIP_CHECK(zalloc(fresh.d_vals, sizeof(uint32_t) * hash_cap));
+    OHMHIP_CHECK(zalloc(fresh.d_seg_count, sizeof(uint32_t) * 2 * hash_cap));
+    OHMHIP_CHECK(zalloc(fresh.d_seg_cursor, sizeof(uint32_t) * 2 * hash_cap));
+    OHMHIP_CHECK(zalloc(fresh.d_hit_count, sizeof(uint32_t) * 2 * hash_cap));
+    OHMHIP_CHECK(zalloc(fresh.d_sort_list, sizeof(uint32_t) * 6 * hash_cap));  // (3 lists x 2 parities)
+    OHMHIP_CHECK(zalloc(fresh.d_seg_offset, sizeof(uint32_t) * 2 * hash_cap));
+    OHMHIP_CHECK(zalloc(fresh.d_touched_flag, sizeof(uint32_t) * 2 * hash_cap));
+    OHMHIP_CHECK(zalloc(fresh.d_touched, sizeof(uint32_t) * 2 * hash_cap));
     if (m->config.mode == OHMHIP_MODE_OCCUPANCY)
     {
-      OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_first_hit), sizeof(uint32_t) * rv * capacity));
+      OHMHIP_CHECK(zalloc(fresh.d_voxel_first_hit, sizeof(uint32_t) * rv * capacity));
     }
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_hit_begin), sizeof(uint32_t) * 2 * capacity));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_hit_end), sizeof(uint32_t) * 2 * capacity));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_miss_counts), sizeof(uint32_t) * rv * capacity));
-    OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_chunks), sizeof(Chunk) * 2 * chunk_capacity));
+    OHMHIP_CHECK(zalloc(fresh.d_hit_begin, sizeof(uint32_t) * 2 * capacity));
+    OHMHIP_CHECK(zalloc(fresh.d_hit_end, sizeof(uint32_t) * 2 * capacity));
+    OHMHIP_CHECK(zalloc(fresh.d_miss_counts, sizeof(uint32_t) * rv * capacity));
+    OHMHIP_CHECK(zalloc(fresh.d_chunks, sizeof(Chunk) * 2 * fresh.chunk_capacity));
     if (m->config.layers & (1u << OHMHIP_LID_TRAVERSAL))
     {
-      OHMHIP_CHECK(zalloc(reinterpret_cast<void **>(&n_traversal_acc), sizeof(unsigned long long) * rv * capacity));
+      OHMHIP_CHECK(zalloc(fresh.d_traversal_acc, sizeof(unsigned long long) * rv * capacity));
     }
-    if (m->d_merge_base)
+    if (old.d_merge_base)
     {
       // replica-merge base (merge_impl.h): moves with the regions; a new region's base is "unobserved"
-      OHMHIP_CHECK(alloc(reinterpret_cast<void **>(&n_merge_base), sizeof(float) * rv * capacity));
+      OHMHIP_CHECK(fresh.d_merge_base.alloc(std::max<size_t>(sizeof(float) * rv * capacity, 4)));
       if (keep)
       {
-        OHMHIP_CHECK(hipMemcpyAsync(n_merge_base, m->d_merge_base, sizeof(float) * rv * keep, hipMemcpyDeviceToDevice, s));
+        OHMHIP_CHECK(hipMemcpyAsync(fresh.d_merge_base, old.d_merge_base, sizeof(float) * rv * keep, hipMemcpyDeviceToDevice, s));
       }
       if (capacity > keep)
       {
-        hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(n_merge_base + rv * keep),
+        hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(fresh.d_merge_base + rv * keep),
                            0x7f800000u, rv * (capacity - keep));
       }
     }
@@ -278,43 +220,11 @@ int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
   if (build_err)
   {
     (void)hipStreamSynchronize(s);
-    for (void *p : fresh)
-    {
-      (void)hipFree(p);
-    }
     (void)hipGetLastError();
     return (build_err == int(hipErrorOutOfMemory)) ? int(OHMHIP_ERR_CAPACITY) : build_err;
   }
 
-  // Swap in.
-  freePool(m);
-  for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
-  {
-    m->layers[l] = new_layers[l];
-  }
-  m->d_slot_keys = new_slot_keys;
-  m->d_hit_mask = new_mask;
-  m->d_dirty = new_dirty;
-  m->d_last_use = new_last_use;
-  m->d_keys = n_keys;
-  m->d_vals = n_vals;
-  m->d_seg_count = n_seg_count;
-  m->d_seg_cursor = n_seg_cursor;
-  m->d_hit_count = n_hit_count;
-  m->d_sort_list = n_sort_list;
-  m->d_seg_offset = n_seg_offset;
-  m->d_touched_flag = n_touched_flag;
-  m->d_touched = n_touched;
-  m->d_voxel_first_hit = n_first_hit;
-  m->d_hit_begin = n_hit_begin;
-  m->d_hit_end = n_hit_end;
-  m->d_miss_counts = n_miss_counts;
-  m->d_chunks = n_chunks;
-  m->d_merge_base = n_merge_base;
-  m->d_traversal_acc = n_traversal_acc;
-  m->chunk_capacity = chunk_capacity;
-  m->slot_capacity = capacity;
-  m->hash_capacity = hash_cap;
+  m->pool = std::move(fresh);  // (releases the old pool)
   OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &keep, sizeof(uint32_t), hipMemcpyHostToDevice, s));
   if (keep)
   {
@@ -361,27 +271,27 @@ void dropHostRegions(ohmhip_map_t m, size_t keep)
 int rollbackTable(ohmhip_map_t m)
 {
   hipStream_t s = m->stream;
-  const size_t hash_words = m->hash_capacity;
+  const size_t hash_words = m->pool.hash_capacity;
   OHMHIP_CHECK(hipStreamSynchronize(s));
-  OHMHIP_CHECK(hipMemsetAsync(m->d_keys, 0, sizeof(unsigned long long) * hash_words, s));
-  OHMHIP_CHECK(hipMemsetAsync(m->d_vals, 0, sizeof(uint32_t) * hash_words, s));
-  uint32_t *per_hash[] = { m->d_seg_count,  m->d_seg_cursor,   m->d_hit_count, m->d_seg_offset,
-                           m->d_touched_flag, m->d_touched };
+  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_keys, 0, sizeof(unsigned long long) * hash_words, s));
+  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_vals, 0, sizeof(uint32_t) * hash_words, s));
+  uint32_t *per_hash[] = { m->pool.d_seg_count,  m->pool.d_seg_cursor,   m->pool.d_hit_count, m->pool.d_seg_offset,
+                           m->pool.d_touched_flag, m->pool.d_touched };
   for (uint32_t *p : per_hash)
   {
     OHMHIP_CHECK(hipMemsetAsync(p, 0, sizeof(uint32_t) * 2 * hash_words, s));  // (both parities)
   }
-  OHMHIP_CHECK(hipMemsetAsync(m->d_sort_list, 0, sizeof(uint32_t) * 6 * hash_words, s));  // (3 lists x 2 parities)
+  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_sort_list, 0, sizeof(uint32_t) * 6 * hash_words, s));  // (3 lists x 2 parities)
   const uint32_t keep = m->slots_committed;
-  if (m->slot_capacity > keep)
+  if (m->pool.slot_capacity > keep)
   {
-    OHMHIP_CHECK(hipMemsetAsync(m->d_slot_keys + keep, 0, sizeof(uint64_t) * (m->slot_capacity - keep), s));
+    OHMHIP_CHECK(hipMemsetAsync(m->pool.d_slot_keys + keep, 0, sizeof(uint64_t) * (m->pool.slot_capacity - keep), s));
   }
-  if (m->slot_capacity > keep)
+  if (m->pool.slot_capacity > keep)
   {
     // the slots the failed batch handed out go back to the pristine state: no modified flags, no use stamp
-    OHMHIP_CHECK(hipMemsetAsync(m->d_dirty + keep, 0, sizeof(uint32_t) * (m->slot_capacity - keep), s));
-    OHMHIP_CHECK(hipMemsetAsync(m->d_last_use + 2 * size_t(keep), 0, sizeof(uint32_t) * 2 * (m->slot_capacity - keep), s));
+    OHMHIP_CHECK(hipMemsetAsync(m->pool.d_dirty + keep, 0, sizeof(uint32_t) * (m->pool.slot_capacity - keep), s));
+    OHMHIP_CHECK(hipMemsetAsync(m->pool.d_last_use + 2 * size_t(keep), 0, sizeof(uint32_t) * 2 * (m->pool.slot_capacity - keep), s));
   }
   OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &keep, sizeof(uint32_t), hipMemcpyHostToDevice, s));
   if (keep)
@@ -400,13 +310,13 @@ int rollbackTable(ohmhip_map_t m)
 int rollbackAndGrow(ohmhip_map_t m, uint32_t needed)
 {
   uint32_t cap = 0;
-  const uint32_t wish = std::max(needed, std::min(m->slot_capacity * 2u, kMaxRegionSlots));
-  if (!grownCapacity(m->slot_capacity, needed, cap))
+  const uint32_t wish = std::max(needed, std::min(m->pool.slot_capacity * 2u, kMaxRegionSlots));
+  if (!grownCapacity(m->pool.slot_capacity, needed, cap))
   {
     return OHMHIP_ERR_CAPACITY;
   }
   uint32_t wished_cap = cap;
-  if (grownCapacity(m->slot_capacity, wish, wished_cap))
+  if (grownCapacity(m->pool.slot_capacity, wish, wished_cap))
   {
     cap = wished_cap;
   }
@@ -443,7 +353,7 @@ int refreshHostRegionTable(ohmhip_map_t m)
   m->slot_keys_host.resize(n);
   if (n > old)
   {
-    OHMHIP_CHECK(hipMemcpy(m->slot_keys_host.data() + old, m->d_slot_keys + old, sizeof(uint64_t) * (n - old),
+    OHMHIP_CHECK(hipMemcpy(m->slot_keys_host.data() + old, m->pool.d_slot_keys + old, sizeof(uint64_t) * (n - old),
                            hipMemcpyDeviceToHost));
     for (size_t i = old; i < n; ++i)
     {
@@ -459,13 +369,8 @@ int ensureStage(ohmhip_map_t m, size_t bytes)
   {
     return OHMHIP_OK;
   }
-  if (m->h_stage)
-  {
-    OHMHIP_CHECK(hipHostFree(m->h_stage));
-    m->h_stage = nullptr;
-    m->h_stage_bytes = 0;
-  }
-  OHMHIP_CHECK(hipHostMalloc(&m->h_stage, bytes, hipHostMallocDefault));
+  m->h_stage_bytes = 0;
+  OHMHIP_CHECK(m->h_stage.alloc(bytes, hipHostMallocDefault));
   m->h_stage_bytes = bytes;
   return OHMHIP_OK;
 }
@@ -481,7 +386,7 @@ int reserveStoreRecords(ohmhip_map_t m, size_t records)
     for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
     {
       st.layer_offset[l] = at;
-      if (m->layers[l])
+      if (m->pool.layers[l])
       {
         at += (rv * kLayerBytes[l] + 255) & ~size_t(255);
       }
@@ -495,17 +400,17 @@ int reserveStoreRecords(ohmhip_map_t m, size_t records)
   {
     // slabs of about 64 MiB, at least the shortfall (one pinning call for a large reservation)
     const size_t want = std::max<size_t>(records - st.free_records.size(), (size_t(64) << 20) / st.record_bytes + 1);
-    void *slab = nullptr;
-    if (hipHostMalloc(&slab, want * st.record_bytes, hipHostMallocDefault) != hipSuccess)
+    PinnedBuf<void> slab;
+    if (slab.alloc(want * st.record_bytes, hipHostMallocDefault) != hipSuccess)
     {
       (void)hipGetLastError();
       return OHMHIP_ERR_CAPACITY;
     }
-    st.slabs.push_back(slab);
     for (size_t i = 0; i < want; ++i)
     {
-      st.free_records.push_back(static_cast<char *>(slab) + i * st.record_bytes);
+      st.free_records.push_back(static_cast<char *>(slab.get()) + i * st.record_bytes);
     }
+    st.slabs.push_back(std::move(slab));
     st.records_total += want;
   }
   return OHMHIP_OK;
@@ -528,15 +433,6 @@ void releaseStoreRecord(ohmhip_map_t m, char *record)
   {
     m->store.free_records.push_back(record);
   }
-}
-
-void freeHostStore(ohmhip_map_t m)
-{
-  for (void *slab : m->store.slabs)
-  {
-    (void)hipHostFree(slab);
-  }
-  m->store = ohmhip_map_s::HostStore{};
 }
 
 /// Run a list of byte copies as one kernel on `stream` (k_copy_jobs); returns with the launch queued.
@@ -565,7 +461,7 @@ unsigned sortEndBit(uint32_t slots)
   }
   return std::min<unsigned>(64u, unsigned(kHitSlotShift) + bits + 1u);
 }
-unsigned sortEndBit(ohmhip_map_t m) { return sortEndBit(m->slot_capacity); }
+unsigned sortEndBit(ohmhip_map_t m) { return sortEndBit(m->pool.slot_capacity); }
 
 /// rocPRIM falls back to a 20-launch merge sort for up to 2^20 keys by default; the one-sweep radix path is several
 /// times faster on the 1M-key sample lists of a typical batch.

@@ -58,7 +58,7 @@ int integrateRaysDevice(ohmhip_map_t m, const double *d_rays, size_t element_cou
   switch (m->config.mode)
   {
   case OHMHIP_MODE_OCCUPANCY:
-    if (!m->layers[OHMHIP_LID_OCCUPANCY])
+    if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
     {
       return OHMHIP_ERR_INVALID_ARG;
     }
@@ -66,18 +66,18 @@ int integrateRaysDevice(ohmhip_map_t m, const double *d_rays, size_t element_cou
     break;
   case OHMHIP_MODE_NDT_OM:
   case OHMHIP_MODE_NDT_TM:
-    if (!m->layers[OHMHIP_LID_OCCUPANCY] || !m->layers[OHMHIP_LID_MEAN] || !m->layers[OHMHIP_LID_COVARIANCE])
+    if (!m->pool.layers[OHMHIP_LID_OCCUPANCY] || !m->pool.layers[OHMHIP_LID_MEAN] || !m->pool.layers[OHMHIP_LID_COVARIANCE])
     {
       return OHMHIP_ERR_INVALID_ARG;
     }
-    if (m->config.mode == OHMHIP_MODE_NDT_TM && (!m->layers[OHMHIP_LID_INTENSITY] || !m->layers[OHMHIP_LID_HIT_MISS]))
+    if (m->config.mode == OHMHIP_MODE_NDT_TM && (!m->pool.layers[OHMHIP_LID_INTENSITY] || !m->pool.layers[OHMHIP_LID_HIT_MISS]))
     {
       return OHMHIP_ERR_INVALID_ARG;
     }
     err = integrateBatch(m, d_rays, d_intensities, d_timestamps, uint32_t(n_rays), ray_flags);
     break;
   case OHMHIP_MODE_TSDF:
-    if (!m->layers[OHMHIP_LID_TSDF])
+    if (!m->pool.layers[OHMHIP_LID_TSDF])
     {
       return OHMHIP_ERR_INVALID_ARG;
     }
@@ -87,7 +87,7 @@ int integrateRaysDevice(ohmhip_map_t m, const double *d_rays, size_t element_cou
     break;
   }
   if (err == OHMHIP_ERR_CAPACITY && m->spill_enabled && m->batch_exceeds_limit && n_rays >= 2 &&
-      !m->layers[OHMHIP_LID_TRAVERSAL])
+      !m->pool.layers[OHMHIP_LID_TRAVERSAL])
   {
     // (only this cause: a full hash, a refused hipMalloc or the slot field's end would cost log2(n) futile attempts,
     // each with a roll-back and a device synchronisation -- ADVICE r5)
@@ -149,7 +149,7 @@ try
   // run as one device batch once coalesce_min_rays have accumulated, or as soon as anything observes the map.  The
   // call's own count of integrated rays comes from a one-workgroup pass of the map's ray filter over its staged rays.
   const bool defer = m && d_rays && n_rays > 0 && m->coalesce_min_rays > 0 && n_rays < m->coalesce_min_rays &&
-                     !m->layers[OHMHIP_LID_TRAVERSAL] && !m->spill_enabled;
+                     !m->pool.layers[OHMHIP_LID_TRAVERSAL] && !m->spill_enabled;
   if (!defer)
   {
     OHMHIP_SETTLE(m);  // batches presented earlier come first
@@ -209,7 +209,7 @@ try
     MapConst count_mc = m->mc;
     count_mc.batch_filter_flags = nullptr;
     hipLaunchKernelGGL(k_count_passed, dim3(1), dim3(1024), 0, cs, count_mc, static_cast<const double *>(staged),
-                       uint32_t(n_rays), ray_flags, m->h_passed_dev);
+                       uint32_t(n_rays), ray_flags, m->h_passed.dev);
     OHMHIP_CHECK(hipEventRecord(m->ev_passed, cs));
     OHMHIP_CHECK(hipEventSynchronize(m->ev_passed));  // (also: the caller's arrays have been copied)
     *integrated = size_t(*m->h_passed) * 2;
@@ -252,20 +252,20 @@ int validateBatchRequest(ohmhip_map_t m, unsigned ray_flags)
       // flag whose effect is not local to a voxel, hence not available on a region-partitioned map.
       return OHMHIP_ERR_UNSUPPORTED;
     }
-    return m->layers[OHMHIP_LID_OCCUPANCY] ? OHMHIP_OK : OHMHIP_ERR_INVALID_ARG;
+    return m->pool.layers[OHMHIP_LID_OCCUPANCY] ? OHMHIP_OK : OHMHIP_ERR_INVALID_ARG;
   case OHMHIP_MODE_NDT_OM:
   case OHMHIP_MODE_NDT_TM:
-    if (!m->layers[OHMHIP_LID_OCCUPANCY] || !m->layers[OHMHIP_LID_MEAN] || !m->layers[OHMHIP_LID_COVARIANCE])
+    if (!m->pool.layers[OHMHIP_LID_OCCUPANCY] || !m->pool.layers[OHMHIP_LID_MEAN] || !m->pool.layers[OHMHIP_LID_COVARIANCE])
     {
       return OHMHIP_ERR_INVALID_ARG;
     }
-    if (m->config.mode == OHMHIP_MODE_NDT_TM && (!m->layers[OHMHIP_LID_INTENSITY] || !m->layers[OHMHIP_LID_HIT_MISS]))
+    if (m->config.mode == OHMHIP_MODE_NDT_TM && (!m->pool.layers[OHMHIP_LID_INTENSITY] || !m->pool.layers[OHMHIP_LID_HIT_MISS]))
     {
       return OHMHIP_ERR_INVALID_ARG;
     }
     return OHMHIP_OK;
   case OHMHIP_MODE_TSDF:
-    if (!m->layers[OHMHIP_LID_TSDF])
+    if (!m->pool.layers[OHMHIP_LID_TSDF])
     {
       return OHMHIP_ERR_INVALID_ARG;
     }
@@ -489,7 +489,7 @@ int integrateRaysHost(ohmhip_map_t m, const double *rays, size_t element_count, 
   }
   // Batches only share a device launch when they are integrated the same way; the traversal layer's exit range is
   // carried from ray to ray WITHIN one call (secondary_device.h: lastExitRange), so its batches are never merged.
-  const bool coalesce = m->coalesce_min_rays > 0 && !m->layers[OHMHIP_LID_TRAVERSAL];
+  const bool coalesce = m->coalesce_min_rays > 0 && !m->pool.layers[OHMHIP_LID_TRAVERSAL];
   if (m->pending_rays &&
       (!coalesce || m->pending_on_device || m->pending_flags != ray_flags || m->pending_intens != (intensities != nullptr) ||
        m->pending_times != (timestamps != nullptr) || m->pending_fflags != (filter_flags != nullptr) ||

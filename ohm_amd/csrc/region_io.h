@@ -77,7 +77,7 @@ try
   std::vector<uint32_t> dirty(m->slots_committed);
   if (!dirty.empty())
   {
-    OHMHIP_CHECK(hipMemcpy(dirty.data(), m->d_dirty, sizeof(uint32_t) * dirty.size(), hipMemcpyDeviceToHost));
+    OHMHIP_CHECK(hipMemcpy(dirty.data(), m->pool.d_dirty, sizeof(uint32_t) * dirty.size(), hipMemcpyDeviceToHost));
   }
   size_t n = 0;
   for (size_t i = 0; i < dirty.size(); ++i)
@@ -115,7 +115,7 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  hipLaunchKernelGGL(k_and_u32, dim3(256), dim3(256), 0, m->stream, m->d_dirty, ~kDirtySync, size_t(m->slot_capacity));
+  hipLaunchKernelGGL(k_and_u32, dim3(256), dim3(256), 0, m->stream, m->pool.d_dirty, ~kDirtySync, size_t(m->pool.slot_capacity));
   for (auto &entry : m->spilled)
   {
     entry.second.dirty &= ~kDirtySync;
@@ -160,11 +160,11 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->layers[layer_id])
+  if (!m->pool.layers[layer_id])
   {
     return OHMHIP_ERR_NOT_FOUND;
   }
-  *device_ptr = m->layers[layer_id];
+  *device_ptr = m->pool.layers[layer_id];
   if (region_stride_bytes)
   {
     *region_stride_bytes = size_t(m->mc.region_voxels) * kLayerBytes[layer_id];
@@ -181,7 +181,7 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->layers[layer_id])
+  if (!m->pool.layers[layer_id])
   {
     return OHMHIP_ERR_NOT_FOUND;
   }
@@ -226,7 +226,7 @@ try
   {
     return err;
   }
-  char *stage[2] = { static_cast<char *>(m->h_stage), static_cast<char *>(m->h_stage) + burst * stride };
+  char *stage[2] = { static_cast<char *>(m->h_stage.get()), static_cast<char *>(m->h_stage.get()) + burst * stride };
   hipEvent_t done[2] = { m->ev[6], nullptr };
   // Requests in pool-slot order: consecutive slots are one contiguous device range and travel as ONE copy (a first
   // sync of a freshly built map is a handful of large copies instead of one small copy per region).
@@ -242,7 +242,9 @@ try
     order[k] = { it->second, k };
   }
   std::sort(order.begin(), order.end());
-  OHMHIP_CHECK(hipEventCreate(&done[1]));
+  Event second_done;  // (local to this call)
+  OHMHIP_CHECK(second_done.create());
+  done[1] = second_done;
   size_t pending_base[2] = { 0, 0 };
   size_t pending_n[2] = { 0, 0 };
   int status = OHMHIP_OK;
@@ -298,7 +300,7 @@ try
       {
         ++run;
       }
-      const char *src = static_cast<const char *>(m->layers[layer_id]) + size_t(order[base + k].first) * stride;
+      const char *src = static_cast<const char *>(m->pool.layers[layer_id].get()) + size_t(order[base + k].first) * stride;
       const hipError_t e =
         hipMemcpyAsync(stage[b] + k * stride, src, run * stride, hipMemcpyDeviceToHost, m->copy_stream);
       if (e != hipSuccess)
@@ -327,7 +329,6 @@ try
     status = drain(1);
   }
   (void)hipStreamSynchronize(m->copy_stream);
-  (void)hipEventDestroy(done[1]);
   return status;
 }
 OHMHIP_ABI_CATCH
@@ -341,7 +342,7 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->layers[layer_id])
+  if (!m->pool.layers[layer_id])
   {
     return OHMHIP_ERR_NOT_FOUND;
   }
@@ -379,7 +380,7 @@ try
   {
     const uint32_t total = uint32_t(m->slot_keys_host.size());
     const uint32_t old = m->slots_committed;
-    if (total > m->slot_capacity)
+    if (total > m->pool.slot_capacity)
     {
       err = growPoolForNamedRegions(m, total, old);
       if (err)
@@ -388,10 +389,10 @@ try
         return err;
       }
     }
-    OHMHIP_CHECK(hipMemcpy(m->d_slot_keys + old, m->slot_keys_host.data() + old, sizeof(uint64_t) * (total - old),
+    OHMHIP_CHECK(hipMemcpy(m->pool.d_slot_keys + old, m->slot_keys_host.data() + old, sizeof(uint64_t) * (total - old),
                            hipMemcpyHostToDevice));
     // Rebuild the hash from slot_keys (cheap: one lane per region).
-    OHMHIP_CHECK(hipMemsetAsync(m->d_keys, 0, sizeof(unsigned long long) * m->hash_capacity, m->stream));
+    OHMHIP_CHECK(hipMemsetAsync(m->pool.d_keys, 0, sizeof(unsigned long long) * m->pool.hash_capacity, m->stream));
     OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &total, sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(k_rehash, dim3((total + 255) / 256), dim3(256), 0, m->stream, regionTable(m), total);
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));
@@ -410,9 +411,9 @@ try
     {
       const int16_t *key = keys_xyz + 3 * (base + k);
       const uint32_t slot = m->region_slots[packRegionKey(key[0], key[1], key[2])];
-      std::memcpy(static_cast<char *>(m->h_stage) + k * stride, srcs[base + k], stride);
-      OHMHIP_CHECK(hipMemcpyAsync(static_cast<char *>(m->layers[layer_id]) + size_t(slot) * stride,
-                                  static_cast<char *>(m->h_stage) + k * stride, stride, hipMemcpyHostToDevice,
+      std::memcpy(static_cast<char *>(m->h_stage.get()) + k * stride, srcs[base + k], stride);
+      OHMHIP_CHECK(hipMemcpyAsync(static_cast<char *>(m->pool.layers[layer_id].get()) + size_t(slot) * stride,
+                                  static_cast<char *>(m->h_stage.get()) + k * stride, stride, hipMemcpyHostToDevice,
                                   m->copy_stream));
     }
     OHMHIP_CHECK(hipStreamSynchronize(m->copy_stream));
@@ -427,8 +428,8 @@ try
     {
       const uint32_t slot = m->region_slots[packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2])];
       hipLaunchKernelGGL(k_rebuild_mask, dim3(4), dim3(256), 0, m->stream, m->mc, slot,
-                         ndt ? static_cast<const uint32_t *>(m->layers[OHMHIP_LID_MEAN]) : nullptr,
-                         tsdf ? static_cast<const float *>(m->layers[OHMHIP_LID_TSDF]) : nullptr, m->d_hit_mask);
+                         ndt ? static_cast<const uint32_t *>(m->pool.layers[OHMHIP_LID_MEAN].get()) : nullptr,
+                         tsdf ? static_cast<const float *>(m->pool.layers[OHMHIP_LID_TSDF].get()) : nullptr, m->pool.d_hit_mask);
     }
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   }
@@ -487,7 +488,7 @@ try
   const uint32_t total = uint32_t(m->slot_keys_host.size());
   if (total > old)
   {
-    if (total > m->slot_capacity)
+    if (total > m->pool.slot_capacity)
     {
       err = growPoolForNamedRegions(m, total, old);
       if (err)
@@ -496,9 +497,9 @@ try
         return err;
       }
     }
-    OHMHIP_CHECK(hipMemcpy(m->d_slot_keys + old, m->slot_keys_host.data() + old, sizeof(uint64_t) * (total - old),
+    OHMHIP_CHECK(hipMemcpy(m->pool.d_slot_keys + old, m->slot_keys_host.data() + old, sizeof(uint64_t) * (total - old),
                            hipMemcpyHostToDevice));
-    OHMHIP_CHECK(hipMemsetAsync(m->d_keys, 0, sizeof(unsigned long long) * m->hash_capacity, m->stream));
+    OHMHIP_CHECK(hipMemsetAsync(m->pool.d_keys, 0, sizeof(unsigned long long) * m->pool.hash_capacity, m->stream));
     OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &total, sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(k_rehash, dim3((total + 255) / 256), dim3(256), 0, m->stream, regionTable(m), total);
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));
@@ -524,7 +525,7 @@ try
   {
     return tiledRemoveRegions(m, keys_xyz, count, removed);
   }
-  if (m->layers[OHMHIP_LID_CLEARANCE])
+  if (m->pool.layers[OHMHIP_LID_CLEARANCE])
   {
     // (a removal makes the neighbourhood's clearance stale)
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));

@@ -71,23 +71,23 @@ static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t
     // (source slots lie in the tail [new_n, n), destinations below new_n: no job reads what another writes)
     for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
     {
-      if (m->layers[l])
+      if (m->pool.layers[l])
       {
         const size_t stride = rv * kLayerBytes[l];
-        jobs.push_back(CopyJob{ static_cast<const char *>(m->layers[l]) + stride * src,
-                                static_cast<char *>(m->layers[l]) + stride * dst, stride });
+        jobs.push_back(CopyJob{ static_cast<const char *>(m->pool.layers[l].get()) + stride * src,
+                                static_cast<char *>(m->pool.layers[l].get()) + stride * dst, stride });
       }
     }
-    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->d_hit_mask) + mask_row * src,
-                            reinterpret_cast<char *>(m->d_hit_mask) + mask_row * dst, mask_row });
-    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->d_dirty + src), reinterpret_cast<char *>(m->d_dirty + dst),
+    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_hit_mask.get()) + mask_row * src,
+                            reinterpret_cast<char *>(m->pool.d_hit_mask.get()) + mask_row * dst, mask_row });
+    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_dirty + src), reinterpret_cast<char *>(m->pool.d_dirty + dst),
                             sizeof(uint32_t) });
-    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->d_last_use + 2 * size_t(src)),
-                            reinterpret_cast<char *>(m->d_last_use + 2 * size_t(dst)), 2 * sizeof(uint32_t) });
-    if (m->d_merge_base)
+    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_last_use + 2 * size_t(src)),
+                            reinterpret_cast<char *>(m->pool.d_last_use + 2 * size_t(dst)), 2 * sizeof(uint32_t) });
+    if (m->pool.d_merge_base)
     {
-      jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->d_merge_base + rv * src),
-                              reinterpret_cast<char *>(m->d_merge_base + rv * dst), sizeof(float) * rv });
+      jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_merge_base + rv * src),
+                              reinterpret_cast<char *>(m->pool.d_merge_base + rv * dst), sizeof(float) * rv });
     }
     m->slot_keys_host[dst] = m->slot_keys_host[src];
     ++src;
@@ -95,12 +95,12 @@ static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t
   OHMHIP_CHECK(launchCopyJobs(m, jobs, s));
   for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
   {
-    if (!m->layers[l])
+    if (!m->pool.layers[l])
     {
       continue;
     }
     const size_t stride = rv * kLayerBytes[l];
-    char *tail = static_cast<char *>(m->layers[l]) + stride * new_n;
+    char *tail = static_cast<char *>(m->pool.layers[l].get()) + stride * new_n;
     if (layerClearWord(l) != 0u)
     {
       hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(tail), layerClearWord(l),
@@ -111,12 +111,12 @@ static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t
       OHMHIP_CHECK(hipMemsetAsync(tail, 0, stride * k, s));
     }
   }
-  OHMHIP_CHECK(hipMemsetAsync(reinterpret_cast<char *>(m->d_hit_mask) + mask_row * new_n, 0, mask_row * k, s));
-  OHMHIP_CHECK(hipMemsetAsync(m->d_dirty + new_n, 0, sizeof(uint32_t) * k, s));
-  OHMHIP_CHECK(hipMemsetAsync(m->d_last_use + 2 * size_t(new_n), 0, sizeof(uint32_t) * 2 * k, s));
-  if (m->d_merge_base)
+  OHMHIP_CHECK(hipMemsetAsync(reinterpret_cast<char *>(m->pool.d_hit_mask.get()) + mask_row * new_n, 0, mask_row * k, s));
+  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_dirty + new_n, 0, sizeof(uint32_t) * k, s));
+  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_last_use + 2 * size_t(new_n), 0, sizeof(uint32_t) * 2 * k, s));
+  if (m->pool.d_merge_base)
   {
-    hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(m->d_merge_base + rv * new_n),
+    hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(m->pool.d_merge_base + rv * new_n),
                        0x7f800000u, rv * k);
   }
   m->slot_keys_host.resize(new_n);
@@ -125,13 +125,13 @@ static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t
   {
     m->region_slots[m->slot_keys_host[i]] = i;
   }
-  OHMHIP_CHECK(hipMemsetAsync(m->d_slot_keys, 0, sizeof(uint64_t) * n, s));
+  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_slot_keys, 0, sizeof(uint64_t) * n, s));
   if (new_n)
   {
-    OHMHIP_CHECK(hipMemcpyAsync(m->d_slot_keys, m->slot_keys_host.data(), sizeof(uint64_t) * new_n,
+    OHMHIP_CHECK(hipMemcpyAsync(m->pool.d_slot_keys, m->slot_keys_host.data(), sizeof(uint64_t) * new_n,
                                 hipMemcpyHostToDevice, s));
   }
-  OHMHIP_CHECK(hipMemsetAsync(m->d_keys, 0, sizeof(unsigned long long) * m->hash_capacity, s));
+  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_keys, 0, sizeof(unsigned long long) * m->pool.hash_capacity, s));
   OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &new_n, sizeof(uint32_t), hipMemcpyHostToDevice, s));
   if (new_n)
   {
@@ -162,14 +162,14 @@ static int evictColdRegions(ohmhip_map_t m, uint32_t want_free, uint32_t max_evi
   OHMHIP_CHECK(hipStreamSynchronize(s));
   OHMHIP_CHECK(refreshHostRegionTable(m));
   const uint32_t n = m->slots_committed;
-  if (n == 0 || m->d_merge_base)
+  if (n == 0 || m->pool.d_merge_base)
   {
     return OHMHIP_ERR_CAPACITY;  // nothing to evict / replica-merge maps keep a base copy per region: not spilled
   }
   const uint32_t k = std::min(std::min(n, std::max(want_free, n / 4u)), std::max(want_free, max_evict));
   std::vector<uint32_t> stamps(2 * size_t(n)), dirty(n);
-  OHMHIP_CHECK(hipMemcpy(stamps.data(), m->d_last_use, sizeof(uint32_t) * 2 * n, hipMemcpyDeviceToHost));
-  OHMHIP_CHECK(hipMemcpy(dirty.data(), m->d_dirty, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  OHMHIP_CHECK(hipMemcpy(stamps.data(), m->pool.d_last_use, sizeof(uint32_t) * 2 * n, hipMemcpyDeviceToHost));
+  OHMHIP_CHECK(hipMemcpy(dirty.data(), m->pool.d_dirty, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
   // Who goes: the regions whose NEXT use is expected to be farthest away (rankForEviction, writeback_impl.h).
   const uint32_t now = uint32_t(m->batch_seq + 1u);
   std::vector<uint64_t> rank;
@@ -309,7 +309,7 @@ static int evictColdRegions(ohmhip_map_t m, uint32_t want_free, uint32_t max_evi
 static int growPoolForNamedRegions(ohmhip_map_t m, uint32_t total, uint32_t keep)
 {
   uint32_t cap = 0;
-  if (!grownCapacity(m->slot_capacity, total, cap))
+  if (!grownCapacity(m->pool.slot_capacity, total, cap))
   {
     return OHMHIP_ERR_CAPACITY;
   }
@@ -369,7 +369,7 @@ static int makeRoomForNamedRegions(ohmhip_map_t m, const int16_t *keys_xyz, size
   std::sort(named_resident.begin(), named_resident.end());
   named_resident.erase(std::unique(named_resident.begin(), named_resident.end()), named_resident.end());
   const uint64_t evictable = uint64_t(m->slots_committed) - named_resident.size();
-  if (!m->spill_enabled || m->d_merge_base || need > evictable)
+  if (!m->spill_enabled || m->pool.d_merge_base || need > evictable)
   {
     return OHMHIP_ERR_CAPACITY;
   }
@@ -379,7 +379,7 @@ static int makeRoomForNamedRegions(ohmhip_map_t m, const int16_t *keys_xyz, size
     OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * named_resident.size(), false, m->stream));
     OHMHIP_CHECK(hipMemcpy(m->merge_slots.ptr, named_resident.data(), sizeof(uint32_t) * named_resident.size(),
                            hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_touch_use_at, dim3(64), dim3(256), 0, m->stream, m->d_last_use,
+    hipLaunchKernelGGL(k_touch_use_at, dim3(64), dim3(256), 0, m->stream, m->pool.d_last_use,
                        static_cast<const uint32_t *>(m->merge_slots.ptr), named_resident.size(),
                        uint32_t(m->batch_seq + 1u));
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));
@@ -423,15 +423,15 @@ int queueReadmission(ohmhip_map_t m, const std::vector<std::pair<uint32_t, ohmhi
     }
     for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
     {
-      if (m->layers[l])
+      if (m->pool.layers[l])
       {
         const size_t stride = rv * kLayerBytes[l];
-        jobs.push_back(CopyJob{ record + st.layer_offset[l], static_cast<char *>(m->layers[l]) + stride * slot, stride });
+        jobs.push_back(CopyJob{ record + st.layer_offset[l], static_cast<char *>(m->pool.layers[l].get()) + stride * slot, stride });
       }
     }
     if (keep_mask)
     {
-      jobs.push_back(CopyJob{ record + st.mask_offset, reinterpret_cast<char *>(m->d_hit_mask) + st.mask_bytes * slot,
+      jobs.push_back(CopyJob{ record + st.mask_offset, reinterpret_cast<char *>(m->pool.d_hit_mask.get()) + st.mask_bytes * slot,
                               st.mask_bytes });
     }
     dirty_slots[entry.second.dirty & kDirtyBits].push_back(slot);
@@ -441,7 +441,7 @@ int queueReadmission(ohmhip_map_t m, const std::vector<std::pair<uint32_t, ohmhi
   // left (the slot itself is new: its own last-use stamp is this batch's, or is set by the caller).
   OHMHIP_CHECK(m->use_scratch.ensure(sizeof(uint32_t) * use_pairs.size(), false, m->copy_stream));
   OHMHIP_CHECK(hipMemcpy(m->use_scratch.ptr, use_pairs.data(), sizeof(uint32_t) * use_pairs.size(), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_set_prev_use, dim3(64), dim3(256), 0, m->copy_stream, m->d_last_use,
+  hipLaunchKernelGGL(k_set_prev_use, dim3(64), dim3(256), 0, m->copy_stream, m->pool.d_last_use,
                      static_cast<const uint32_t *>(m->use_scratch.ptr), back.size());
   // (k_plan may be OR-ing this batch's bits into the same words: atomic ORs, from a persistent index scratch)
   size_t n_index = 0;
@@ -461,7 +461,7 @@ int queueReadmission(ohmhip_map_t m, const std::vector<std::pair<uint32_t, ohmhi
       }
       OHMHIP_CHECK(hipMemcpy(d_index, dirty_slots[bits].data(), sizeof(uint32_t) * dirty_slots[bits].size(),
                              hipMemcpyHostToDevice));  // (blocking: the vector goes out of scope; a few hundred bytes)
-      hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, m->copy_stream, m->d_dirty, d_index,
+      hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, m->copy_stream, m->pool.d_dirty, d_index,
                          dirty_slots[bits].size(), bits);
       d_index += dirty_slots[bits].size();
     }
@@ -480,7 +480,7 @@ static int readmitSpilledSlots(ohmhip_map_t m, uint32_t first_slot, uint32_t end
     return OHMHIP_OK;
   }
   std::vector<uint64_t> keys(end_slot - first_slot);
-  OHMHIP_CHECK(hipMemcpy(keys.data(), m->d_slot_keys + first_slot, sizeof(uint64_t) * keys.size(), hipMemcpyDeviceToHost));
+  OHMHIP_CHECK(hipMemcpy(keys.data(), m->pool.d_slot_keys + first_slot, sizeof(uint64_t) * keys.size(), hipMemcpyDeviceToHost));
   // (slot, stored content) of the new slots that have content waiting, in slot order
   std::vector<std::pair<uint32_t, ohmhip_map_s::SpilledRegion>> back;
   for (size_t i = 0; i < keys.size(); ++i)
@@ -584,7 +584,7 @@ static int readmitSpilledKeys(ohmhip_map_t m, const int16_t *keys_xyz, size_t co
   {
     OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * slots.size(), false, m->stream));
     OHMHIP_CHECK(hipMemcpy(m->merge_slots.ptr, slots.data(), sizeof(uint32_t) * slots.size(), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_touch_use_at, dim3(64), dim3(256), 0, m->stream, m->d_last_use,
+    hipLaunchKernelGGL(k_touch_use_at, dim3(64), dim3(256), 0, m->stream, m->pool.d_last_use,
                        static_cast<const uint32_t *>(m->merge_slots.ptr), slots.size(), uint32_t(m->batch_seq + 1u));
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   }

@@ -83,15 +83,15 @@ void appendSlotToRecordJobs(ohmhip_map_t m, uint32_t slot, char *record, std::ve
   const ohmhip_map_s::HostStore &st = m->store;
   for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
   {
-    if (m->layers[l])
+    if (m->pool.layers[l])
     {
       const size_t stride = rv * kLayerBytes[l];
-      jobs.push_back(CopyJob{ static_cast<const char *>(m->layers[l]) + stride * slot, record + st.layer_offset[l], stride });
+      jobs.push_back(CopyJob{ static_cast<const char *>(m->pool.layers[l].get()) + stride * slot, record + st.layer_offset[l], stride });
     }
   }
   if (m->config.mode != OHMHIP_MODE_OCCUPANCY)  // (transient in occupancy mode: empty between batches)
   {
-    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->d_hit_mask) + st.mask_bytes * slot, record + st.mask_offset,
+    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_hit_mask.get()) + st.mask_bytes * slot, record + st.mask_offset,
                             st.mask_bytes });
   }
   else
@@ -153,15 +153,13 @@ int queueUseStamps(ohmhip_map_t m, hipStream_t stream)
     if (m->h_use)
     {
       OHMHIP_CHECK(hipStreamSynchronize(stream));
-      OHMHIP_CHECK(hipHostFree(m->h_use));
-      m->h_use = nullptr;
       m->h_use_capacity = 0;
     }
     const size_t cap = std::max<size_t>(want + want / 2, 4096);
-    OHMHIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&m->h_use), sizeof(uint32_t) * cap, hipHostMallocDefault));
+    OHMHIP_CHECK(m->h_use.alloc(sizeof(uint32_t) * cap, hipHostMallocDefault));
     m->h_use_capacity = cap;
   }
-  OHMHIP_CHECK(hipMemcpyAsync(m->h_use, m->d_last_use, sizeof(uint32_t) * want, hipMemcpyDeviceToHost, stream));
+  OHMHIP_CHECK(hipMemcpyAsync(m->h_use, m->pool.d_last_use, sizeof(uint32_t) * want, hipMemcpyDeviceToHost, stream));
   m->h_use_slots = m->slots_committed;
   return OHMHIP_OK;
 }
@@ -171,7 +169,7 @@ int queueUseStamps(ohmhip_map_t m, hipStream_t stream)
 /// error the write-back simply does not happen.
 void scheduleWriteBack(ohmhip_map_t m, uint32_t now)
 {
-  if (!m->spill_enabled || m->writeback_off || m->h_use_slots == 0 || m->d_merge_base)
+  if (!m->spill_enabled || m->writeback_off || m->h_use_slots == 0 || m->pool.d_merge_base)
   {
     return;
   }
@@ -211,7 +209,7 @@ void scheduleWriteBack(ohmhip_map_t m, uint32_t now)
   }
   // 2. how many to keep clean ahead of the evictions: what recent evictions took, with a margin
   const uint64_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
-  const uint64_t allowed = m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->slot_capacity;
+  const uint64_t allowed = m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->pool.slot_capacity;
   if (uint64_t(n) * 2 < allowed || m->evictions == 0)
   {
     return;  // the pool is not under pressure (yet): nothing has ever had to leave, or it is half empty
@@ -247,9 +245,9 @@ void scheduleWriteBack(ohmhip_map_t m, uint32_t now)
   // The job list of a write-back lives in one of a few device buffers used in turn; a buffer whose kernel has not
   // finished yet means the link is still busy with earlier write-backs: skip this round.
   ohmhip_map_s::WritebackRing &ring = m->wb_ring[m->wb_next % ohmhip_map_s::kWritebackRing];
-  if (!ring.done && hipEventCreateWithFlags(&ring.done, hipEventDisableTiming) != hipSuccess)
+  if (!ring.done && ring.done.create(hipEventDisableTiming) != hipSuccess)
   {
-    ring.done = nullptr;
+    ring.done.reset();
     return;
   }
   if (ring.used && hipEventQuery(ring.done) != hipSuccess)
@@ -291,9 +289,9 @@ void scheduleWriteBack(ohmhip_map_t m, uint32_t now)
     return;
   }
   // behind the batch BEFORE the running one (the running one does not touch these regions; an earlier one may have)
-  if (!m->wb_stream && hipStreamCreateWithFlags(&m->wb_stream, hipStreamNonBlocking) != hipSuccess)
+  if (!m->wb_stream && m->wb_stream.create() != hipSuccess)
   {
-    m->wb_stream = nullptr;
+    m->wb_stream.reset();
     for (auto &t : taken)
     {
       releaseStoreRecord(m, t.second.record);
@@ -311,26 +309,20 @@ void scheduleWriteBack(ohmhip_map_t m, uint32_t now)
     const size_t bytes = sizeof(CopyJob) * jobs.size();
     if (bytes > ring.capacity)
     {
-      if (ring.jobs_host)
-      {
-        (void)hipHostFree(ring.jobs_host);  // (its last kernel has finished: checked above)
-        ring.jobs_host = ring.jobs_dev = nullptr;
-        ring.capacity = 0;
-      }
+      // (the last kernel that read the block being replaced has finished: checked above)
       const size_t cap = std::max<size_t>(bytes + bytes / 2, size_t(1) << 16);
-      ok = hipHostMalloc(&ring.jobs_host, cap, hipHostMallocMapped) == hipSuccess &&
-           hipHostGetDevicePointer(&ring.jobs_dev, ring.jobs_host, 0) == hipSuccess;
+      ok = ring.jobs.alloc(cap, hipHostMallocMapped) == hipSuccess;
       ring.capacity = ok ? cap : 0;
     }
     if (ok)
     {
-      std::memcpy(ring.jobs_host, jobs.data(), bytes);
+      std::memcpy(ring.jobs, jobs.data(), bytes);
     }
   }
   if (ok)
   {
     hipLaunchKernelGGL(k_copy_jobs_few, dim3(m->writeback_workgroups), dim3(256), 0, cs,
-                       static_cast<const CopyJob *>(ring.jobs_dev), uint32_t(jobs.size()));
+                       static_cast<const CopyJob *>(ring.jobs.dev), uint32_t(jobs.size()));
     ok = hipGetLastError() == hipSuccess && hipEventRecord(ring.done, cs) == hipSuccess;
     ring.used = ok;
     ++m->wb_next;
