@@ -385,7 +385,13 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_reserve_rays(ohmhip_map_t map, size_t ray_cou
  * encoded against (milliseconds since it, ohm/VoxelTouchTimeCompute.h:24-37).  Like the reference the map takes it from
  * the first time stamp it is ever given; set it explicitly where that is not the map's to decide -- the ranks of a
  * partitioned map must share ONE base (the first stamp of the whole job), not each the first stamp that happens to be
- * routed to it.  A negative value means "not set yet". */
+ * routed to it.  A negative value means "not set yet".
+ * CONTRACT for stamps outside [base, base + 2^32 ms): the touch time is (stamp - base) / 0.001 truncated toward zero to
+ * a 64-bit integer, of which the low 32 bits are kept -- 5 s before the base reads 4294962296, 5e6 s after it 705032704.
+ * That is what the reference's x86-64 build yields for a cast C leaves undefined; a quotient that does not fit 64 bits,
+ * or NaN, gives 0.  A map whose first stamp is not its earliest therefore holds wrapped, not clamped, touch times.
+ * A host mirror that filters rays before the library sees them (GpuMap::setRayFilter) sets the base from the first stamp
+ * of the call as submitted, as the reference does, not from the first ray that survives the filter. */
 int ohmhip_map_set_first_ray_time(ohmhip_map_t map, double time);
 int ohmhip_map_first_ray_time(ohmhip_map_t map, double *time);
 /* Device batches the map has launched since it was created.  An integrate call that only collects its rays (batch

@@ -72,10 +72,15 @@ __device__ inline uint32_t updateIncidentNormal(uint32_t packed, const float ray
   return encodeNormal(normal);
 }
 
-/// ohm/VoxelTouchTimeCompute.h:24-27
+/// ohm/VoxelTouchTimeCompute.h:24-27.  The reference casts the quotient straight to `unsigned`: undefined in C for a
+/// stamp before the base or 2^32 ms or more after it, and lowered here to a saturating conversion where the reference's
+/// x86-64 build truncates toward zero to 64 bits and keeps the low 32.  The latter is the contract (include/ohmhip.h),
+/// in defined operations; a quotient outside the int64 range, or NaN, gives 0 as it does there.
 __device__ inline uint32_t encodeVoxelTouchTime(double timebase, double timestamp)
 {
-  return uint32_t((timestamp - timebase) / 0.001);
+  const double q = (timestamp - timebase) / 0.001;
+  const bool in_range = q > -9223372036854775808.0 && q < 9223372036854775808.0;
+  return in_range ? uint32_t(uint64_t((long long)q) & 0xffffffffull) : 0u;
 }
 
 /// Range at which ray `r`'s LAST reported voxel is exited, as the CPU mapper's `last_exit_range` holds it when the

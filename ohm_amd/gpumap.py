@@ -364,6 +364,13 @@ class GpuMap(RayMapper):
         if self.rayFilter() is not None:
             # The reference runs the RayFilterFunction per ray on the host before upload (ohmgpu/GpuMap.cpp:736-746):
             # rejected rays are dropped, the others go on with their (possibly moved) end points and filter flags.
+            if ts is not None and len(ts) and not getattr(self, "_time_base_checked", False):
+                # The reference takes the map's time base from the first stamp of the call BEFORE it filters
+                # (ohmgpu/GpuMap.cpp:593 against :736-746): the library only sees the kept rays' stamps, so a base still
+                # unset is set here -- also by a call whose rays are all rejected.
+                if self.firstRayTime() < 0:
+                    self.setFirstRayTime(ts[0])
+                self._time_base_checked = True
             keep, starts, ends, fflags = self.rayFilter()(rays[0::2].copy(), rays[1::2].copy())
             keep = np.asarray(keep, dtype=bool)
             n_keep = int(keep.sum())
@@ -429,6 +436,7 @@ class GpuMap(RayMapper):
         """OccupancyMap::setFirstRayTime (ohm/OccupancyMap.h:346): the base the touch-time layer is encoded against.  The
         ranks of a partitioned map share one (PartitionedIntegrator sets it from the first stamp of the whole job)."""
         L.check(L.lib.ohmhip_map_set_first_ray_time(self._handle, float(time)), "set_first_ray_time")
+        self._time_base_checked = False
 
     def firstRayTime(self):
         t = C.c_double(-1.0)

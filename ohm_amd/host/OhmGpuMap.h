@@ -414,6 +414,17 @@ public:
     size_t integrated = 0;
     if (ray_filter_)
     {
+      if (timestamps && !time_base_checked_)
+      {
+        // The reference takes the map's time base from the first stamp of the call BEFORE it filters
+        // (ohmgpu/GpuMap.cpp:593 against :736-746): the library only sees the kept rays' stamps, so a base still unset
+        // is set here -- also by a call whose rays are all rejected.
+        if (firstRayTime() < 0)
+        {
+          ohmhip_map_set_first_ray_time(handle_, timestamps[0]);
+        }
+        time_base_checked_ = true;
+      }
       std::vector<dvec3> kept;
       std::vector<unsigned char> kept_flags;
       std::vector<float> kept_intensities;
@@ -566,7 +577,11 @@ public:
   }
   /// OccupancyMap::setFirstRayTime / firstRayTime (ohm/OccupancyMap.h:342-351): the touch-time layer's time base; the
   /// ranks of a partitioned map share one.
-  void setFirstRayTime(double time) { OHMHIP_GPUAPICHECK(ohmhip_map_set_first_ray_time(handle_, time)); }
+  void setFirstRayTime(double time)
+  {
+    OHMHIP_GPUAPICHECK(ohmhip_map_set_first_ray_time(handle_, time));
+    time_base_checked_ = false;
+  }
   double firstRayTime() const
   {
     double t = -1.0;
@@ -876,6 +891,7 @@ protected:
   size_t last_partial_ = 0;
   unsigned partition_world_ = 1;
   RayFilterFunction ray_filter_;
+  bool time_base_checked_ = false;  ///< a stamped call under a host filter has seen to the time base
   ohmhip_map_config cfg_;
   GpuCache cache_view_{ this };
 };

@@ -93,8 +93,9 @@ class Aabb:
         with np.errstate(invalid="ignore"):
             move_start = hit & (t0 > 0) & (t0 < length)
             move_end = hit & (t1 > 0) & (t1 < length)
-        new_starts = np.where(move_start[:, None], origin + unit * t0[:, None], starts)
-        new_ends = np.where(move_end[:, None], origin + unit * t1[:, None], ends)
+        with np.errstate(invalid="ignore"):  # (degenerate rays carry NaN here and are not selected)
+            new_starts = np.where(move_start[:, None], origin + unit * t0[:, None], starts)
+            new_ends = np.where(move_end[:, None], origin + unit * t1[:, None], ends)
         flags = move_start.astype(np.uint8) * 1 + move_end.astype(np.uint8) * 2
         return move_start | move_end, new_starts, new_ends, flags
 

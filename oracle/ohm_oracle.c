@@ -353,6 +353,7 @@ size_t oracle_region_keys(const OracleMap *m, int16_t *keys_xyz, size_t cap)
 }
 
 /* OccupancyMap::setFirstRayTime (ohm/OccupancyMap.h:346): the touch-time base, set regardless of the current value. */
+double oracle_map_first_ray_time(const OracleMap *m) { return m->first_ray_time; }
 void oracle_map_set_first_ray_time(OracleMap *m, double time)
 {
   m->first_ray_time = time;
@@ -864,11 +865,29 @@ static unsigned update_incident_normal(unsigned packed, const float ray_in[3], u
   return encode_normal(normal);
 }
 
-/* ohm/VoxelTouchTimeCompute.h:24-27 */
+/* ohm/VoxelTouchTimeCompute.h:24-27.  The reference casts the quotient straight to `unsigned`, which C leaves undefined
+ * for a stamp before the base or 2^32 ms or more after it.  Its x86-64 build truncates toward zero to 64 bits and keeps
+ * the low 32 (tests/golden/ref_incident.npz records that); stated here in defined operations, which is also the
+ * library's contract (include/ohmhip.h).  Quotients outside the int64 range (stamps ~3e8 years from the base) and NaN
+ * give 0, as x86-64's conversion leaves 0 in the low half. */
 static unsigned encode_touch_time(double timebase, double timestamp)
 {
-  return (unsigned)((timestamp - timebase) / 0.001);
+  const double q = (timestamp - timebase) / 0.001;
+  if (!(q > -9223372036854775808.0 && q < 9223372036854775808.0))
+  {
+    return 0u;
+  }
+  return (unsigned)((uint64_t)(int64_t)q & 0xffffffffu);
 }
+
+/* Stand-alone entry points of the incident-normal and touch-time leaves (pinned against the reference headers). */
+void oracle_decode_normal(unsigned packed, float n[3]) { decode_normal(packed, n); }
+unsigned oracle_encode_normal(const float normal[3]) { return encode_normal(normal); }
+unsigned oracle_update_incident_normal(unsigned packed, const float incident_ray[3], unsigned point_count)
+{
+  return update_incident_normal(packed, incident_ray, point_count);
+}
+unsigned oracle_encode_touch_time(double timebase, double timestamp) { return encode_touch_time(timebase, timestamp); }
 
 /* ------------------------------------------------------------------------------------------------------------- */
 /* Ray filters: ohm/RayFilter.cpp:12-58                                                                           */

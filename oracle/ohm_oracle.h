@@ -142,6 +142,7 @@ uint64_t oracle_map_visit_count(const OracleMap *map);
 size_t oracle_region_count(const OracleMap *map);
 size_t oracle_region_keys(const OracleMap *map, int16_t *keys_xyz, size_t cap);
 void oracle_map_set_first_ray_time(OracleMap *m, double time);
+double oracle_map_first_ray_time(const OracleMap *m); /* OccupancyMap::firstRayTime(): negative while unset */
 void *oracle_region_layer(OracleMap *map, int rx, int ry, int rz, int layer_id);
 size_t oracle_layer_voxel_bytes(int layer_id);
 
@@ -173,6 +174,11 @@ void oracle_calculate_miss_ndt(const float cov[6], float *value, int *is_miss, c
 unsigned oracle_transform_samples(const double *transform_times, const double *translations, const double *rotations_xyzw,
                                   unsigned transform_count, const double *sample_times, const double *local_samples,
                                   unsigned point_count, double max_range, double *out);
+/* ohm/VoxelIncidentCompute.h:35-112 and ohm/VoxelTouchTimeCompute.h:24-27 (the leaves the mappers above call). */
+void oracle_decode_normal(unsigned packed, float n[3]);
+unsigned oracle_encode_normal(const float normal[3]);
+unsigned oracle_update_incident_normal(unsigned packed, const float incident_ray[3], unsigned point_count);
+unsigned oracle_encode_touch_time(double timebase, double timestamp);
 float oracle_probability_to_value(float p);
 float oracle_value_to_probability(float v);
 

@@ -18,7 +18,10 @@ def build(force=False):
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < os.path.getmtime(
             os.path.join(_HERE, "ohm_oracle.c")):
         subprocess.check_call(["make", "-C", _HERE, "libohm_oracle.so"], stdout=subprocess.DEVNULL)
-    if os.path.isdir("/root/reference/ohm") and (force or not os.path.exists(REF_LIB_PATH)):
+    shims = [os.path.join(_HERE, f) for f in ("ref_shim.cpp", "ref_shim_incident.cpp")]
+    if os.path.isdir("/root/reference/ohm") and (force or not os.path.exists(REF_LIB_PATH) or os.path.getmtime(
+            REF_LIB_PATH) < max(os.path.getmtime(f) for f in shims) or not hasattr(
+            C.CDLL(REF_LIB_PATH), "ref_update_incident_normal")):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
 
 
@@ -77,6 +80,8 @@ lib.oracle_region_count.argtypes = [_vp]
 lib.oracle_region_keys.restype = C.c_size_t
 lib.oracle_region_keys.argtypes = [_vp, _vp, C.c_size_t]
 lib.oracle_map_set_first_ray_time.argtypes = [_vp, C.c_double]
+lib.oracle_map_first_ray_time.restype = C.c_double
+lib.oracle_map_first_ray_time.argtypes = [_vp]
 lib.oracle_region_layer.restype = _vp
 lib.oracle_region_layer.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int]
 for _n in ("hit", "miss", "up", "down"):
@@ -99,6 +104,13 @@ lib.oracle_calculate_hit_with_covariance.argtypes = [_fp, _fp, _dp, _dp, C.c_uin
                                                      C.c_float, C.c_uint]
 lib.oracle_calculate_miss_ndt.argtypes = [_fp, _fp, C.POINTER(C.c_int), _dp, _dp, _dp, C.c_uint, C.c_float,
                                           C.c_float, C.c_float, C.c_float, C.c_uint]
+lib.oracle_decode_normal.argtypes = [C.c_uint, _fp]
+lib.oracle_encode_normal.restype = C.c_uint
+lib.oracle_encode_normal.argtypes = [_fp]
+lib.oracle_update_incident_normal.restype = C.c_uint
+lib.oracle_update_incident_normal.argtypes = [C.c_uint, _fp, C.c_uint]
+lib.oracle_encode_touch_time.restype = C.c_uint
+lib.oracle_encode_touch_time.argtypes = [C.c_double, C.c_double]
 lib.oracle_probability_to_value.restype = C.c_float
 lib.oracle_probability_to_value.argtypes = [C.c_float]
 lib.oracle_value_to_probability.restype = C.c_float
@@ -224,6 +236,10 @@ class OracleMap:
     def set_first_ray_time(self, time):
         """OccupancyMap::setFirstRayTime: the base the touch-time layer is encoded against."""
         lib.oracle_map_set_first_ray_time(self._h, C.c_double(float(time)))
+
+    def first_ray_time(self):
+        """OccupancyMap::firstRayTime(): negative while no stamped call has been made."""
+        return float(lib.oracle_map_first_ray_time(self._h))
 
     def region_layer_view(self, key, name):
         """The live block itself (no copy): tests that restate a reference case which writes single voxels on the CPU

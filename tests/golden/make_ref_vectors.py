@@ -7,6 +7,13 @@ inputs + the reference's results) and is what tests/test_oracle_golden.py holds 
 that have neither the reference checkout nor the library.
 
     python tests/golden/make_ref_vectors.py
+
+tests/golden/ref_incident.npz is the second fixture: ohm/VoxelIncidentCompute.h (device form, oracle/ref_shim_incident.cpp)
+on seeded rows, the reference leaf chained over the constructed set of tests/secondary_cases.py, and
+encodeVoxelTouchTime on that set's stamps and on stamps outside [base, base + 2^32 ms).  To write it alone and leave
+ref_vectors.npz as it is:
+
+    python tests/golden/make_ref_vectors.py --incident
 """
 import ctypes as C
 import os
@@ -129,5 +136,65 @@ def main():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def incident():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import secondary_cases as S
+
+    leaf = S.CLeaf(ref, "ref")
+    out = {}
+    bits = lambda a: np.asarray(a, dtype=np.float32).view(np.uint32)  # noqa: E731
+    # --- decodeNormal (:35-53): random words, and every combination of the field ends with the two flag bits
+    n = 600
+    words = (u(21, n, 0) * 2.0**32).astype(np.uint64).astype(np.uint32)
+    ends = [x | (y << 15) | f for x in (0, 1, 8191, 8192, 16382, 16383) for y in (0, 8191, 16383)
+            for f in (0, 1 << 30, 1 << 31, 3 << 30)]
+    words = np.concatenate([words, np.array(ends, dtype=np.uint32)])
+    out["dec_in"] = words
+    out["dec_out"] = np.array([bits(leaf.decode(w)) for w in words], dtype=np.uint32)
+    # --- encodeNormal (:68-89): unit vectors, vectors past +-1, zeros of either sign, NaN and infinite components
+    n = 600
+    v = np.stack([(u(22, n, s) - 0.5) * 2.0 for s in range(3)], axis=1)
+    v[: n // 2] /= np.sqrt((v[: n // 2] ** 2).sum(axis=1))[:, None]
+    nan, inf = float("nan"), float("inf")
+    special = [(0, 0, 0), (-0.0, -0.0, -0.0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1),
+               (-1, -1, 0), (-1, -1, -0.0), (1.5, -1.5, 2), (nan, 0.5, 0.5), (0.5, nan, -0.5), (nan, nan, nan),
+               (0, 0, nan), (-1, -1, nan), (inf, -inf, 1), (-inf, inf, -1), (nan, -1, 0), (-1, nan, 0)]
+    v = np.concatenate([v, np.array(special, dtype=np.float64)]).astype(np.float32)
+    out["enc_in"] = bits(v)
+    out["enc_out"] = np.array([leaf.encode(row) for row in v], dtype=np.uint32)
+    # --- updateIncidentNormal (:91-112): packed words (a fifth never set), rays from 1e-4 m to 1e3 m, counts
+    n = 1500
+    packed = (u(23, n, 0) * 2.0**32).astype(np.uint64).astype(np.uint32) | np.uint32(1 << 30)
+    packed[::5] = 0
+    ray = np.stack([(u(23, n, 1 + s) - 0.5) for s in range(3)], axis=1)
+    ray *= (10.0 ** (u(23, n, 4) * 7.0 - 4.0))[:, None]
+    ray[7::50] = 0.0
+    counts = np.array([0, 1, 2, 3, 7, 100, 65535, 2**32 - 1], dtype=np.uint32)[(u(23, n, 5) * 8).astype(np.int64)]
+    ray = ray.astype(np.float32)
+    out["upd_packed"], out["upd_ray"], out["upd_count"] = packed, bits(ray), counts
+    out["upd_out"] = np.array([leaf.update_normal(p, r, c) for p, r, c in zip(packed, ray, counts)], dtype=np.uint32)
+    # --- the reference leaf chained over the constructed set, with and without a mean layer
+    cs = S.cases()
+    out["case_digest"] = np.frombuffer(bytes.fromhex(S.digest(cs)), dtype=np.uint8)
+    for name, with_mean in (("mean", True), ("nomean", False)):
+        trace = []
+        S.replay(cs, leaf, with_mean=with_mean, trace=trace)
+        out["case_inc_" + name] = np.array([t[3] for t in trace], dtype=np.uint32)
+        out["case_prev_z_nan_" + name] = np.array([bool(np.isnan(leaf.decode(t[1])[2])) for t in trace])
+    out["case_touch"] = np.array([leaf.encode_time(cs.stamps[0], t) for t in cs.stamps], dtype=np.uint32)
+    # --- encodeVoxelTouchTime outside [base, base + 2^32 ms): what the reference's x86-64 build yields
+    base = np.array([100.0, 1.6e9, 0.0, 12345.678])
+    off = np.array([-5.0, -0.0004, -0.001, -1.0, -4294967.296, -4294967.297, -5e6, 4294967.295, 4294967.296, 4294967.2965,
+                    5e6, 8589934.592, 1e9, 9e15, -9e15, 0.0, 0.0005, 0.001, 1e-9])
+    pairs = np.array([(b, b + o) for b in base for o in off])
+    out["touch_in"] = pairs
+    out["touch_out"] = np.array([leaf.encode_time(b, t) for b, t in pairs], dtype=np.uint32)
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_incident.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    if "--incident" not in sys.argv:
+        main()
+    incident()
