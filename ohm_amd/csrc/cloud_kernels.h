@@ -22,6 +22,7 @@
 #ifndef OHMHIP_CLOUD_KERNELS_H
 #define OHMHIP_CLOUD_KERNELS_H
 
+#include "ndt_tsdf_device.h"
 #include "query_kernels.h"
 
 namespace ohmhip

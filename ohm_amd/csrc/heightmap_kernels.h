@@ -27,6 +27,7 @@
 #ifndef OHMHIP_HEIGHTMAP_KERNELS_H
 #define OHMHIP_HEIGHTMAP_KERNELS_H
 
+#include "ndt_tsdf_device.h"
 #include "query_kernels.h"
 
 namespace ohmhip

@@ -409,7 +409,7 @@ struct ohmhip_map_s
   DevArray<uint32_t> d_event_count;  ///< per parity: [0] deferred event count, [1] walk kernel chunk cursor, [2] replay group count, [3] stop iteration flag
   uint32_t walk_workgroups = 256;     ///< persistent walk workgroups: one per CU
   /// Regions / tiles of at most 4 096 voxels (16^3) are walked by the WalkHalf shape of k_region_walk: 512-thread workgroups with
-  /// half of everything, two per CU (occupancy_kernels.h; OHMHIP_WALK_HALF=0 keeps the full shape for A/B runs).
+  /// half of everything, two per CU (walk_kernel.h; OHMHIP_WALK_HALF=0 keeps the full shape for A/B runs).
   bool walk_half = false;
   uint32_t walkSlots() const { return walk_workgroups * (walk_half ? 2u : 1u); }  ///< persistent walk workgroups of a launch
   DevArray<unsigned long long> d_dbg;  ///< 8 debug counters (OHMHIP_DEBUG_FLAGS & 64)

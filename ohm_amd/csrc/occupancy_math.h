@@ -1,0 +1,129 @@
+// occupancy_math.h -- the per-voxel arithmetic of the occupancy mapper, shared by the walk kernel's inline apply and the
+// apply kernels.
+//
+// Ordering argument (why integer counting reproduces the sequential CPU result exactly): every miss applies the
+// same function m(x) and every hit the same h(x) to a voxel's value.  The CPU result for a voxel is the composition
+// of its events in ray order; that composition is fully determined by the NUMBER of misses between consecutive
+// hits.  Integer atomics are order-independent, so counting is deterministic, and the float updates are then
+// replayed one voxel per lane in exactly the CPU order -> bit-identical log-odds.
+#ifndef OHMHIP_OCCUPANCY_MATH_H
+#define OHMHIP_OCCUPANCY_MATH_H
+
+#include "walk_device.h"
+
+namespace ohmhip
+{
+// ---------------------------------------------------------------------------------------------------------------------
+// Occupancy update functions (bit-for-bit the CPU mapper's per-voxel arithmetic).
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ inline float fInf()
+{
+  return __int_as_float(0x7f800000);
+}
+
+/// One miss: ohm/RayMapperOccupancy.cpp:143-163 + ohm/VoxelOccupancyCompute.h:110-120 (null_update == false).
+__device__ inline float occMiss(const MapConst &mc, unsigned ray_flags, float initial)
+{
+  const float inf = fInf();
+  const bool unobserved = initial == inf;
+  const bool is_free = !unobserved && initial < mc.threshold_value;
+  const bool is_occ = !unobserved && initial >= mc.threshold_value;
+  float adj = mc.miss_value;
+  adj = (unobserved && (ray_flags & OHMHIP_RF_EXCLUDE_UNOBSERVED)) ? inf : adj;
+  adj = (is_free && (ray_flags & OHMHIP_RF_EXCLUDE_FREE)) ? 0.0f : adj;
+  adj = (is_occ && (ray_flags & OHMHIP_RF_EXCLUDE_OCCUPIED)) ? 0.0f : adj;
+  const float base = unobserved ? 0.0f : initial;
+  adj = (unobserved || (mc.sat_min < initial && initial < mc.sat_max)) ? adj : 0.0f;
+  return (base != inf) ? fmaxf(mc.min_value, base + adj) : base;
+}
+
+/// One hit: ohm/RayMapperOccupancy.cpp:261-281 + ohm/VoxelOccupancyCompute.h:44-54.
+__device__ inline float occHit(const MapConst &mc, unsigned ray_flags, float initial)
+{
+  const float inf = fInf();
+  const bool unobserved = initial == inf;
+  const bool is_free = !unobserved && initial < mc.threshold_value;
+  const bool is_occ = !unobserved && initial >= mc.threshold_value;
+  float adj = mc.hit_value;
+  adj = (unobserved && (ray_flags & OHMHIP_RF_EXCLUDE_UNOBSERVED)) ? inf : adj;
+  adj = (is_free && (ray_flags & OHMHIP_RF_EXCLUDE_FREE)) ? 0.0f : adj;
+  adj = (is_occ && (ray_flags & OHMHIP_RF_EXCLUDE_OCCUPIED)) ? 0.0f : adj;
+  const float base = unobserved ? 0.0f : initial;
+  adj = (unobserved || (mc.sat_min < initial && initial < mc.sat_max)) ? adj : 0.0f;
+  return (base != inf) ? fminf(base + adj, mc.max_value) : base;
+}
+
+/// n sequential misses.  The update is a deterministic function of the value alone, so once it reaches a fixed point
+/// (the min clamp) the remaining applications are the identity and can be skipped without changing the result.
+__device__ inline float occMissN(const MapConst &mc, unsigned ray_flags, float x, uint32_t n)
+{
+  constexpr unsigned kExcludeFlags = OHMHIP_RF_EXCLUDE_UNOBSERVED | OHMHIP_RF_EXCLUDE_FREE | OHMHIP_RF_EXCLUDE_OCCUPIED;
+  if (n == 0)
+  {
+    return x;
+  }
+  if (!(ray_flags & kExcludeFlags))
+  {
+    // Without the exclusion flags only the FIRST miss can meet an unobserved voxel; every later one is occMiss() of an
+    // observed value, which is these three operations (same operations, same order: bit identical) -- a voxel that is
+    // not yet at the clamp pays them up to ~10 times per batch (a map the sensor is moving through).
+    // The first miss is occMiss() with the exclusion flags known to be clear: its three flag selects and the free / occupied
+    // classification drop out, the remaining operations are the same in the same order (bit identical; -3 us per C1 batch).
+    const bool unobserved = x == fInf();
+    const float base = unobserved ? 0.0f : x;
+    const float first_adj = (unobserved || (mc.sat_min < x && x < mc.sat_max)) ? mc.miss_value : 0.0f;
+    float nx = fmaxf(mc.min_value, base + first_adj);
+    if (nx == x)
+    {
+      return x;
+    }
+    x = nx;
+    for (uint32_t k = 1; k < n; ++k)
+    {
+      const float adj = (mc.sat_min < x && x < mc.sat_max) ? mc.miss_value : 0.0f;
+      nx = fmaxf(mc.min_value, x + adj);
+      if (nx == x)
+      {
+        break;
+      }
+      x = nx;
+    }
+    return x;
+  }
+  for (uint32_t k = 0; k < n; ++k)
+  {
+    const float nx = occMiss(mc, ray_flags, x);
+    if (nx == x)
+    {
+      break;
+    }
+    x = nx;
+  }
+  return x;
+}
+
+/// ohm/VoxelMeanCompute.h:134-152 with Vec3 = dvec3, coord_real = double (as the CPU mappers instantiate it).
+__device__ inline uint32_t subVoxelUpdate(uint32_t coord, uint32_t point_count, const double v[3], double resolution)
+{
+  const int mean_positions = (1 << 10) - 1;
+  const double mean_resolution = resolution / double(mean_positions);
+  const double offset = double(0.5f) * resolution;
+  double mean[3];
+  mean[0] = int(coord & mean_positions) * mean_resolution - offset;
+  mean[1] = int((coord >> 10) & mean_positions) * mean_resolution - offset;
+  mean[2] = int((coord >> 20) & mean_positions) * mean_resolution - offset;
+  const double one_on_count_plus_one = double(1) / double(point_count + 1);
+  uint32_t pattern = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+  {
+    mean[a] += (v[a] - mean[a]) * one_on_count_plus_one;
+    int pos = pointToRegionCoord(mean[a] + offset, mean_resolution);
+    pos = (pos >= 0 ? (pos < (1 << 10) ? pos : mean_positions) : 0);
+    pattern |= uint32_t(pos) << (10 * a);
+  }
+  return pattern | (1u << 31);
+}
+}  // namespace ohmhip
+
+#endif  // OHMHIP_OCCUPANCY_MATH_H

@@ -215,6 +215,35 @@ constexpr int kHitVoxelBits = 15;
 constexpr int kHitSlotShift = kHitRayBits + kHitVoxelBits;
 constexpr uint64_t kHitInvalid = ~0ull;
 
+__host__ __device__ inline uint32_t hitSlot(uint64_t key)
+{
+  return uint32_t(key >> kHitSlotShift);
+}
+
+__host__ __device__ inline uint32_t hitVoxel(uint64_t key)
+{
+  return uint32_t(key >> kHitRayBits) & ((1u << kHitVoxelBits) - 1u);
+}
+
+/// slot | voxel: equal for the keys of one voxel
+__host__ __device__ inline uint64_t hitGroup(uint64_t key)
+{
+  return key >> kHitRayBits;
+}
+
+__host__ __device__ inline uint32_t hitRay(uint64_t key)
+{
+  return uint32_t(key & ((1ull << kHitRayBits) - 1ull));
+}
+
+/// ray_shift == 1 (NDT / TSDF event streams): the ray field holds [ray:28][is_sample:1], and the low bit tags the key as
+/// a sample (hit) event.
+__host__ __device__ inline uint64_t packHitKey(uint32_t slot, uint32_t voxel, uint32_t ray, int ray_shift)
+{
+  return (uint64_t(slot) << kHitSlotShift) | (uint64_t(voxel) << kHitRayBits) | (uint64_t(ray) << ray_shift) |
+         uint64_t(ray_shift ? 1u : 0u);
+}
+
 __host__ __device__ inline uint64_t packRegionKey(int rx, int ry, int rz)
 {
   return kKeyOccupied | uint64_t(uint16_t(rx)) | (uint64_t(uint16_t(ry)) << 16) | (uint64_t(uint16_t(rz)) << 32);

@@ -3,7 +3,13 @@
 #include <cstring>
 #include <string.h>
 
-#include "occupancy_kernels.h"
+#include "apply_kernels.h"
+#include "batch_scratch.h"
+#include "pool_kernels.h"
+#include "ray_front_kernels.h"
+#include "region_table.h"
+#include "sample_sort_kernels.h"
+#include "walk_kernel.h"
 #include "replay_kernels.h"
 #include "traversal_kernels.h"
 #include "query_kernels.h"
@@ -888,411 +894,6 @@ try
 }
 OHMHIP_ABI_CATCH
 
-int ohmhip_map_line_keys(ohmhip_map_t m, const double *lines, size_t line_count, uint32_t max_keys_per_line,
-                         void *keys_out, uint32_t *counts_out)
-try
-{
-  if (!m || (line_count && (!lines || !keys_out || !counts_out)) || max_keys_per_line == 0)
-  {
-    return OHMHIP_ERR_INVALID_ARG;
-  }
-  if (line_count == 0)
-  {
-    return OHMHIP_OK;
-  }
-  OHMHIP_CHECK(settleLaunch(m));  // (the query shares the map's stream and reads its configuration)
-  hipStream_t s = m->stream;
-  const size_t key_bytes = sizeof(GpuKeyOut) * line_count * size_t(max_keys_per_line);
-  DevArray<double> d_lines;
-  DevArray<GpuKeyOut> d_keys;
-  DevArray<uint32_t> d_counts;
-  OHMHIP_CHECK(d_lines.alloc(sizeof(double) * 6 * line_count));
-  OHMHIP_CHECK(d_keys.alloc(key_bytes));
-  OHMHIP_CHECK(d_counts.alloc(sizeof(uint32_t) * line_count));
-  int status = hipMemcpyAsync(d_lines, lines, sizeof(double) * 6 * line_count, hipMemcpyHostToDevice, s);
-  if (!status)
-  {
-    hipLaunchKernelGGL(k_line_keys, dim3(uint32_t((line_count + 255) / 256)), dim3(256), 0, s, m->mc, d_lines,
-                       uint32_t(line_count), max_keys_per_line, d_keys, d_counts);
-    status = hipMemcpyAsync(keys_out, d_keys, key_bytes, hipMemcpyDeviceToHost, s);
-  }
-  if (!status)
-  {
-    status = hipMemcpyAsync(counts_out, d_counts, sizeof(uint32_t) * line_count, hipMemcpyDeviceToHost, s);
-  }
-  if (!status)
-  {
-    status = hipStreamSynchronize(s);
-  }
-  return status;
-}
-OHMHIP_ABI_CATCH
-
-}  // extern "C"
-
-namespace
-{
-/// The map as the read-only kernels see it (MapReadView): configuration, region hash, occupancy layer and the table of
-/// the host store's regions (QuerySpillTable; empty without spill to host).
-int mapReadView(ohmhip_map_t m, MapReadView &view)
-{
-  hipStream_t s = m->stream;
-  ohmhip_map_s::QueryState &qs = m->query;
-  view.mc = m->mc;
-  view.rt = regionTable(m);
-  view.occupancy = static_cast<const float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get());
-  view.spill = QuerySpillTable{ nullptr, nullptr, 0 };
-  if (!m->spilled.empty())
-  {
-    // Regions in the host store answer from their pinned records (device visible), without re-admission.  The table is
-    // rebuilt per call: the store changes with every batch that evicts or re-admits.  (Evictions copy on the copy
-    // stream; the previous query may still read the table being replaced.)
-    OHMHIP_CHECK(hipStreamSynchronize(m->copy_stream));
-    OHMHIP_CHECK(hipStreamSynchronize(s));
-    uint32_t cap = 16;
-    while (cap < 2 * m->spilled.size())
-    {
-      cap <<= 1;
-    }
-    std::vector<unsigned long long> keys(cap, 0ull);
-    std::vector<const float *> blocks(cap, nullptr);
-    for (const auto &entry : m->spilled)
-    {
-      uint32_t idx = hashRegionKey(entry.first, cap - 1);
-      while (keys[idx] != 0)
-      {
-        idx = (idx + 1) & (cap - 1);
-      }
-      keys[idx] = entry.first;
-      blocks[idx] = reinterpret_cast<const float *>(entry.second.record + m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
-    }
-    OHMHIP_CHECK(qs.spill_keys.ensure(sizeof(unsigned long long) * cap, false, s));
-    OHMHIP_CHECK(qs.spill_blocks.ensure(sizeof(const float *) * cap, false, s));
-    OHMHIP_CHECK(hipMemcpy(qs.spill_keys.ptr, keys.data(), sizeof(unsigned long long) * cap, hipMemcpyHostToDevice));
-    OHMHIP_CHECK(hipMemcpy(qs.spill_blocks.ptr, blocks.data(), sizeof(const float *) * cap, hipMemcpyHostToDevice));
-    view.spill = QuerySpillTable{ static_cast<const unsigned long long *>(qs.spill_keys.ptr),
-                                  static_cast<const float *const *>(qs.spill_blocks.ptr), cap - 1 };
-  }
-  return OHMHIP_OK;
-}
-
-/// What both query entry points check before any device work (OHMHIP_ERR_INVALID_ARG / OHMHIP_ERR_UNSUPPORTED).
-int raysQueryRefusal(ohmhip_map_t m, const void *rays, size_t element_count, const void *ranges,
-                     const void *unobserved_volumes, const void *terminal_types)
-{
-  const size_t n = element_count / 2;
-  if (!m || (n && (!rays || !ranges || !unobserved_volumes || !terminal_types)) || n > size_t(0x7fffffff))
-  {
-    return OHMHIP_ERR_INVALID_ARG;
-  }
-  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // the CPU query refuses maps without the layer too (valid_layers)
-  }
-  if (m->mc.owner_world > 1u)
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
-  }
-  return OHMHIP_OK;
-}
-
-/// The query on device arrays, enqueued on the map's stream.  The map is observed as ohmhip_map_read_regions would
-/// observe it: collected rays launched and an asynchronous launch settled first (the caller's OHMHIP_SETTLE), regions
-/// of the host store included.  It changes nothing of the map: no voxel, dirty bit, residency, use stamp or counter.
-int raysQueryDevice(ohmhip_map_t m, const double *d_rays, uint32_t n, double coef, double *d_ranges, double *d_volumes,
-                    int8_t *d_types, GpuKeyOut *d_keys)
-{
-  hipStream_t s = m->stream;
-  ohmhip_map_s::QueryState &qs = m->query;
-  RaysQueryArgs a;
-  OHMHIP_CHECK(mapReadView(m, a));
-  if (n == 0)
-  {
-    return OHMHIP_OK;
-  }
-  OHMHIP_CHECK(qs.walked.ensure(sizeof(int32_t) * n, false, s));
-  OHMHIP_CHECK(qs.last_walked.ensure(sizeof(int32_t) * n, false, s));
-  size_t scan_bytes = 0;
-  int32_t *walked = static_cast<int32_t *>(qs.walked.ptr);
-  int32_t *last_walked = static_cast<int32_t *>(qs.last_walked.ptr);
-  OHMHIP_CHECK(rocprim::inclusive_scan(nullptr, scan_bytes, walked, last_walked, size_t(n), rocprim::maximum<int32_t>(), s));
-  OHMHIP_CHECK(qs.scan_temp.ensure(scan_bytes, false, s));
-  a.rays = d_rays;
-  a.n_rays = n;
-  a.coef = coef;
-  a.ranges = d_ranges;
-  a.volumes = d_volumes;
-  a.types = d_types;
-  a.keys = d_keys;
-  a.walked = walked;
-  hipLaunchKernelGGL(k_rays_query, dim3((n + 255) / 256), dim3(256), 0, s, a);
-  OHMHIP_CHECK(hipGetLastError());
-  OHMHIP_CHECK(rocprim::inclusive_scan(qs.scan_temp.ptr, scan_bytes, walked, last_walked, size_t(n),
-                                       rocprim::maximum<int32_t>(), s));
-  hipLaunchKernelGGL(k_rays_query_carry, dim3((n + 255) / 256), dim3(256), 0, s, d_types, d_keys,
-                     static_cast<const int32_t *>(last_walked), n);
-  return hipGetLastError();
-}
-}  // namespace
-
-extern "C" {
-
-int ohmhip_map_rays_query(ohmhip_map_t m, const double *rays, size_t element_count, double volume_coefficient,
-                          double *ranges, double *unobserved_volumes, int8_t *terminal_types, void *terminal_keys)
-try
-{
-  OHMHIP_CHECK(raysQueryRefusal(m, rays, element_count, ranges, unobserved_volumes, terminal_types));
-  OHMHIP_SETTLE(m);
-  const uint32_t n = uint32_t(element_count / 2);
-  hipStream_t s = m->stream;
-  ohmhip_map_s::QueryState &qs = m->query;
-  if (n)
-  {
-    OHMHIP_CHECK(qs.rays.ensure(sizeof(double) * 6 * n, false, s));
-    OHMHIP_CHECK(qs.ranges.ensure(sizeof(double) * n, false, s));
-    OHMHIP_CHECK(qs.volumes.ensure(sizeof(double) * n, false, s));
-    OHMHIP_CHECK(qs.types.ensure(n, false, s));
-    if (terminal_keys)
-    {
-      OHMHIP_CHECK(qs.keys.ensure(sizeof(GpuKeyOut) * n, false, s));
-    }
-    OHMHIP_CHECK(hipMemcpyAsync(qs.rays.ptr, rays, sizeof(double) * 6 * n, hipMemcpyHostToDevice, s));
-  }
-  double *d_ranges = static_cast<double *>(qs.ranges.ptr);
-  double *d_volumes = static_cast<double *>(qs.volumes.ptr);
-  int8_t *d_types = static_cast<int8_t *>(qs.types.ptr);
-  GpuKeyOut *d_keys = terminal_keys ? static_cast<GpuKeyOut *>(qs.keys.ptr) : nullptr;
-  OHMHIP_CHECK(raysQueryDevice(m, static_cast<const double *>(qs.rays.ptr), n, volume_coefficient, d_ranges, d_volumes,
-                               d_types, d_keys));
-  if (n)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(ranges, d_ranges, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    OHMHIP_CHECK(hipMemcpyAsync(unobserved_volumes, d_volumes, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    OHMHIP_CHECK(hipMemcpyAsync(terminal_types, d_types, n, hipMemcpyDeviceToHost, s));
-    if (terminal_keys)
-    {
-      OHMHIP_CHECK(hipMemcpyAsync(terminal_keys, d_keys, sizeof(GpuKeyOut) * n, hipMemcpyDeviceToHost, s));
-    }
-  }
-  return hipStreamSynchronize(s);
-}
-OHMHIP_ABI_CATCH
-
-int ohmhip_map_rays_query_device(ohmhip_map_t m, const double *d_rays, size_t element_count, double volume_coefficient,
-                                 double *d_ranges, double *d_unobserved_volumes, int8_t *d_terminal_types,
-                                 void *d_terminal_keys)
-try
-{
-  OHMHIP_CHECK(raysQueryRefusal(m, d_rays, element_count, d_ranges, d_unobserved_volumes, d_terminal_types));
-  OHMHIP_SETTLE(m);
-  return raysQueryDevice(m, d_rays, uint32_t(element_count / 2), volume_coefficient, d_ranges, d_unobserved_volumes,
-                         d_terminal_types, static_cast<GpuKeyOut *>(d_terminal_keys));
-}
-OHMHIP_ABI_CATCH
-
-}  // extern "C"
-
-namespace
-{
-/// ClearanceArgs of a clearance query: the checks every entry point makes before any device work, then the search
-/// parameters.  OHMHIP_ERR_INVALID_ARG / OHMHIP_ERR_UNSUPPORTED as include/ohmhip.h lists them.
-int clearanceSetup(ohmhip_map_t m, const void *keys, size_t count, const ohmhip_clearance_params *p, const void *out,
-                   ClearanceArgs &a)
-{
-  if (!m || !p || (count && (!keys || !out)) || count > size_t(0x7fffffff))
-  {
-    return OHMHIP_ERR_INVALID_ARG;
-  }
-  if (!(p->search_radius >= 0.0f) || !std::isfinite(p->search_radius))
-  {
-    return OHMHIP_ERR_INVALID_ARG;
-  }
-  for (int c = 0; c < 3; ++c)
-  {
-    if (!std::isfinite(p->axis_scaling[c]) || p->axis_scaling[c] == 0.0f)
-    {
-      return OHMHIP_ERR_INVALID_ARG;
-    }
-  }
-  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
-  {
-    return OHMHIP_ERR_UNSUPPORTED;
-  }
-  if (m->mc.owner_world > 1u || m->mc.owner_table)
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
-  }
-  // calculateVoxelSearchHalfExtents (ohm/private/VoxelAlgorithms.cpp:16): float radius / double resolution
-  const double h = std::ceil(double(p->search_radius) / m->mc.resolution);
-  if (!(h <= double(kClearanceMaxH)))
-  {
-    return OHMHIP_ERR_UNSUPPORTED;
-  }
-  a = ClearanceArgs{};
-  a.mc = m->mc;
-  a.h = int(h);
-  a.radius = p->search_radius;
-  for (int c = 0; c < 3; ++c)
-  {
-    a.scale[c] = p->axis_scaling[c];
-  }
-  a.unknown_as_occupied = (p->flags & OHMHIP_QF_UNKNOWN_AS_OCCUPIED) ? 1 : 0;
-  a.report_unscaled = (p->flags & OHMHIP_QF_REPORT_UNSCALED) ? 1 : 0;
-  return OHMHIP_OK;
-}
-
-/// Region mode on the map's stream: `count` caller region keys (host), every voxel of each into d_out
-/// ([count][region voxels]).  The map is settled by the caller; the map is read, never written.
-int clearanceRegionsDevice(ohmhip_map_t m, ClearanceArgs &a, const int16_t *keys_xyz, uint32_t count, float *d_out)
-{
-  hipStream_t s = m->stream;
-  ohmhip_map_s::QueryState &qs = m->query;
-  if (count == 0)
-  {
-    return OHMHIP_OK;
-  }
-  OHMHIP_CHECK(mapReadView(m, a));
-  OHMHIP_CHECK(qs.clear_regions.ensure(sizeof(int16_t) * 3 * count, false, s));
-  OHMHIP_CHECK(hipMemcpyAsync(qs.clear_regions.ptr, keys_xyz, sizeof(int16_t) * 3 * count, hipMemcpyHostToDevice, s));
-  const int16_t *d_regions = static_cast<const int16_t *>(qs.clear_regions.ptr);
-  const MapConst &mc = m->mc;
-  const size_t kvox = size_t(mc.kdim[0]) * size_t(mc.kdim[1]) * size_t(mc.kdim[2]);
-  // The LDS path while the window's bitmask and its table of tiles fit: a window of W coordinates touches at most
-  // ceil((W - 1) / dim) + 1 tiles per axis.
-  const int w = kClearanceTile + 2 * a.h;
-  size_t tiles = 1;
-  for (int c = 0; c < 3; ++c)
-  {
-    tiles *= size_t((w - 1 + mc.dim[c] - 1) / mc.dim[c] + 1);
-  }
-  if (a.h <= kClearanceLdsMaxH && tiles <= size_t(kClearanceMaxTileBlocks))
-  {
-    const size_t lds = clearanceLdsBytes(a.h);
-    OHMHIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_clearance_regions_lds),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    const size_t per_region =
-      size_t(clearanceSubTiles(mc.kdim[0])) * clearanceSubTiles(mc.kdim[1]) * clearanceSubTiles(mc.kdim[2]);
-    // (grid.x < 2^31: batches of regions)
-    const uint32_t batch = uint32_t(std::max<size_t>(1, std::min<size_t>(count, size_t(0x7fffffff) / per_region)));
-    for (uint32_t r0 = 0; r0 < count; r0 += batch)
-    {
-      const uint32_t nb = std::min(batch, count - r0);
-      a.regions = d_regions + size_t(r0) * 3;
-      a.n = nb;
-      a.out = d_out + size_t(r0) * kvox;
-      hipLaunchKernelGGL(k_clearance_regions_lds, dim3(uint32_t(nb * per_region)), dim3(kClearanceThreads), lds, s, a);
-      OHMHIP_CHECK(hipGetLastError());
-    }
-    return OHMHIP_OK;
-  }
-  // Large windows: the bitmask of each region's padded box in global memory, in batches of at most 256 MiB.
-  for (int c = 0; c < 3; ++c)
-  {
-    a.pad[c] = mc.kdim[c] + 2 * a.h;
-  }
-  a.words = (a.pad[0] + 63) / 64;
-  const size_t mask_words = size_t(a.pad[2]) * size_t(a.pad[1]) * size_t(a.words);
-  const uint32_t batch = uint32_t(std::max<size_t>(1, std::min<size_t>(count, (size_t(256) << 20) / (8 * mask_words))));
-  OHMHIP_CHECK(qs.clear_mask.ensure(8 * mask_words * batch, false, s));
-  a.mask = static_cast<unsigned long long *>(qs.clear_mask.ptr);
-  for (uint32_t r0 = 0; r0 < count; r0 += batch)
-  {
-    const uint32_t nb = std::min(batch, count - r0);
-    a.regions = d_regions + size_t(r0) * 3;
-    a.n = nb;
-    a.out = d_out + size_t(r0) * kvox;
-    const size_t items = mask_words * nb;
-    hipLaunchKernelGGL(k_clearance_mask, dim3(uint32_t(std::min<size_t>((items + 3) / 4, 65536))), dim3(256), 0, s, a);
-    OHMHIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_clearance_regions_global, dim3(uint32_t((kvox * nb + 255) / 256)), dim3(256), 0, s, a);
-    OHMHIP_CHECK(hipGetLastError());
-  }
-  return OHMHIP_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int ohmhip_map_clearance_regions(ohmhip_map_t m, const int16_t *keys_xyz, size_t count,
-                                 const ohmhip_clearance_params *params, float *const *dsts)
-try
-{
-  ClearanceArgs a;
-  OHMHIP_CHECK(clearanceSetup(m, keys_xyz, count, params, dsts, a));
-  for (size_t i = 0; i < count; ++i)
-  {
-    if (!dsts[i])
-    {
-      return OHMHIP_ERR_INVALID_ARG;
-    }
-  }
-  OHMHIP_SETTLE(m);
-  if (count == 0)
-  {
-    return OHMHIP_OK;
-  }
-  hipStream_t s = m->stream;
-  const size_t kvox = size_t(m->mc.kdim[0]) * size_t(m->mc.kdim[1]) * size_t(m->mc.kdim[2]);
-  OHMHIP_CHECK(m->query.clear_out.ensure(sizeof(float) * kvox * count, false, s));
-  float *d_out = static_cast<float *>(m->query.clear_out.ptr);
-  OHMHIP_CHECK(clearanceRegionsDevice(m, a, keys_xyz, uint32_t(count), d_out));
-  for (size_t i = 0; i < count; ++i)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(dsts[i], d_out + i * kvox, sizeof(float) * kvox, hipMemcpyDeviceToHost, s));
-  }
-  return hipStreamSynchronize(s);
-}
-OHMHIP_ABI_CATCH
-
-int ohmhip_map_clearance_regions_device(ohmhip_map_t m, const int16_t *keys_xyz, size_t count,
-                                        const ohmhip_clearance_params *params, float *d_out)
-try
-{
-  ClearanceArgs a;
-  OHMHIP_CHECK(clearanceSetup(m, keys_xyz, count, params, d_out, a));
-  OHMHIP_SETTLE(m);
-  return clearanceRegionsDevice(m, a, keys_xyz, uint32_t(count), d_out);
-}
-OHMHIP_ABI_CATCH
-
-int ohmhip_map_clearance_keys(ohmhip_map_t m, const void *keys, size_t count, const ohmhip_clearance_params *params,
-                              float *out)
-try
-{
-  ClearanceArgs a;
-  OHMHIP_CHECK(clearanceSetup(m, keys, count, params, out, a));
-  const GpuKeyOut *k = static_cast<const GpuKeyOut *>(keys);
-  for (size_t i = 0; i < count; ++i)
-  {
-    for (int c = 0; c < 3; ++c)
-    {
-      if (int(k[i].voxel[c]) >= m->mc.kdim[c])
-      {
-        return OHMHIP_ERR_INVALID_ARG;  // not a voxel of the map's regions
-      }
-    }
-  }
-  OHMHIP_SETTLE(m);
-  if (count == 0)
-  {
-    return OHMHIP_OK;
-  }
-  hipStream_t s = m->stream;
-  ohmhip_map_s::QueryState &qs = m->query;
-  OHMHIP_CHECK(mapReadView(m, a));
-  OHMHIP_CHECK(qs.clear_keys.ensure(sizeof(GpuKeyOut) * count, false, s));
-  OHMHIP_CHECK(qs.clear_out.ensure(sizeof(float) * count, false, s));
-  OHMHIP_CHECK(hipMemcpyAsync(qs.clear_keys.ptr, keys, sizeof(GpuKeyOut) * count, hipMemcpyHostToDevice, s));
-  a.keys = static_cast<const GpuKeyOut *>(qs.clear_keys.ptr);
-  a.n = uint32_t(count);
-  a.out = static_cast<float *>(qs.clear_out.ptr);
-  hipLaunchKernelGGL(k_clearance_keys, dim3(uint32_t((count + 255) / 256)), dim3(256), 0, s, a);
-  OHMHIP_CHECK(hipGetLastError());
-  OHMHIP_CHECK(hipMemcpyAsync(out, a.out, sizeof(float) * count, hipMemcpyDeviceToHost, s));
-  return hipStreamSynchronize(s);
-}
-OHMHIP_ABI_CATCH
-
 int ohmhip_map_clear(ohmhip_map_t m)
 try
 {
@@ -1321,6 +922,8 @@ OHMHIP_ABI_CATCH
 #include "merge_impl.h"
 #include "partition_impl.h"
 #include "tiling_impl.h"
+#include "query_impl.h"
+#include "clearance_impl.h"
 #include "clearance_update.h"
 #include "heightmap_impl.h"
 #include "cloud_impl.h"

@@ -19,7 +19,8 @@
 #ifndef OHMHIP_QUERY_KERNELS_H
 #define OHMHIP_QUERY_KERNELS_H
 
-#include "occupancy_kernels.h"
+#include "region_table.h"
+#include "walk_device.h"
 
 namespace ohmhip
 {

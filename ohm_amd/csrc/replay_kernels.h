@@ -10,12 +10,14 @@
 #define OHMHIP_REPLAY_KERNELS_H
 
 #include "ndt_tsdf_device.h"
-#include "occupancy_kernels.h"
+#include "batch_scratch.h"
+#include "occupancy_math.h"
+#include "region_table.h"
+#include "secondary_device.h"
 
 namespace ohmhip
 {
 constexpr int kEvRayShift = 1;
-constexpr unsigned long long kEvRayMask = (1ull << kHitRayBits) - 1ull;
 
 __device__ inline void voxelCentreOf(const MapConst &mc, const RegionTable &rt, uint32_t slot, uint32_t vi,
                                      double centre[3])
@@ -92,7 +94,7 @@ __global__ void __launch_bounds__(256)
     if (i < n_events)
     {
       const unsigned long long key = sorted[i];
-      head = key != kHitInvalid && (i == 0 || (sorted[i - 1] >> kHitRayBits) != (key >> kHitRayBits));
+      head = key != kHitInvalid && (i == 0 || hitGroup(sorted[i - 1]) != hitGroup(key));
     }
     const unsigned long long mask = __ballot(head);
     if (mask)
@@ -149,9 +151,9 @@ __device__ inline void replayNdtGroup(const MapConst &mc, const RegionTable &rt,
   float *intensity_layer = ly.intensity;
   uint32_t *hit_miss_layer = ly.hit_miss;
   const unsigned long long key = sorted[i];
-  const unsigned long long group = key >> kHitRayBits;
-  const uint32_t slot = uint32_t(key >> kHitSlotShift);
-  const uint32_t vi = uint32_t(key >> kHitRayBits) & ((1u << kHitVoxelBits) - 1u);
+  const unsigned long long group = hitGroup(key);
+  const uint32_t slot = hitSlot(key);
+  const uint32_t vi = hitVoxel(key);
   const size_t gi = size_t(slot) * size_t(mc.region_voxels) + vi;
 
   double centre_a[3];
@@ -184,11 +186,11 @@ __device__ inline void replayNdtGroup(const MapConst &mc, const RegionTable &rt,
   for (uint32_t j = i; j < n_events; ++j)
   {
     const unsigned long long kj = sorted[j];
-    if ((kj >> kHitRayBits) != group)
+    if (hitGroup(kj) != group)
     {
       break;
     }
-    const uint32_t ray = uint32_t((kj & kEvRayMask) >> kEvRayShift);
+    const uint32_t ray = hitRay(kj) >> kEvRayShift;
     const bool is_sample = (kj & 1ull) != 0;
     double start[3], end[3];
 #pragma unroll
@@ -298,9 +300,9 @@ __device__ inline void replayTsdfGroup(const MapConst &mc, const RegionTable &rt
                                        float *__restrict__ tsdf_layer)
 {
   const unsigned long long key = sorted[i];
-  const unsigned long long group = key >> kHitRayBits;
-  const uint32_t slot = uint32_t(key >> kHitSlotShift);
-  const uint32_t vi = uint32_t(key >> kHitRayBits) & ((1u << kHitVoxelBits) - 1u);
+  const unsigned long long group = hitGroup(key);
+  const uint32_t slot = hitSlot(key);
+  const uint32_t vi = hitVoxel(key);
   const size_t gi = size_t(slot) * size_t(mc.region_voxels) + vi;
   double centre_a[3];
   voxelCentreOf(mc, rt, slot, vi, centre_a);
@@ -310,11 +312,11 @@ __device__ inline void replayTsdfGroup(const MapConst &mc, const RegionTable &rt
   for (uint32_t j = i; j < n_events; ++j)
   {
     const unsigned long long kj = sorted[j];
-    if ((kj >> kHitRayBits) != group)
+    if (hitGroup(kj) != group)
     {
       break;
     }
-    const uint32_t ray = uint32_t((kj & kEvRayMask) >> kEvRayShift);
+    const uint32_t ray = hitRay(kj) >> kEvRayShift;
     // calculateTsdf takes the ORIGINAL (unfiltered) sensor / sample (ohm/RayMapperTsdf.cpp:163-164).
     const D3 sensor = d3(rays[size_t(ray) * 6 + 0], rays[size_t(ray) * 6 + 1], rays[size_t(ray) * 6 + 2]);
     const D3 sample = d3(rays[size_t(ray) * 6 + 3], rays[size_t(ray) * 6 + 4], rays[size_t(ray) * 6 + 5]);
@@ -341,7 +343,7 @@ __global__ void __launch_bounds__(128)
   {
     const uint32_t i = heads ? heads[h] : h;
     const unsigned long long key = sorted[i];
-    if (!heads && (key == kHitInvalid || (i > 0 && (sorted[i - 1] >> kHitRayBits) == (key >> kHitRayBits))))
+    if (!heads && (key == kHitInvalid || (i > 0 && hitGroup(sorted[i - 1]) == hitGroup(key))))
     {
       continue;
     }
@@ -465,13 +467,13 @@ __global__ void __launch_bounds__(128)
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_events; i += gridDim.x * blockDim.x)
   {
     const unsigned long long key = sorted[i];
-    const unsigned long long group = key >> kHitRayBits;
-    if (key == kHitInvalid || (i > 0 && (sorted[i - 1] >> kHitRayBits) == group))
+    const unsigned long long group = hitGroup(key);
+    if (key == kHitInvalid || (i > 0 && hitGroup(sorted[i - 1]) == group))
     {
       continue;  // not the head of its voxel group
     }
-    const uint32_t slot = uint32_t(key >> kHitSlotShift);
-    const uint32_t vi = uint32_t(key >> kHitRayBits) & ((1u << kHitVoxelBits) - 1u);
+    const uint32_t slot = hitSlot(key);
+    const uint32_t vi = hitVoxel(key);
     const size_t gi = size_t(slot) * size_t(mc.region_voxels) + vi;
     int16_t rk[3];
     unpackRegionKey(rt.slot_keys[slot], rk);
@@ -504,11 +506,11 @@ __global__ void __launch_bounds__(128)
     for (uint32_t j = i; j < n_events; ++j)
     {
       const unsigned long long kj = sorted[j];
-      if ((kj >> kHitRayBits) != group)
+      if (hitGroup(kj) != group)
       {
         break;
       }
-      const uint32_t ray = uint32_t((kj & kEvRayMask) >> kEvRayShift);
+      const uint32_t ray = hitRay(kj) >> kEvRayShift;
       const bool is_sample = (kj & 1ull) != 0;
       const uint32_t ray_stop = stop[ray];
       if (is_sample)

@@ -19,7 +19,8 @@
 #ifndef OHMHIP_TRAVERSAL_KERNELS_H
 #define OHMHIP_TRAVERSAL_KERNELS_H
 
-#include "occupancy_kernels.h"
+#include "walk_device.h"
+#include "walk_kernel.h"
 
 namespace ohmhip
 {
