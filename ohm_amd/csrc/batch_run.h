@@ -520,7 +520,11 @@ struct BatchRun
         // applied straight from LDS by the first launch (the repeat only regenerates their events) and the traversal
         // layer has its sums already.
         wa.rewalk = (walk_attempt > 0 && (direct_occ || tsdf_mode)) ? 1 : 0;
-        wa.flag_all = ((tsdf_mode && m->mc.tsdf_dropoff > 0) || stop_mode) ? 1 : 0;
+        // TSDF counts free-space visits only where (min(w + n, max), trunc) is what calculateTsdf gives: integer weights up
+        // to kTsdfCountedWeightLimit and no drop-off.  Above that limit the float32 average of a visit just past the
+        // margin rounds below trunc and w + 1 stops being exact, so every visit is replayed (tests/test_gpu_tsdf_weights.py).
+        wa.flag_all =
+          ((tsdf_mode && (m->mc.tsdf_dropoff > 0 || m->mc.tsdf_max_weight > kTsdfCountedWeightLimit)) || stop_mode) ? 1 : 0;
         wa.inline_hits = occ_inline ? 1 : 0;
         // Traversal layer: its own fp64 pass over the chunk list after the count walk (traversal_kernels.h).
         const bool traversal_pass = sec.traversal != nullptr && walk_attempt == 0;

@@ -435,6 +435,10 @@ __global__ void __launch_bounds__(256) k_batch_reset(BatchScratch bs, uint32_t n
 /// sdf >= kTsdfFreeMargin * trunc leaves a (weight, trunc) voxel at (min(weight + 1, max), trunc) exactly, including
 /// float rounding of (sdf + trunc * w) / (w + 1) for w <= 1e4 (needs > 2e-3 relative margin; 1 % is used).
 constexpr float kTsdfFreeMargin = 1.01f;
+/// The weights that argument covers.  A map whose max_weight lies above it replays every visit (batch_run.h), and an
+/// uploaded voxel whose weight lies above it, or is no integer (n unit increments are then n roundings, w + float(n)
+/// one), is flagged for the ordered replay by k_rebuild_mask.
+constexpr float kTsdfCountedWeightLimit = 1e4f;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // kRfStopOnFirstOccupied (ohm/RayFlag.h:28; ohm/RayMapperOccupancy.cpp:105-193, 222-239).
@@ -688,7 +692,8 @@ __global__ void __launch_bounds__(256)
 }
 
 /// Rebuild the persistent "ordered replay" voxel mask of one region from its stored layers (after a CPU upload):
-/// NDT: voxels holding samples (mean.count > 0); TSDF: observed voxels whose distance is not the free-space value.
+/// NDT: voxels holding samples (mean.count > 0); TSDF: observed voxels whose distance is not the free-space value or
+/// whose weight the counting shortcut does not cover (kTsdfCountedWeightLimit).
 __global__ void __launch_bounds__(256)
   k_rebuild_mask(MapConst mc, uint32_t slot, const uint32_t *__restrict__ mean_layer,
                  const float *__restrict__ tsdf_layer, uint32_t *__restrict__ hit_mask)
@@ -713,6 +718,7 @@ __global__ void __launch_bounds__(256)
           const float wgt = tsdf_layer[2 * (base + vi)];
           const float dist = tsdf_layer[2 * (base + vi) + 1];
           flag = flag || (wgt != 0.0f && dist != mc.tsdf_trunc) || (wgt == 0.0f && dist != 0.0f);
+          flag = flag || wgt > kTsdfCountedWeightLimit || wgt != truncf(wgt);
         }
         bits |= flag ? (1u << b) : 0u;
       }
