@@ -708,6 +708,70 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_cloud_device(ohmhip_map_t map, const ohmhip_c
                                                 double *d_positions_xyz, void *d_keys10, float *d_values,
                                                 uint64_t *d_count);
 
+/* POINT QUERIES.  ohm::NearestNeighbours (ohm/NearestNeighbours.cpp:35-181, 240-284) and voxels read by key or by world
+ * point (ohm::Voxel<T>, OccupancyMap::voxelKey) against the resident map: only the answers cross to the host, where
+ * ohmhip_map_read_regions moves whole region blocks.
+ *  NEAREST NEIGHBOURS.  The CPU query, operation for operation, for query_count near points at once; every obstructing
+ *    voxel within search_radius of a point, or only the closest.  Flags honoured: OHMHIP_QF_UNKNOWN_AS_OCCUPIED and
+ *    OHMHIP_QF_NEAREST_RESULT (ohm/QueryFlag.h:36-42).
+ *    Regions: those with regionKey(near - r) <= key <= regionKey(near + r) per axis (:251-263; regionKey as for the
+ *    cloud's extents, stored in an int16), r the float radius widened to double; visited ascending z, then y, then x
+ *    (ohm/private/OccupancyQueryAlg.h:47-58), their voxels in MapChunk index order x + y * dx + z * dx * dy.
+ *    A voxel obstructs when v != +inf && v >= threshold, or when v == +inf and UNKNOWN_AS_OCCUPIED is set; a NaN never
+ *    obstructs (:78-85).  A region the map does not hold contributes nothing without the flag and all of its voxels
+ *    with it (:54-69); a tile of a tiled region that holds no data reads +inf.
+ *    Range test, fp32 as written (:108-114): q = vec3(near - origin), a double subtract, then narrowed; d = vec3(
+ *    voxelCentreLocal(key)) - q, the centre narrowed first; r2 = (d.x * d.x + d.y * d.y) + d.z * d.z; the voxel passes
+ *    when r2 <= search_radius * search_radius; its range is sqrtf(r2).
+ *    With NEAREST_RESULT the single result of a query is the first voxel in visiting order whose r2 is strictly smaller
+ *    than that of every earlier one (:116-120; ClosestResult, ohm/private/QueryDetail.h:39-43): counts[q] is 0 or 1.
+ *    Results: those of query q start at sum(counts[0 .. q)).  counts and *total are always the full numbers; the
+ *    arrays receive the first min(total, capacity) results -- keys10 in the 10-byte GpuKey layout, ranges (nullable)
+ *    one float each.  capacity == 0 with null arrays only counts.  Two calls on the same map state return identical
+ *    bytes.
+ *    The map is observed as the cloud observes it -- collected rays launched, an asynchronous launch settled, regions of
+ *    the host store from their pinned records, tiled regions in the caller's coordinates -- and nothing of it changes:
+ *    no voxel, dirty bit, residency, use stamp or cache counter.
+ *    OHMHIP_ERR_INVALID_ARG, before any device work, for a null map, params, points (when query_count > 0), counts or
+ *    total, a non-finite point, a negative or non-finite radius, unknown flag bits and capacity > 0 with null keys;
+ *    OHMHIP_ERR_UNSUPPORTED for a map without the occupancy layer and for a map with region ownership or a partition;
+ *    OHMHIP_ERR_CAPACITY, before any kernel runs, when the work list -- one entry per query and OHMHIP_CLOUD_CHUNK_VOXELS
+ *    voxels that may lie in reach -- would exceed 2^24 entries.  query_count == 0 is OK and does nothing.
+ *  VOXEL KEYS.  ohmhip_map_voxel_keys is OccupancyMap::voxelKey(point) (ohm/OccupancyMap.cpp:859-886) of the map's
+ *    geometry: the caller's key in the GpuKey layout, Key::kNull (region lowest() x 3, voxel 0) where the reference
+ *    yields it.  Host arithmetic only.
+ *  VOXEL READS.  ohmhip_map_read_voxels copies, for each key, the ohmhip_layer_voxel_bytes(layer_id) bytes of that voxel
+ *    into values, and sets present[i] = 1 when the map holds the key's region (ohmhip_map_regions lists it).  An absent
+ *    region or a null key: the layer's clear value (occupancy +inf, clearance -1, zeros otherwise) and present 0.  A
+ *    tile of a present tiled region that holds no data: the clear value and present 1.  Resident regions and regions of
+ *    the host store alike; duplicate keys are fine; the map is observed as above and not changed.
+ *    OHMHIP_ERR_INVALID_ARG for a key whose local coordinates lie outside the region dimensions (host arrays only: the
+ *    device variant reads such a key as a null key), a layer id out of range and null arrays with count > 0;
+ *    OHMHIP_ERR_UNSUPPORTED for a layer the map lacks and for a map with region ownership or a partition. */
+#define OHMHIP_QF_NEAREST_RESULT (1u << 1) /* ohm::kQfNearestResult (ohm/QueryFlag.h:40) */
+typedef struct ohmhip_neighbours_params
+{
+  float search_radius;
+  unsigned query_flags; /* OHMHIP_QF_UNKNOWN_AS_OCCUPIED | OHMHIP_QF_NEAREST_RESULT */
+} ohmhip_neighbours_params;
+/* Host pointers; synchronous.  points_xyz: 3 doubles per query. */
+int ohmhip_map_nearest_neighbours(ohmhip_map_t map, const double *points_xyz, size_t query_count,
+                                  const ohmhip_neighbours_params *params, uint64_t capacity, uint64_t *counts,
+                                  void *keys10, float *ranges, uint64_t *total);
+/* The same into DEVICE arrays (d_counts query_count uint64, d_total one uint64), enqueued on the map's stream;
+ * ohmhip_map_sync is the fence.  points_xyz stays a host array: the work list is laid out on the host. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_nearest_neighbours_device(ohmhip_map_t map, const double *points_xyz,
+                                                             size_t query_count,
+                                                             const ohmhip_neighbours_params *params, uint64_t capacity,
+                                                             uint64_t *d_counts, void *d_keys10, float *d_ranges,
+                                                             uint64_t *d_total);
+int ohmhip_map_voxel_keys(ohmhip_map_t map, const double *points_xyz, size_t count, void *keys10);
+int ohmhip_map_read_voxels(ohmhip_map_t map, int layer_id, const void *keys10, size_t count, void *values,
+                           uint8_t *present);
+/* The same on DEVICE arrays, enqueued on the map's stream; ohmhip_map_sync is the fence. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_read_voxels_device(ohmhip_map_t map, int layer_id, const void *d_keys10, size_t count,
+                                                      void *d_values, uint8_t *d_present);
+
 /* GpuTransformSamples::transform (ohmgpu/GpuTransformSamples.h:75-79, .cpp:97-210; kernel transformTimestampedPoints,
  * ohmgpu/gpu/TransformSamples.cl:94-228): sensor-frame samples with time stamps + a timestamped trajectory (translations
  * xyz, rotations as quaternions x,y,z,w) -> world-frame ray pairs (sensor origin, sample), 6 doubles per valid sample,

@@ -6,7 +6,7 @@ is the thin host-side mirror of the reference's interface used by the tests and 
 from ._lib import OhmHipError, LIB_PATH, EXPORTED_SYMBOLS  # noqa: F401
 from .gpumap import (GpuMap, GpuNdtMap, GpuTransformSamples, GpuTsdfMap, LineKeysQueryGpu, NdtMode, OccupancyMap, RayFlag,  # noqa: F401
                      OccupancyType, RaysQueryGpu, RayMapper, LAYERS, QueryFlag, ClearanceProcess, LineQueryGpu,
-                     MappingProcessResult, Mapper,
+                     MappingProcessResult, Mapper, NearestNeighbours,
                      device_count, device_info, probability_to_value, value_to_probability)
 from .heightmap import Heightmap, HeightmapMode, HeightmapVoxelType, UpAxis, HEIGHTMAP_VOXEL_DTYPE  # noqa: F401
 from .cloud import (CloudMode, VoxelCloud, GPU_KEY_DTYPE, CLOUD_CHUNK_VOXELS, cloud_params, count_cloud,  # noqa: F401

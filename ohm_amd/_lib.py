@@ -79,6 +79,14 @@ CLOUD_EXPORT_FREE, CLOUD_IGNORE_VOXEL_MEAN, CLOUD_USE_EXTENTS = 1, 2, 4
 CLOUD_CHUNK_VOXELS = 4096  # OHMHIP_CLOUD_CHUNK_VOXELS
 
 
+class NeighboursParams(C.Structure):
+    """ohmhip_neighbours_params"""
+    _fields_ = [("search_radius", C.c_float), ("query_flags", C.c_uint)]
+
+
+QF_UNKNOWN_AS_OCCUPIED, QF_NEAREST_RESULT = 1, 2
+
+
 class MapConfig(C.Structure):
     _fields_ = [("resolution", C.c_double), ("region_dim", C.c_int * 3), ("origin", C.c_double * 3),
                 ("layers", C.c_uint), ("mode", C.c_int), ("hit_value", C.c_float), ("miss_value", C.c_float),
@@ -195,6 +203,13 @@ _sigs = {
     "ohmhip_map_cloud_count": (C.c_int, [_vp, C.POINTER(CloudParams), C.POINTER(C.c_uint64)]),
     "ohmhip_map_cloud": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "ohmhip_map_cloud_device": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, _vp]),
+    "ohmhip_map_nearest_neighbours": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(NeighboursParams), C.c_uint64, _vp, _vp,
+                                                _vp, C.POINTER(C.c_uint64)]),
+    "ohmhip_map_nearest_neighbours_device": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(NeighboursParams), C.c_uint64,
+                                                       _vp, _vp, _vp, _vp]),
+    "ohmhip_map_voxel_keys": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
+    "ohmhip_map_read_voxels": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
+    "ohmhip_map_read_voxels_device": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
     "ohmhip_map_device_layer_ptr": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "ohmhip_map_region_slot": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "ohmhip_map_ensure_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

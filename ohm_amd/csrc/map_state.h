@@ -387,6 +387,11 @@ struct ohmhip_map_s
     DevBuf hm_winner, hm_rec_occ, hm_rec_vox, hm_rec_mean, hm_counts, hm_out_occ, hm_out_vox, hm_out_mean, hm_out_col;
     /// point clouds (cloud_kernels.h): the work list, per-wave counts and their scan; device copies of the host arrays
     DevBuf cloud_chunks, cloud_partials, cloud_offsets, cloud_scan_temp, cloud_pos, cloud_keys, cloud_values;
+    /// NearestNeighbours (neighbours_kernels.h): the work list, the near points, per-wave counts / closest voxels and
+    /// their scan, per-query counts / closest voxels and their scan; device copies of the host arrays
+    DevBuf nn_chunks, nn_chunk_begin, nn_near, nn_partials, nn_offsets, nn_best, nn_scan_temp;
+    DevBuf nn_query_counts, nn_query_offsets, nn_query_found, nn_query_best, nn_keys, nn_ranges;
+    DevBuf rv_keys, rv_values, rv_present;  ///< voxels read by key: device copies of the host arrays
   } query;
   /// The clearance layer's bookkeeping (clearance_update.h), by the caller's region key -- so it needs no care when a
   /// region changes slot, leaves the pool or comes back.  An update folds the kDirtyClearance bits into `changed` at a

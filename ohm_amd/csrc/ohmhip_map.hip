@@ -16,6 +16,7 @@
 #include "clearance_kernels.h"
 #include "heightmap_kernels.h"
 #include "cloud_kernels.h"
+#include "neighbours_kernels.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -927,3 +928,4 @@ OHMHIP_ABI_CATCH
 #include "clearance_update.h"
 #include "heightmap_impl.h"
 #include "cloud_impl.h"
+#include "neighbours_impl.h"

@@ -51,14 +51,15 @@ OHMHIP_ABI_CATCH
 namespace
 {
 /// The map as the read-only kernels see it (MapReadView): configuration, region hash, occupancy layer and the table of
-/// the host store's regions (QuerySpillTable; empty without spill to host).
-int mapReadView(ohmhip_map_t m, MapReadView &view)
+/// the host store's regions (QuerySpillTable; empty without spill to host).  `layer`: the layer whose blocks the view
+/// addresses (the voxel reads by key look at any layer through the same view).
+int mapReadView(ohmhip_map_t m, MapReadView &view, int layer = OHMHIP_LID_OCCUPANCY)
 {
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
   view.mc = m->mc;
   view.rt = regionTable(m);
-  view.occupancy = static_cast<const float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get());
+  view.occupancy = static_cast<const float *>(m->pool.layers[layer].get());
   view.spill = QuerySpillTable{ nullptr, nullptr, 0 };
   if (!m->spilled.empty())
   {
@@ -82,7 +83,7 @@ int mapReadView(ohmhip_map_t m, MapReadView &view)
         idx = (idx + 1) & (cap - 1);
       }
       keys[idx] = entry.first;
-      blocks[idx] = reinterpret_cast<const float *>(entry.second.record + m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
+      blocks[idx] = reinterpret_cast<const float *>(entry.second.record + m->store.layer_offset[layer]);
     }
     OHMHIP_CHECK(qs.spill_keys.ensure(sizeof(unsigned long long) * cap, false, s));
     OHMHIP_CHECK(qs.spill_blocks.ensure(sizeof(const float *) * cap, false, s));

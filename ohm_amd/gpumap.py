@@ -82,6 +82,10 @@ def _key_records(keys):
     return np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 10)
 
 
+#: ohm::GpuKey (ohmgpu/GpuKey.h:37-46), the record of ohm_amd.GPU_KEY_DTYPE
+_GPU_KEY = np.dtype([("region", "<i2", (3,)), ("voxel", "u1", (4,))])
+
+
 class NdtMode(enum.IntEnum):
     """ohm/NdtMode.h"""
     kNone = 0
@@ -738,6 +742,71 @@ class GpuMap(RayMapper):
                 "clearanceUpdateRegions")
         return int(processed.value)
 
+    def nearestNeighbours(self, points, search_radius, flags=0, capacity=None):
+        """ohm::NearestNeighbours on the device for every row of points ((Q, 3) float64) at once (ohmhip_map_nearest_
+        neighbours; ohm/NearestNeighbours.cpp:35-181, 240-284, operation for operation): every obstructing voxel within
+        search_radius of a point, in the CPU query's visiting order, or with QueryFlag.kQfNearestResult only the closest.
+        flags: kQfUnknownAsOccupied, kQfNearestResult.  Returns (counts (Q,) uint64, keys GPU_KEY_DTYPE, ranges float32);
+        the results of query q start at counts[:q].sum().  capacity: at most that many results are fetched (None: all;
+        0: count only) -- counts are always the full numbers.  The map is read, never changed."""
+        self._push_config_if_changed()
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        nq = points.shape[0]
+        params = L.NeighboursParams(float(search_radius), int(flags) & 0xffffffff)
+        counts = np.zeros(nq, dtype=np.uint64)
+        total = C.c_uint64(0)
+        def call(cap, keys, ranges):
+            L.check(L.lib.ohmhip_map_nearest_neighbours(self._handle, points.ctypes.data, nq, C.byref(params), cap,
+                                                        counts.ctypes.data, keys.ctypes.data if cap else None,
+                                                        ranges.ctypes.data if cap else None, C.byref(total)),
+                    "nearestNeighbours")
+
+        keys, ranges = np.zeros(0, dtype=_GPU_KEY), np.zeros(0, dtype=np.float32)
+        if capacity is None:
+            call(0, keys, ranges)  # count, then fetch exactly that many
+            capacity = int(total.value)
+            if capacity == 0:
+                return counts, keys, ranges
+        capacity = int(capacity)
+        keys, ranges = np.zeros(capacity, dtype=_GPU_KEY), np.zeros(capacity, dtype=np.float32)
+        call(capacity, keys, ranges)
+        n = min(capacity, int(total.value))
+        return counts, keys[:n], ranges[:n]
+
+    def voxelKeys(self, points):
+        """OccupancyMap::voxelKey of every row of points ((N, 3) float64) in the map's geometry (ohmhip_map_voxel_keys):
+        (N,) GPU_KEY_DTYPE records, Key::kNull (region -32768 x 3, voxel 0) where the reference yields it."""
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        keys = np.zeros(points.shape[0], dtype=_GPU_KEY)
+        L.check(L.lib.ohmhip_map_voxel_keys(self._handle, points.ctypes.data, points.shape[0], keys.ctypes.data),
+                "voxelKeys")
+        return keys
+
+    def readVoxels(self, keys, layer_name):
+        """The voxels of layer `layer_name` at keys -- GPU_KEY_DTYPE / (N, 10) uint8 records or a (regions, locals) pair --
+        read on the device (ohmhip_map_read_voxels): (values, present), values typed through LAYERS ((N,) or (N,
+        components)), present (N,) uint8: 1 when the map holds the key's region.  A voxel the map does not hold reads the
+        layer's clear value."""
+        self._push_config_if_changed()
+        lid, dtype, comps = LAYERS[layer_name]
+        rec = _key_records(keys.view(np.uint8) if isinstance(keys, np.ndarray) and keys.dtype == _GPU_KEY else keys)
+        n = rec.shape[0]
+        values = np.zeros((n, comps) if comps > 1 else n, dtype=dtype)
+        present = np.zeros(n, dtype=np.uint8)
+        L.check(L.lib.ohmhip_map_read_voxels(self._handle, lid, rec.ctypes.data, n, values.ctypes.data,
+                                             present.ctypes.data), "readVoxels")
+        return values, present
+
+    def occupancyTypes(self, keys):
+        """OccupancyType of the voxels at keys: kNull where the map does not hold the region, else occupancyType (ohm/
+        VoxelOccupancy.h:116-128: a NaN is unobserved).  (N,) int8."""
+        values, present = self.readVoxels(keys, "occupancy")
+        with np.errstate(invalid="ignore"):
+            types = np.where(values < np.float32(np.inf),
+                             np.where(values < np.float32(self._map.occupancy_threshold_value), OccupancyType.kFree,
+                                      OccupancyType.kOccupied), OccupancyType.kUnobserved)
+        return np.where(present != 0, types, OccupancyType.kNull).astype(np.int8)
+
     def raysQueryDevice(self, d_rays, element_count, d_ranges, d_volumes, d_types, d_keys=None,
                         volume_coefficient=1.0, sync=True):
         """raysQuery on device memory (ohmhip_map_rays_query_device), for rays already in HBM: raw device pointers
@@ -1349,6 +1418,67 @@ class LineQueryGpu:
     def intersectedVoxels(self):
         """(regions (K, 3) int16, local keys (K, 3) uint8) in walk order (one with kQfNearestResult)."""
         return self._regions, self._locals
+
+    def ranges(self):
+        return self._ranges
+
+
+class NearestNeighbours:
+    """ohm::NearestNeighbours (ohm/NearestNeighbours.h) against the device-resident map: the obstructing voxels within
+    search_radius of near_point, or with kQfNearestResult the closest one -- the CPU query's results in its order
+    (GpuMap.nearestNeighbours).  Ranges are float results widened to double, as the reference stores them."""
+
+    def __init__(self, gpu_map, near_point=(0.0, 0.0, 0.0), search_radius=0.0, query_flags=0):
+        self._map = gpu_map
+        self._near_point = tuple(float(v) for v in near_point)
+        self._search_radius = float(np.float32(search_radius))
+        self._flags = int(query_flags)
+        self.reset()
+
+    def nearPoint(self):
+        return self._near_point
+
+    def setNearPoint(self, point):
+        self._near_point = tuple(float(v) for v in point)
+
+    def searchRadius(self):
+        return self._search_radius
+
+    def setSearchRadius(self, radius):
+        self._search_radius = float(np.float32(radius))
+
+    def queryFlags(self):
+        return self._flags
+
+    def setQueryFlags(self, flags):
+        self._flags = int(flags)
+
+    def reset(self, hard_reset=True):
+        self._keys = np.zeros(0, dtype=_GPU_KEY)
+        self._ranges = np.zeros(0, dtype=np.float64)
+
+    def execute(self):
+        self.reset()
+        if self._map is None:
+            return False
+        honoured = int(QueryFlag.kQfUnknownAsOccupied | QueryFlag.kQfNearestResult)
+        _, keys, ranges = self._map.nearestNeighbours([self._near_point], self._search_radius, self._flags & honoured)
+        self._keys = keys
+        self._ranges = ranges.astype(np.float64)
+        return True
+
+    def executeAsync(self):
+        return False  # as the reference's CPU query (ohm/NearestNeighbours.cpp:287-290)
+
+    def wait(self, timeout_ms=0xffffffff):
+        return True
+
+    def numberOfResults(self):
+        return int(self._keys.shape[0])
+
+    def intersectedVoxels(self):
+        """GPU_KEY_DTYPE records."""
+        return self._keys
 
     def ranges(self):
         return self._ranges

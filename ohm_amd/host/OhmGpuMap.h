@@ -347,6 +347,14 @@ public:
 };
 
 /// ohm::GpuMap (ohmgpu/GpuMap.h:143-384)
+/// ohm::GpuKey (ohmgpu/GpuKey.h:37-46): the voxel key record the device reads and writes.
+struct CloudKey
+{
+  int16_t region[3];
+  uint8_t voxel[4];
+};
+static_assert(sizeof(CloudKey) == 10, "CloudKey keeps the 10-byte GpuKey layout");
+
 class GpuMap : public RayMapper
 {
 public:
@@ -753,6 +761,88 @@ public:
       }
       capacity = routed.size() / (6 * sizeof(double));
     }
+  }
+
+  /// ohm::NearestNeighbours for `query_count` near points at once (ohmhip_map_nearest_neighbours): every obstructing voxel
+  /// within search_radius of a point in the CPU query's visiting order, or with kQfNearestResult (1 << 1) the closest;
+  /// kQfUnknownAsOccupied (1 << 0).  counts: results per query; those of query q start at the sum of the counts before
+  /// it.  @return the status (lastStatus() too).
+  int nearestNeighbours(const dvec3 *points, size_t query_count, float search_radius, unsigned query_flags,
+                        std::vector<uint64_t> &counts, std::vector<CloudKey> &keys, std::vector<float> &ranges)
+  {
+    static_assert(sizeof(dvec3) == 3 * sizeof(double), "points are read as 3 doubles each");
+    counts.assign(query_count, 0);
+    keys.clear();
+    ranges.clear();
+    if (!gpuOk() || !pushConfigIfChanged())
+    {
+      return last_status_ = OHMHIP_ERR_INVALID_ARG;
+    }
+    ohmhip_neighbours_params p{};
+    p.search_radius = search_radius;
+    p.query_flags = query_flags & (OHMHIP_QF_UNKNOWN_AS_OCCUPIED | OHMHIP_QF_NEAREST_RESULT);
+    uint64_t total = 0, unused = 0;
+    const double *xyz = query_count ? &points[0].x : nullptr;
+    last_status_ = ohmhip_map_nearest_neighbours(handle_, xyz, query_count, &p, 0, query_count ? counts.data() : &unused,
+                                                 nullptr, nullptr, &total);
+    if (last_status_ != OHMHIP_OK || total == 0)
+    {
+      return last_status_;
+    }
+    keys.resize(size_t(total));
+    ranges.resize(size_t(total));
+    const uint64_t capacity = total;
+    last_status_ = ohmhip_map_nearest_neighbours(handle_, xyz, query_count, &p, capacity, counts.data(), keys.data(),
+                                                 ranges.data(), &total);
+    const size_t held = (last_status_ == OHMHIP_OK) ? size_t(std::min(total, capacity)) : 0;
+    keys.resize(held);
+    ranges.resize(held);
+    return last_status_;
+  }
+
+  /// OccupancyMap::voxelKey of each point in the map's geometry (ohmhip_map_voxel_keys): Key::kNull -- region lowest()
+  /// x 3, voxel 0 -- where the reference yields it.
+  std::vector<CloudKey> voxelKeys(const dvec3 *points, size_t count)
+  {
+    std::vector<CloudKey> keys(count);
+    last_status_ = gpuOk() ? ohmhip_map_voxel_keys(handle_, count ? &points[0].x : nullptr, count, keys.data()) :
+                             OHMHIP_ERR_INVALID_ARG;
+    return keys;
+  }
+
+  /// The voxels of layer `layer_id` at `keys` (ohmhip_map_read_voxels): ohmhip_layer_voxel_bytes(layer_id) bytes each into
+  /// `values`; present[i] = 1 when the map holds the key's region, else the value is the layer's clear value.
+  int readVoxels(int layer_id, const std::vector<CloudKey> &keys, std::vector<uint8_t> &values,
+                 std::vector<uint8_t> &present)
+  {
+    values.assign(keys.size() * ohmhip_layer_voxel_bytes(layer_id), 0);
+    present.assign(keys.size(), 0);
+    if (!gpuOk() || !pushConfigIfChanged())
+    {
+      return last_status_ = OHMHIP_ERR_INVALID_ARG;
+    }
+    return last_status_ = ohmhip_map_read_voxels(handle_, layer_id, keys.data(), keys.size(), values.data(), present.data());
+  }
+
+  /// ohm::OccupancyType of the voxels at `keys`: kNull (-2) where the map does not hold the region, else occupancyType
+  /// (ohm/VoxelOccupancy.h:116-128: unobserved -1 -- a NaN too --, free 0, occupied 1).
+  std::vector<int8_t> occupancyTypes(const std::vector<CloudKey> &keys)
+  {
+    std::vector<uint8_t> values, present;
+    std::vector<int8_t> types(keys.size(), int8_t(-2));
+    if (readVoxels(OHMHIP_LID_OCCUPANCY, keys, values, present) != OHMHIP_OK)
+    {
+      return types;
+    }
+    const float threshold = map_->occupancyThresholdValue();
+    for (size_t i = 0; i < keys.size(); ++i)
+    {
+      float v;
+      std::memcpy(&v, &values[i * sizeof(float)], sizeof(float));
+      const int type = (v < std::numeric_limits<float>::infinity()) ? ((v < threshold) ? 0 : 1) : -1;
+      types[i] = present[i] ? int8_t(type) : int8_t(-2);
+    }
+    return types;
   }
 
   ohmhip_map_t handle() const { return handle_; }
@@ -2075,14 +2165,6 @@ struct CloudOptions
   dvec3 min_extents{ 0, 0, 0 }, max_extents{ 0, 0, 0 };
 };
 
-/// ohm::GpuKey (ohmgpu/GpuKey.h:37-46)
-struct CloudKey
-{
-  int16_t region[3];
-  uint8_t voxel[4];
-};
-static_assert(sizeof(CloudKey) == 10, "CloudKey keeps the 10-byte GpuKey layout");
-
 /// The points of a cloud in the library's fixed order -- regions ascending by (z, y, x), voxels by MapChunk index --
 /// and the number of all matching voxels.
 struct VoxelCloud
@@ -2137,6 +2219,79 @@ inline VoxelCloud extractCloud(GpuMap &gpu_map, const CloudOptions &options = Cl
   cloud.values.resize(held);
   return cloud;
 }
+
+/// ohm::NearestNeighbours (ohm/NearestNeighbours.h; the interface of ohm/Query.h:51-121) against the device-resident map:
+/// the obstructing voxels within searchRadius() of nearPoint(), in the CPU query's visiting order, or with
+/// kQfNearestResult the closest one (GpuMap::nearestNeighbours).  ranges() are float results widened to double, as the
+/// reference stores them.
+class NearestNeighbours
+{
+public:
+  NearestNeighbours(GpuMap &gpu_map, const dvec3 &near_point, float search_radius, unsigned query_flags)
+    : gpu_map_(&gpu_map)
+    , near_point_(near_point)
+    , search_radius_(search_radius)
+    , query_flags_(query_flags)
+  {}
+
+  dvec3 nearPoint() const { return near_point_; }
+  void setNearPoint(const dvec3 &point) { near_point_ = point; }
+  float searchRadius() const { return search_radius_; }
+  void setSearchRadius(float range) { search_radius_ = range; }
+  unsigned queryFlags() const { return query_flags_; }
+  void setQueryFlags(unsigned flags) { query_flags_ = flags; }
+
+  void reset(bool /*hard_reset*/ = true)
+  {
+    intersected_voxels_.clear();
+    ranges_.clear();
+  }
+
+  bool execute()
+  {
+    reset();
+    if (!gpu_map_)
+    {
+      return false;
+    }
+    std::vector<uint64_t> counts;
+    std::vector<CloudKey> keys;
+    std::vector<float> ranges;
+    last_status_ = gpu_map_->nearestNeighbours(&near_point_, 1, search_radius_, query_flags_, counts, keys, ranges);
+    if (last_status_ != OHMHIP_OK)
+    {
+      return false;
+    }
+    for (size_t i = 0; i < keys.size(); ++i)
+    {
+      Key k;
+      for (int c = 0; c < 3; ++c)
+      {
+        k.region[c] = keys[i].region[c];
+        k.local[c] = keys[i].voxel[c];
+      }
+      intersected_voxels_.push_back(k);
+      ranges_.push_back(double(ranges[i]));
+    }
+    return true;
+  }
+  bool executeAsync() { return false; }  // as the reference's CPU query (ohm/NearestNeighbours.cpp:287-290)
+  bool wait(unsigned /*timeout_ms*/ = ~0u) { return true; }
+
+  size_t numberOfResults() const { return intersected_voxels_.size(); }
+  const std::vector<Key> &intersectedVoxels() const { return intersected_voxels_; }
+  const std::vector<double> &ranges() const { return ranges_; }
+  int lastStatus() const { return last_status_; }
+
+private:
+  GpuMap *gpu_map_ = nullptr;
+  dvec3 near_point_{ 0, 0, 0 };
+  float search_radius_ = 0.0f;
+  unsigned query_flags_ = 0;
+  std::vector<Key> intersected_voxels_;
+  std::vector<double> ranges_;
+  int last_status_ = OHMHIP_OK;
+};
 
 /// ohm::configureGpu / gpuDevice (ohmgpu/OhmGpu.h:40-66): select the process-wide device.
 inline int configureGpu(int device_index = 0)

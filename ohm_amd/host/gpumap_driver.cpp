@@ -3,7 +3,7 @@
 // (tests/ohmtestgpu/GpuMapTest.cpp:68-205), syncs, and dumps every region layer for the Python parity test to check
 // against the CPU oracle.  Links libohmhip.so only; built with plain g++ (no hipcc, no glm).
 //
-//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|heightmap|cloud|transform|...> <resolution> <batch_rays>
+//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|heightmap|cloud|neighbours|voxels|transform|...> <resolution> <batch_rays>
 //                 <rays.bin> <out.bin> [search radius] [query flags]
 //   occdev: the sample points (odd entries) go through ohm::GpuTransformSamples with a static identity trajectory and
 //   are integrated straight from the device buffer (all rays then start at the origin).
@@ -455,6 +455,94 @@ int main(int argc, char **argv)
       std::fwrite(cloud.positions.data(), sizeof(ohm::dvec3), cloud.positions.size(), out);
       std::fwrite(cloud.keys.data(), sizeof(ohm::CloudKey), cloud.keys.size(), out);
       std::fwrite(cloud.values.data(), sizeof(float), cloud.values.size(), out);
+      std::fclose(out);
+      return 0;
+    }
+
+    if (mode == "neighbours" || mode == "voxels")
+    {
+      // ohm::NearestNeighbours / GpuMap::nearestNeighbours and the voxel reads: the map (occupancy + mean) is built by
+      // ohm::GpuMap::integrateRays in batches, still collected by batch coalescing when the first query is asked; the
+      // query points are the end points of every 97th ray.
+      //   neighbours: [search radius] [query flags]; out.bin = u64 queries, u64 results, the counts (u64 each), the keys
+      //   (10 bytes each), the ranges (f32), then what an ohm::NearestNeighbours object reports for the first point: u64
+      //   results, per result i16[3] region, u8[3] local, f64 range.
+      //   voxels: out.bin = u64 keys, the keys of GpuMap::voxelKeys (10 bytes each), the occupancy values (f32), the mean
+      //   voxels (8 bytes each), present (u8 each), the occupancy types (i8 each).
+      ohm::OccupancyMap point_map(resolution);
+      point_map.addLayer(OHMHIP_LID_MEAN);
+      ohm::GpuMap point_gpu_map(&point_map, true);
+      const size_t step = std::max<size_t>(2, batch_rays * 2);
+      for (size_t at = 0; at + 1 < rays.size(); at += step)
+      {
+        const size_t count = std::min(step, (rays.size() - at) & ~size_t(1));
+        if (point_gpu_map.integrateRays(rays.data() + at, count) != count)
+        {
+          return 8;
+        }
+      }
+      std::vector<ohm::dvec3> points;
+      for (size_t i = 1; i < rays.size(); i += 2 * 97)
+      {
+        points.push_back(rays[i]);
+      }
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      const uint64_t n_points = points.size();
+      std::fwrite(&n_points, sizeof(n_points), 1, out);
+      if (mode == "neighbours")
+      {
+        const float radius = (argc > 6) ? float(std::atof(argv[6])) : 0.25f;
+        const unsigned flags = (argc > 7) ? unsigned(std::atoi(argv[7])) : 0u;
+        std::vector<uint64_t> counts;
+        std::vector<ohm::CloudKey> keys;
+        std::vector<float> ranges;
+        if (point_gpu_map.nearestNeighbours(points.data(), points.size(), radius, flags, counts, keys, ranges) != OHMHIP_OK)
+        {
+          std::fclose(out);
+          return 8;
+        }
+        const uint64_t n_results = keys.size();
+        std::fwrite(&n_results, sizeof(n_results), 1, out);
+        std::fwrite(counts.data(), sizeof(uint64_t), counts.size(), out);
+        std::fwrite(keys.data(), sizeof(ohm::CloudKey), keys.size(), out);
+        std::fwrite(ranges.data(), sizeof(float), ranges.size(), out);
+        ohm::NearestNeighbours query(point_gpu_map, points.empty() ? ohm::dvec3{ 0, 0, 0 } : points[0], radius, flags);
+        if (!query.execute())
+        {
+          std::fclose(out);
+          return 8;
+        }
+        const uint64_t n_query = query.numberOfResults();
+        std::fwrite(&n_query, sizeof(n_query), 1, out);
+        for (size_t i = 0; i < query.numberOfResults(); ++i)
+        {
+          std::fwrite(query.intersectedVoxels()[i].region, sizeof(int16_t), 3, out);
+          std::fwrite(query.intersectedVoxels()[i].local, 1, 3, out);
+          std::fwrite(&query.ranges()[i], sizeof(double), 1, out);
+        }
+      }
+      else
+      {
+        const std::vector<ohm::CloudKey> keys = point_gpu_map.voxelKeys(points.data(), points.size());
+        std::vector<uint8_t> occupancy, mean, present, present_mean;
+        if (point_gpu_map.lastStatus() != OHMHIP_OK ||
+            point_gpu_map.readVoxels(OHMHIP_LID_OCCUPANCY, keys, occupancy, present) != OHMHIP_OK ||
+            point_gpu_map.readVoxels(OHMHIP_LID_MEAN, keys, mean, present_mean) != OHMHIP_OK || present != present_mean)
+        {
+          std::fclose(out);
+          return 8;
+        }
+        const std::vector<int8_t> types = point_gpu_map.occupancyTypes(keys);
+        std::fwrite(keys.data(), sizeof(ohm::CloudKey), keys.size(), out);
+        std::fwrite(occupancy.data(), 1, occupancy.size(), out);
+        std::fwrite(mean.data(), 1, mean.size(), out);
+        std::fwrite(present.data(), 1, present.size(), out);
+        std::fwrite(types.data(), 1, types.size(), out);
+      }
       std::fclose(out);
       return 0;
     }
