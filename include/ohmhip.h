@@ -772,6 +772,74 @@ int ohmhip_map_read_voxels(ohmhip_map_t map, int layer_id, const void *keys10, s
 OHMHIP_EXPERIMENTAL int ohmhip_map_read_voxels_device(ohmhip_map_t map, int layer_id, const void *d_keys10, size_t count,
                                                       void *d_values, uint8_t *d_present);
 
+/* POINT FILTER.  ohmfilter's filterCloud (utils/ohmfilter/ohmfilter.cpp:150-279): of a point cloud, the points that fall
+ * in an occupied voxel of the resident map and -- on a map with the NDT layers -- inside that voxel's Gaussian
+ * (filterPointByCovariance, :67-91); how a map strips transient objects from a scan.  Per point, only the answers cross
+ * to the host.  For each point p (three doubles):
+ *  1. KEY.  key = OccupancyMap::voxelKey(p) (ohm/OccupancyMap.cpp:859-886), as ohmhip_map_voxel_keys evaluates it.  A
+ *     null key (Key::isNull, ohm/Key.h:206) gives status 0.
+ *  2. OCCUPANCY.  v = the voxel's occupancy; +inf for a region the map does not hold and for a tile of a present tiled
+ *     region that holds no data.  The point is occupied iff v != +inf && v >= threshold (isOccupied, ohm/
+ *     VoxelOccupancy.h:161-164); a NaN is not occupied.  Not occupied: status 0.
+ *  3. COVARIANCE TEST.  It runs iff OHMHIP_PF_OCCUPANCY_ONLY is not set, the map carries both the mean and the covariance
+ *     layer, and expected_value_tolerance >= 0; otherwise an occupied point has status 1 (ohmfilter.cpp:187-221: layer
+ *     availability selects the filter, and a negative tolerance keeps every occupied point).  The test (:67-91,
+ *     :197-203), fp64 throughout with contraction off:
+ *       mean = voxelCentreGlobal(key) + subVoxelToLocalCoord(mean.coord, resolution) -- positionUnsafe, ohm/VoxelMean.h:
+ *         47-54, per axis the centre (ohm/OccupancyMap.h:757-778) and then the decoded offset added; a coord of 0
+ *         decodes like any other, as for the POINT CLOUDS;
+ *       d = p - mean;
+ *       S = covarianceSqrtMatrix (ohm/CovarianceVoxel.h:71-91): the six floats c0..c5 widened to double, the lower
+ *         triangular [[c0,0,0],[c1,c2,0],[c3,c4,c5]], stored by columns m[column][row]: m[0] = (c0, c1, c3), m[1] =
+ *         (0, c2, c4), m[2] = (0, 0, c5);
+ *       v = inverse(S) * d, the inverse as glm writes it, the adjugate times 1 / determinant over the full 3 x 3 matrix,
+ *         zeros included.  glm is not installed beside this library, so the operation order inside inverse is not
+ *         pinned to the reference bit for bit; THIS is the order used:
+ *           r = 1 / (m00 * (m11 * m22 - m21 * m12) - m10 * (m01 * m22 - m21 * m02) + m20 * (m01 * m12 - m11 * m02))
+ *           i00 =  (m11 * m22 - m21 * m12) * r   i10 = -(m10 * m22 - m20 * m12) * r   i20 =  (m10 * m21 - m20 * m11) * r
+ *           i01 = -(m01 * m22 - m21 * m02) * r   i11 =  (m00 * m22 - m20 * m02) * r   i21 = -(m00 * m21 - m20 * m01) * r
+ *           i02 =  (m01 * m12 - m11 * m02) * r   i12 = -(m00 * m12 - m10 * m02) * r   i22 =  (m00 * m11 - m10 * m01) * r
+ *         with mCR = m[C][R] and the sum in r taken left to right; v.x = (i00 * d.x + i10 * d.y) + i20 * d.z, v.y =
+ *         (i01 * d.x + i11 * d.y) + i21 * d.z, v.z = (i02 * d.x + i12 * d.y) + i22 * d.z;
+ *       a = (v.x * v.x + v.y * v.y) + v.z * v.z;
+ *       kept iff fabs(a) < 3.0 + expected_value_tolerance, that sum in fp64.  Status 1 when kept, 2 when removed by this
+ *         test.
+ *     The adjugate form is deliberate: a zero on the diagonal gives a determinant of 0, NaNs in v, and the point is
+ *     removed -- as are points of a voxel with a NaN or infinite entry.  The reference behaves the same way.
+ *  OUTPUTS.  status [count] (nullable): 0 / 1 / 2.  kept_indices [capacity] (null only with capacity == 0): the indices
+ *    of the status-1 points, ascending; it receives the first min(*kept, capacity).  values [count] (nullable): a where
+ *    the covariance test ran, a quiet NaN (0x7ff8000000000000) elsewhere.  keys10 [count] (nullable): each point's key in
+ *    the 10-byte GpuKey layout, Key::kNull as ohmhip_map_voxel_keys writes it.  *kept: always the full number of kept
+ *    points.  Two calls on the same map state return identical bytes: nothing that determines an output uses an atomic.
+ *  The map is observed as the other read-side calls observe it -- collected rays launched, an asynchronous launch
+ *  settled, regions of the host store from their pinned records, tiled regions in the caller's coordinates -- and
+ *  nothing of it changes: no voxel, dirty bit, residency, use stamp or cache counter.
+ *  OHMHIP_ERR_INVALID_ARG, before any device work, for a null map, params or kept, null points with count > 0, unknown
+ *  flag bits, a NaN tolerance, stride_doubles < 3, capacity > 0 with null kept_indices and -- host variant -- a
+ *  non-finite point (the device variant gives such a point status 0 and a null key); OHMHIP_ERR_UNSUPPORTED for a map
+ *  without the occupancy layer and for a map with region ownership or a partition.  count == 0 is OK and writes *kept
+ *  = 0. */
+#define OHMHIP_PF_OCCUPANCY_ONLY (1u << 0) /* ohmfilter --occupancy-only */
+#define OHMHIP_PF_PIECE_POINTS (1u << 18)  /* points per staged piece of the host variant; tests straddle it */
+typedef struct ohmhip_point_filter_params
+{
+  double expected_value_tolerance; /* ohmfilter --tolerance: < 0 turns the covariance test off */
+  uint32_t flags;                  /* OHMHIP_PF_* */
+} ohmhip_point_filter_params;
+/* Host pointers; synchronous.  points_xyz: 3 doubles per point, staged through pinned memory in pieces of
+ * OHMHIP_PF_PIECE_POINTS; indices continue across pieces. */
+int ohmhip_map_filter_points(ohmhip_map_t map, const double *points_xyz, uint64_t count,
+                             const ohmhip_point_filter_params *params, uint64_t capacity, uint8_t *status,
+                             uint64_t *kept_indices, double *values, void *keys10, uint64_t *kept);
+/* The same on DEVICE arrays, enqueued on the map's stream; ohmhip_map_sync is the fence.  Point i is read at d_points +
+ * i * stride_doubles, stride_doubles >= 3: the sample ends of a ray buffer (ohmhip_transform_samples' output: stride 6,
+ * the pointer advanced by 3) are read where they lie.  d_kept: one uint64 on the device.  OHMHIP_ERR_CAPACITY for more
+ * than 2^36 points in one call. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_filter_points_device(ohmhip_map_t map, const double *d_points, uint64_t stride_doubles,
+                                                        uint64_t count, const ohmhip_point_filter_params *params,
+                                                        uint64_t capacity, uint8_t *d_status, uint64_t *d_kept_indices,
+                                                        double *d_values, void *d_keys10, uint64_t *d_kept);
+
 /* GpuTransformSamples::transform (ohmgpu/GpuTransformSamples.h:75-79, .cpp:97-210; kernel transformTimestampedPoints,
  * ohmgpu/gpu/TransformSamples.cl:94-228): sensor-frame samples with time stamps + a timestamped trajectory (translations
  * xyz, rotations as quaternions x,y,z,w) -> world-frame ray pairs (sensor origin, sample), 6 doubles per valid sample,

@@ -87,6 +87,15 @@ class NeighboursParams(C.Structure):
 QF_UNKNOWN_AS_OCCUPIED, QF_NEAREST_RESULT = 1, 2
 
 
+class PointFilterParams(C.Structure):
+    """ohmhip_point_filter_params"""
+    _fields_ = [("expected_value_tolerance", C.c_double), ("flags", C.c_uint32)]
+
+
+PF_OCCUPANCY_ONLY = 1
+PF_PIECE_POINTS = 1 << 18  # OHMHIP_PF_PIECE_POINTS
+
+
 class MapConfig(C.Structure):
     _fields_ = [("resolution", C.c_double), ("region_dim", C.c_int * 3), ("origin", C.c_double * 3),
                 ("layers", C.c_uint), ("mode", C.c_int), ("hit_value", C.c_float), ("miss_value", C.c_float),
@@ -210,6 +219,10 @@ _sigs = {
     "ohmhip_map_voxel_keys": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "ohmhip_map_read_voxels": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
     "ohmhip_map_read_voxels_device": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
+    "ohmhip_map_filter_points": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(PointFilterParams), C.c_uint64, _vp, _vp, _vp,
+                                           _vp, C.POINTER(C.c_uint64)]),
+    "ohmhip_map_filter_points_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.POINTER(PointFilterParams),
+                                                  C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "ohmhip_map_device_layer_ptr": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(C.c_size_t)]),
     "ohmhip_map_region_slot": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "ohmhip_map_ensure_regions": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

@@ -132,3 +132,34 @@ def save_clearance_cloud(file_name, gpu_map, min_extents, max_extents, colour_ra
     export_type is an ohm::OccupancyType, -1 unobserved and up, 0 free and up, 1 occupied."""
     return write_ply(file_name, extract_cloud(gpu_map, CloudMode.CLEARANCE, colour_range=colour_range,
                                               export_type=export_type, extents=(min_extents, max_extents)), colour)
+
+
+def write_filtered_ply(file_name, points, timestamps):
+    """The cloud ohmfilter writes (utils/ohmfilter/ohmfilter.cpp:226-256), in write_ply's conventions: binary little-endian
+    PLY with x y z time, all doubles, one vertex per row of points.  Returns the number of points written."""
+    points = np.ascontiguousarray(points, dtype="<f8").reshape(-1, 3)
+    n = points.shape[0]
+    timestamps = np.ascontiguousarray(timestamps, dtype="<f8").reshape(n)
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n, "property double x",
+              "property double y", "property double z", "property double time", "end_header"]
+    vertices = np.empty(n, dtype=np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("time", "<f8")]))
+    vertices["x"], vertices["y"], vertices["z"], vertices["time"] = points[:, 0], points[:, 1], points[:, 2], timestamps
+    with open(file_name, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(vertices.tobytes())
+    return n
+
+
+def filter_cloud(file_name, gpu_map, points, timestamps, expected_value_tolerance=-1.0, occupancy_only=False):
+    """ohmfilter's filterCloud (utils/ohmfilter/ohmfilter.cpp:158-279) against gpu_map's device map: the points that fall
+    in an occupied voxel -- and, on an NDT map with a tolerance >= 0, inside its Gaussian -- written with their time stamps
+    in input order (GpuMap.filterPoints, write_filtered_ply).  timestamps=None writes zeros.  Returns (points exported,
+    points removed)."""
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    timestamps = np.zeros(points.shape[0]) if timestamps is None else np.asarray(timestamps, dtype=np.float64).reshape(-1)
+    if timestamps.shape[0] != points.shape[0]:
+        raise ValueError("one time stamp per point")
+    _, kept, _, _ = gpu_map.filterPoints(points, expected_value_tolerance, occupancy_only)
+    kept = kept.astype(np.int64)
+    exported = write_filtered_ply(file_name, points[kept], timestamps[kept])
+    return exported, points.shape[0] - exported

@@ -392,6 +392,10 @@ struct ohmhip_map_s
     DevBuf nn_chunks, nn_chunk_begin, nn_near, nn_partials, nn_offsets, nn_best, nn_scan_temp;
     DevBuf nn_query_counts, nn_query_offsets, nn_query_found, nn_query_best, nn_keys, nn_ranges;
     DevBuf rv_keys, rv_values, rv_present;  ///< voxels read by key: device copies of the host arrays
+    /// point filter (point_filter_kernels.h): per-wave kept counts and their scan; one piece of the host variant's
+    /// arrays on the device, and the pinned block its points are staged through (two pieces + the piece's kept count)
+    DevBuf pf_counts, pf_offsets, pf_scan_temp, pf_points, pf_status, pf_values, pf_keys, pf_kept;
+    PinnedBuf<char> pf_staging;
   } query;
   /// The clearance layer's bookkeeping (clearance_update.h), by the caller's region key -- so it needs no care when a
   /// region changes slot, leaves the pool or comes back.  An update folds the kDirtyClearance bits into `changed` at a

@@ -17,6 +17,7 @@
 #include "heightmap_kernels.h"
 #include "cloud_kernels.h"
 #include "neighbours_kernels.h"
+#include "point_filter_kernels.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -929,3 +930,4 @@ OHMHIP_ABI_CATCH
 #include "heightmap_impl.h"
 #include "cloud_impl.h"
 #include "neighbours_impl.h"
+#include "point_filter_impl.h"

@@ -807,6 +807,35 @@ class GpuMap(RayMapper):
                                       OccupancyType.kOccupied), OccupancyType.kUnobserved)
         return np.where(present != 0, types, OccupancyType.kNull).astype(np.int8)
 
+    def filterPoints(self, points, expected_value_tolerance=-1.0, occupancy_only=False, capacity=None):
+        """ohmfilter's test of every row of points ((N, 3) float64) on the device (ohmhip_map_filter_points; utils/
+        ohmfilter/ohmfilter.cpp:150-279): a point is kept when its voxel is occupied and -- on a map with the mean and
+        covariance layers, unless occupancy_only is set or the tolerance is negative -- it lies inside the voxel's
+        Gaussian, a < 3 + expected_value_tolerance (filterPointByCovariance, :67-91).  Returns (status (N,) uint8: 0 not
+        occupied, 1 kept, 2 removed by the covariance test; kept indices uint64, ascending; values (N,) float64: a where
+        the covariance test ran, NaN elsewhere; keys (N,) GPU_KEY_DTYPE).  capacity: at most that many kept indices are
+        fetched (None: room for all; 0: none).  lastFilterKept() is always the full number of kept points.  The map is
+        read, never changed."""
+        self._push_config_if_changed()
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        n = points.shape[0]
+        capacity = n if capacity is None else int(capacity)
+        params = L.PointFilterParams(float(expected_value_tolerance), L.PF_OCCUPANCY_ONLY if occupancy_only else 0)
+        status = np.zeros(n, dtype=np.uint8)
+        indices = np.zeros(capacity, dtype=np.uint64)
+        values = np.zeros(n, dtype=np.float64)
+        keys = np.zeros(n, dtype=_GPU_KEY)
+        kept = C.c_uint64(0)
+        L.check(L.lib.ohmhip_map_filter_points(self._handle, points.ctypes.data if n else None, n, C.byref(params),
+                                               capacity, status.ctypes.data, indices.ctypes.data if capacity else None,
+                                               values.ctypes.data, keys.ctypes.data, C.byref(kept)), "filterPoints")
+        self._last_filter_kept = int(kept.value)
+        return status, indices[:min(capacity, int(kept.value))], values, keys
+
+    def lastFilterKept(self):
+        """The number of points the last filterPoints() kept, whatever its capacity."""
+        return getattr(self, "_last_filter_kept", 0)
+
     def raysQueryDevice(self, d_rays, element_count, d_ranges, d_volumes, d_types, d_keys=None,
                         volume_coefficient=1.0, sync=True):
         """raysQuery on device memory (ohmhip_map_rays_query_device), for rays already in HBM: raw device pointers

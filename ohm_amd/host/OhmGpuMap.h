@@ -845,6 +845,35 @@ public:
     return types;
   }
 
+  /// ohmfilter's test of `count` points (ohmhip_map_filter_points; utils/ohmfilter/ohmfilter.cpp:150-279): status 0 not
+  /// occupied, 1 kept, 2 removed by the covariance test, which runs on a map with the mean and covariance layers unless
+  /// occupancy_only is set or expected_value_tolerance is negative; kept_indices: the indices of the kept points,
+  /// ascending; values: filterPointByCovariance's value where the test ran, NaN elsewhere; keys: each point's voxel key.
+  /// @return the status (lastStatus() too).
+  int filterPoints(const dvec3 *points, size_t count, double expected_value_tolerance, bool occupancy_only,
+                   std::vector<uint8_t> &status, std::vector<uint64_t> &kept_indices, std::vector<double> &values,
+                   std::vector<CloudKey> &keys)
+  {
+    static_assert(sizeof(dvec3) == 3 * sizeof(double), "points are read as 3 doubles each");
+    status.assign(count, 0);
+    kept_indices.assign(count, 0);
+    values.assign(count, 0.0);
+    keys.assign(count, CloudKey{});
+    if (!gpuOk() || !pushConfigIfChanged())
+    {
+      kept_indices.clear();
+      return last_status_ = OHMHIP_ERR_INVALID_ARG;
+    }
+    ohmhip_point_filter_params p{};
+    p.expected_value_tolerance = expected_value_tolerance;
+    p.flags = occupancy_only ? OHMHIP_PF_OCCUPANCY_ONLY : 0u;
+    uint64_t kept = 0;
+    last_status_ = ohmhip_map_filter_points(handle_, count ? &points[0].x : nullptr, count, &p, count, status.data(),
+                                            kept_indices.data(), values.data(), keys.data(), &kept);
+    kept_indices.resize((last_status_ == OHMHIP_OK) ? size_t(kept) : 0);
+    return last_status_;
+  }
+
   ohmhip_map_t handle() const { return handle_; }
   /// Push the map's current parameters (threshold, built-in ray filter, ...) to the device, as a batch would: what a
   /// query of the map (RaysQueryGpu) calls first.  @return false when the device refuses them.

@@ -3,7 +3,7 @@
 // (tests/ohmtestgpu/GpuMapTest.cpp:68-205), syncs, and dumps every region layer for the Python parity test to check
 // against the CPU oracle.  Links libohmhip.so only; built with plain g++ (no hipcc, no glm).
 //
-//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|heightmap|cloud|neighbours|voxels|transform|...> <resolution> <batch_rays>
+//   gpumap_driver <mode: occ|occmean|occdev|ndt|tsdf|linekeys|raysquery|clearance|clearanceupdate|linequery|heightmap|cloud|neighbours|voxels|filter|transform|...> <resolution> <batch_rays>
 //                 <rays.bin> <out.bin> [search radius] [query flags]
 //   occdev: the sample points (odd entries) go through ohm::GpuTransformSamples with a static identity trajectory and
 //   are integrated straight from the device buffer (all rays then start at the origin).
@@ -543,6 +543,62 @@ int main(int argc, char **argv)
         std::fwrite(present.data(), 1, present.size(), out);
         std::fwrite(types.data(), 1, types.size(), out);
       }
+      std::fclose(out);
+      return 0;
+    }
+
+    if (mode == "filter")
+    {
+      // GpuMap::filterPoints: the map (occupancy + mean) is built as for `neighbours`; the points are every ray's end
+      // point and, displaced by [offset] (default 0.35) along x, the same again.  [tolerance] (default -1) [occupancy only].
+      //   out.bin = u64 points, u64 kept, the status (u8 each), the kept indices (u64 each), the values (f64 each), the
+      //   keys (10 bytes each).
+      ohm::OccupancyMap filter_map(resolution);
+      filter_map.addLayer(OHMHIP_LID_MEAN);
+      ohm::GpuMap filter_gpu_map(&filter_map, true);
+      const size_t step = std::max<size_t>(2, batch_rays * 2);
+      for (size_t at = 0; at + 1 < rays.size(); at += step)
+      {
+        const size_t count = std::min(step, (rays.size() - at) & ~size_t(1));
+        if (filter_gpu_map.integrateRays(rays.data() + at, count) != count)
+        {
+          return 8;
+        }
+      }
+      const double tolerance = (argc > 6) ? std::atof(argv[6]) : -1.0;
+      const bool occupancy_only = argc > 7 && std::atoi(argv[7]) != 0;
+      const double offset = (argc > 8) ? std::atof(argv[8]) : 0.35;
+      std::vector<ohm::dvec3> points;
+      for (int pass = 0; pass < 2; ++pass)
+      {
+        for (size_t i = 1; i < rays.size(); i += 2)
+        {
+          ohm::dvec3 p = rays[i];
+          p.x += pass * offset;
+          points.push_back(p);
+        }
+      }
+      std::vector<uint8_t> status;
+      std::vector<uint64_t> kept;
+      std::vector<double> values;
+      std::vector<ohm::CloudKey> keys;
+      if (filter_gpu_map.filterPoints(points.data(), points.size(), tolerance, occupancy_only, status, kept, values, keys) !=
+          OHMHIP_OK)
+      {
+        return 8;
+      }
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      const uint64_t n_points = points.size(), n_kept = kept.size();
+      std::fwrite(&n_points, sizeof(n_points), 1, out);
+      std::fwrite(&n_kept, sizeof(n_kept), 1, out);
+      std::fwrite(status.data(), 1, status.size(), out);
+      std::fwrite(kept.data(), sizeof(uint64_t), kept.size(), out);
+      std::fwrite(values.data(), sizeof(double), values.size(), out);
+      std::fwrite(keys.data(), sizeof(ohm::CloudKey), keys.size(), out);
       std::fclose(out);
       return 0;
     }
