@@ -586,8 +586,8 @@ int ohmhip_map_clearance_update_regions(ohmhip_map_t map, const int16_t *keys_xy
  * voxelKey of the heightmap for voxelCentreGlobal(min_ext_key) - resolution / 2 and voxelCentreGlobal(max_ext_key) +
  * resolution / 2 on a and b.  Cells nobody wrote hold +inf / zeros, as a cleared chunk does.  source_column (optional):
  * the walk index of the column that wrote the cell, 0xffffffff for none.
- * NOT PROVIDED: the flood-fill modes (kSimpleFill, kLayeredFill*: their visiting order depends on earlier results) and
- * with them the virtual-surface filter; blur, mesh, serialisation.  mode != 0: OHMHIP_ERR_UNSUPPORTED.  Surface normals
+ * NOT PROVIDED: the layered fill modes (kLayeredFill*: multi-layer sorting) and with them the virtual-surface filter;
+ * blur, mesh, serialisation.  kSimpleFill is a call of its own (the next block); here mode != 0: OHMHIP_ERR_UNSUPPORTED.  Surface normals
  * from an NDT map's covariance are left 0: the reference derives them with an eigen solver chosen at compile time
  * (Eigen, or 20 rounds of glm::qr_decompose, ohm/CovarianceVoxel.cpp:49-144), so there is no single answer to be
  * exact against.
@@ -608,7 +608,7 @@ typedef struct ohmhip_heightmap_params
   double origin[3];
   uint8_t region_size;             /* 0 = 128 (Heightmap::kDefaultRegionSize) */
   int8_t up_axis;                  /* ohm::UpAxis: -3 (kNegZ) .. 2 (kZ) */
-  uint8_t mode;                    /* 0 = planar; others OHMHIP_ERR_UNSUPPORTED */
+  uint8_t mode;                    /* ohm::HeightmapMode: 0 planar, 1 simple fill (ohmhip_map_heightmap_fill); 2, 3 refused */
   double floor, ceiling, min_clearance;
   unsigned flags;                  /* OHMHIP_HM_* */
 } ohmhip_heightmap_params;
@@ -637,6 +637,64 @@ int ohmhip_map_heightmap(ohmhip_map_t map, const ohmhip_heightmap_params *params
 OHMHIP_EXPERIMENTAL int ohmhip_map_heightmap_device(ohmhip_map_t map, const ohmhip_heightmap_params *params,
                                                     float *d_occupancy, void *d_voxels24, void *d_mean8,
                                                     uint32_t *d_source_column, uint64_t *d_counts);
+
+/* HEIGHTMAP, FLOOD FILL.  ohm::Heightmap::buildHeightmap in HeightmapMode::kSimpleFill, the default of the reference's
+ * ohmheightmap tool (utils/ohmheightmap/ohmheightmap.cpp:158): buildHeightmapT<PlaneFillWalker> (ohmheightmap/Heightmap.
+ * cpp:381-389, 522-700; PlaneFillWalker.cpp/.h).  Every column is searched from the height of the ground found next to
+ * it, so the surface is followed up a ramp or onto a second storey.  Equal to the CPU algorithm for every cell and every
+ * field, and the order of the visits is returned so that it can be held to the reference's FIFO.  Rules 1, 3, 4 and 5
+ * are those of the block above; new or different:
+ *  F1 EXTENTS.  Rule 1.  The visit grid is na x nb over [min_ext_key, max_ext_key]; (a, b, up) as in rule 2.
+ *  F2 SEED.  walk_key = voxelKey(reference_pos); a null key builds nothing.  isBounded / clampToAxis (Heightmap.cpp:552-
+ *    556) and PlaneFillWalker::begin (PlaneFillWalker.cpp:27-41) together clamp it into [min_ext_key, max_ext_key] on all
+ *    three axes.  begin only clears the grid: the seed's cell is not marked visited and the seed is never popped.
+ *  F3 A VISIT of queued key (cell, h), h = the key's offset from min_ext_key on the up index (keyHeight, PlaneFillWalker.
+ *    cpp:153-156: the raw key axis whatever the sign of up_axis): candidate = findNearestSupportingVoxel (rule 3) with
+ *    kVirtualSurfaces / kPromoteVirtualBelow only on the first visit and kBiasAbove added on every later one (Heightmap.
+ *    cpp:385-388, :674) -- with a voxel found below and one above the closer is taken, the one above on a tie -- and
+ *    never kIgnoreVirtualAbove; then findGround (rule 4).  ground_key = the ground found, else the walk key; hg its
+ *    height offset.
+ *  F4 NEIGHBOURS (PlaneFillWalker::visit, PlaneFillWalker.cpp:65-122; the visit mode is ignored except kIgnoreNeighbours,
+ *    which is never passed).  row_delta -1 .. 1 on b (outer), col_delta -1 .. 1 on a (inner), self and cells off the
+ *    grid skipped.  Neighbour n is offered hg and accepts when grid[n] < 0 || hg < grid[n] (Revisit::kLower, the
+ *    constructor default: PlaneFillWalker.h:95-96); an accepted offer appends (n, hg) to the FIFO and sets grid[n] = hg.
+ *    The visiting cell's own entry is not touched.
+ *  F5 POP (walkNext, PlaneFillWalker.cpp:44-62).  The front key is taken and grid[cell] = h of the popped key -- which
+ *    can RAISE the value after a lower offer was accepted in between, so that a later offer gets in again.
+ *  F6 CELL.  Rule 5 with layer 0.  The mode is not multi-layered: a write overwrites, and of all visits that write one
+ *    heightmap cell the one with the LARGEST VISIT SEQUENCE NUMBER stands.  populated counts every write.  No
+ *    virtual-surface filter (ordered layers only).  The walk ends when the FIFO is empty.
+ * Visits are numbered in FIFO order from 0 (the seed).  The device walks one GENERATION of the queue per round --
+ * generation 0 is the seed, generation t + 1 the keys accepted while generation t is visited -- and replays the grid
+ * events of a generation per cell in the reference's order, so the calls below make one host round trip
+ * per generation, the _device variant too.
+ * Results as for the planar call, with source_visit (nullable) in place of source_column: the sequence number of the
+ * visit that wrote the cell, 0xffffffff for none; visit_log (nullable): per visit in sequence order three uint32 ia, ib,
+ * h, the first visit_log_capacity visits (a smaller capacity is not an error; stats.visits is the full count).
+ * stats.revisits: accepted offers to a cell that already held a height.
+ * mode 1 builds; mode 0 is OHMHIP_ERR_INVALID_ARG (the planar call); modes 2 and 3 (kLayeredFillUnordered, kLayeredFill:
+ * multi-layer sorting, the virtual-surface filter) are NOT PROVIDED: OHMHIP_ERR_UNSUPPORTED.  Every other refusal, and
+ * how the map is observed, is the planar call's; OHMHIP_ERR_CAPACITY also when the visits exceed 2^32 - 1 or one
+ * generation 2^31 / 9 keys.  Nothing of the map changes. */
+typedef struct ohmhip_heightmap_fill_stats
+{
+  uint64_t visits;     /* keys visited, the seed included */
+  uint64_t populated;  /* cell writes, overwritten or not */
+  uint64_t cells;      /* cells that hold a value */
+  uint64_t revisits;
+  uint32_t generations, largest_generation;
+} ohmhip_heightmap_fill_stats;
+int ohmhip_map_heightmap_fill_extents(ohmhip_map_t map, const ohmhip_heightmap_params *params,
+                                      ohmhip_heightmap_extents *extents);
+int ohmhip_map_heightmap_fill(ohmhip_map_t map, const ohmhip_heightmap_params *params, float *occupancy, void *voxels24,
+                              void *mean8, uint32_t *source_visit, uint32_t *visit_log, uint64_t visit_log_capacity,
+                              ohmhip_heightmap_fill_stats *stats);
+/* The same into DEVICE arrays (d_visit_log: 3 * visit_log_capacity uint32); the results stay in device memory, stats is
+ * a host struct.  The call still makes the generation loop's host round trips and returns with the map's stream idle. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_heightmap_fill_device(ohmhip_map_t map, const ohmhip_heightmap_params *params,
+                                                         float *d_occupancy, void *d_voxels24, void *d_mean8,
+                                                         uint32_t *d_source_visit, uint32_t *d_visit_log,
+                                                         uint64_t visit_log_capacity, ohmhip_heightmap_fill_stats *stats);
 
 /* POINT CLOUDS.  The voxels of the map that pass a test, as points, compacted on the device: what ohmtools::saveCloud,
  * saveDensityCloud, saveTsdfCloud and saveClearanceCloud (ohmtools/OhmCloud.cpp, driven by ohm2ply) collect on the host

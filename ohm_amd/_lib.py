@@ -64,6 +64,12 @@ class HeightmapExtents(C.Structure):
                 ("mb", C.c_uint32)]
 
 
+class HeightmapFillStats(C.Structure):
+    """ohmhip_heightmap_fill_stats"""
+    _fields_ = [("visits", C.c_uint64), ("populated", C.c_uint64), ("cells", C.c_uint64), ("revisits", C.c_uint64),
+                ("generations", C.c_uint32), ("largest_generation", C.c_uint32)]
+
+
 HM_GENERATE_VIRTUAL_SURFACE, HM_PROMOTE_VIRTUAL_BELOW, HM_IGNORE_VOXEL_MEAN = 1, 2, 4
 
 
@@ -209,6 +215,11 @@ _sigs = {
     "ohmhip_map_heightmap": (C.c_int, [_vp, C.POINTER(HeightmapParams), _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]),
     "ohmhip_map_heightmap_device": (C.c_int, [_vp, C.POINTER(HeightmapParams), _vp, _vp, _vp, _vp, _vp]),
+    "ohmhip_map_heightmap_fill_extents": (C.c_int, [_vp, C.POINTER(HeightmapParams), C.POINTER(HeightmapExtents)]),
+    "ohmhip_map_heightmap_fill": (C.c_int, [_vp, C.POINTER(HeightmapParams), _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                            C.POINTER(HeightmapFillStats)]),
+    "ohmhip_map_heightmap_fill_device": (C.c_int, [_vp, C.POINTER(HeightmapParams), _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                                   C.POINTER(HeightmapFillStats)]),
     "ohmhip_map_cloud_count": (C.c_int, [_vp, C.POINTER(CloudParams), C.POINTER(C.c_uint64)]),
     "ohmhip_map_cloud": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "ohmhip_map_cloud_device": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, _vp]),

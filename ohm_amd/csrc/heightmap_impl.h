@@ -6,8 +6,9 @@
 
 namespace
 {
-/// What every heightmap entry point checks before any device work.
-int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p)
+/// What every heightmap entry point checks before any device work.  `fill`: the flood-fill entry points
+/// (heightmap_fill_impl.h), which build mode 1 and send mode 0 to the planar ones.
+int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p, bool fill = false)
 {
   if (!p)
   {
@@ -24,9 +25,13 @@ int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p)
       return OHMHIP_ERR_INVALID_ARG;
     }
   }
-  if (p->mode != 0)
+  if (fill && p->mode == 0)
   {
-    return OHMHIP_ERR_UNSUPPORTED;  // the flood-fill modes
+    return OHMHIP_ERR_INVALID_ARG;  // planar: ohmhip_map_heightmap
+  }
+  if (p->mode != (fill ? 1 : 0))
+  {
+    return OHMHIP_ERR_UNSUPPORTED;  // the flood-fill modes here; the layered ones everywhere
   }
   if (!m)
   {

@@ -385,6 +385,11 @@ struct ohmhip_map_s
     DevBuf clear_regions, clear_keys, clear_out, clear_mask;  ///< clearance queries (clearance_kernels.h)
     /// heightmap (heightmap_kernels.h): per-cell winner, per-column records, counters; device copies of the host arrays
     DevBuf hm_winner, hm_rec_occ, hm_rec_vox, hm_rec_mean, hm_counts, hm_out_occ, hm_out_vox, hm_out_mean, hm_out_col;
+    /// flood-fill heightmap (heightmap_fill_kernels.h): the visit grid, the queue of every visit, per key of a
+    /// generation its ground height and heightmap cell, the cell events unsorted / sorted, the accept flags and their
+    /// scan, sort and scan scratch, the log's device copy; the pinned word the next generation's size is read through
+    DevBuf hmf_grid, hmf_queue, hmf_ground, hmf_rec_cell, hmf_keys_a, hmf_keys_b, hmf_accept, hmf_accept_at, hmf_temp, hmf_log;
+    PinnedBuf<uint32_t> hmf_next;
     /// point clouds (cloud_kernels.h): the work list, per-wave counts and their scan; device copies of the host arrays
     DevBuf cloud_chunks, cloud_partials, cloud_offsets, cloud_scan_temp, cloud_pos, cloud_keys, cloud_values;
     /// NearestNeighbours (neighbours_kernels.h): the work list, the near points, per-wave counts / closest voxels and

@@ -1,6 +1,6 @@
-"""ohm::Heightmap (ohmheightmap/Heightmap.h) in planar mode, built on the device from the resident map of a GpuMap
-(ohmhip_map_heightmap: include/ohmhip.h, "HEIGHTMAP").  Only the results cross to the host: three dense (mb, ma) arrays
-over the heightmap cells the source's extents cover."""
+"""ohm::Heightmap (ohmheightmap/Heightmap.h) in planar and simple-fill mode, built on the device from the resident map of
+a GpuMap (ohmhip_map_heightmap, ohmhip_map_heightmap_fill: include/ohmhip.h, "HEIGHTMAP").  Only the results cross to
+the host: three dense (mb, ma) arrays over the heightmap cells the source's extents cover."""
 import ctypes as C
 import enum
 
@@ -28,7 +28,7 @@ class HeightmapVoxelType(enum.IntEnum):
 
 
 class HeightmapMode(enum.IntEnum):
-    """ohm::HeightmapMode (ohmheightmap/HeightmapMode.h); only kPlanar is built on the device."""
+    """ohm::HeightmapMode (ohmheightmap/HeightmapMode.h); kPlanar and kSimpleFill are built on the device."""
     kPlanar = 0
     kSimpleFill = 1
     kLayeredFillUnordered = 2
@@ -41,13 +41,17 @@ HEIGHTMAP_VOXEL_DTYPE = np.dtype([("height", "<f4"), ("clearance", "<f4"), ("nor
                                   ("contributing_samples", "<u2")])
 kHvfObservedAbove = 1
 kNoSourceColumn = 0xFFFFFFFF
+kNoSourceVisit = 0xFFFFFFFF
 
 
 class Heightmap:
     """Heightmap(grid_resolution, min_clearance, up_axis=UpAxis.kZ, region_size=0): the reference's setters are
     properties.  After build_heightmap(): occupancy (float32: +1 surface, -1 virtual surface, +inf nothing), voxels
     (HEIGHTMAP_VOXEL_DTYPE), mean ((mb, ma, 2) uint32 or None), source_column (walk index of the source column that
-    wrote the cell), populated_count, cell_count, extents (the _lib.HeightmapExtents of the build)."""
+    wrote the cell), populated_count, cell_count, extents (the _lib.HeightmapExtents of the build).
+    mode = HeightmapMode.kSimpleFill builds the flood fill: source_visit (sequence number of the visit that wrote the
+    cell) stands in place of source_column, fill_stats is the _lib.HeightmapFillStats of the build and, with
+    keep_visit_log set, visit_log the (visits, 3) uint32 array ia, ib, h of every visit in the reference's FIFO order."""
 
     kDefaultRegionSize = 128
 
@@ -62,12 +66,14 @@ class Heightmap:
         self.generate_virtual_surface = False
         self.promote_virtual_below = False
         self.mode = HeightmapMode.kPlanar
+        self.keep_visit_log = False
         self.heightmap_origin = (0.0, 0.0, 0.0)
         self._gpu_map = None
         self._clear()
 
     def _clear(self):
         self.occupancy = self.voxels = self.mean = self.source_column = None
+        self.source_visit = self.visit_log = self.fill_stats = None
         self.populated_count = 0
         self.cell_count = 0
         self.extents = None
@@ -113,6 +119,8 @@ class Heightmap:
             return False
         handle = self._gpu_map._handle
         p = self.params(reference_pos, cull_to)
+        if self.mode == HeightmapMode.kSimpleFill:
+            return self._build_fill(handle, p)
         e = L.HeightmapExtents()
         L.check(L.lib.ohmhip_map_heightmap_extents(handle, C.byref(p), C.byref(e)), "ohmhip_map_heightmap_extents")
         self.extents = e
@@ -130,6 +138,38 @@ class Heightmap:
                 "ohmhip_map_heightmap")
         self.populated_count = int(populated.value)
         self.cell_count = int(cells.value)
+        return self.populated_count != 0
+
+    def _build_fill(self, handle, p):
+        e = L.HeightmapExtents()
+        L.check(L.lib.ohmhip_map_heightmap_fill_extents(handle, C.byref(p), C.byref(e)),
+                "ohmhip_map_heightmap_fill_extents")
+        self.extents = e
+        if not e.populated:
+            return False
+        shape = (int(e.mb), int(e.ma))
+        self.occupancy = np.empty(shape, dtype=np.float32)
+        self.voxels = np.empty(shape, dtype=HEIGHTMAP_VOXEL_DTYPE)
+        self.mean = np.empty(shape + (2,), dtype=np.uint32) if e.use_mean else None
+        self.source_visit = np.empty(shape, dtype=np.uint32)
+        stats = L.HeightmapFillStats()
+        # the number of visits is known after the walk: a log too small for it is fetched by a second build
+        capacity = 4 * int(e.na) * int(e.nb) if self.keep_visit_log else 0
+        while True:
+            log = np.empty((capacity, 3), dtype=np.uint32) if capacity else None
+            L.check(L.lib.ohmhip_map_heightmap_fill(handle, C.byref(p), self.occupancy.ctypes.data,
+                                                    self.voxels.ctypes.data,
+                                                    self.mean.ctypes.data if self.mean is not None else None,
+                                                    self.source_visit.ctypes.data,
+                                                    log.ctypes.data if log is not None else None, capacity,
+                                                    C.byref(stats)), "ohmhip_map_heightmap_fill")
+            if log is None or int(stats.visits) <= capacity:
+                break
+            capacity = int(stats.visits)
+        self.fill_stats = stats
+        self.visit_log = log[:int(stats.visits)].copy() if log is not None else None
+        self.populated_count = int(stats.populated)
+        self.cell_count = int(stats.cells)
         return self.populated_count != 0
 
     def _hm_dims(self):

@@ -1937,7 +1937,7 @@ enum class HeightmapVoxelType : uint8_t
   kVirtualSurface
 };
 
-/// ohm::HeightmapMode (ohmheightmap/HeightmapMode.h); only kPlanar is built on the device.
+/// ohm::HeightmapMode (ohmheightmap/HeightmapMode.h); kPlanar and kSimpleFill are built on the device.
 enum class HeightmapMode : int
 {
   kPlanar = 0,
@@ -1965,8 +1965,9 @@ struct VoxelMean
   uint32_t count;
 };
 
-/// ohm::Heightmap (ohmheightmap/Heightmap.h) in planar mode, built on the device from the resident map of a GpuMap
-/// (ohmhip_map_heightmap: include/ohmhip.h, "HEIGHTMAP"), equal to the CPU algorithm for every cell and field.  Only the
+/// ohm::Heightmap (ohmheightmap/Heightmap.h) in planar and simple-fill mode, built on the device from the resident map
+/// of a GpuMap (ohmhip_map_heightmap, ohmhip_map_heightmap_fill: include/ohmhip.h, "HEIGHTMAP"), equal to the CPU
+/// algorithm for every cell and field; the layered fill modes are refused (OHMHIP_ERR_UNSUPPORTED).  Only the
 /// results cross to the host: the heightmap's layers as dense arrays of heightmapCellsA() x heightmapCellsB() cells, a
 /// fastest, over the cell range the source's extents cover (extents()).
 class Heightmap
@@ -2020,6 +2021,9 @@ public:
     occupancy_.clear();
     voxels_.clear();
     mean_.clear();
+    source_visit_.clear();
+    visit_log_.clear();
+    fill_stats_ = ohmhip_heightmap_fill_stats{};
     populated_ = cells_ = 0;
     extents_ = ohmhip_heightmap_extents{};
     if (!gpu_map_ || !gpu_map_->gpuOk() || !gpu_map_->syncConfig())
@@ -2048,7 +2052,9 @@ public:
     p.flags = (generate_virtual_surface_ ? OHMHIP_HM_GENERATE_VIRTUAL_SURFACE : 0u) |
               (promote_virtual_below_ ? OHMHIP_HM_PROMOTE_VIRTUAL_BELOW : 0u) |
               (ignore_voxel_mean_ ? OHMHIP_HM_IGNORE_VOXEL_MEAN : 0u);
-    last_status_ = ohmhip_map_heightmap_extents(gpu_map_->handle(), &p, &extents_);
+    const bool fill = mode_ == HeightmapMode::kSimpleFill;  // the layered modes: refused by the planar call
+    last_status_ = fill ? ohmhip_map_heightmap_fill_extents(gpu_map_->handle(), &p, &extents_) :
+                          ohmhip_map_heightmap_extents(gpu_map_->handle(), &p, &extents_);
     if (last_status_ != OHMHIP_OK || !extents_.populated)
     {
       return false;
@@ -2059,6 +2065,10 @@ public:
     if (extents_.use_mean)
     {
       mean_.resize(n);
+    }
+    if (fill)
+    {
+      return buildFill(p, n);
     }
     uint64_t populated = 0, cells = 0;
     last_status_ = ohmhip_map_heightmap(gpu_map_->handle(), &p, occupancy_.data(), voxels_.data(),
@@ -2086,6 +2096,13 @@ public:
   const std::vector<float> &occupancy() const { return occupancy_; }
   const std::vector<HeightmapVoxel> &heightmapVoxels() const { return voxels_; }
   const std::vector<VoxelMean> &voxelMeans() const { return mean_; }
+  /// HeightmapMode::kSimpleFill: per cell the sequence number of the visit that wrote it (0xffffffff: none), the
+  /// walk's counts and, after setKeepVisitLog(true), ia, ib, h of every visit in the reference's FIFO order.
+  const std::vector<uint32_t> &sourceVisits() const { return source_visit_; }
+  const ohmhip_heightmap_fill_stats &fillStats() const { return fill_stats_; }
+  void setKeepVisitLog(bool keep) { keep_visit_log_ = keep; }
+  bool keepVisitLog() const { return keep_visit_log_; }
+  const std::vector<uint32_t> &visitLog() const { return visit_log_; }
 
   /// voxelCentreGlobal of the heightmap's own OccupancyMap (ohm/OccupancyMap.h:757-778).
   dvec3 voxelCentreGlobal(const Key &key) const
@@ -2153,6 +2170,39 @@ public:
   }
 
 private:
+  /// ohmhip_map_heightmap_fill into the arrays sized by buildHeightmap.  The number of visits is known after the walk:
+  /// a log too small for it is fetched by a second build.
+  bool buildFill(const ohmhip_heightmap_params &p, size_t n)
+  {
+    source_visit_.resize(n);
+    uint64_t capacity = keep_visit_log_ ? 4ull * extents_.na * extents_.nb : 0;
+    for (;;)
+    {
+      visit_log_.resize(size_t(3 * capacity));
+      last_status_ = ohmhip_map_heightmap_fill(gpu_map_->handle(), &p, occupancy_.data(), voxels_.data(),
+                                               extents_.use_mean ? mean_.data() : nullptr, source_visit_.data(),
+                                               capacity ? visit_log_.data() : nullptr, capacity, &fill_stats_);
+      if (last_status_ != OHMHIP_OK)
+      {
+        occupancy_.clear();
+        voxels_.clear();
+        mean_.clear();
+        source_visit_.clear();
+        visit_log_.clear();
+        return false;
+      }
+      if (!capacity || fill_stats_.visits <= capacity)
+      {
+        break;
+      }
+      capacity = fill_stats_.visits;
+    }
+    visit_log_.resize(capacity ? size_t(3 * fill_stats_.visits) : 0);
+    populated_ = fill_stats_.populated;
+    cells_ = fill_stats_.cells;
+    return populated_ != 0;
+  }
+
   GpuMap *gpu_map_ = nullptr;
   double grid_resolution_;
   double min_clearance_;
@@ -2166,6 +2216,9 @@ private:
   std::vector<float> occupancy_;
   std::vector<HeightmapVoxel> voxels_;
   std::vector<VoxelMean> mean_;
+  std::vector<uint32_t> source_visit_, visit_log_;
+  ohmhip_heightmap_fill_stats fill_stats_{};
+  bool keep_visit_log_ = false;
   uint64_t populated_ = 0, cells_ = 0;
   int last_status_ = OHMHIP_OK;
 };

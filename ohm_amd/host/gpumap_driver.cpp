@@ -10,6 +10,8 @@
 //   transform: <rays.bin> is a trajectory-and-samples file instead and <out.bin> receives the ray buffer of
 //   ohm::GpuTransformSamples::transform (layouts at the mode below); <resolution> and <batch_rays> are not used.
 //   filter:<clipbounded|cliptobounds|clipray|goodray>: host only, one record per ray (layout at the mode below).
+//   heightmapfill: <rays.bin> is a scene file (voxels written directly) and <out.bin> receives the flood-fill
+//   heightmap of ohm::Heightmap in HeightmapMode::kSimpleFill (layouts at the mode below); <batch_rays> is not used.
 //   rays.bin: u64 n_points, then n_points * 3 doubles.  out.bin: u64 regions, per region i16[3] key, then per enabled
 //   layer (ascending id): u32 layer id, u64 bytes, payload.
 #include "OhmGpuMap.h"
@@ -176,6 +178,101 @@ int main(int argc, char **argv)
         const double xyz[3] = { world[i].x, world[i].y, world[i].z };
         std::fwrite(xyz, sizeof(double), 3, out);
       }
+      std::fclose(out);
+      return 0;
+    }
+
+    if (mode == "heightmapfill")
+    {
+      // ohm::Heightmap in HeightmapMode::kSimpleFill over a map whose voxels are written directly; <rays.bin> is a scene
+      // file instead (<batch_rays> is not used).  in: i32 region dims[3], f64 reference[3], f64 floor, ceiling,
+      // min_clearance, i32 up axis, u32 flags (1 virtual surfaces, 2 promote below), u64 regions, then per region i16[3]
+      // key and its occupancy block.  out: u32 ma, u32 mb, the ohmhip_heightmap_fill_stats, u64 surface and u64 virtual
+      // cells as getHeightmapVoxelInfo names them, then the occupancy, HeightmapVoxel, source visit arrays and the log.
+      FILE *sin = std::fopen(argv[4], "rb");
+      if (!sin)
+      {
+        return 4;
+      }
+      int32_t dims[3] = { 0, 0, 0 }, up_axis = 2;
+      double numbers[6] = {};
+      uint32_t flags = 0;
+      uint64_t regions = 0;
+      bool read_ok = std::fread(dims, sizeof(int32_t), 3, sin) == 3 && std::fread(numbers, sizeof(double), 6, sin) == 6 &&
+                     std::fread(&up_axis, sizeof(up_axis), 1, sin) == 1 && std::fread(&flags, sizeof(flags), 1, sin) == 1 &&
+                     std::fread(&regions, sizeof(regions), 1, sin) == 1;
+      ohm::OccupancyMap fill_map(resolution, dims[0], dims[1], dims[2]);
+      for (uint64_t i = 0; read_ok && i < regions; ++i)
+      {
+        std::array<int16_t, 3> key{};
+        read_ok = std::fread(key.data(), sizeof(int16_t), 3, sin) == 3;
+        if (read_ok)
+        {
+          std::vector<uint8_t> &block = fill_map.region(key).voxel_blocks[OHMHIP_LID_OCCUPANCY];
+          block.resize(sizeof(float) * fill_map.regionVoxelVolume());
+          read_ok = std::fread(block.data(), 1, block.size(), sin) == block.size();
+        }
+      }
+      std::fclose(sin);
+      if (!read_ok)
+      {
+        return 4;
+      }
+      ohm::GpuMap fill_gpu_map(&fill_map, true);
+      fill_gpu_map.uploadRegions(nullptr, 0);
+      ohm::Heightmap heightmap(resolution, numbers[5], ohm::UpAxis(up_axis));
+      heightmap.setOccupancyMap(&fill_gpu_map);
+      heightmap.setFloor(numbers[3]);
+      heightmap.setCeiling(numbers[4]);
+      heightmap.setGenerateVirtualSurface((flags & 1u) != 0);
+      heightmap.setPromoteVirtualBelow((flags & 2u) != 0);
+      heightmap.setKeepVisitLog(true);
+      heightmap.setMode(ohm::HeightmapMode::kLayeredFill);
+      if (heightmap.buildHeightmap(ohm::dvec3{ numbers[0], numbers[1], numbers[2] }) ||
+          heightmap.lastStatus() != OHMHIP_ERR_UNSUPPORTED)
+      {
+        return 7;  // the layered modes stay refused
+      }
+      heightmap.setMode(ohm::HeightmapMode::kSimpleFill);
+      if (!heightmap.buildHeightmap(ohm::dvec3{ numbers[0], numbers[1], numbers[2] }))
+      {
+        return 8;
+      }
+      uint64_t types[2] = { 0, 0 };
+      const ohmhip_heightmap_extents &e = heightmap.extents();
+      const int axis_a = heightmap.surfaceAxisIndexA(), axis_b = heightmap.surfaceAxisIndexB();
+      const long region_size = long(ohm::Heightmap::kDefaultRegionSize);
+      for (uint32_t cb = 0; cb < e.mb; ++cb)
+      {
+        for (uint32_t ca = 0; ca < e.ma; ++ca)
+        {
+          ohm::Key key{};
+          const long ga = long(e.first_region[0]) * region_size + e.first_local[0] + long(ca);
+          const long gb = long(e.first_region[1]) * region_size + e.first_local[1] + long(cb);
+          key.region[axis_a] = int16_t(ga >= 0 ? ga / region_size : -((-ga + region_size - 1) / region_size));
+          key.local[axis_a] = uint8_t(ga - long(key.region[axis_a]) * region_size);
+          key.region[axis_b] = int16_t(gb >= 0 ? gb / region_size : -((-gb + region_size - 1) / region_size));
+          key.local[axis_b] = uint8_t(gb - long(key.region[axis_b]) * region_size);
+          ohm::dvec3 pos{};
+          const ohm::HeightmapVoxelType type = heightmap.getHeightmapVoxelInfo(key, &pos);
+          types[0] += type == ohm::HeightmapVoxelType::kSurface;
+          types[1] += type == ohm::HeightmapVoxelType::kVirtualSurface;
+        }
+      }
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      const uint32_t ma = uint32_t(heightmap.heightmapCellsA()), mb = uint32_t(heightmap.heightmapCellsB());
+      std::fwrite(&ma, sizeof(ma), 1, out);
+      std::fwrite(&mb, sizeof(mb), 1, out);
+      std::fwrite(&heightmap.fillStats(), sizeof(ohmhip_heightmap_fill_stats), 1, out);
+      std::fwrite(types, sizeof(uint64_t), 2, out);
+      std::fwrite(heightmap.occupancy().data(), sizeof(float), heightmap.occupancy().size(), out);
+      std::fwrite(heightmap.heightmapVoxels().data(), sizeof(ohm::HeightmapVoxel), heightmap.heightmapVoxels().size(), out);
+      std::fwrite(heightmap.sourceVisits().data(), sizeof(uint32_t), heightmap.sourceVisits().size(), out);
+      std::fwrite(heightmap.visitLog().data(), sizeof(uint32_t), heightmap.visitLog().size(), out);
       std::fclose(out);
       return 0;
     }
