@@ -1,6 +1,6 @@
 // clearance_impl.h -- host side of the clearance queries (clearance_kernels.h): argument checks and search parameters
 // (clearanceSetup), the per-region search on the map's stream (clearanceRegionsDevice) and the three entry points.
-// Included at the end of ohmhip_map.hip's translation unit, after query_impl.h (it needs mapReadView).
+// Included at the end of ohmhip_map.hip's translation unit, after read_side.h (mapReadView, the refusal).
 #ifndef OHMHIP_CLEARANCE_IMPL_H
 #define OHMHIP_CLEARANCE_IMPL_H
 
@@ -26,14 +26,7 @@ int clearanceSetup(ohmhip_map_t m, const void *keys, size_t count, const ohmhip_
       return OHMHIP_ERR_INVALID_ARG;
     }
   }
-  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
-  {
-    return OHMHIP_ERR_UNSUPPORTED;
-  }
-  if (m->mc.owner_world > 1u || m->mc.owner_table)
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
-  }
+  OHMHIP_CHECK(readSideRefusal(m, OHMHIP_LID_OCCUPANCY));
   // calculateVoxelSearchHalfExtents (ohm/private/VoxelAlgorithms.cpp:16): float radius / double resolution
   const double h = std::ceil(double(p->search_radius) / m->mc.resolution);
   if (!(h <= double(kClearanceMaxH)))

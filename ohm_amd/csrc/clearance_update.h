@@ -12,7 +12,8 @@
 //     parameters.  Lanes are in ascending (z, y, x) key order, the reference's cursor order, so the flags are the list.
 //  3. compute: k_clearance_regions_lds / _global into staging, for the first `max_regions` stale regions.
 //  4. scatter (k_copy_jobs): each present tile's part of a region's result into its layer block -- the pool slot, or the
-//     pinned host-store record of a spilled tile (device visible: nothing is re-admitted) -- then the sync mark.
+//     pinned host-store record of a spilled tile (device visible: nothing is re-admitted; read_side.h: tileHome) --
+//     then the sync mark.
 // Tiles of a tiled region that hold no data yet are not created: they read -1 like any cleared block.
 #ifndef OHMHIP_CLEARANCE_UPDATE_H
 #define OHMHIP_CLEARANCE_UPDATE_H
@@ -136,24 +137,13 @@ int clearanceSelect(ohmhip_map_t m, uint32_t params, int h, std::vector<uint64_t
   OHMHIP_CHECK(clearanceFold(m));
   auto &cl = m->clearance_layer;
   hipStream_t s = m->stream;
-  present.clear();
-  present.reserve(m->region_slots.size() + m->spilled.size());
-  for (const auto &entry : m->region_slots)
+  presentRegionOrders(m, present);  // (clearanceFold refreshed the host mirror of the region table)
+  for (uint64_t &key : present)
   {
-    present.push_back(callerRegionKey(m, entry.first));
-  }
-  for (const auto &entry : m->spilled)
-  {
-    present.push_back(callerRegionKey(m, entry.first));
-  }
-  auto order = [](uint64_t k) {
     int16_t r[3];
-    unpackRegionKey(k, r);
-    return (uint64_t(uint16_t(r[2]) ^ 0x8000u) << 32) | (uint64_t(uint16_t(r[1]) ^ 0x8000u) << 16) |
-           uint64_t(uint16_t(r[0]) ^ 0x8000u);
-  };
-  std::sort(present.begin(), present.end(), [&](uint64_t x, uint64_t y) { return order(x) < order(y); });
-  present.erase(std::unique(present.begin(), present.end()), present.end());
+    regionOfOrder(key, r);
+    key = packRegionKey(r[0], r[1], r[2]);
+  }
   const uint32_t n = uint32_t(present.size());
   stale.assign(n, 0);
   if (n == 0)
@@ -234,7 +224,6 @@ int clearanceProcess(ohmhip_map_t m, ClearanceArgs &a, const std::vector<uint64_
   const uint32_t batch = uint32_t(std::max<size_t>(1, std::min<size_t>(count, (size_t(256) << 20) / (sizeof(float) * kvox))));
   OHMHIP_CHECK(m->query.clear_out.ensure(sizeof(float) * kvox * batch, false, s));
   const float *d_out = static_cast<const float *>(m->query.clear_out.ptr);
-  char *layer = static_cast<char *>(m->pool.layers[OHMHIP_LID_CLEARANCE].get());
   std::vector<int16_t> keys_xyz(3 * size_t(count));
   for (uint32_t i = 0; i < count; ++i)
   {
@@ -255,23 +244,23 @@ int clearanceProcess(ohmhip_map_t m, ClearanceArgs &a, const std::vector<uint64_
       {
         const uint64_t tile_key = packRegionKey(t.key[0], t.key[1], t.key[2]);
         const char *src = reinterpret_cast<const char *>(d_out + size_t(i) * kvox + t.voxel_offset);
-        const auto slot = m->region_slots.find(tile_key);
-        if (slot != m->region_slots.end())
+        const TileHome home = tileHome(m, tile_key);
+        char *dst = tileLayerBlock(m, home, OHMHIP_LID_CLEARANCE);
+        if (!dst)
         {
-          if (!m->precleaned.empty())
-          {
-            dropPrecleanedKey(m, tile_key);  // (the write-back's copy of the region is void)
-          }
-          jobs.push_back(CopyJob{ src, layer + size_t(slot->second) * tile_bytes, tile_bytes });
-          slots.push_back(slot->second);
           continue;
         }
-        const auto spilled = m->spilled.find(tile_key);
-        if (spilled != m->spilled.end())
+        jobs.push_back(CopyJob{ src, dst, tile_bytes });
+        if (home.stored)
         {
-          jobs.push_back(CopyJob{ src, spilled->second.record + m->store.layer_offset[OHMHIP_LID_CLEARANCE], tile_bytes });
-          spilled->second.dirty |= kDirtySync;
+          home.stored->dirty |= kDirtySync;
+          continue;
         }
+        if (!m->precleaned.empty())
+        {
+          dropPrecleanedKey(m, tile_key);  // (the write-back's copy of the region is void)
+        }
+        slots.push_back(home.slot);
       }
     }
     OHMHIP_CHECK(launchCopyJobs(m, jobs, s));

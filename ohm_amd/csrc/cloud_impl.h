@@ -1,5 +1,6 @@
 // cloud_impl.h -- host side of the point clouds (cloud_kernels.h): argument checks, the ordered work list, then count,
-// scan and emit on the map's stream.  Included at the end of ohmhip_map.hip's translation unit.
+// scan and emit on the map's stream.  Where tiles live, the region order, the chunks of a tile and the count-and-scan
+// are read_side.h's.  Included at the end of ohmhip_map.hip's translation unit.
 #ifndef OHMHIP_CLOUD_IMPL_H
 #define OHMHIP_CLOUD_IMPL_H
 
@@ -36,20 +37,15 @@ int cloudRefusal(ohmhip_map_t m, const ohmhip_cloud_params *p, const uint64_t *c
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (m->mc.owner_world > 1u || m->mc.owner_table)
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
-  }
-  return OHMHIP_OK;
+  return readSideRefusal(m, -1);  // (a missing layer is an empty cloud: cloudWorkList)
 }
 
-/// Where a tile's record lives: a pool slot, or (slot == kSlotUnassigned) a record of the host store, or neither.
+/// A tile of the map as the cloud's order sees it.
 struct CloudTileSource
 {
-  uint64_t order;   ///< (rz, ry, rx) of the caller's region, biased: ascending == the cloud's region order
-  uint32_t tile;    ///< index of the tile in its region, in block order (tilesOfRegion)
-  uint32_t slot;
-  const char *record;
+  uint64_t order;  ///< regionOrder of the caller's region
+  uint32_t tile;   ///< index of the tile in its region, in block order (tilesOfRegion)
+  uint64_t key;    ///< the tile's packed key
 };
 
 /// The work list of a call, in the cloud's order, and the kernel arguments that do not depend on the result arrays.
@@ -97,11 +93,7 @@ int cloudWorkList(ohmhip_map_t m, const ohmhip_cloud_params *p, CloudArgs &a, st
     a.mc.origin[0] = a.mc.origin[1] = a.mc.origin[2] = 0.0;  // voxelCentreLocal
   }
 
-  OHMHIP_CHECK(refreshHostRegionTable(m));
-  if (!m->spilled.empty())
-  {
-    OHMHIP_CHECK(hipStreamSynchronize(m->copy_stream));  // (evictions fill the store's records on the copy stream)
-  }
+  OHMHIP_CHECK(readTilesBegin(m));
   // OccupancyMap::regionKey of the extents (the region coordinate is stored in an int16)
   int16_t rmin[3] = { -32768, -32768, -32768 }, rmax[3] = { 32767, 32767, 32767 };
   if (p->flags & OHMHIP_CLOUD_USE_EXTENTS)
@@ -114,72 +106,54 @@ int cloudWorkList(ohmhip_map_t m, const ohmhip_cloud_params *p, CloudArgs &a, st
   }
   const int split_y = mc.tile_split[1], split_z = mc.tile_split[2];
   std::vector<CloudTileSource> tiles;
-  tiles.reserve(m->slot_keys_host.size() + m->spilled.size());
-  auto add = [&](uint64_t key, uint32_t slot, const char *record) {
-    int16_t t[3];
+  for (const uint64_t key : tileKeys(m))
+  {
+    int16_t t[3], r[3];
     unpackRegionKey(key, t);
-    const int r[3] = { int(t[0]), floorDiv(t[1], split_y), floorDiv(t[2], split_z) };
+    regionOfTile(mc, t, r);
+    bool inside = true;
     for (int c = 0; c < 3; ++c)
     {
-      if (r[c] < rmin[c] || r[c] > rmax[c])
-      {
-        return;
-      }
+      inside = inside && r[c] >= rmin[c] && r[c] <= rmax[c];
     }
-    CloudTileSource s;
-    s.order = (uint64_t(r[2] + 32768) << 32) | (uint64_t(r[1] + 32768) << 16) | uint64_t(r[0] + 32768);
-    s.tile = uint32_t((int(t[2]) - r[2] * split_z) * split_y + (int(t[1]) - r[1] * split_y));
-    s.slot = slot;
-    s.record = record;
-    tiles.push_back(s);
-  };
-  for (size_t i = 0; i < m->slot_keys_host.size(); ++i)
-  {
-    add(m->slot_keys_host[i], uint32_t(i), nullptr);
-  }
-  for (const auto &entry : m->spilled)
-  {
-    add(entry.first, kSlotUnassigned, entry.second.record);
+    if (inside)
+    {
+      const uint32_t tile = uint32_t((int(t[2]) - int(r[2]) * split_z) * split_y + (int(t[1]) - int(r[1]) * split_y));
+      tiles.push_back(CloudTileSource{ regionOrder(r[0], r[1], r[2]), tile, key });
+    }
   }
   std::sort(tiles.begin(), tiles.end(), [](const CloudTileSource &l, const CloudTileSource &r) {
     return l.order < r.order || (l.order == r.order && l.tile < r.tile);
   });
 
-  const size_t tile_voxels = size_t(mc.region_voxels);
   const size_t sel_bytes = kLayerBytes[sel_layer];
   const size_t aux_bytes = (aux_layer >= 0) ? kLayerBytes[aux_layer] : 0;
-  auto block = [&](const CloudTileSource &s, int layer) -> const char * {
-    return (s.slot != kSlotUnassigned) ?
-             static_cast<const char *>(m->pool.layers[layer].get()) + size_t(s.slot) * tile_voxels * kLayerBytes[layer] :
-             s.record + m->store.layer_offset[layer];
-  };
   const uint32_t tiles_per_region = uint32_t(split_y * split_z);
   for (size_t at = 0; at < tiles.size();)
   {
     // one region: its tiles in block order; a tile without data reads as a cleared chunk does
     size_t next = at;
+    int16_t region[3];
+    regionOfOrder(tiles[at].order, region);
     for (uint32_t j = 0; j < tiles_per_region; ++j)
     {
       const bool present = next < tiles.size() && tiles[next].order == tiles[at].order && tiles[next].tile == j;
-      const char *sel = present ? block(tiles[next], sel_layer) : nullptr;
-      const char *aux = (present && aux_layer >= 0) ? block(tiles[next], aux_layer) : nullptr;
-      const uint32_t jy = j % uint32_t(split_y), jz = j / uint32_t(split_y);
-      // (tilesOfRegion's voxel_offset)
-      const size_t tile_first =
-        (size_t(jz) * size_t(mc.dim[2]) * size_t(mc.kdim[1]) + size_t(jy) * size_t(mc.dim[1])) * size_t(mc.kdim[0]);
-      for (size_t off = 0; off < tile_voxels; off += kCloudChunkVoxels)
-      {
+      const TileHome home = present ? tileHome(m, tiles[next].key) : TileHome{};
+      const char *sel = tileLayerBlock(m, home, sel_layer);
+      const char *aux = (aux_layer >= 0) ? tileLayerBlock(m, home, aux_layer) : nullptr;
+      forEachTileChunk(mc, j, [&](uint32_t first, uint32_t count, size_t off) {
         CloudChunk c;
         c.sel = sel ? sel + off * sel_bytes : nullptr;
         c.aux = aux ? aux + off * aux_bytes : nullptr;
-        c.first = uint32_t(tile_first + off);
-        c.count = uint32_t(std::min<size_t>(kCloudChunkVoxels, tile_voxels - off));
-        c.region[0] = int16_t(int(tiles[at].order & 0xffffu) - 32768);
-        c.region[1] = int16_t(int((tiles[at].order >> 16) & 0xffffu) - 32768);
-        c.region[2] = int16_t(int((tiles[at].order >> 32) & 0xffffu) - 32768);
+        c.first = first;
+        c.count = count;
+        c.region[0] = region[0];
+        c.region[1] = region[1];
+        c.region[2] = region[2];
         c.wide = (a.mode != OHMHIP_CLOUD_TSDF && (reinterpret_cast<uintptr_t>(c.sel) & 15u) == 0u) ? 1 : 0;
         chunks.push_back(c);
-      }
+        return OHMHIP_OK;
+      });
       next += present ? 1 : 0;
     }
     at = std::max(next, at + 1);
@@ -197,26 +171,16 @@ int cloudCount(ohmhip_map_t m, CloudArgs &a, const std::vector<CloudChunk> &chun
 {
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
-  const size_t parts = chunks.size() * kCloudWaves;
   OHMHIP_CHECK(qs.cloud_chunks.ensure(sizeof(CloudChunk) * chunks.size(), false, s));
-  OHMHIP_CHECK(qs.cloud_partials.ensure(sizeof(uint32_t) * (parts + 1), false, s));
-  OHMHIP_CHECK(qs.cloud_offsets.ensure(sizeof(unsigned long long) * (parts + 1), false, s));
-  uint32_t *counts = static_cast<uint32_t *>(qs.cloud_partials.ptr);
-  unsigned long long *offsets = static_cast<unsigned long long *>(qs.cloud_offsets.ptr);
-  size_t scan_bytes = 0;
-  OHMHIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, counts, offsets, 0ull, parts + 1,
-                                       rocprim::plus<unsigned long long>(), s));
-  OHMHIP_CHECK(qs.cloud_scan_temp.ensure(scan_bytes, false, s));
   // (the stream is idle -- cloudWorkList's caller waited for it -- so no earlier call still reads the list)
   OHMHIP_CHECK(hipMemcpy(qs.cloud_chunks.ptr, chunks.data(), sizeof(CloudChunk) * chunks.size(), hipMemcpyHostToDevice));
   a.chunks = static_cast<const CloudChunk *>(qs.cloud_chunks.ptr);
-  a.counts = counts;
-  a.offsets = offsets;
-  OHMHIP_CHECK(hipMemsetAsync(counts + parts, 0, sizeof(uint32_t), s));
-  hipLaunchKernelGGL(k_cloud_count, dim3(uint32_t(chunks.size())), dim3(64 * kCloudWaves), 0, s, a);
-  OHMHIP_CHECK(hipGetLastError());
-  return rocprim::exclusive_scan(qs.cloud_scan_temp.ptr, scan_bytes, counts, offsets, 0ull, parts + 1,
-                                 rocprim::plus<unsigned long long>(), s);
+  CountScan cs;
+  return countAndScan(qs.cloud_scan, chunks.size() * kCloudWaves, s, cs, [&] {
+    a.counts = cs.counts;
+    a.offsets = cs.offsets;
+    hipLaunchKernelGGL(k_cloud_count, dim3(uint32_t(chunks.size())), dim3(64 * kCloudWaves), 0, s, a);
+  });
 }
 
 int cloudEmit(ohmhip_map_t m, CloudArgs &a, size_t n_chunks, uint64_t capacity, double *d_pos, void *d_keys, float *d_values)
@@ -278,27 +242,16 @@ try
   }
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
-  OHMHIP_CHECK(qs.cloud_pos.ensure(sizeof(double) * 3 * n, false, s));
-  if (keys10)
-  {
-    OHMHIP_CHECK(qs.cloud_keys.ensure(sizeof(GpuKeyOut) * n, false, s));
-  }
-  if (values)
-  {
-    OHMHIP_CHECK(qs.cloud_values.ensure(sizeof(float) * n, false, s));
-  }
-  OHMHIP_CHECK(cloudEmit(m, a, chunks.size(), n, static_cast<double *>(qs.cloud_pos.ptr),
-                         keys10 ? qs.cloud_keys.ptr : nullptr,
-                         values ? static_cast<float *>(qs.cloud_values.ptr) : nullptr));
-  OHMHIP_CHECK(hipMemcpyAsync(positions_xyz, qs.cloud_pos.ptr, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
-  if (keys10)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(keys10, qs.cloud_keys.ptr, sizeof(GpuKeyOut) * n, hipMemcpyDeviceToHost, s));
-  }
-  if (values)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(values, qs.cloud_values.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, s));
-  }
+  double *d_pos;
+  GpuKeyOut *d_keys;
+  float *d_values;
+  OHMHIP_CHECK(stageOut(qs.cloud_pos, positions_xyz, 3 * n, s, d_pos));
+  OHMHIP_CHECK(stageOut(qs.cloud_keys, keys10, n, s, d_keys));
+  OHMHIP_CHECK(stageOut(qs.cloud_values, values, n, s, d_values));
+  OHMHIP_CHECK(cloudEmit(m, a, chunks.size(), n, d_pos, d_keys, d_values));
+  OHMHIP_CHECK(copyOut(positions_xyz, d_pos, 3 * n, s));
+  OHMHIP_CHECK(copyOut(keys10, d_keys, n, s));
+  OHMHIP_CHECK(copyOut(values, d_values, n, s));
   return hipStreamSynchronize(s);
 }
 OHMHIP_ABI_CATCH

@@ -1,7 +1,7 @@
 // heightmap_fill_impl.h -- host side of the flood-fill heightmap (heightmap_fill_kernels.h): the planar call's checks
 // and geometry (heightmap_impl.h), the seed, then one round of kernels per generation of the reference's queue with the
-// next generation's size read back through a pinned word.  Included after heightmap_impl.h in ohmhip_map.hip's
-// translation unit.
+// next generation's size read back through a pinned word (its scan is 32 bit: not read_side.h's countAndScan).
+// Included after heightmap_impl.h in ohmhip_map.hip's translation unit.
 #ifndef OHMHIP_HEIGHTMAP_FILL_IMPL_H
 #define OHMHIP_HEIGHTMAP_FILL_IMPL_H
 
@@ -233,35 +233,24 @@ try
   {
     visit_log_capacity = 0;
   }
-  OHMHIP_CHECK(qs.hm_out_occ.ensure(sizeof(float) * n, false, s));
-  OHMHIP_CHECK(qs.hm_out_vox.ensure(24 * n, false, s));
-  if (mean8)
-  {
-    OHMHIP_CHECK(qs.hm_out_mean.ensure(8 * n, false, s));
-  }
-  if (source_visit)
-  {
-    OHMHIP_CHECK(qs.hm_out_col.ensure(sizeof(uint32_t) * n, false, s));
-  }
-  OHMHIP_CHECK(heightmapFillDevice(m, params, a, static_cast<float *>(qs.hm_out_occ.ptr), qs.hm_out_vox.ptr,
-                                   mean8 ? qs.hm_out_mean.ptr : nullptr,
-                                   source_visit ? static_cast<uint32_t *>(qs.hm_out_col.ptr) : nullptr, nullptr,
-                                   &qs.hmf_log, visit_log_capacity, *stats));
+  float *d_occ;
+  char *d_vox, *d_mean;
+  uint32_t *d_visit;
+  OHMHIP_CHECK(stageOut(qs.hm_out_occ, occupancy, n, s, d_occ));
+  OHMHIP_CHECK(stageOut(qs.hm_out_vox, voxels24, 24 * n, s, d_vox));
+  OHMHIP_CHECK(stageOut(qs.hm_out_mean, mean8, 8 * n, s, d_mean));
+  OHMHIP_CHECK(stageOut(qs.hm_out_col, source_visit, n, s, d_visit));
+  OHMHIP_CHECK(heightmapFillDevice(m, params, a, d_occ, d_vox, d_mean, d_visit, nullptr, &qs.hmf_log,
+                                   visit_log_capacity, *stats));
   const uint64_t logged = std::min<uint64_t>(visit_log_capacity, stats->visits);
   if (logged)
   {
     OHMHIP_CHECK(hipMemcpyAsync(visit_log, qs.hmf_log.ptr, sizeof(uint32_t) * 3 * logged, hipMemcpyDeviceToHost, s));
   }
-  OHMHIP_CHECK(hipMemcpyAsync(occupancy, qs.hm_out_occ.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, s));
-  OHMHIP_CHECK(hipMemcpyAsync(voxels24, qs.hm_out_vox.ptr, 24 * n, hipMemcpyDeviceToHost, s));
-  if (mean8)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(mean8, qs.hm_out_mean.ptr, 8 * n, hipMemcpyDeviceToHost, s));
-  }
-  if (source_visit)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(source_visit, qs.hm_out_col.ptr, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-  }
+  OHMHIP_CHECK(copyOut(occupancy, d_occ, n, s));
+  OHMHIP_CHECK(copyOut(voxels24, d_vox, 24 * n, s));
+  OHMHIP_CHECK(copyOut(mean8, d_mean, 8 * n, s));
+  OHMHIP_CHECK(copyOut(source_visit, d_visit, n, s));
   return hipStreamSynchronize(s);
 }
 OHMHIP_ABI_CATCH

@@ -1,6 +1,6 @@
 // heightmap_impl.h -- host side of the planar heightmap (heightmap_kernels.h): argument checks, rule 1 (extents) and
 // the dense result grid in fp64 on the host, then the two kernels on the map's stream.  Included at the end of
-// ohmhip_map.hip's translation unit.
+// ohmhip_map.hip's translation unit, after read_side.h (mapReadView, the refusal, the optional outputs).
 #ifndef OHMHIP_HEIGHTMAP_IMPL_H
 #define OHMHIP_HEIGHTMAP_IMPL_H
 
@@ -37,15 +37,7 @@ int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p, bool fill
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
-  {
-    return OHMHIP_ERR_UNSUPPORTED;
-  }
-  if (m->mc.owner_world > 1u || m->mc.owner_table)
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
-  }
-  return OHMHIP_OK;
+  return readSideRefusal(m, OHMHIP_LID_OCCUPANCY);
 }
 
 /// Rules 1 and 2 and the dense grid, on the host in fp64: fills the geometry fields of `a` and `e`.  The map is settled
@@ -258,29 +250,18 @@ try
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
   const size_t n = size_t(a.ma) * size_t(a.mb);
-  OHMHIP_CHECK(qs.hm_out_occ.ensure(sizeof(float) * n, false, s));
-  OHMHIP_CHECK(qs.hm_out_vox.ensure(24 * n, false, s));
-  if (mean8)
-  {
-    OHMHIP_CHECK(qs.hm_out_mean.ensure(8 * n, false, s));
-  }
-  if (source_column)
-  {
-    OHMHIP_CHECK(qs.hm_out_col.ensure(sizeof(uint32_t) * n, false, s));
-  }
-  OHMHIP_CHECK(heightmapDevice(m, a, static_cast<float *>(qs.hm_out_occ.ptr), qs.hm_out_vox.ptr,
-                               mean8 ? qs.hm_out_mean.ptr : nullptr,
-                               source_column ? static_cast<uint32_t *>(qs.hm_out_col.ptr) : nullptr));
-  OHMHIP_CHECK(hipMemcpyAsync(occupancy, qs.hm_out_occ.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, s));
-  OHMHIP_CHECK(hipMemcpyAsync(voxels24, qs.hm_out_vox.ptr, 24 * n, hipMemcpyDeviceToHost, s));
-  if (mean8)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(mean8, qs.hm_out_mean.ptr, 8 * n, hipMemcpyDeviceToHost, s));
-  }
-  if (source_column)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(source_column, qs.hm_out_col.ptr, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-  }
+  float *d_occ;
+  char *d_vox, *d_mean;
+  uint32_t *d_col;
+  OHMHIP_CHECK(stageOut(qs.hm_out_occ, occupancy, n, s, d_occ));
+  OHMHIP_CHECK(stageOut(qs.hm_out_vox, voxels24, 24 * n, s, d_vox));
+  OHMHIP_CHECK(stageOut(qs.hm_out_mean, mean8, 8 * n, s, d_mean));
+  OHMHIP_CHECK(stageOut(qs.hm_out_col, source_column, n, s, d_col));
+  OHMHIP_CHECK(heightmapDevice(m, a, d_occ, d_vox, d_mean, d_col));
+  OHMHIP_CHECK(copyOut(occupancy, d_occ, n, s));
+  OHMHIP_CHECK(copyOut(voxels24, d_vox, 24 * n, s));
+  OHMHIP_CHECK(copyOut(mean8, d_mean, 8 * n, s));
+  OHMHIP_CHECK(copyOut(source_column, d_col, n, s));
   unsigned long long counts[4] = { 0, 0, 0, 0 };
   OHMHIP_CHECK(hipMemcpyAsync(counts, a.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
   OHMHIP_CHECK(hipStreamSynchronize(s));

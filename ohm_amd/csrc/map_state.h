@@ -187,6 +187,13 @@ struct PinnedBuf
 template <typename T>
 constexpr bool kMoveOnly = std::is_nothrow_move_constructible<T>::value && std::is_nothrow_move_assignable<T>::value &&
                            !std::is_copy_constructible<T>::value && !std::is_copy_assignable<T>::value;
+/// The buffers of one count-and-scan (read_side.h: countAndScan): a count per part and a zero behind them, their
+/// exclusive scan in 64 bit, rocPRIM's scratch.
+struct ScanScratch
+{
+  DevBuf counts, offsets, temp;
+};
+
 static_assert(kMoveOnly<DevBuf> && kMoveOnly<DevArray<uint32_t>> && kMoveOnly<PinnedBuf<uint32_t>> && kMoveOnly<Stream> &&
                 kMoveOnly<Event>,
               "the owning types move and do not copy");
@@ -391,15 +398,18 @@ struct ohmhip_map_s
     DevBuf hmf_grid, hmf_queue, hmf_ground, hmf_rec_cell, hmf_keys_a, hmf_keys_b, hmf_accept, hmf_accept_at, hmf_temp, hmf_log;
     PinnedBuf<uint32_t> hmf_next;
     /// point clouds (cloud_kernels.h): the work list, per-wave counts and their scan; device copies of the host arrays
-    DevBuf cloud_chunks, cloud_partials, cloud_offsets, cloud_scan_temp, cloud_pos, cloud_keys, cloud_values;
+    DevBuf cloud_chunks, cloud_pos, cloud_keys, cloud_values;
+    ScanScratch cloud_scan;
     /// NearestNeighbours (neighbours_kernels.h): the work list, the near points, per-wave counts / closest voxels and
-    /// their scan, per-query counts / closest voxels and their scan; device copies of the host arrays
-    DevBuf nn_chunks, nn_chunk_begin, nn_near, nn_partials, nn_offsets, nn_best, nn_scan_temp;
-    DevBuf nn_query_counts, nn_query_offsets, nn_query_found, nn_query_best, nn_keys, nn_ranges;
+    /// their scan, per-query counts / closest voxels and the scan of the queries that found one (both scans' results
+    /// are read by the emit pass, so each has its buffers); device copies of the host arrays
+    DevBuf nn_chunks, nn_chunk_begin, nn_near, nn_best, nn_query_counts, nn_query_best, nn_keys, nn_ranges;
+    ScanScratch nn_scan, nn_query_scan;
     DevBuf rv_keys, rv_values, rv_present;  ///< voxels read by key: device copies of the host arrays
     /// point filter (point_filter_kernels.h): per-wave kept counts and their scan; one piece of the host variant's
     /// arrays on the device, and the pinned block its points are staged through (two pieces + the piece's kept count)
-    DevBuf pf_counts, pf_offsets, pf_scan_temp, pf_points, pf_status, pf_values, pf_keys, pf_kept;
+    DevBuf pf_points, pf_status, pf_values, pf_keys, pf_kept;
+    ScanScratch pf_scan;
     PinnedBuf<char> pf_staging;
   } query;
   /// The clearance layer's bookkeeping (clearance_update.h), by the caller's region key -- so it needs no care when a

@@ -1,6 +1,7 @@
 // neighbours_impl.h -- host side of the point queries (neighbours_kernels.h): argument checks, the ordered and pruned
 // work list of a NearestNeighbours call, count, scan and emit on the map's stream; voxel keys of points; voxels read by
-// key.  Included at the end of ohmhip_map.hip's translation unit, after cloud_impl.h.
+// key.  Where tiles live, the region order, the chunks of a tile and the count-and-scan are read_side.h's.  Included at
+// the end of ohmhip_map.hip's translation unit, after cloud_impl.h.
 #ifndef OHMHIP_NEIGHBOURS_IMPL_H
 #define OHMHIP_NEIGHBOURS_IMPL_H
 
@@ -35,29 +36,7 @@ int nnRefusal(ohmhip_map_t m, const double *points, size_t query_count, const oh
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
-  {
-    return OHMHIP_ERR_UNSUPPORTED;
-  }
-  if (m->mc.owner_world > 1u || m->mc.owner_table)
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
-  }
-  return OHMHIP_OK;
-}
-
-/// Where the layer block of a tile lives (pool slot or pinned store record); null: the map has no such tile.
-const char *tileLayerBlock(ohmhip_map_t m, uint64_t tile_key, int layer)
-{
-  const auto slot = m->region_slots.find(tile_key);
-  if (slot != m->region_slots.end() && slot->second < m->slot_keys_host.size() &&
-      m->slot_keys_host[slot->second] == tile_key)
-  {
-    return static_cast<const char *>(m->pool.layers[layer].get()) +
-           size_t(slot->second) * size_t(m->mc.region_voxels) * kLayerBytes[layer];
-  }
-  const auto stored = m->spilled.find(tile_key);
-  return (stored != m->spilled.end()) ? stored->second.record + m->store.layer_offset[layer] : nullptr;
+  return readSideRefusal(m, OHMHIP_LID_OCCUPANCY);
 }
 
 /// Smallest distance between p and the box [lo, hi], squared.
@@ -97,38 +76,18 @@ int nnWorkList(ohmhip_map_t m, const double *points, size_t query_count, const o
   a.n_queries = uint32_t(query_count);
   const MapConst &mc = m->mc;
 
-  OHMHIP_CHECK(refreshHostRegionTable(m));
-  if (!m->spilled.empty())
-  {
-    OHMHIP_CHECK(hipStreamSynchronize(m->copy_stream));  // (evictions fill the store's records on the copy stream)
-  }
+  OHMHIP_CHECK(readTilesBegin(m));
   const char *prune_env = std::getenv("OHMHIP_NN_PRUNE");
   const bool prune = !(prune_env && std::atoi(prune_env) == 0) && std::isfinite(a.radius2);
   const double radius = double(p->search_radius);
   const int split_y = mc.tile_split[1], split_z = mc.tile_split[2];
   const uint32_t dx = uint32_t(mc.kdim[0]), dy = uint32_t(mc.kdim[1]);
-  const size_t tile_voxels = size_t(mc.region_voxels);
 
   // the map's regions in the caller's coordinates, in visiting order: what a query without kQfUnknownAsOccupied can see
-  std::vector<uint64_t> present;  // (rz, ry, rx) biased
+  std::vector<uint64_t> present;  // (regionOrder)
   if (!a.unknown_as_occupied)
   {
-    auto add = [&](uint64_t key) {
-      int16_t t[3];
-      unpackRegionKey(key, t);
-      const int r[3] = { int(t[0]), floorDiv(t[1], split_y), floorDiv(t[2], split_z) };
-      present.push_back((uint64_t(r[2] + 32768) << 32) | (uint64_t(r[1] + 32768) << 16) | uint64_t(r[0] + 32768));
-    };
-    for (const uint64_t key : m->slot_keys_host)
-    {
-      add(key);
-    }
-    for (const auto &entry : m->spilled)
-    {
-      add(entry.first);
-    }
-    std::sort(present.begin(), present.end());
-    present.erase(std::unique(present.begin(), present.end()), present.end());
+    presentRegionOrders(m, present);
   }
 
   std::vector<const char *> tile_blocks(size_t(split_y) * size_t(split_z));
@@ -171,8 +130,8 @@ int nnWorkList(ohmhip_map_t m, const double *points, size_t query_count, const o
       {
         for (int jy = 0; jy < split_y; ++jy)
         {
-          const char *block =
-            fits ? tileLayerBlock(m, packRegionKey(rx, ry * split_y + jy, rz * split_z + jz), OHMHIP_LID_OCCUPANCY) : nullptr;
+          const TileHome home = fits ? tileHome(m, packRegionKey(rx, ry * split_y + jy, rz * split_z + jz)) : TileHome{};
+          const char *block = tileLayerBlock(m, home, OHMHIP_LID_OCCUPANCY);
           tile_blocks[size_t(jz) * split_y + jy] = block;
           any = any || block != nullptr;
         }
@@ -183,15 +142,10 @@ int nnWorkList(ohmhip_map_t m, const double *points, size_t query_count, const o
       }
       for (size_t j = 0; j < tile_blocks.size(); ++j)
       {
-        const uint32_t jy = uint32_t(j % size_t(split_y)), jz = uint32_t(j / size_t(split_y));
-        // (tilesOfRegion's voxel_offset)
-        const size_t tile_first =
-          (size_t(jz) * size_t(mc.dim[2]) * size_t(mc.kdim[1]) + size_t(jy) * size_t(mc.dim[1])) * size_t(mc.kdim[0]);
-        for (size_t off = 0; off < tile_voxels; off += kCloudChunkVoxels)
-        {
+        OHMHIP_CHECK(forEachTileChunk(mc, uint32_t(j), [&](uint32_t first, uint32_t count, size_t off) -> int {
           NnChunk c{};
-          c.first = uint32_t(tile_first + off);
-          c.count = uint32_t(std::min<size_t>(kCloudChunkVoxels, tile_voxels - off));
+          c.first = first;
+          c.count = count;
           if (prune)
           {
             // the box of the chunk's voxels: whole layers, else whole rows of one layer, else a piece of one row
@@ -215,7 +169,7 @@ int nnWorkList(ohmhip_map_t m, const double *points, size_t query_count, const o
             }
             if (boxDistance2(near_d, clo, chi) > reach2)
             {
-              continue;
+              return OHMHIP_OK;
             }
           }
           const char *block = tile_blocks[j];
@@ -229,7 +183,8 @@ int nnWorkList(ohmhip_map_t m, const double *points, size_t query_count, const o
             return OHMHIP_ERR_CAPACITY;
           }
           chunks.push_back(c);
-        }
+          return OHMHIP_OK;
+        }));
       }
       return OHMHIP_OK;
     };
@@ -264,13 +219,13 @@ int nnWorkList(ohmhip_map_t m, const double *points, size_t query_count, const o
     {
       for (const uint64_t order : present)
       {
-        const int rx = int(order & 0xffffu) - 32768, ry = int((order >> 16) & 0xffffu) - 32768,
-                  rz = int((order >> 32) & 0xffffu) - 32768;
-        if (rx < rmin[0] || rx > rmax[0] || ry < rmin[1] || ry > rmax[1] || rz < rmin[2] || rz > rmax[2])
+        int16_t r[3];
+        regionOfOrder(order, r);
+        if (r[0] < rmin[0] || r[0] > rmax[0] || r[1] < rmin[1] || r[1] > rmax[1] || r[2] < rmin[2] || r[2] > rmax[2])
         {
           continue;
         }
-        const int err = visit(rx, ry, rz);
+        const int err = visit(r[0], r[1], r[2]);
         if (err != OHMHIP_OK)
         {
           chunks.clear();
@@ -293,13 +248,8 @@ int nnCount(ohmhip_map_t m, NnArgs &a, const std::vector<NnChunk> &chunks, const
   const size_t nq = a.n_queries;
   const size_t parts = chunks.size() * kCloudWaves;
   OHMHIP_CHECK(qs.nn_query_counts.ensure(sizeof(unsigned long long) * (nq + 1), false, s));
-  OHMHIP_CHECK(qs.nn_query_offsets.ensure(sizeof(unsigned long long) * (nq + 1), false, s));
-  OHMHIP_CHECK(qs.nn_query_found.ensure(sizeof(uint32_t) * (nq + 1), false, s));
   unsigned long long *query_counts = static_cast<unsigned long long *>(qs.nn_query_counts.ptr);
-  unsigned long long *query_offsets = static_cast<unsigned long long *>(qs.nn_query_offsets.ptr);
   a.query_counts = query_counts;
-  a.query_offsets = query_offsets;
-  a.query_found = static_cast<uint32_t *>(qs.nn_query_found.ptr);
   if (chunks.empty())
   {
     *d_total = query_counts + nq;
@@ -308,22 +258,11 @@ int nnCount(ohmhip_map_t m, NnArgs &a, const std::vector<NnChunk> &chunks, const
   OHMHIP_CHECK(qs.nn_chunks.ensure(sizeof(NnChunk) * chunks.size(), false, s));
   OHMHIP_CHECK(qs.nn_chunk_begin.ensure(sizeof(uint32_t) * (nq + 1), false, s));
   OHMHIP_CHECK(qs.nn_near.ensure(sizeof(float) * 3 * nq, false, s));
-  OHMHIP_CHECK(qs.nn_partials.ensure(sizeof(uint32_t) * (parts + 1), false, s));
-  OHMHIP_CHECK(qs.nn_offsets.ensure(sizeof(unsigned long long) * (parts + 1), false, s));
-  uint32_t *counts = static_cast<uint32_t *>(qs.nn_partials.ptr);
-  unsigned long long *offsets = static_cast<unsigned long long *>(qs.nn_offsets.ptr);
-  size_t scan_bytes = 0, query_scan_bytes = 0;
-  OHMHIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, counts, offsets, 0ull, parts + 1,
-                                       rocprim::plus<unsigned long long>(), s));
   if (a.nearest)
   {
     OHMHIP_CHECK(qs.nn_best.ensure(sizeof(unsigned long long) * parts, false, s));
     OHMHIP_CHECK(qs.nn_query_best.ensure(sizeof(NnBest) * nq, false, s));
-    OHMHIP_CHECK(rocprim::exclusive_scan(nullptr, query_scan_bytes, a.query_found, query_offsets, 0ull, nq + 1,
-                                         rocprim::plus<unsigned long long>(), s));
   }
-  // (never a null pointer: that would ask rocPRIM for the size again)
-  OHMHIP_CHECK(qs.nn_scan_temp.ensure(std::max<size_t>(std::max(scan_bytes, query_scan_bytes), 16), false, s));
   // (the stream is idle -- the caller waited for it -- so no earlier call still reads the lists)
   OHMHIP_CHECK(hipMemcpy(qs.nn_chunks.ptr, chunks.data(), sizeof(NnChunk) * chunks.size(), hipMemcpyHostToDevice));
   OHMHIP_CHECK(hipMemcpy(qs.nn_chunk_begin.ptr, chunk_begin.data(), sizeof(uint32_t) * (nq + 1), hipMemcpyHostToDevice));
@@ -331,28 +270,31 @@ int nnCount(ohmhip_map_t m, NnArgs &a, const std::vector<NnChunk> &chunks, const
   a.chunks = static_cast<const NnChunk *>(qs.nn_chunks.ptr);
   a.chunk_begin = static_cast<const uint32_t *>(qs.nn_chunk_begin.ptr);
   a.near_local = static_cast<const float *>(qs.nn_near.ptr);
-  a.counts = counts;
-  a.offsets = offsets;
   a.best = static_cast<unsigned long long *>(qs.nn_best.ptr);
   a.query_best = static_cast<NnBest *>(qs.nn_query_best.ptr);
-  OHMHIP_CHECK(hipMemsetAsync(counts + parts, 0, sizeof(uint32_t), s));
-  hipLaunchKernelGGL(k_nn_count, dim3(uint32_t(chunks.size())), dim3(64 * kCloudWaves), 0, s, a);
-  OHMHIP_CHECK(hipGetLastError());
-  const uint32_t query_blocks = uint32_t((nq + 255) / 256);
+  CountScan waves, found;
+  auto count = [&] {
+    a.counts = waves.counts;
+    a.offsets = waves.offsets;
+    hipLaunchKernelGGL(k_nn_count, dim3(uint32_t(chunks.size())), dim3(64 * kCloudWaves), 0, s, a);
+  };
   if (!a.nearest)
   {
-    OHMHIP_CHECK(rocprim::exclusive_scan(qs.nn_scan_temp.ptr, scan_bytes, counts, offsets, 0ull, parts + 1,
-                                         rocprim::plus<unsigned long long>(), s));
-    hipLaunchKernelGGL(k_nn_query_counts, dim3(query_blocks), dim3(256), 0, s, a);
-    *d_total = offsets + parts;
+    OHMHIP_CHECK(countAndScan(qs.nn_scan, parts, s, waves, count));
+    hipLaunchKernelGGL(k_nn_query_counts, dim3(uint32_t((nq + 255) / 256)), dim3(256), 0, s, a);
+    *d_total = waves.total;
     return hipGetLastError();
   }
-  OHMHIP_CHECK(hipMemsetAsync(a.query_found + nq, 0, sizeof(uint32_t), s));
-  hipLaunchKernelGGL(k_nn_nearest, dim3(uint32_t(nq)), dim3(64), 0, s, a);
-  OHMHIP_CHECK(hipGetLastError());
-  *d_total = query_offsets + nq;
-  return rocprim::exclusive_scan(qs.nn_scan_temp.ptr, query_scan_bytes, a.query_found, query_offsets, 0ull, nq + 1,
-                                 rocprim::plus<unsigned long long>(), s);
+  // the closest voxel per wave, then per query; the scan is over the queries that found one
+  OHMHIP_CHECK(scanReserve(qs.nn_scan, parts, s, waves));
+  const int err = countAndScan(qs.nn_query_scan, nq, s, found, [&] {
+    count();
+    a.query_found = found.counts;
+    a.query_offsets = found.offsets;
+    hipLaunchKernelGGL(k_nn_nearest, dim3(uint32_t(nq)), dim3(64), 0, s, a);
+  });
+  *d_total = found.total;
+  return err;
 }
 
 int nnEmit(ohmhip_map_t m, NnArgs &a, size_t n_chunks, uint64_t capacity, void *d_keys, float *d_ranges)
@@ -380,15 +322,7 @@ int readVoxelsRefusal(ohmhip_map_t m, int layer_id, const void *keys, size_t cou
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->pool.layers[layer_id])
-  {
-    return OHMHIP_ERR_UNSUPPORTED;
-  }
-  if (m->mc.owner_world > 1u || m->mc.owner_table)
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
-  }
-  return OHMHIP_OK;
+  return readSideRefusal(m, layer_id);
 }
 
 /// The read on device arrays, enqueued on the map's stream; the map is settled.
@@ -446,17 +380,13 @@ try
   {
     return OHMHIP_OK;
   }
-  OHMHIP_CHECK(qs.nn_keys.ensure(sizeof(GpuKeyOut) * n, false, s));
-  if (ranges)
-  {
-    OHMHIP_CHECK(qs.nn_ranges.ensure(sizeof(float) * n, false, s));
-  }
-  OHMHIP_CHECK(nnEmit(m, a, chunks.size(), n, qs.nn_keys.ptr, ranges ? static_cast<float *>(qs.nn_ranges.ptr) : nullptr));
-  OHMHIP_CHECK(hipMemcpyAsync(keys10, qs.nn_keys.ptr, sizeof(GpuKeyOut) * n, hipMemcpyDeviceToHost, s));
-  if (ranges)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(ranges, qs.nn_ranges.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, s));
-  }
+  GpuKeyOut *d_keys;
+  float *d_ranges;
+  OHMHIP_CHECK(stageOut(qs.nn_keys, keys10, n, s, d_keys));
+  OHMHIP_CHECK(stageOut(qs.nn_ranges, ranges, n, s, d_ranges));
+  OHMHIP_CHECK(nnEmit(m, a, chunks.size(), n, d_keys, d_ranges));
+  OHMHIP_CHECK(copyOut(keys10, d_keys, n, s));
+  OHMHIP_CHECK(copyOut(ranges, d_ranges, n, s));
   return hipStreamSynchronize(s);
 }
 OHMHIP_ABI_CATCH

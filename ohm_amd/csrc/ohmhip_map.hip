@@ -925,6 +925,7 @@ OHMHIP_ABI_CATCH
 #include "merge_impl.h"
 #include "partition_impl.h"
 #include "tiling_impl.h"
+#include "read_side.h"
 #include "query_impl.h"
 #include "clearance_impl.h"
 #include "clearance_update.h"

@@ -1,6 +1,6 @@
 // point_filter_impl.h -- host side of the point filter (point_filter_kernels.h): argument checks, the map as the kernels
-// see it with its three layers, classify, scan and emit on the map's stream; the host variant's pieces.  Included at
-// the end of ohmhip_map.hip's translation unit, after neighbours_impl.h.
+// see it with its three layers, classify, scan (read_side.h: countAndScan) and emit on the map's stream; the host
+// variant's pieces.  Included at the end of ohmhip_map.hip's translation unit, after neighbours_impl.h.
 #ifndef OHMHIP_POINT_FILTER_IMPL_H
 #define OHMHIP_POINT_FILTER_IMPL_H
 
@@ -32,15 +32,7 @@ int pointFilterRefusal(ohmhip_map_t m, const double *points, uint64_t stride, ui
       }
     }
   }
-  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // ohmfilter refuses such a map too (ohmfilter.cpp:178-182)
-  }
-  if (m->mc.owner_world > 1u || m->mc.owner_table)
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
-  }
-  return OHMHIP_OK;
+  return readSideRefusal(m, OHMHIP_LID_OCCUPANCY);  // (ohmfilter refuses a map without the layer too: ohmfilter.cpp:178-182)
 }
 
 /// The kernel arguments that do not depend on the points: the read view with the mean and covariance layers beside
@@ -68,27 +60,16 @@ int pointFilterView(ohmhip_map_t m, const ohmhip_point_filter_params *p, PointFi
 int pointFilterClassify(ohmhip_map_t m, PointFilterArgs &a, uint64_t n, const unsigned long long **d_total)
 {
   hipStream_t s = m->stream;
-  ohmhip_map_s::QueryState &qs = m->query;
   const uint32_t blocks = uint32_t((n + 255u) / 256u);
-  const size_t waves = size_t(blocks) * 4;
-  OHMHIP_CHECK(qs.pf_counts.ensure(sizeof(uint32_t) * (waves + 1), false, s));
-  OHMHIP_CHECK(qs.pf_offsets.ensure(sizeof(unsigned long long) * (waves + 1), false, s));
-  uint32_t *counts = static_cast<uint32_t *>(qs.pf_counts.ptr);
-  unsigned long long *offsets = static_cast<unsigned long long *>(qs.pf_offsets.ptr);
-  size_t scan_bytes = 0;
-  OHMHIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, counts, offsets, 0ull, waves + 1,
-                                       rocprim::plus<unsigned long long>(), s));
-  // (never a null pointer: that would ask rocPRIM for the size again)
-  OHMHIP_CHECK(qs.pf_scan_temp.ensure(std::max<size_t>(scan_bytes, 16), false, s));
-  a.n = n;
-  a.counts = counts;
-  a.offsets = offsets;
-  OHMHIP_CHECK(hipMemsetAsync(counts + waves, 0, sizeof(uint32_t), s));
-  hipLaunchKernelGGL(k_pf_classify, dim3(blocks), dim3(256), 0, s, a);
-  OHMHIP_CHECK(hipGetLastError());
-  *d_total = offsets + waves;
-  return rocprim::exclusive_scan(qs.pf_scan_temp.ptr, scan_bytes, counts, offsets, 0ull, waves + 1,
-                                 rocprim::plus<unsigned long long>(), s);
+  CountScan cs;
+  const int err = countAndScan(m->query.pf_scan, size_t(blocks) * 4, s, cs, [&] {
+    a.n = n;
+    a.counts = cs.counts;
+    a.offsets = cs.offsets;
+    hipLaunchKernelGGL(k_pf_classify, dim3(blocks), dim3(256), 0, s, a);
+  });
+  *d_total = cs.total;
+  return err;
 }
 
 int pointFilterEmit(ohmhip_map_t m, const PointFilterArgs &a)
@@ -126,14 +107,8 @@ try
   }
   OHMHIP_CHECK(qs.pf_points.ensure(sizeof(double) * 3 * most, false, s));
   OHMHIP_CHECK(qs.pf_status.ensure(most, false, s));
-  if (values)
-  {
-    OHMHIP_CHECK(qs.pf_values.ensure(sizeof(double) * most, false, s));
-  }
-  if (keys10)
-  {
-    OHMHIP_CHECK(qs.pf_keys.ensure(sizeof(GpuKeyOut) * most, false, s));
-  }
+  OHMHIP_CHECK(stageOut(qs.pf_values, values, most, s, a.values));
+  OHMHIP_CHECK(stageOut(qs.pf_keys, keys10, most, s, a.keys));
   if (capacity > 0)
   {
     OHMHIP_CHECK(qs.pf_kept.ensure(sizeof(unsigned long long) * size_t(std::min<uint64_t>(capacity, most)), false, s));
@@ -143,8 +118,6 @@ try
   a.points = static_cast<const double *>(qs.pf_points.ptr);
   a.stride = 3;
   a.status = static_cast<uint8_t *>(qs.pf_status.ptr);
-  a.values = values ? static_cast<double *>(qs.pf_values.ptr) : nullptr;
-  a.keys = keys10 ? static_cast<GpuKeyOut *>(qs.pf_keys.ptr) : nullptr;
   a.capacity = capacity;
   a.kept = static_cast<unsigned long long *>(qs.pf_kept.ptr);
   OHMHIP_CHECK(hipStreamSynchronize(s));  // (an earlier call's copies out of the staging block)
@@ -177,18 +150,9 @@ try
       OHMHIP_CHECK(pointFilterEmit(m, a));
       OHMHIP_CHECK(hipMemcpyAsync(kept_indices + kept_so_far, a.kept, sizeof(uint64_t) * size_t(fetch), hipMemcpyDeviceToHost, s));
     }
-    if (status)
-    {
-      OHMHIP_CHECK(hipMemcpyAsync(status + at, a.status, n, hipMemcpyDeviceToHost, s));
-    }
-    if (values)
-    {
-      OHMHIP_CHECK(hipMemcpyAsync(values + at, a.values, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    }
-    if (keys10)
-    {
-      OHMHIP_CHECK(hipMemcpyAsync(static_cast<GpuKeyOut *>(keys10) + at, a.keys, sizeof(GpuKeyOut) * n, hipMemcpyDeviceToHost, s));
-    }
+    OHMHIP_CHECK(copyOut(status ? status + at : nullptr, a.status, n, s));
+    OHMHIP_CHECK(copyOut(values ? values + at : nullptr, a.values, n, s));
+    OHMHIP_CHECK(copyOut(keys10 ? static_cast<GpuKeyOut *>(keys10) + at : nullptr, a.keys, n, s));
     OHMHIP_CHECK(hipStreamSynchronize(s));
     kept_so_far += piece_kept;
   }

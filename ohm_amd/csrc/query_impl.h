@@ -1,6 +1,6 @@
-// query_impl.h -- host side of the read-only queries (query_kernels.h): the line-keys query, the map as the read-side
-// kernels see it (mapReadView, which the clearance, heightmap and cloud host code share) and the rays query with its
-// two entry points.  Included at the end of ohmhip_map.hip's translation unit, ahead of the other read-side parts.
+// query_impl.h -- host side of the read-only queries (query_kernels.h): the line-keys query and the rays query with its
+// two entry points.  Included at the end of ohmhip_map.hip's translation unit, after read_side.h (mapReadView, the
+// refusal, the optional outputs).
 #ifndef OHMHIP_QUERY_IMPL_H
 #define OHMHIP_QUERY_IMPL_H
 
@@ -50,51 +50,6 @@ OHMHIP_ABI_CATCH
 
 namespace
 {
-/// The map as the read-only kernels see it (MapReadView): configuration, region hash, occupancy layer and the table of
-/// the host store's regions (QuerySpillTable; empty without spill to host).  `layer`: the layer whose blocks the view
-/// addresses (the voxel reads by key look at any layer through the same view).
-int mapReadView(ohmhip_map_t m, MapReadView &view, int layer = OHMHIP_LID_OCCUPANCY)
-{
-  hipStream_t s = m->stream;
-  ohmhip_map_s::QueryState &qs = m->query;
-  view.mc = m->mc;
-  view.rt = regionTable(m);
-  view.occupancy = static_cast<const float *>(m->pool.layers[layer].get());
-  view.spill = QuerySpillTable{ nullptr, nullptr, 0 };
-  if (!m->spilled.empty())
-  {
-    // Regions in the host store answer from their pinned records (device visible), without re-admission.  The table is
-    // rebuilt per call: the store changes with every batch that evicts or re-admits.  (Evictions copy on the copy
-    // stream; the previous query may still read the table being replaced.)
-    OHMHIP_CHECK(hipStreamSynchronize(m->copy_stream));
-    OHMHIP_CHECK(hipStreamSynchronize(s));
-    uint32_t cap = 16;
-    while (cap < 2 * m->spilled.size())
-    {
-      cap <<= 1;
-    }
-    std::vector<unsigned long long> keys(cap, 0ull);
-    std::vector<const float *> blocks(cap, nullptr);
-    for (const auto &entry : m->spilled)
-    {
-      uint32_t idx = hashRegionKey(entry.first, cap - 1);
-      while (keys[idx] != 0)
-      {
-        idx = (idx + 1) & (cap - 1);
-      }
-      keys[idx] = entry.first;
-      blocks[idx] = reinterpret_cast<const float *>(entry.second.record + m->store.layer_offset[layer]);
-    }
-    OHMHIP_CHECK(qs.spill_keys.ensure(sizeof(unsigned long long) * cap, false, s));
-    OHMHIP_CHECK(qs.spill_blocks.ensure(sizeof(const float *) * cap, false, s));
-    OHMHIP_CHECK(hipMemcpy(qs.spill_keys.ptr, keys.data(), sizeof(unsigned long long) * cap, hipMemcpyHostToDevice));
-    OHMHIP_CHECK(hipMemcpy(qs.spill_blocks.ptr, blocks.data(), sizeof(const float *) * cap, hipMemcpyHostToDevice));
-    view.spill = QuerySpillTable{ static_cast<const unsigned long long *>(qs.spill_keys.ptr),
-                                  static_cast<const float *const *>(qs.spill_blocks.ptr), cap - 1 };
-  }
-  return OHMHIP_OK;
-}
-
 /// What both query entry points check before any device work (OHMHIP_ERR_INVALID_ARG / OHMHIP_ERR_UNSUPPORTED).
 int raysQueryRefusal(ohmhip_map_t m, const void *rays, size_t element_count, const void *ranges,
                      const void *unobserved_volumes, const void *terminal_types)
@@ -104,15 +59,7 @@ int raysQueryRefusal(ohmhip_map_t m, const void *rays, size_t element_count, con
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  if (!m->pool.layers[OHMHIP_LID_OCCUPANCY])
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // the CPU query refuses maps without the layer too (valid_layers)
-  }
-  if (m->mc.owner_world > 1u)
-  {
-    return OHMHIP_ERR_UNSUPPORTED;  // a rank holds only its territory
-  }
-  return OHMHIP_OK;
+  return readSideRefusal(m, OHMHIP_LID_OCCUPANCY);  // (the CPU query refuses maps without the layer too: valid_layers)
 }
 
 /// The query on device arrays, enqueued on the map's stream.  The map is observed as ohmhip_map_read_regions would
@@ -165,33 +112,26 @@ try
   const uint32_t n = uint32_t(element_count / 2);
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
+  double *d_ranges = nullptr, *d_volumes = nullptr;
+  int8_t *d_types = nullptr;
+  GpuKeyOut *d_keys = nullptr;
   if (n)
   {
     OHMHIP_CHECK(qs.rays.ensure(sizeof(double) * 6 * n, false, s));
-    OHMHIP_CHECK(qs.ranges.ensure(sizeof(double) * n, false, s));
-    OHMHIP_CHECK(qs.volumes.ensure(sizeof(double) * n, false, s));
-    OHMHIP_CHECK(qs.types.ensure(n, false, s));
-    if (terminal_keys)
-    {
-      OHMHIP_CHECK(qs.keys.ensure(sizeof(GpuKeyOut) * n, false, s));
-    }
+    OHMHIP_CHECK(stageOut(qs.ranges, ranges, n, s, d_ranges));
+    OHMHIP_CHECK(stageOut(qs.volumes, unobserved_volumes, n, s, d_volumes));
+    OHMHIP_CHECK(stageOut(qs.types, terminal_types, n, s, d_types));
+    OHMHIP_CHECK(stageOut(qs.keys, terminal_keys, n, s, d_keys));
     OHMHIP_CHECK(hipMemcpyAsync(qs.rays.ptr, rays, sizeof(double) * 6 * n, hipMemcpyHostToDevice, s));
   }
-  double *d_ranges = static_cast<double *>(qs.ranges.ptr);
-  double *d_volumes = static_cast<double *>(qs.volumes.ptr);
-  int8_t *d_types = static_cast<int8_t *>(qs.types.ptr);
-  GpuKeyOut *d_keys = terminal_keys ? static_cast<GpuKeyOut *>(qs.keys.ptr) : nullptr;
   OHMHIP_CHECK(raysQueryDevice(m, static_cast<const double *>(qs.rays.ptr), n, volume_coefficient, d_ranges, d_volumes,
                                d_types, d_keys));
   if (n)
   {
-    OHMHIP_CHECK(hipMemcpyAsync(ranges, d_ranges, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    OHMHIP_CHECK(hipMemcpyAsync(unobserved_volumes, d_volumes, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    OHMHIP_CHECK(hipMemcpyAsync(terminal_types, d_types, n, hipMemcpyDeviceToHost, s));
-    if (terminal_keys)
-    {
-      OHMHIP_CHECK(hipMemcpyAsync(terminal_keys, d_keys, sizeof(GpuKeyOut) * n, hipMemcpyDeviceToHost, s));
-    }
+    OHMHIP_CHECK(copyOut(ranges, d_ranges, n, s));
+    OHMHIP_CHECK(copyOut(unobserved_volumes, d_volumes, n, s));
+    OHMHIP_CHECK(copyOut(terminal_types, d_types, n, s));
+    OHMHIP_CHECK(copyOut(terminal_keys, d_keys, n, s));
   }
   return hipStreamSynchronize(s);
 }

@@ -58,6 +58,12 @@ struct TileRef
   size_t voxel_offset;  ///< of the tile's first voxel in the region's block
 };
 
+/// Tile (jy, jz) of a region: its first voxel in the region's block.
+size_t tileVoxelOffset(const MapConst &mc, int jy, int jz)
+{
+  return (size_t(jz) * size_t(mc.dim[2]) * size_t(mc.kdim[1]) + size_t(jy) * size_t(mc.dim[1])) * size_t(mc.kdim[0]);
+}
+
 /// The tiles of region `key`, in block order.
 void tilesOfRegion(const MapConst &mc, const int16_t *key, std::vector<TileRef> &out)
 {
@@ -70,7 +76,7 @@ void tilesOfRegion(const MapConst &mc, const int16_t *key, std::vector<TileRef> 
       t.key[0] = key[0];
       t.key[1] = int16_t(int(key[1]) * mc.tile_split[1] + jy);
       t.key[2] = int16_t(int(key[2]) * mc.tile_split[2] + jz);
-      t.voxel_offset = (size_t(jz) * size_t(mc.dim[2]) * size_t(mc.kdim[1]) + size_t(jy) * size_t(mc.dim[1])) * size_t(mc.kdim[0]);
+      t.voxel_offset = tileVoxelOffset(mc, jy, jz);
       out.push_back(t);
     }
   }
