@@ -307,7 +307,8 @@ struct BatchRun
     // Pool exhausted: forget what this batch inserted, grow, retry.
     OHMHIP_CHECK(hipStreamSynchronize(s));
     m->spec_bucket_ok = false;
-    const int err = rollbackAndGrow(m, info.n_slots);
+    // (at least doubled where the budget allows: amortised growth)
+    const int err = growPool(m, info.n_slots, m->pool.slot_capacity * 2u, m->slots_committed);
     if (err)
     {
       // The pool may not grow (memory limit / device memory / slot field): forget what the batch inserted.
@@ -321,9 +322,7 @@ struct BatchRun
       {
         // Spill to host: make room by moving the least recently used regions to the host store, then repeat the
         // batch.  (The failed attempt's k_plan stamped the regions this batch touches: they go last.)
-        const uint64_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
-        const uint64_t allowed =
-          m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->pool.slot_capacity;
+        const uint64_t allowed = poolBudget(m).regions;
         const uint64_t wanted = uint64_t(info.n_slots);  // committed + the batch's new regions
         // (the one cause integrateRaysDevice answers by presenting the batch in halves: the batch ALONE does not fit)
         m->batch_exceeds_limit = wanted > allowed && wanted - allowed > m->slots_committed;

@@ -99,33 +99,15 @@ int clearanceFold(ohmhip_map_t m)
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   OHMHIP_CHECK(refreshHostRegionTable(m));
   const uint32_t epoch = ++cl.epoch;
-  std::vector<uint32_t> dirty(m->slots_committed);
-  if (!dirty.empty())
-  {
-    OHMHIP_CHECK(hipMemcpy(dirty.data(), m->pool.d_dirty, sizeof(uint32_t) * dirty.size(), hipMemcpyDeviceToHost));
-  }
   bool any = false;
-  for (size_t i = 0; i < dirty.size(); ++i)
-  {
-    if (dirty[i] & kDirtyClearance)
-    {
-      cl.regions[callerRegionKey(m, m->slot_keys_host[i])].changed = epoch;
-      any = true;
-    }
-  }
+  OHMHIP_CHECK(forEachDirtyRegion(m, kDirtyClearance, [&](uint64_t key) {
+    cl.regions[callerRegionKey(m, key)].changed = epoch;
+    any = true;
+  }));
   if (any)
   {
-    hipLaunchKernelGGL(k_and_u32, dim3(256), dim3(256), 0, m->stream, m->pool.d_dirty, ~kDirtyClearance,
-                       size_t(m->pool.slot_capacity));
+    clearDirtyBit(m, kDirtyClearance);
     OHMHIP_CHECK(hipGetLastError());
-  }
-  for (auto &entry : m->spilled)
-  {
-    if (entry.second.dirty & kDirtyClearance)
-    {
-      cl.regions[callerRegionKey(m, entry.first)].changed = epoch;
-      entry.second.dirty &= ~kDirtyClearance;
-    }
   }
   return OHMHIP_OK;
 }
@@ -142,7 +124,7 @@ int clearanceSelect(ohmhip_map_t m, uint32_t params, int h, std::vector<uint64_t
   {
     int16_t r[3];
     regionOfOrder(key, r);
-    key = packRegionKey(r[0], r[1], r[2]);
+    key = packRegionKey(r);
   }
   const uint32_t n = uint32_t(present.size());
   stale.assign(n, 0);
@@ -242,7 +224,7 @@ int clearanceProcess(ohmhip_map_t m, ClearanceArgs &a, const std::vector<uint64_
       tilesOfRegion(mc, &keys_xyz[3 * size_t(r0 + i)], tiles);
       for (const TileRef &t : tiles)
       {
-        const uint64_t tile_key = packRegionKey(t.key[0], t.key[1], t.key[2]);
+        const uint64_t tile_key = packRegionKey(t.key);
         const char *src = reinterpret_cast<const char *>(d_out + size_t(i) * kvox + t.voxel_offset);
         const TileHome home = tileHome(m, tile_key);
         char *dst = tileLayerBlock(m, home, OHMHIP_LID_CLEARANCE);
@@ -268,10 +250,9 @@ int clearanceProcess(ohmhip_map_t m, ClearanceArgs &a, const std::vector<uint64_
   }
   if (!slots.empty())
   {
-    OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * slots.size(), false, s));
-    OHMHIP_CHECK(hipMemcpyAsync(m->merge_slots.ptr, slots.data(), sizeof(uint32_t) * slots.size(), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, s, m->pool.d_dirty, static_cast<const uint32_t *>(m->merge_slots.ptr),
-                       slots.size(), kDirtySync);
+    const uint32_t *d_index = nullptr;
+    OHMHIP_CHECK(uploadSlotIndex(m, slots.data(), slots.size(), s, false, d_index));
+    orSlotBits(m, d_index, slots.size(), kDirtySync, s);
     OHMHIP_CHECK(hipGetLastError());
   }
   auto &cl = m->clearance_layer;
@@ -396,7 +377,7 @@ try
   std::unordered_map<uint64_t, char> listed;
   for (size_t i = 0; i < count; ++i)
   {
-    listed.emplace(packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]), 1);
+    listed.emplace(packRegionKey(keys_xyz + 3 * i), 1);
   }
   std::vector<uint64_t> todo;
   for (size_t i = 0; i < present.size(); ++i)

@@ -621,7 +621,7 @@ int tiledRemoveRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t count, si
 static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t count, size_t *removed);
 static int evictColdRegions(ohmhip_map_t m, uint32_t want_free, uint32_t max_evict = 0xffffffffu);
 static int makeRoomForNamedRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t count);
-static int growPoolForNamedRegions(ohmhip_map_t m, uint32_t total, uint32_t keep);
+static int appendNamedRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t count, uint32_t *slots);
 static int readmitSpilledSlots(ohmhip_map_t m, uint32_t first_slot, uint32_t end_slot);
 static int readmitSpilledKeys(ohmhip_map_t m, const int16_t *keys_xyz, size_t count);
 

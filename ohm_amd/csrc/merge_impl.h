@@ -196,7 +196,7 @@ try
     return OHMHIP_ERR_UNSUPPORTED;  // a merging map keeps a base copy per resident region: not combined with spilling
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
-  const size_t bytes = size_t(m->mc.region_voxels) * sizeof(float) * m->pool.slot_capacity;
+  const size_t bytes = mergeBaseStride(m->mc) * m->pool.slot_capacity;
   if (m->pool.d_merge_base.alloc(bytes) != hipSuccess)
   {
     (void)hipGetLastError();
@@ -206,7 +206,7 @@ try
   // What the map holds now is what all replicas are taken to share.
   OHMHIP_CHECK(hipMemcpyAsync(m->pool.d_merge_base, m->pool.layers[OHMHIP_LID_OCCUPANCY], bytes, hipMemcpyDeviceToDevice,
                               m->stream));
-  hipLaunchKernelGGL(k_and_u32, dim3(256), dim3(256), 0, m->stream, m->pool.d_dirty, ~kDirtyMerge, size_t(m->pool.slot_capacity));
+  clearDirtyBit(m, kDirtyMerge);
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   return OHMHIP_OK;
 }
@@ -226,23 +226,15 @@ try
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   OHMHIP_CHECK(refreshHostRegionTable(m));
-  std::vector<uint32_t> dirty(m->slots_committed);
-  if (!dirty.empty())
-  {
-    OHMHIP_CHECK(hipMemcpy(dirty.data(), m->pool.d_dirty, sizeof(uint32_t) * dirty.size(), hipMemcpyDeviceToHost));
-  }
   size_t n = 0;
-  for (size_t i = 0; i < dirty.size(); ++i)
-  {
-    if (dirty[i] & kDirtyMerge)
+  // (a merging map does not spill: every pending region is resident)
+  OHMHIP_CHECK(forEachDirtyRegion(m, kDirtyMerge, [&](uint64_t key) {
+    if (n < capacity)
     {
-      if (n < capacity)
-      {
-        unpackRegionKey(m->slot_keys_host[i], keys_xyz + 3 * n);
-      }
-      ++n;
+      unpackRegionKey(key, keys_xyz + 3 * n);
     }
-  }
+    ++n;
+  }));
   *count = n;
   return OHMHIP_OK;
 }

@@ -249,6 +249,9 @@ __host__ __device__ inline uint64_t packRegionKey(int rx, int ry, int rz)
   return kKeyOccupied | uint64_t(uint16_t(rx)) | (uint64_t(uint16_t(ry)) << 16) | (uint64_t(uint16_t(rz)) << 32);
 }
 
+/// ... of a key as the C ABI passes it: three int16.
+__host__ __device__ inline uint64_t packRegionKey(const int16_t *xyz) { return packRegionKey(xyz[0], xyz[1], xyz[2]); }
+
 __host__ __device__ inline void unpackRegionKey(uint64_t key, int16_t out[3])
 {
   out[0] = int16_t(uint16_t(key & 0xffffu));

@@ -42,6 +42,7 @@
 using namespace ohmhip;
 
 #include "map_state.h"
+#include "slot_state.h"
 #include "pool_impl.h"
 #include "batch_run.h"
 #include "pending_rays.h"
@@ -439,11 +440,11 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_sync(ohmhip_map_t m)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   OHMHIP_CHECK(hipStreamSynchronize(m->front_stream));
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   if (m->debug_flags & (64u | 128u))
@@ -505,11 +506,11 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_batch_timings(ohmhip_map_t m, uint32_t batches_back, float ms[4])
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || !ms)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (batches_back >= kTimingRing || uint64_t(batches_back) >= m->batch_seq)
   {
     return OHMHIP_ERR_INVALID_ARG;
@@ -691,11 +692,11 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_cache_stats(ohmhip_map_t m, ohmhip_cache_stats *stats, int reset)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || !stats)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   stats->hits = m->cache_hits;
   stats->misses = m->cache_misses;
   stats->full = m->cache_full;
@@ -736,11 +737,11 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_set_spill_to_host(ohmhip_map_t m, int enable)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (enable && m->pool.d_merge_base)
   {
     return OHMHIP_ERR_UNSUPPORTED;  // replica-merge maps keep a base copy per region: they do not spill
@@ -752,9 +753,7 @@ try
     // The eager part is capped in bytes (8 GiB): a multi-layer NDT map with a large pool and no memory limit would
     // otherwise pin tens of GB before anything spills.  Reserved BEFORE the mode is switched: a failed reservation
     // leaves spilling off and the coalescing threshold as it was.
-    const uint64_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
-    const uint64_t pool_regions =
-      m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->pool.slot_capacity;
+    const uint64_t per_region = poolBudget(m).per_region, pool_regions = poolBudget(m).regions;
     // (what the pool holds + the quarter an eviction moves out while as much again may still be waiting in the store)
     const uint64_t by_count = std::min<uint64_t>(pool_regions + pool_regions / 2 + 64, 16384);
     const uint64_t by_bytes = std::max<uint64_t>((uint64_t(8) << 30) / std::max<uint64_t>(per_region, 1), 64);
@@ -771,18 +770,16 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_set_spill_writeback(ohmhip_map_t m, int enable)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (enable && m->spill_enabled)
   {
     // the copies the write-back keeps ahead of the evictions live in store records of their own: pinned here, not in
     // the middle of a batch (up to half the pool, capped like the store's eager reservation)
-    const uint64_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
-    const uint64_t pool_regions =
-      m->memory_limit ? std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots) : m->pool.slot_capacity;
+    const uint64_t per_region = poolBudget(m).per_region, pool_regions = poolBudget(m).regions;
     const uint64_t extra = std::min<uint64_t>(pool_regions / 2 + 64, (uint64_t(4) << 30) / std::max<uint64_t>(per_region, 1));
     OHMHIP_CHECK(reserveStoreRecords(m, m->store.free_records.size() + size_t(extra)));
   }
@@ -798,11 +795,11 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_last_stats(ohmhip_map_t m, ohmhip_batch_stats *stats)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || !stats)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (m->stats_pending)
   {
     float ms[4] = { 0, 0, 0, 0 };
@@ -831,11 +828,11 @@ extern "C" {
 int ohmhip_map_mark_dirty(ohmhip_map_t m, const uint32_t *slots, size_t count)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || (count && !slots))
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   for (size_t i = 0; i < count; ++i)
   {
     if (slots[i] >= m->pool.slot_capacity)
@@ -848,11 +845,9 @@ try
     // (the caller rewrote these slots behind the library's back: no use stamp moved, so the background write-back's
     // copies cannot tell -- all of them are void)
     dropPrecleaned(m);
-    OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * count, false, m->stream));
-    OHMHIP_CHECK(hipMemcpyAsync(m->merge_slots.ptr, slots, sizeof(uint32_t) * count, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, m->stream, m->pool.d_dirty,
-                       static_cast<const uint32_t *>(m->merge_slots.ptr), count,
-                       kDirtySync | kDirtyMerge | kDirtyClearance);
+    const uint32_t *d_index = nullptr;
+    OHMHIP_CHECK(uploadSlotIndex(m, slots, count, m->stream, false, d_index));
+    orSlotBits(m, d_index, count, kDirtySync | kDirtyMerge | kDirtyClearance, m->stream);
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   return hipGetLastError();
@@ -900,11 +895,11 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_clear(ohmhip_map_t m)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   dropPrecleaned(m);
   m->slots_committed = 0;

@@ -7,18 +7,6 @@
 
 namespace
 {
-RegionTable regionTable(ohmhip_map_t m)
-{
-  RegionTable rt;
-  rt.keys = m->pool.d_keys;
-  rt.vals = m->pool.d_vals;
-  rt.slot_keys = m->pool.d_slot_keys;
-  rt.n_slots = m->d_n_slots;
-  rt.hash_mask = m->pool.hash_capacity - 1;
-  rt.slot_capacity = m->pool.slot_capacity;
-  return rt;
-}
-
 BatchScratch batchScratch(ohmhip_map_t m)
 {
   // The counters a batch's set-up pass writes exist twice (allocPool makes the arrays twice as long): batch N+1 sets up
@@ -53,27 +41,6 @@ inline Chunk *batchChunks(ohmhip_map_t m) { return m->pool.d_chunks + size_t(m->
 inline uint32_t *batchEventCount(ohmhip_map_t m) { return m->d_event_count + 4u * m->parity; }
 inline DevBuf &batchWalks(ohmhip_map_t m) { return m->walks_buf[m->parity]; }
 
-__global__ void k_rehash(RegionTable rt, uint32_t n)
-{
-  const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-  if (slot >= n)
-  {
-    return;
-  }
-  const uint64_t key = rt.slot_keys[slot];
-  uint32_t idx = hashRegionKey(key, rt.hash_mask);
-  while (true)
-  {
-    const unsigned long long prev = atomicCAS(&rt.keys[idx], 0ull, (unsigned long long)key);
-    if (prev == 0)
-    {
-      rt.vals[idx] = slot;
-      return;
-    }
-    idx = (idx + 1) & rt.hash_mask;
-  }
-}
-
 uint32_t nextPow2(uint32_t v)
 {
   uint32_t p = 1;
@@ -84,26 +51,10 @@ uint32_t nextPow2(uint32_t v)
   return p;
 }
 
-size_t bytesPerRegionAllLayers(const ohmhip_map_config &c, int region_voxels)
-{
-  size_t b = 0;
-  for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
-  {
-    if (c.layers & (1u << l))
-    {
-      b += kLayerBytes[l] * size_t(region_voxels);
-    }
-  }
-  // + miss count layer + hit mask
-  b += 4 * size_t(region_voxels) + size_t((region_voxels + 31) / 32) * 4;
-  // + first-sample table (occupancy mode), traversal accumulator (traversal layer)
-  b += (c.mode == OHMHIP_MODE_OCCUPANCY) ? 4 * size_t(region_voxels) : 0;
-  b += (c.layers & (1u << OHMHIP_LID_TRAVERSAL)) ? 8 * size_t(region_voxels) : 0;
-  return b;
-}
-
 /// (Re)allocate the region pool for `capacity` regions, preserving the first `keep` slots' contents.  Everything new is
-/// allocated before anything old is released: a failed allocation leaves the map exactly as it was.
+/// allocated before anything old is released: a failed allocation leaves the map exactly as it was.  `keep` is the
+/// committed slot count at every caller (or the count it is about to commit: 0, in ohmhip_map_clear), so the table
+/// commit at the end may set slots_committed like every other commit does.
 int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
 {
   const size_t rv = size_t(m->mc.region_voxels);
@@ -124,62 +75,20 @@ int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
     OHMHIP_CHECK(hipMemsetAsync(array, 0, std::max<size_t>(bytes, 4), s));
     return OHMHIP_OK;
   };
-  // The per-voxel mask is persistent state for NDT / TSDF (voxels that take the ordered replay path): it moves with
-  // the regions it describes.
-  const size_t mask_row = ((rv + 31) / 32) * sizeof(uint32_t);
   auto build = [&]() -> int {
-    for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
-    {
-      if (!(m->config.layers & (1u << l)))
-      {
-        continue;
-      }
-      const size_t stride = rv * kLayerBytes[l];
-      OHMHIP_CHECK(fresh.layers[l].alloc(std::max<size_t>(stride * capacity, 4)));
-      if (keep && old.layers[l])
-      {
-        OHMHIP_CHECK(hipMemcpyAsync(fresh.layers[l], old.layers[l], stride * keep, hipMemcpyDeviceToDevice, s));
-      }
-      char *tail = static_cast<char *>(fresh.layers[l].get()) + stride * keep;
-      const size_t tail_bytes = stride * (capacity - keep);
-      if (layerClearWord(l) != 0u)
-      {
-        // Occupancy clears to +inf == unobserved (ohm/DefaultLayer.cpp:87-91, ohm/VoxelOccupancy.h:42-45), clearance
-        // to -1 (:174-193).
-        const size_t count = tail_bytes / 4;
-        if (count)
-        {
-          hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(tail),
-                             layerClearWord(l), count);
-        }
-      }
-      else if (tail_bytes)
-      {
-        OHMHIP_CHECK(hipMemsetAsync(tail, 0, tail_bytes, s));
-      }
-    }
+    // The persistent per-slot state (slot_state.h): the kept slots' content, the rest pristine.
+    OHMHIP_CHECK(allocSlotArrays(m, fresh, capacity, bool(old.d_merge_base)));
+    OHMHIP_CHECK(copySlots(m, old, fresh, keep, s));
+    OHMHIP_CHECK(clearSlots(m, fresh, keep, capacity - keep, s));
+    // The table: the kept slots' keys (the hash is rebuilt from them below: commitSlotTable clears d_keys).
     OHMHIP_CHECK(zalloc(fresh.d_slot_keys, sizeof(uint64_t) * capacity));
-    OHMHIP_CHECK(zalloc(fresh.d_hit_mask, mask_row * capacity));
-    OHMHIP_CHECK(zalloc(fresh.d_dirty, sizeof(uint32_t) * capacity));
     if (keep && old.d_slot_keys)
     {
       OHMHIP_CHECK(hipMemcpyAsync(fresh.d_slot_keys, old.d_slot_keys, sizeof(uint64_t) * keep, hipMemcpyDeviceToDevice, s));
     }
-    if (keep && old.d_hit_mask)
-    {
-      OHMHIP_CHECK(hipMemcpyAsync(fresh.d_hit_mask, old.d_hit_mask, mask_row * keep, hipMemcpyDeviceToDevice, s));
-    }
-    if (keep && old.d_dirty)
-    {
-      OHMHIP_CHECK(hipMemcpyAsync(fresh.d_dirty, old.d_dirty, sizeof(uint32_t) * keep, hipMemcpyDeviceToDevice, s));
-    }
-    OHMHIP_CHECK(zalloc(fresh.d_last_use, sizeof(uint32_t) * 2 * capacity));
-    if (keep && old.d_last_use)
-    {
-      OHMHIP_CHECK(hipMemcpyAsync(fresh.d_last_use, old.d_last_use, sizeof(uint32_t) * 2 * keep, hipMemcpyDeviceToDevice, s));
-    }
-    OHMHIP_CHECK(zalloc(fresh.d_keys, sizeof(unsigned long long) * hash_cap));
+    OHMHIP_CHECK(fresh.d_keys.alloc(sizeof(unsigned long long) * hash_cap));
     OHMHIP_CHECK(zalloc(fresh.d_vals, sizeof(uint32_t) * hash_cap));
+    // The per-batch scratch: zero between batches.
     OHMHIP_CHECK(zalloc(fresh.d_seg_count, sizeof(uint32_t) * 2 * hash_cap));
     OHMHIP_CHECK(zalloc(fresh.d_seg_cursor, sizeof(uint32_t) * 2 * hash_cap));
     OHMHIP_CHECK(zalloc(fresh.d_hit_count, sizeof(uint32_t) * 2 * hash_cap));
@@ -199,20 +108,6 @@ int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
     {
       OHMHIP_CHECK(zalloc(fresh.d_traversal_acc, sizeof(unsigned long long) * rv * capacity));
     }
-    if (old.d_merge_base)
-    {
-      // replica-merge base (merge_impl.h): moves with the regions; a new region's base is "unobserved"
-      OHMHIP_CHECK(fresh.d_merge_base.alloc(std::max<size_t>(sizeof(float) * rv * capacity, 4)));
-      if (keep)
-      {
-        OHMHIP_CHECK(hipMemcpyAsync(fresh.d_merge_base, old.d_merge_base, sizeof(float) * rv * keep, hipMemcpyDeviceToDevice, s));
-      }
-      if (capacity > keep)
-      {
-        hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(fresh.d_merge_base + rv * keep),
-                           0x7f800000u, rv * (capacity - keep));
-      }
-    }
     OHMHIP_CHECK(hipStreamSynchronize(s));
     return OHMHIP_OK;
   };
@@ -225,18 +120,8 @@ int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
   }
 
   m->pool = std::move(fresh);  // (releases the old pool)
-  OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &keep, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  if (keep)
-  {
-    hipLaunchKernelGGL(k_rehash, dim3((keep + 255) / 256), dim3(256), 0, s, regionTable(m), keep);
-  }
-  OHMHIP_CHECK(hipStreamSynchronize(s));
-  OHMHIP_CHECK(hipGetLastError());
-  return OHMHIP_OK;
+  return commitSlotTable(m, keep);
 }
-
-/// Largest region pool the 20-bit slot field of the sample / event sort keys can address.
-constexpr uint32_t kMaxRegionSlots = (1u << 20) - 2u;
 
 /// Pool capacity for `needed` regions: doubling, clamped to what the sort keys can address.  False when `needed` itself
 /// is beyond that (the caller reports OHMHIP_ERR_CAPACITY: a larger slot would be truncated in the keys and alias
@@ -273,7 +158,6 @@ int rollbackTable(ohmhip_map_t m)
   hipStream_t s = m->stream;
   const size_t hash_words = m->pool.hash_capacity;
   OHMHIP_CHECK(hipStreamSynchronize(s));
-  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_keys, 0, sizeof(unsigned long long) * hash_words, s));
   OHMHIP_CHECK(hipMemsetAsync(m->pool.d_vals, 0, sizeof(uint32_t) * hash_words, s));
   uint32_t *per_hash[] = { m->pool.d_seg_count,  m->pool.d_seg_cursor,   m->pool.d_hit_count, m->pool.d_seg_offset,
                            m->pool.d_touched_flag, m->pool.d_touched };
@@ -286,60 +170,50 @@ int rollbackTable(ohmhip_map_t m)
   if (m->pool.slot_capacity > keep)
   {
     OHMHIP_CHECK(hipMemsetAsync(m->pool.d_slot_keys + keep, 0, sizeof(uint64_t) * (m->pool.slot_capacity - keep), s));
-  }
-  if (m->pool.slot_capacity > keep)
-  {
-    // the slots the failed batch handed out go back to the pristine state: no modified flags, no use stamp
-    OHMHIP_CHECK(hipMemsetAsync(m->pool.d_dirty + keep, 0, sizeof(uint32_t) * (m->pool.slot_capacity - keep), s));
-    OHMHIP_CHECK(hipMemsetAsync(m->pool.d_last_use + 2 * size_t(keep), 0, sizeof(uint32_t) * 2 * (m->pool.slot_capacity - keep), s));
-  }
-  OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &keep, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  if (keep)
-  {
-    hipLaunchKernelGGL(k_rehash, dim3((keep + 255) / 256), dim3(256), 0, s, regionTable(m), keep);
+    // the slots the failed batch handed out go back to the pristine state: no modified flags, no use stamp (its set-up
+    // pass wrote nothing else of theirs)
+    OHMHIP_CHECK(clearSlots(m, m->pool, keep, m->pool.slot_capacity - keep, s, SlotArray::kInSpilledRegion));
   }
   OHMHIP_CHECK(hipMemsetAsync(m->d_info, 0, 3 * sizeof(BatchInfo), s));
   m->info_clean = false;
   m->spec_bucket_ok = false;
-  OHMHIP_CHECK(hipStreamSynchronize(s));
-  return hipGetLastError();
+  return commitSlotTable(m, keep);
 }
 
-/// Restore the region table after a batch that overflowed the pool: drop regions the failed batch inserted.
-/// `needed`: the slots the batch must have; the pool is at least doubled beyond that where it may (amortised growth).
-int rollbackAndGrow(ohmhip_map_t m, uint32_t needed)
+/// Grow the pool so that it holds `needed` regions, keeping the first `keep` slots -- and `wish` regions where the
+/// budget allows: a batch that overflowed the pool wishes for double the pool (amortised growth), regions created by
+/// name for what they need.  Refused, in this order, when `needed` is beyond the slot field of the sort keys, beyond
+/// the map's memory limit (the largest pool the limit allows is still tried when the wish overshoots it), or when the
+/// new pool does not fit in free device memory.
+int growPool(ohmhip_map_t m, uint32_t needed, uint32_t wish, uint32_t keep)
 {
   uint32_t cap = 0;
-  const uint32_t wish = std::max(needed, std::min(m->pool.slot_capacity * 2u, kMaxRegionSlots));
   if (!grownCapacity(m->pool.slot_capacity, needed, cap))
   {
     return OHMHIP_ERR_CAPACITY;
   }
   uint32_t wished_cap = cap;
-  if (grownCapacity(m->pool.slot_capacity, wish, wished_cap))
+  if (grownCapacity(m->pool.slot_capacity, std::max(needed, std::min(wish, kMaxRegionSlots)), wished_cap))
   {
     cap = wished_cap;
   }
-  // Check memory budget: refuse if the new pool cannot fit in free device memory, or in the map's own limit (the
-  // largest pool the limit allows is still tried when doubling overshoots it).
-  const size_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
+  const PoolBudget budget = poolBudget(m);
   if (m->memory_limit)
   {
-    const uint64_t allowed = m->memory_limit / per_region;
-    if (allowed < needed)
+    if (budget.regions < needed)
     {
       return OHMHIP_ERR_CAPACITY;
     }
-    cap = uint32_t(std::min<uint64_t>(cap, allowed));
+    cap = uint32_t(std::min<uint64_t>(cap, budget.regions));
   }
   size_t free_b = 0, total_b = 0;
   OHMHIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-  if (per_region * size_t(cap) > free_b)
+  if (budget.per_region * cap > free_b)
   {
     return OHMHIP_ERR_CAPACITY;
   }
   ++m->cache_full;
-  return allocPool(m, cap, m->slots_committed);
+  return allocPool(m, cap, keep);
 }
 
 int refreshHostRegionTable(ohmhip_map_t m)
@@ -381,20 +255,7 @@ int reserveStoreRecords(ohmhip_map_t m, size_t records)
   ohmhip_map_s::HostStore &st = m->store;
   if (st.record_bytes == 0)
   {
-    const size_t rv = size_t(m->mc.region_voxels);
-    size_t at = 0;
-    for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
-    {
-      st.layer_offset[l] = at;
-      if (m->pool.layers[l])
-      {
-        at += (rv * kLayerBytes[l] + 255) & ~size_t(255);
-      }
-    }
-    st.mask_offset = at;
-    st.mask_bytes = ((rv + 31) / 32) * sizeof(uint32_t);
-    at += (st.mask_bytes + 255) & ~size_t(255);
-    st.record_bytes = at;
+    layoutStoreRecord(m);
   }
   while (st.free_records.size() < records)
   {

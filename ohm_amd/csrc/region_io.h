@@ -10,11 +10,11 @@ extern "C" {
 int ohmhip_map_region_count(ohmhip_map_t m, size_t *count)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || !count)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (tiledBoundary(m))
   {
     return tiledListRegions(m, false, nullptr, 0, count);
@@ -24,102 +24,56 @@ try
 }
 OHMHIP_ABI_CATCH
 
-int ohmhip_map_regions(ohmhip_map_t m, int16_t *keys_xyz, size_t capacity, size_t *count)
-try
+/// ohmhip_map_regions / ohmhip_map_dirty_regions: the regions whose dirty word has `bit` set (0: all), the resident ones
+/// first.
+static int listRegions(ohmhip_map_t m, uint32_t bit, int16_t *keys_xyz, size_t capacity, size_t *count)
 {
-  OHMHIP_SETTLE(m);
   if (!m || !count)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (tiledBoundary(m))
   {
-    return tiledListRegions(m, false, keys_xyz, capacity, count);
+    return tiledListRegions(m, bit != 0, keys_xyz, capacity, count);
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
-  const int err = refreshHostRegionTable(m);
-  if (err)
-  {
-    return err;
-  }
-  *count = m->slot_keys_host.size() + m->spilled.size();
-  size_t at = 0;
-  for (; at < m->slot_keys_host.size() && at < capacity && keys_xyz; ++at)
-  {
-    unpackRegionKey(m->slot_keys_host[at], keys_xyz + 3 * at);
-  }
-  for (auto it = m->spilled.begin(); it != m->spilled.end() && at < capacity && keys_xyz; ++it, ++at)
-  {
-    unpackRegionKey(it->first, keys_xyz + 3 * at);
-  }
+  OHMHIP_CHECK(refreshHostRegionTable(m));
+  size_t n = 0;
+  OHMHIP_CHECK(forEachDirtyRegion(m, bit, [&](uint64_t key) {
+    if (keys_xyz && n < capacity)
+    {
+      unpackRegionKey(key, keys_xyz + 3 * n);
+    }
+    ++n;
+  }));
+  *count = n;
   return OHMHIP_OK;
+}
+
+int ohmhip_map_regions(ohmhip_map_t m, int16_t *keys_xyz, size_t capacity, size_t *count)
+try
+{
+  return listRegions(m, 0u, keys_xyz, capacity, count);
 }
 OHMHIP_ABI_CATCH
 
 int ohmhip_map_dirty_regions(ohmhip_map_t m, int16_t *keys_xyz, size_t capacity, size_t *count)
 try
 {
-  OHMHIP_SETTLE(m);
-  if (!m || !count)
-  {
-    return OHMHIP_ERR_INVALID_ARG;
-  }
-  if (tiledBoundary(m))
-  {
-    return tiledListRegions(m, true, keys_xyz, capacity, count);
-  }
-  OHMHIP_CHECK(hipStreamSynchronize(m->stream));
-  int err = refreshHostRegionTable(m);
-  if (err)
-  {
-    return err;
-  }
-  std::vector<uint32_t> dirty(m->slots_committed);
-  if (!dirty.empty())
-  {
-    OHMHIP_CHECK(hipMemcpy(dirty.data(), m->pool.d_dirty, sizeof(uint32_t) * dirty.size(), hipMemcpyDeviceToHost));
-  }
-  size_t n = 0;
-  for (size_t i = 0; i < dirty.size(); ++i)
-  {
-    if (dirty[i] & kDirtySync)
-    {
-      if (keys_xyz && n < capacity)
-      {
-        unpackRegionKey(m->slot_keys_host[i], keys_xyz + 3 * n);
-      }
-      ++n;
-    }
-  }
-  for (const auto &entry : m->spilled)
-  {
-    if (entry.second.dirty & kDirtySync)
-    {
-      if (keys_xyz && n < capacity)
-      {
-        unpackRegionKey(entry.first, keys_xyz + 3 * n);
-      }
-      ++n;
-    }
-  }
-  *count = n;
-  return OHMHIP_OK;
+  return listRegions(m, kDirtySync, keys_xyz, capacity, count);
 }
 OHMHIP_ABI_CATCH
 
 int ohmhip_map_clear_dirty(ohmhip_map_t m)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  hipLaunchKernelGGL(k_and_u32, dim3(256), dim3(256), 0, m->stream, m->pool.d_dirty, ~kDirtySync, size_t(m->pool.slot_capacity));
-  for (auto &entry : m->spilled)
-  {
-    entry.second.dirty &= ~kDirtySync;
-  }
+  OHMHIP_SETTLE(m);
+  clearDirtyBit(m, kDirtySync);
   return hipGetLastError();
 }
 OHMHIP_ABI_CATCH
@@ -127,11 +81,11 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_region_slot(ohmhip_map_t m, const int16_t key_xyz[3], uint32_t *slot)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || !key_xyz || !slot)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (tiledBoundary(m))
   {
     return OHMHIP_ERR_UNSUPPORTED;  // a region cut into tiles has no single slot (zero-copy views: 32^3 regions)
@@ -142,7 +96,7 @@ try
   {
     return err;
   }
-  const auto it = m->region_slots.find(packRegionKey(key_xyz[0], key_xyz[1], key_xyz[2]));
+  const auto it = m->region_slots.find(packRegionKey(key_xyz));
   if (it == m->region_slots.end())
   {
     return OHMHIP_ERR_NOT_FOUND;
@@ -155,11 +109,11 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_device_layer_ptr(ohmhip_map_t m, int layer_id, void **device_ptr, size_t *region_stride_bytes)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || layer_id < 0 || layer_id >= OHMHIP_LID_COUNT || !device_ptr)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (!m->pool.layers[layer_id])
   {
     return OHMHIP_ERR_NOT_FOUND;
@@ -176,11 +130,11 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_read_regions(ohmhip_map_t m, int layer_id, const int16_t *keys_xyz, size_t count, void *const *dsts)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || layer_id < 0 || layer_id >= OHMHIP_LID_COUNT || (count && (!keys_xyz || !dsts)))
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (!m->pool.layers[layer_id])
   {
     return OHMHIP_ERR_NOT_FOUND;
@@ -204,7 +158,7 @@ try
     for (size_t k = 0; k < count; ++k)
     {
       const int16_t *key = keys_xyz + 3 * k;
-      const auto it = m->spilled.find(packRegionKey(key[0], key[1], key[2]));
+      const auto it = m->spilled.find(packRegionKey(key));
       if (it != m->spilled.end())
       {
         std::memcpy(dsts[k], it->second.record + m->store.layer_offset[layer_id], stride);
@@ -234,7 +188,7 @@ try
   for (size_t k = 0; k < count; ++k)
   {
     const int16_t *key = keys_xyz + 3 * k;
-    const auto it = m->region_slots.find(packRegionKey(key[0], key[1], key[2]));
+    const auto it = m->region_slots.find(packRegionKey(key));
     if (it == m->region_slots.end())
     {
       return OHMHIP_ERR_NOT_FOUND;
@@ -337,11 +291,11 @@ int ohmhip_map_write_regions(ohmhip_map_t m, int layer_id, const int16_t *keys_x
                              const void *const *srcs)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || layer_id < 0 || layer_id >= OHMHIP_LID_COUNT || (count && (!keys_xyz || !srcs)))
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (!m->pool.layers[layer_id])
   {
     return OHMHIP_ERR_NOT_FOUND;
@@ -354,52 +308,12 @@ try
   for (size_t i = 0; i < count && !m->precleaned.empty(); ++i)
   {
     // (the write-back's copy of a region that is being rewritten is void)
-    dropPrecleanedKey(m, packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]));
+    dropPrecleanedKey(m, packRegionKey(keys_xyz + 3 * i));
   }
-  OHMHIP_CHECK(readmitSpilledKeys(m, keys_xyz, count));  // (an upload edits the region where it lives: in the pool)
-  OHMHIP_CHECK(makeRoomForNamedRegions(m, keys_xyz, count));
-  int err = refreshHostRegionTable(m);
-  if (err)
-  {
-    return err;
-  }
+  OHMHIP_CHECK(appendNamedRegions(m, keys_xyz, count, nullptr));  // (an upload edits the region where it lives: in the pool)
   const size_t stride = size_t(m->mc.region_voxels) * kLayerBytes[layer_id];
-  // Create any regions which are not resident yet (host-side insert, then rebuild the device hash).
-  std::vector<uint64_t> new_keys;
-  for (size_t i = 0; i < count; ++i)
-  {
-    const uint64_t key = packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]);
-    if (m->region_slots.find(key) == m->region_slots.end())
-    {
-      m->region_slots[key] = uint32_t(m->slot_keys_host.size());
-      m->slot_keys_host.push_back(key);
-      new_keys.push_back(key);
-    }
-  }
-  if (!new_keys.empty())
-  {
-    const uint32_t total = uint32_t(m->slot_keys_host.size());
-    const uint32_t old = m->slots_committed;
-    if (total > m->pool.slot_capacity)
-    {
-      err = growPoolForNamedRegions(m, total, old);
-      if (err)
-      {
-        dropHostRegions(m, old);  // the device never saw them
-        return err;
-      }
-    }
-    OHMHIP_CHECK(hipMemcpy(m->pool.d_slot_keys + old, m->slot_keys_host.data() + old, sizeof(uint64_t) * (total - old),
-                           hipMemcpyHostToDevice));
-    // Rebuild the hash from slot_keys (cheap: one lane per region).
-    OHMHIP_CHECK(hipMemsetAsync(m->pool.d_keys, 0, sizeof(unsigned long long) * m->pool.hash_capacity, m->stream));
-    OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &total, sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(k_rehash, dim3((total + 255) / 256), dim3(256), 0, m->stream, regionTable(m), total);
-    OHMHIP_CHECK(hipStreamSynchronize(m->stream));
-    m->slots_committed = total;
-  }
   const size_t burst = 64;
-  err = ensureStage(m, std::max(m->h_stage_bytes, burst * stride));
+  int err = ensureStage(m, std::max(m->h_stage_bytes, burst * stride));
   if (err)
   {
     return err;
@@ -410,7 +324,7 @@ try
     for (size_t k = 0; k < n; ++k)
     {
       const int16_t *key = keys_xyz + 3 * (base + k);
-      const uint32_t slot = m->region_slots[packRegionKey(key[0], key[1], key[2])];
+      const uint32_t slot = m->region_slots[packRegionKey(key)];
       std::memcpy(static_cast<char *>(m->h_stage.get()) + k * stride, srcs[base + k], stride);
       OHMHIP_CHECK(hipMemcpyAsync(static_cast<char *>(m->pool.layers[layer_id].get()) + size_t(slot) * stride,
                                   static_cast<char *>(m->h_stage.get()) + k * stride, stride, hipMemcpyHostToDevice,
@@ -426,7 +340,7 @@ try
   {
     for (size_t i = 0; i < count; ++i)
     {
-      const uint32_t slot = m->region_slots[packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2])];
+      const uint32_t slot = m->region_slots[packRegionKey(keys_xyz + 3 * i)];
       hipLaunchKernelGGL(k_rebuild_mask, dim3(4), dim3(256), 0, m->stream, m->mc, slot,
                          ndt ? static_cast<const uint32_t *>(m->pool.layers[OHMHIP_LID_MEAN].get()) : nullptr,
                          tsdf ? static_cast<const float *>(m->pool.layers[OHMHIP_LID_TSDF].get()) : nullptr, m->pool.d_hit_mask);
@@ -436,7 +350,7 @@ try
   // (an occupancy upload makes the neighbourhood's clearance stale; a clearance upload makes the region's own)
   for (size_t i = 0; i < count && (layer_id == OHMHIP_LID_OCCUPANCY || layer_id == OHMHIP_LID_CLEARANCE); ++i)
   {
-    const uint64_t key = packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]);
+    const uint64_t key = packRegionKey(keys_xyz + 3 * i);
     if (layer_id == OHMHIP_LID_OCCUPANCY)
     {
       clearanceMarkChanged(m, key);
@@ -453,59 +367,17 @@ OHMHIP_ABI_CATCH
 int ohmhip_map_ensure_regions(ohmhip_map_t m, const int16_t *keys_xyz, size_t count, uint32_t *slots)
 try
 {
-  OHMHIP_SETTLE(m);
   if (!m || (count && !keys_xyz))
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  OHMHIP_SETTLE(m);
   if (tiledBoundary(m))
   {
     return OHMHIP_ERR_UNSUPPORTED;  // slots are per tile: the zero-copy / merge plumbing is for one-tile regions
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
-  OHMHIP_CHECK(readmitSpilledKeys(m, keys_xyz, count));
-  OHMHIP_CHECK(makeRoomForNamedRegions(m, keys_xyz, count));
-  int err = refreshHostRegionTable(m);
-  if (err)
-  {
-    return err;
-  }
-  const uint32_t old = m->slots_committed;
-  for (size_t i = 0; i < count; ++i)
-  {
-    const uint64_t key = packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]);
-    auto it = m->region_slots.find(key);
-    if (it == m->region_slots.end())
-    {
-      it = m->region_slots.emplace(key, uint32_t(m->slot_keys_host.size())).first;
-      m->slot_keys_host.push_back(key);
-    }
-    if (slots)
-    {
-      slots[i] = it->second;
-    }
-  }
-  const uint32_t total = uint32_t(m->slot_keys_host.size());
-  if (total > old)
-  {
-    if (total > m->pool.slot_capacity)
-    {
-      err = growPoolForNamedRegions(m, total, old);
-      if (err)
-      {
-        dropHostRegions(m, old);  // the device never saw them
-        return err;
-      }
-    }
-    OHMHIP_CHECK(hipMemcpy(m->pool.d_slot_keys + old, m->slot_keys_host.data() + old, sizeof(uint64_t) * (total - old),
-                           hipMemcpyHostToDevice));
-    OHMHIP_CHECK(hipMemsetAsync(m->pool.d_keys, 0, sizeof(unsigned long long) * m->pool.hash_capacity, m->stream));
-    OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &total, sizeof(uint32_t), hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(k_rehash, dim3((total + 255) / 256), dim3(256), 0, m->stream, regionTable(m), total);
-    OHMHIP_CHECK(hipStreamSynchronize(m->stream));
-    m->slots_committed = total;
-  }
-  return OHMHIP_OK;
+  return appendNamedRegions(m, keys_xyz, count, slots);
 }
 OHMHIP_ABI_CATCH
 
@@ -532,7 +404,7 @@ try
     OHMHIP_CHECK(refreshHostRegionTable(m));
     for (size_t i = 0; i < count; ++i)
     {
-      const uint64_t key = packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]);
+      const uint64_t key = packRegionKey(keys_xyz + 3 * i);
       if (m->region_slots.count(key) || m->spilled.count(key))
       {
         clearanceMarkChanged(m, key);
@@ -544,7 +416,7 @@ try
   size_t forgotten = 0;
   for (size_t i = 0; i < count && !m->spilled.empty(); ++i)
   {
-    const auto it = m->spilled.find(packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]));
+    const auto it = m->spilled.find(packRegionKey(keys_xyz + 3 * i));
     if (it != m->spilled.end())
     {
       releaseStoreRecord(m, it->second.record);

@@ -29,7 +29,7 @@ static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t
   uint32_t k = 0;
   for (size_t i = 0; i < count; ++i)
   {
-    const uint64_t packed = packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]);
+    const uint64_t packed = packRegionKey(keys_xyz + 3 * i);
     const auto it = m->region_slots.find(packed);
     if (it != m->region_slots.end() && !drop[it->second])
     {
@@ -54,8 +54,6 @@ static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t
   // Slots stay dense: the survivors at the tail move into the holes the removed regions leave further down, the vacated
   // tail goes back to the pristine state every unassigned slot is in, and the hash table is rebuilt from the slot keys.
   const uint32_t new_n = n - k;
-  const size_t rv = size_t(m->mc.region_voxels);
-  const size_t mask_row = ((rv + 31) / 32) * sizeof(uint32_t);
   uint32_t src = new_n;
   std::vector<CopyJob> jobs;
   for (uint32_t dst = 0; dst < new_n; ++dst)
@@ -69,56 +67,12 @@ static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t
       ++src;
     }
     // (source slots lie in the tail [new_n, n), destinations below new_n: no job reads what another writes)
-    for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
-    {
-      if (m->pool.layers[l])
-      {
-        const size_t stride = rv * kLayerBytes[l];
-        jobs.push_back(CopyJob{ static_cast<const char *>(m->pool.layers[l].get()) + stride * src,
-                                static_cast<char *>(m->pool.layers[l].get()) + stride * dst, stride });
-      }
-    }
-    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_hit_mask.get()) + mask_row * src,
-                            reinterpret_cast<char *>(m->pool.d_hit_mask.get()) + mask_row * dst, mask_row });
-    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_dirty + src), reinterpret_cast<char *>(m->pool.d_dirty + dst),
-                            sizeof(uint32_t) });
-    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_last_use + 2 * size_t(src)),
-                            reinterpret_cast<char *>(m->pool.d_last_use + 2 * size_t(dst)), 2 * sizeof(uint32_t) });
-    if (m->pool.d_merge_base)
-    {
-      jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_merge_base + rv * src),
-                              reinterpret_cast<char *>(m->pool.d_merge_base + rv * dst), sizeof(float) * rv });
-    }
+    appendSlotMoveJobs(m, src, dst, jobs);
     m->slot_keys_host[dst] = m->slot_keys_host[src];
     ++src;
   }
   OHMHIP_CHECK(launchCopyJobs(m, jobs, s));
-  for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
-  {
-    if (!m->pool.layers[l])
-    {
-      continue;
-    }
-    const size_t stride = rv * kLayerBytes[l];
-    char *tail = static_cast<char *>(m->pool.layers[l].get()) + stride * new_n;
-    if (layerClearWord(l) != 0u)
-    {
-      hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(tail), layerClearWord(l),
-                         stride * k / 4);
-    }
-    else
-    {
-      OHMHIP_CHECK(hipMemsetAsync(tail, 0, stride * k, s));
-    }
-  }
-  OHMHIP_CHECK(hipMemsetAsync(reinterpret_cast<char *>(m->pool.d_hit_mask.get()) + mask_row * new_n, 0, mask_row * k, s));
-  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_dirty + new_n, 0, sizeof(uint32_t) * k, s));
-  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_last_use + 2 * size_t(new_n), 0, sizeof(uint32_t) * 2 * k, s));
-  if (m->pool.d_merge_base)
-  {
-    hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t *>(m->pool.d_merge_base + rv * new_n),
-                       0x7f800000u, rv * k);
-  }
+  OHMHIP_CHECK(clearSlots(m, m->pool, new_n, k, s));
   m->slot_keys_host.resize(new_n);
   m->region_slots.clear();
   for (uint32_t i = 0; i < new_n; ++i)
@@ -131,15 +85,7 @@ static int removeResidentRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t
     OHMHIP_CHECK(hipMemcpyAsync(m->pool.d_slot_keys, m->slot_keys_host.data(), sizeof(uint64_t) * new_n,
                                 hipMemcpyHostToDevice, s));
   }
-  OHMHIP_CHECK(hipMemsetAsync(m->pool.d_keys, 0, sizeof(unsigned long long) * m->pool.hash_capacity, s));
-  OHMHIP_CHECK(hipMemcpyAsync(m->d_n_slots, &new_n, sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  if (new_n)
-  {
-    hipLaunchKernelGGL(k_rehash, dim3((new_n + 255) / 256), dim3(256), 0, s, regionTable(m), new_n);
-  }
-  OHMHIP_CHECK(hipStreamSynchronize(s));
-  OHMHIP_CHECK(hipGetLastError());
-  m->slots_committed = new_n;
+  OHMHIP_CHECK(commitSlotTable(m, new_n));
   m->spec_bucket_ok = false;  // per-slot sample ranges of the previous batch no longer describe these slots
   return OHMHIP_OK;
 }
@@ -296,41 +242,54 @@ static int evictColdRegions(ohmhip_map_t m, uint32_t want_free, uint32_t max_evi
   lap(2, t_mark);
   for (uint32_t v = 0; v < k; ++v)
   {
-    m->spilled[packRegionKey(victim_keys[3 * size_t(v)], victim_keys[3 * size_t(v) + 1], victim_keys[3 * size_t(v) + 2])] =
-      content[v];
+    m->spilled[packRegionKey(&victim_keys[3 * size_t(v)])] = content[v];
   }
   m->evictions += removed;
   m->evicted_per_call = k;
   return OHMHIP_OK;
 }
 
-/// Pool growth on behalf of regions created by name (ohmhip_map_write_regions / ohmhip_map_ensure_regions): the same
-/// budget rules as a batch's growth (rollbackAndGrow) -- the map's memory limit and the device's free memory.
-static int growPoolForNamedRegions(ohmhip_map_t m, uint32_t total, uint32_t keep)
+/// Create the named regions that the map does not hold in the pool yet (ohmhip_map_write_regions,
+/// ohmhip_map_ensure_regions; `slots`, where not null, receives every named region's slot): stored ones come back from
+/// the host store, room is made under a memory limit, the new keys are appended to the host table and the device's and
+/// the table is committed.  The caller has drained the compute stream.  On failure the map holds what it held.
+static int appendNamedRegions(ohmhip_map_t m, const int16_t *keys_xyz, size_t count, uint32_t *slots)
 {
-  uint32_t cap = 0;
-  if (!grownCapacity(m->pool.slot_capacity, total, cap))
+  OHMHIP_CHECK(readmitSpilledKeys(m, keys_xyz, count));  // (a region is edited where it lives: in the pool)
+  OHMHIP_CHECK(makeRoomForNamedRegions(m, keys_xyz, count));
+  OHMHIP_CHECK(refreshHostRegionTable(m));
+  const uint32_t old = m->slots_committed;
+  for (size_t i = 0; i < count; ++i)
   {
-    return OHMHIP_ERR_CAPACITY;
-  }
-  const size_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
-  if (m->memory_limit)
-  {
-    const uint64_t allowed = m->memory_limit / per_region;
-    if (allowed < total)
+    const uint64_t key = packRegionKey(keys_xyz + 3 * i);
+    auto it = m->region_slots.find(key);
+    if (it == m->region_slots.end())
     {
-      return OHMHIP_ERR_CAPACITY;
+      it = m->region_slots.emplace(key, uint32_t(m->slot_keys_host.size())).first;
+      m->slot_keys_host.push_back(key);
     }
-    cap = uint32_t(std::min<uint64_t>(cap, allowed));
+    if (slots)
+    {
+      slots[i] = it->second;
+    }
   }
-  size_t free_b = 0, total_b = 0;
-  OHMHIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-  if (per_region * size_t(cap) > free_b)
+  const uint32_t total = uint32_t(m->slot_keys_host.size());
+  if (total == old)
   {
-    return OHMHIP_ERR_CAPACITY;
+    return OHMHIP_OK;
   }
-  ++m->cache_full;
-  return allocPool(m, cap, keep);
+  if (total > m->pool.slot_capacity)
+  {
+    const int err = growPool(m, total, total, old);
+    if (err)
+    {
+      dropHostRegions(m, old);  // the device never saw them
+      return err;
+    }
+  }
+  OHMHIP_CHECK(hipMemcpy(m->pool.d_slot_keys + old, m->slot_keys_host.data() + old, sizeof(uint64_t) * (total - old),
+                         hipMemcpyHostToDevice));
+  return commitSlotTable(m, total);
 }
 
 /// Before regions are created by name under a memory limit: if the named keys that are not resident yet would push the
@@ -343,13 +302,12 @@ static int makeRoomForNamedRegions(ohmhip_map_t m, const int16_t *keys_xyz, size
     return OHMHIP_OK;
   }
   OHMHIP_CHECK(refreshHostRegionTable(m));
-  const uint64_t per_region = bytesPerRegionAllLayers(m->config, m->mc.region_voxels);
-  const uint64_t allowed = std::min<uint64_t>(m->memory_limit / per_region, kMaxRegionSlots);
+  const uint64_t allowed = poolBudget(m).regions;
   std::vector<uint32_t> named_resident;
   std::vector<uint64_t> fresh;
   for (size_t i = 0; i < count; ++i)
   {
-    const uint64_t key = packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]);
+    const uint64_t key = packRegionKey(keys_xyz + 3 * i);
     const auto it = m->region_slots.find(key);
     if (it != m->region_slots.end())
     {
@@ -376,12 +334,9 @@ static int makeRoomForNamedRegions(ohmhip_map_t m, const int16_t *keys_xyz, size
   if (!named_resident.empty())
   {
     // the named regions are in use now: newest stamp, so the eviction below takes others
-    OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * named_resident.size(), false, m->stream));
-    OHMHIP_CHECK(hipMemcpy(m->merge_slots.ptr, named_resident.data(), sizeof(uint32_t) * named_resident.size(),
-                           hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_touch_use_at, dim3(64), dim3(256), 0, m->stream, m->pool.d_last_use,
-                       static_cast<const uint32_t *>(m->merge_slots.ptr), named_resident.size(),
-                       uint32_t(m->batch_seq + 1u));
+    const uint32_t *d_index = nullptr;
+    OHMHIP_CHECK(uploadSlotIndex(m, named_resident.data(), named_resident.size(), m->stream, true, d_index));
+    stampSlotsUsedNow(m, d_index, named_resident.size(), m->stream);
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   }
   return evictColdRegions(m, uint32_t(need), uint32_t(evictable));
@@ -394,9 +349,6 @@ namespace
 /// small kernel per bit pattern behind them.  Returns with everything QUEUED; the caller waits for the copy stream.
 int queueReadmission(ohmhip_map_t m, const std::vector<std::pair<uint32_t, ohmhip_map_s::SpilledRegion>> &back)
 {
-  const size_t rv = size_t(m->mc.region_voxels);
-  const ohmhip_map_s::HostStore &st = m->store;
-  const bool keep_mask = m->config.mode != OHMHIP_MODE_OCCUPANCY;
   constexpr uint32_t kDirtyBits = kDirtySync | kDirtyMerge | kDirtyClearance;
   std::vector<uint32_t> dirty_slots[kDirtyBits + 1];
   std::vector<uint32_t> use_pairs;  // (slot, stamp of the region's last use before it left the pool)
@@ -421,19 +373,7 @@ int queueReadmission(ohmhip_map_t m, const std::vector<std::pair<uint32_t, ohmhi
         m->readmit_periods[m->readmit_period_at++ % 256] = gap;
       }
     }
-    for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
-    {
-      if (m->pool.layers[l])
-      {
-        const size_t stride = rv * kLayerBytes[l];
-        jobs.push_back(CopyJob{ record + st.layer_offset[l], static_cast<char *>(m->pool.layers[l].get()) + stride * slot, stride });
-      }
-    }
-    if (keep_mask)
-    {
-      jobs.push_back(CopyJob{ record + st.mask_offset, reinterpret_cast<char *>(m->pool.d_hit_mask.get()) + st.mask_bytes * slot,
-                              st.mask_bytes });
-    }
+    appendRecordToSlotJobs(m, record, slot, jobs);
     dirty_slots[entry.second.dirty & kDirtyBits].push_back(slot);
   }
   OHMHIP_CHECK(launchCopyJobs(m, jobs, m->copy_stream));
@@ -443,27 +383,24 @@ int queueReadmission(ohmhip_map_t m, const std::vector<std::pair<uint32_t, ohmhi
   OHMHIP_CHECK(hipMemcpy(m->use_scratch.ptr, use_pairs.data(), sizeof(uint32_t) * use_pairs.size(), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_set_prev_use, dim3(64), dim3(256), 0, m->copy_stream, m->pool.d_last_use,
                      static_cast<const uint32_t *>(m->use_scratch.ptr), back.size());
-  // (k_plan may be OR-ing this batch's bits into the same words: atomic ORs, from a persistent index scratch)
-  size_t n_index = 0;
+  // (k_plan may be OR-ing this batch's bits into the same words: atomic ORs, from a persistent index scratch -- the
+  // lists of all bit patterns in one upload, blocking: the vector goes out of scope; a few hundred bytes)
+  std::vector<uint32_t> index;
   for (uint32_t bits = 1; bits <= kDirtyBits; ++bits)
   {
-    n_index += dirty_slots[bits].size();
+    index.insert(index.end(), dirty_slots[bits].begin(), dirty_slots[bits].end());
   }
-  if (n_index)
+  if (!index.empty())
   {
-    OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * n_index, false, m->copy_stream));
-    uint32_t *d_index = static_cast<uint32_t *>(m->merge_slots.ptr);
+    const uint32_t *d_index = nullptr;
+    OHMHIP_CHECK(uploadSlotIndex(m, index.data(), index.size(), m->copy_stream, true, d_index));
     for (uint32_t bits = 1; bits <= kDirtyBits; ++bits)
     {
-      if (dirty_slots[bits].empty())
+      if (!dirty_slots[bits].empty())
       {
-        continue;
+        orSlotBits(m, d_index, dirty_slots[bits].size(), bits, m->copy_stream);
+        d_index += dirty_slots[bits].size();
       }
-      OHMHIP_CHECK(hipMemcpy(d_index, dirty_slots[bits].data(), sizeof(uint32_t) * dirty_slots[bits].size(),
-                             hipMemcpyHostToDevice));  // (blocking: the vector goes out of scope; a few hundred bytes)
-      hipLaunchKernelGGL(k_or_at_u32, dim3(64), dim3(256), 0, m->copy_stream, m->pool.d_dirty, d_index,
-                         dirty_slots[bits].size(), bits);
-      d_index += dirty_slots[bits].size();
     }
   }
   return hipGetLastError();
@@ -517,6 +454,14 @@ static int readmitSpilledSlots(ohmhip_map_t m, uint32_t first_slot, uint32_t end
   return OHMHIP_OK;
 }
 
+/// appendNamedRegions behind the C ABI's exception barrier: readmitSpilledKeys holds store entries that a throw would lose.
+static int appendNamedRegionsNoThrow(ohmhip_map_t m, const int16_t *keys_xyz, size_t count, uint32_t *slots)
+try
+{
+  return appendNamedRegions(m, keys_xyz, count, slots);
+}
+OHMHIP_ABI_CATCH
+
 /// Bring stored regions back for an upload / a caller that wants their slots (ohmhip_map_write_regions,
 /// ohmhip_map_ensure_regions): afterwards the keys are ordinary resident regions.
 static int readmitSpilledKeys(ohmhip_map_t m, const int16_t *keys_xyz, size_t count)
@@ -529,7 +474,7 @@ static int readmitSpilledKeys(ohmhip_map_t m, const int16_t *keys_xyz, size_t co
   std::vector<uint64_t> wanted_packed;
   for (size_t i = 0; i < count; ++i)
   {
-    const uint64_t packed = packRegionKey(keys_xyz[3 * i], keys_xyz[3 * i + 1], keys_xyz[3 * i + 2]);
+    const uint64_t packed = packRegionKey(keys_xyz + 3 * i);
     if (m->spilled.count(packed) && std::find(wanted_packed.begin(), wanted_packed.end(), packed) == wanted_packed.end())
     {
       wanted.insert(wanted.end(), keys_xyz + 3 * i, keys_xyz + 3 * i + 3);
@@ -540,8 +485,8 @@ static int readmitSpilledKeys(ohmhip_map_t m, const int16_t *keys_xyz, size_t co
   {
     return OHMHIP_OK;
   }
-  // Take the entries out of the store while ensure_regions runs (it would otherwise come straight back here); they go
-  // back in if anything fails before their content is in the pool.
+  // Take the entries out of the store while appendNamedRegions runs (it would otherwise come straight back here); they
+  // go back in if anything fails before their content is in the pool.
   std::vector<ohmhip_map_s::SpilledRegion> content(wanted_packed.size());
   for (size_t i = 0; i < content.size(); ++i)
   {
@@ -556,10 +501,12 @@ static int readmitSpilledKeys(ohmhip_map_t m, const int16_t *keys_xyz, size_t co
     }
   };
   std::vector<uint32_t> slots(content.size());
-  int err = ohmhip_map_ensure_regions(m, wanted.data(), content.size(), slots.data());
+  // (not through ohmhip_map_ensure_regions: what that adds -- settling the map, draining the compute stream -- is a
+  // no-op here, the callers have done both)
+  int err = appendNamedRegionsNoThrow(m, wanted.data(), content.size(), slots.data());
   if (err)
   {
-    // ensure_regions created some of the regions fresh before it failed: those must not shadow the stored content
+    // appendNamedRegions created some of the regions fresh before it failed: those must not shadow the stored content
     size_t removed = 0;
     (void)removeResidentRegions(m, wanted.data(), content.size(), &removed);
     putBack();
@@ -582,10 +529,9 @@ static int readmitSpilledKeys(ohmhip_map_t m, const int16_t *keys_xyz, size_t co
   }
   // re-admitted by name: they are in use NOW -- stamp them so the next eviction does not pick them first
   {
-    OHMHIP_CHECK(m->merge_slots.ensure(sizeof(uint32_t) * slots.size(), false, m->stream));
-    OHMHIP_CHECK(hipMemcpy(m->merge_slots.ptr, slots.data(), sizeof(uint32_t) * slots.size(), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_touch_use_at, dim3(64), dim3(256), 0, m->stream, m->pool.d_last_use,
-                       static_cast<const uint32_t *>(m->merge_slots.ptr), slots.size(), uint32_t(m->batch_seq + 1u));
+    const uint32_t *d_index = nullptr;
+    OHMHIP_CHECK(uploadSlotIndex(m, slots.data(), slots.size(), m->stream, true, d_index));
+    stampSlotsUsedNow(m, d_index, slots.size(), m->stream);
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   }
   for (auto &c : content)

@@ -111,7 +111,7 @@ void regionsOfTiles(const MapConst &mc, const std::vector<int16_t> &tiles, std::
   {
     int16_t r[3];
     regionOfTile(mc, &tiles[i], r);
-    if (seen.emplace(packRegionKey(r[0], r[1], r[2]), 1).second)
+    if (seen.emplace(packRegionKey(r), 1).second)
     {
       regions.insert(regions.end(), r, r + 3);
     }
@@ -161,7 +161,7 @@ int tiledListRegions(ohmhip_map_t m, bool dirty_only, int16_t *keys_xyz, size_t 
 
 bool tileExists(ohmhip_map_t m, const int16_t *tile)
 {
-  const uint64_t packed = packRegionKey(tile[0], tile[1], tile[2]);
+  const uint64_t packed = packRegionKey(tile);
   return m->region_slots.find(packed) != m->region_slots.end() || m->spilled.find(packed) != m->spilled.end();
 }
 

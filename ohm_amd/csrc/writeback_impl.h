@@ -75,31 +75,6 @@ void rankForEviction(ohmhip_map_t m, const uint32_t *stamps, uint32_t n, uint32_
   }
 }
 
-/// Copy jobs that move slot `slot`'s block of every layer (+ its replay mask row where that is persistent state) into
-/// store record `record`.
-void appendSlotToRecordJobs(ohmhip_map_t m, uint32_t slot, char *record, std::vector<CopyJob> &jobs)
-{
-  const size_t rv = size_t(m->mc.region_voxels);
-  const ohmhip_map_s::HostStore &st = m->store;
-  for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
-  {
-    if (m->pool.layers[l])
-    {
-      const size_t stride = rv * kLayerBytes[l];
-      jobs.push_back(CopyJob{ static_cast<const char *>(m->pool.layers[l].get()) + stride * slot, record + st.layer_offset[l], stride });
-    }
-  }
-  if (m->config.mode != OHMHIP_MODE_OCCUPANCY)  // (transient in occupancy mode: empty between batches)
-  {
-    jobs.push_back(CopyJob{ reinterpret_cast<const char *>(m->pool.d_hit_mask.get()) + st.mask_bytes * slot, record + st.mask_offset,
-                            st.mask_bytes });
-  }
-  else
-  {
-    std::memset(record + st.mask_offset, 0, st.mask_bytes);
-  }
-}
-
 /// Wait for the write-back copies in flight (they read pool slots and write store records).
 int drainWriteBack(ohmhip_map_t m)
 {
