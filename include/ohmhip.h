@@ -238,7 +238,9 @@ int ohmhip_map_destroy(ohmhip_map_t map);
  * effect from the next batch.  Same here: pass the configuration again; resolution, region dimensions, origin, mode and
  * layer set must equal those of creation (OHMHIP_ERR_INVALID_ARG otherwise), everything else applies to batches
  * presented afterwards.  One exception: the TSDF truncation distance of a map that already holds regions cannot
- * change (OHMHIP_ERR_UNSUPPORTED; free-space TSDF updates are exact only against one truncation distance). */
+ * change (OHMHIP_ERR_UNSUPPORTED; free-space TSDF updates are exact only against one truncation distance).  A change of
+ * the TSDF max_weight or dropoff_epsilon is accepted, as in the reference, and costs one pass over the map's TSDF layer:
+ * which voxels may take free-space visits as counts is re-derived from what the earlier options left in them. */
 int ohmhip_map_update_config(ohmhip_map_t map, const ohmhip_map_config *config);
 
 /* GpuMap::integrateRays (ohmgpu/GpuMap.cpp:416, 540-875): rays = element_count dvec3 (origin, sample pairs).

@@ -522,6 +522,7 @@ struct BatchRun
         // TSDF counts free-space visits only where (min(w + n, max), trunc) is what calculateTsdf gives: integer weights up
         // to kTsdfCountedWeightLimit and no drop-off.  Above that limit the float32 average of a visit just past the
         // margin rounds below trunc and w + 1 stops being exact, so every visit is replayed (tests/test_gpu_tsdf_weights.py).
+        // (What such a batch leaves in voxels the mask does not flag is judged when the option goes: tsdfRebuildMasks.)
         wa.flag_all =
           ((tsdf_mode && (m->mc.tsdf_dropoff > 0 || m->mc.tsdf_max_weight > kTsdfCountedWeightLimit)) || stop_mode) ? 1 : 0;
         wa.inline_hits = occ_inline ? 1 : 0;

@@ -374,6 +374,55 @@ try
 }
 OHMHIP_ABI_CATCH
 
+namespace
+{
+/// TSDF: the "ordered replay" mask of every region the map holds, re-derived from the stored state (tsdfCountable).
+/// An option change needs it: what the earlier options left in a voxel -- the fractional weights of a drop-off or of a
+/// non-integer max_weight -- stays countable under them (or was replayed throughout) and is not under the next ones.
+/// Resident regions by k_rebuild_mask over the committed slots, regions in the host store in their records, whose mask
+/// row moves back into the pool as it is; write-back copies of resident regions carry the old rows and are dropped.
+int tsdfRebuildMasks(ohmhip_map_t m)
+{
+  const float *tsdf = static_cast<const float *>(m->pool.layers[OHMHIP_LID_TSDF].get());
+  if (!tsdf)
+  {
+    return OHMHIP_OK;
+  }
+  dropPrecleaned(m);
+  constexpr uint32_t kSlotsPerLaunch = 32768u;  // (grid y)
+  for (uint32_t first = 0; first < m->slots_committed; first += kSlotsPerLaunch)
+  {
+    const uint32_t n = std::min<uint32_t>(kSlotsPerLaunch, m->slots_committed - first);
+    hipLaunchKernelGGL(k_rebuild_mask, dim3(4, n), dim3(256), 0, m->stream, m->mc, first,
+                       static_cast<const uint32_t *>(nullptr), tsdf, m->pool.d_hit_mask.get());
+  }
+  OHMHIP_CHECK(hipStreamSynchronize(m->stream));
+  OHMHIP_CHECK(hipGetLastError());
+  if (m->spilled.empty())
+  {
+    return OHMHIP_OK;
+  }
+  OHMHIP_CHECK(hipStreamSynchronize(m->copy_stream));
+  const uint32_t voxels = uint32_t(m->mc.region_voxels);
+  for (auto &entry : m->spilled)
+  {
+    const float *state = reinterpret_cast<const float *>(entry.second.record + m->store.layer_offset[OHMHIP_LID_TSDF]);
+    uint32_t *mask = reinterpret_cast<uint32_t *>(entry.second.record + m->store.mask_offset);
+    for (uint32_t w = 0; w < (voxels + 31u) / 32u; ++w)
+    {
+      uint32_t bits = 0;
+      for (uint32_t b = 0; b < 32u && w * 32u + b < voxels; ++b)
+      {
+        const uint32_t vi = w * 32u + b;
+        bits |= tsdfCountable(state[2 * vi], state[2 * vi + 1], m->mc.tsdf_trunc) ? 0u : (1u << b);
+      }
+      mask[w] = bits;
+    }
+  }
+  return OHMHIP_OK;
+}
+}  // namespace
+
 int ohmhip_map_update_config(ohmhip_map_t m, const ohmhip_map_config *config)
 try
 {
@@ -401,13 +450,20 @@ try
     // the truncation distance in force: a new distance on a populated map would be an approximation.
     return OHMHIP_ERR_UNSUPPORTED;
   }
+  // The TSDF options that shape what a free-space visit stores: the voxels they left behind are countable under them
+  // and need not be under the next ones, so the replay mask is re-derived from the stored state (tsdfRebuildMasks).
+  // (The sparsity factor only acts on visits inside the truncation band, which are replayed anyway.)
+  const bool tsdf_weights_change = m->config.mode == OHMHIP_MODE_TSDF &&
+                                   (wanted.tsdf_max_weight != m->config.tsdf_max_weight ||
+                                    wanted.tsdf_dropoff != m->config.tsdf_dropoff) &&
+                                   (m->slots_committed != 0 || !m->spilled.empty());
   const uint64_t gpu_mem_size = m->config.gpu_mem_size;
   const uint32_t region_capacity = m->config.region_capacity;
   m->config = wanted;
   m->config.gpu_mem_size = gpu_mem_size;
   m->config.region_capacity = region_capacity;
   applyValueConfig(m);
-  return OHMHIP_OK;
+  return tsdf_weights_change ? tsdfRebuildMasks(m) : OHMHIP_OK;
 }
 OHMHIP_ABI_CATCH
 

@@ -435,10 +435,30 @@ __global__ void __launch_bounds__(256) k_batch_reset(BatchScratch bs, uint32_t n
 /// sdf >= kTsdfFreeMargin * trunc leaves a (weight, trunc) voxel at (min(weight + 1, max), trunc) exactly, including
 /// float rounding of (sdf + trunc * w) / (w + 1) for w <= 1e4 (needs > 2e-3 relative margin; 1 % is used).
 constexpr float kTsdfFreeMargin = 1.01f;
-/// The weights that argument covers.  A map whose max_weight lies above it replays every visit (batch_run.h), and an
-/// uploaded voxel whose weight lies above it, or is no integer (n unit increments are then n roundings, w + float(n)
-/// one), is flagged for the ordered replay by k_rebuild_mask.
+/// The weights that argument covers.  A map whose max_weight lies above it replays every visit (batch_run.h), and a
+/// stored voxel whose state tsdfCountable() does not cover is flagged for the ordered replay by k_rebuild_mask.
 constexpr float kTsdfCountedWeightLimit = 1e4f;
+
+/// The stored states on which n free-space visits are (min(w + float(n), max_weight), trunc), as calculateTsdf gives
+/// them one by one (tests/tsdf_ref.py counted()):
+///   - never observed: weight 0 with distance 0, either zero of either sign (the first visit stores (1, trunc));
+///   - an integer weight in [1, kTsdfCountedWeightLimit] at exactly the truncation distance in force.
+/// Everything else takes the ordered replay.  That is: a distance off trunc; a weight above the limit (the float32
+/// average of a visit just past the margin rounds below trunc from w ~ 7e5, w + 1 == w from 2^24); a fraction, as a
+/// drop-off or a non-integer max_weight leaves behind (n unit increments are n roundings, w + float(n) is one); a
+/// negative weight (w + 1 lands in calculateTsdf's near-zero band at -1, where nothing is written, and below it the
+/// average moves the distance off trunc); NaN and the infinities.  (weight 0 at a distance other than 0 is replayed
+/// too: the first visit would be exact, but such a voxel is not "never observed" and nothing is gained by telling.)
+/// A function of the stored state and the truncation distance alone, so the mask can be re-derived at any time: after
+/// an upload, and for every region of the map when an option that shapes stored weights changes (tsdfRebuildMasks).
+__host__ __device__ inline bool tsdfCountable(float wgt, float dist, float trunc)
+{
+  if (wgt == 0.0f)
+  {
+    return dist == 0.0f;
+  }
+  return dist == trunc && wgt >= 1.0f && wgt <= kTsdfCountedWeightLimit && wgt == truncf(wgt);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // kRfStopOnFirstOccupied (ohm/RayFlag.h:28; ohm/RayMapperOccupancy.cpp:105-193, 222-239).
@@ -691,13 +711,14 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-/// Rebuild the persistent "ordered replay" voxel mask of one region from its stored layers (after a CPU upload):
-/// NDT: voxels holding samples (mean.count > 0); TSDF: observed voxels whose distance is not the free-space value or
-/// whose weight the counting shortcut does not cover (kTsdfCountedWeightLimit).
+/// Rebuild the persistent "ordered replay" voxel mask of the regions in slots first_slot + blockIdx.y from their stored
+/// layers (after a CPU upload; for every slot after a TSDF option change): NDT: voxels holding samples
+/// (mean.count > 0); TSDF: every voxel whose state the counting shortcut does not cover (tsdfCountable).
 __global__ void __launch_bounds__(256)
-  k_rebuild_mask(MapConst mc, uint32_t slot, const uint32_t *__restrict__ mean_layer,
+  k_rebuild_mask(MapConst mc, uint32_t first_slot, const uint32_t *__restrict__ mean_layer,
                  const float *__restrict__ tsdf_layer, uint32_t *__restrict__ hit_mask)
 {
+  const uint32_t slot = first_slot + blockIdx.y;
   const uint32_t mask_words = uint32_t(mc.region_voxels + 31) >> 5;
   const size_t base = size_t(slot) * size_t(mc.region_voxels);
   for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < mask_words; w += gridDim.x * blockDim.x)
@@ -715,10 +736,7 @@ __global__ void __launch_bounds__(256)
         }
         if (tsdf_layer)
         {
-          const float wgt = tsdf_layer[2 * (base + vi)];
-          const float dist = tsdf_layer[2 * (base + vi) + 1];
-          flag = flag || (wgt != 0.0f && dist != mc.tsdf_trunc) || (wgt == 0.0f && dist != 0.0f);
-          flag = flag || wgt > kTsdfCountedWeightLimit || wgt != truncf(wgt);
+          flag = flag || !tsdfCountable(tsdf_layer[2 * (base + vi)], tsdf_layer[2 * (base + vi) + 1], mc.tsdf_trunc);
         }
         bits |= flag ? (1u << b) : 0u;
       }
