@@ -156,20 +156,17 @@ struct BatchRun
     // (small batches -- 128-ray workgroups -- run the instantiation with the small LDS table: more workgroups per CU)
     // tev[1], the kernel's own stop event, is what the next batch's set-up pass waits for (see map_state.h: a stop event
     // costs nothing, an event record behind the kernel would idle the queue for microseconds).
-    if (bin_tab_mask < kLtabSmall)
-    {
-      hipExtLaunchKernelGGL(k_ray_bin<kLtabSmall>, dim3(bin_blocks), dim3(bin_threads), 0, s, nullptr, tev[1], 0, m->mc,
-                            regionTable(m), batchScratch(m), static_cast<const RayWalk *>(batchWalks(m).ptr), n_rays,
-                            static_cast<Segment *>(m->segments.ptr), seg_capacity, hit_keys, m->pool.d_hit_mask.get(), ray_shift,
-                            bucket ? 1 : 0, bin_rays_per_block, bin_tab_mask);
-    }
-    else
-    {
-      hipExtLaunchKernelGGL(k_ray_bin<kLtabSize>, dim3(bin_blocks), dim3(bin_threads), 0, s, nullptr, tev[1], 0, m->mc,
-                            regionTable(m), batchScratch(m), static_cast<const RayWalk *>(batchWalks(m).ptr), n_rays,
-                            static_cast<Segment *>(m->segments.ptr), seg_capacity, hit_keys, m->pool.d_hit_mask.get(), ray_shift,
-                            bucket ? 1 : 0, bin_rays_per_block, bin_tab_mask);
-    }
+    // (a map that is not partitioned and whose region edges are powers of two -- the default -- runs the instantiation
+    // without the ownership test and the floor-modulo coordinates in its per-segment loop)
+    const auto pow2 = [](int v) { return (v & (v - 1)) == 0; };
+    const bool plain = m->mc.owner_world <= 1u && pow2(m->mc.dim[0]) && pow2(m->mc.dim[1]) && pow2(m->mc.dim[2]);
+    const bool small = bin_tab_mask < kLtabSmall;
+    const auto kernel = small ? (plain ? k_ray_bin<kLtabSmall, true> : k_ray_bin<kLtabSmall, false>) :
+                                (plain ? k_ray_bin<kLtabSize, true> : k_ray_bin<kLtabSize, false>);
+    hipExtLaunchKernelGGL(kernel, dim3(bin_blocks), dim3(bin_threads), 0, s, nullptr, tev[1], 0, m->mc, regionTable(m),
+                          batchScratch(m), static_cast<const RayWalk *>(batchWalks(m).ptr), n_rays,
+                          static_cast<Segment *>(m->segments.ptr), seg_capacity, hit_keys, m->pool.d_hit_mask.get(), ray_shift,
+                          bucket ? 1 : 0, bin_rays_per_block, bin_tab_mask);
     mark(1);
     m->tev_pre_walk[ring] = 1;
     m->bin_done_event = tev[1];

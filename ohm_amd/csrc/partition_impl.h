@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(kRouteThreads)
       // every region the walk touches, whoever owns it (the enumeration's own ownership filter switched off)
       MapConst all = mc;
       all.owner_world = 0;
-      forEachSegment(all, rw, false, [&](uint64_t key, const SegmentEntry &) { mask |= 1ull << regionOwnerOf(mc, key); });
+      forEachSegment(all, rw, [&](uint64_t key) { mask |= 1ull << regionOwnerOf(mc, key); });
       if (rw.flags & kRwApplySample)
       {
         uint64_t key;

@@ -45,8 +45,10 @@ __device__ inline void regionCursorInit(const MapConst &mc, const RayWalk &rw, R
 }
 
 /// Advance to the next region crossing.  Returns false when the ray crosses no further region boundary.
-/// On success `axis`/`j` identify the step which enters the new region and rc.region is updated.
-__device__ inline bool regionCursorNext(const MapConst &mc, const RayWalk &rw, RegionCursor &rc, int &axis, int &j)
+/// On success `axis`/`j` identify the step which enters the new region, `t_entry` is that step's time -- stepTime() of the
+/// winning axis, the value the merge has just compared -- and rc.region is updated.
+__device__ inline bool regionCursorNext(const MapConst &mc, const RayWalk &rw, RegionCursor &rc, int &axis, int &j,
+                                        double &t_entry)
 {
   int best = -1;
   double best_t = 0;
@@ -68,6 +70,7 @@ __device__ inline bool regionCursorNext(const MapConst &mc, const RayWalk &rw, R
     return false;
   }
   axis = best;
+  t_entry = best_t;
   j = sel3(best, rc.next_j[0], rc.next_j[1], rc.next_j[2]);
   // Per-axis updates spelled out: a run-time index here would push the cursor into scratch memory.
   if (best == 0)
@@ -89,15 +92,13 @@ __device__ inline bool regionCursorNext(const MapConst &mc, const RayWalk &rw, R
 }
 
 /// Is the voxel reached by step (axis, j) the ray's end voxel?  (All three axes exhausted.)  True only when j is the
-/// last step on its axis and every step of the other axes precedes it.
-__device__ inline bool stepReachesEnd(const RayWalk &rw, int axis, int j)
+/// last step on its axis and every step of the other axes precedes it.  `ta` is the step's time.
+__device__ inline bool stepReachesEnd(const RayWalk &rw, int axis, int j, double ta)
 {
   if (j != sel3(axis, rw.total[0], rw.total[1], rw.total[2]))
   {
     return false;
   }
-  const double ta =
-    stepTime(sel3(axis, rw.init[0], rw.init[1], rw.init[2]), sel3(axis, rw.delta[0], rw.delta[1], rw.delta[2]), j);
   bool all_before = true;
 #pragma unroll
   for (int b = 0; b < 3; ++b)
@@ -111,29 +112,29 @@ __device__ inline bool stepReachesEnd(const RayWalk &rw, int axis, int j)
   return all_before;
 }
 
-/// Where a ray enters a region and how much of it lies inside (forEachSegment with resume state).
-struct SegmentEntry
+/// ... for a caller that has not got the step's time at hand: computed only where the step is its axis' last.  (The
+/// counting passes: with the time handed through their loop k_ray_setup's and k_route_mask's register allocation moves,
+/// k_route_mask's across an occupancy step.)
+__device__ inline bool stepReachesEnd(const RayWalk &rw, int axis, int j)
 {
-  uint32_t k0 = 0, k1 = 0, k2 = 0;  ///< steps taken per axis at the moment the region is entered
-  uint32_t count = 0;               ///< voxels the ray visits inside the region
-  double t_base = 0;                ///< time of the step that enters the region (0 for the ray's first segment)
-  bool first = false;               ///< the segment starts at the ray's origin voxel
-  bool end = false;                 ///< the segment's last voxel is the ray's end voxel (visited as part of the ray)
-};
+  if (j != sel3(axis, rw.total[0], rw.total[1], rw.total[2]))
+  {
+    return false;
+  }
+  return stepReachesEnd(rw, axis, j, stepTime(sel3(axis, rw.init[0], rw.init[1], rw.init[2]),
+                                              sel3(axis, rw.delta[0], rw.delta[1], rw.delta[2]), j));
+}
 
-/// Walk the regions a ray crosses and call emit(region key, entry) for every ray-region segment which produces at
-/// least one voxel visit.  With `with_resume_state` the entry is filled in: the per-axis step counts at the moment the
-/// region is entered, the time of the entering step, the first / end flags and the number of voxels visited in the
-/// region; otherwise it is empty (the counting passes only need the keys).  Segments in regions another replica owns
-/// (MapConst::owner_world > 1) are skipped: every segment carries its own resume state, so dropping some of a ray's
-/// segments does not change what the others do.
+/// Walk the regions a ray crosses and call emit(region key) for every ray-region segment which produces at least one
+/// voxel visit: what the counting passes need (k_ray_bin enumerates the same segments with forEachBinSegment, which
+/// also builds their records).  Segments in regions another replica owns (MapConst::owner_world > 1) are skipped.
 template <typename F>
-__device__ inline void forEachSegment(const MapConst &mc, const RayWalk &rw, bool with_resume_state, F emit)
+__device__ inline void forEachSegment(const MapConst &mc, const RayWalk &rw, F emit)
 {
-  auto f = [&](uint64_t key, const SegmentEntry &entry) {
+  auto f = [&](uint64_t key) {
     if (ownsRegion(mc, key))
     {
-      emit(key, entry);
+      emit(key);
     }
   };
   if (!(rw.flags & kRwValid) || !(rw.flags & kRwWalk))
@@ -144,68 +145,20 @@ __device__ inline void forEachSegment(const MapConst &mc, const RayWalk &rw, boo
   const bool include_end = (rw.flags & kRwIncludeEnd) != 0;
   RegionCursor rc;
   regionCursorInit(mc, rw, rc);
-  // A segment's voxel count is known once the NEXT region entry is: emission trails the enumeration by one.
-  bool have = false;
-  uint64_t p_key = 0;
-  SegmentEntry p;
-  int p_sum = 0;
   if (manhattan > 0 || include_end)
   {
-    p_key = packRegionKey(rc.region[0], rc.region[1], rc.region[2]);
-    p.first = true;
-    have = true;
-    if (!with_resume_state)
-    {
-      f(p_key, p);
-    }
-  }
-  // Reciprocals of the step deltas for the step-count estimates (one division per axis per ray, not per crossing).
-  double r0 = 0, r1 = 0, r2 = 0;
-  if (with_resume_state)
-  {
-    r0 = 1.0 / rw.delta[0];
-    r1 = 1.0 / rw.delta[1];
-    r2 = 1.0 / rw.delta[2];
+    f(packRegionKey(rc.region[0], rc.region[1], rc.region[2]));
   }
   int axis, j;
-  while (regionCursorNext(mc, rw, rc, axis, j))
+  double ta;
+  while (regionCursorNext(mc, rw, rc, axis, j, ta))
   {
     // Entering a region at the ray's end voxel only produces work when the end voxel is part of the ray.
     if (stepReachesEnd(rw, axis, j) && !include_end)
     {
       continue;
     }
-    const uint64_t key = packRegionKey(rc.region[0], rc.region[1], rc.region[2]);
-    if (!with_resume_state)
-    {
-      f(key, p);
-      continue;
-    }
-    const double ta = stepTime(sel3(axis, rw.init[0], rw.init[1], rw.init[2]),
-                               sel3(axis, rw.delta[0], rw.delta[1], rw.delta[2]), j);
-    const uint32_t rs0 = uint32_t((axis == 0) ? j : stepsBefore(rw.init[0], rw.delta[0], r0, rw.total[0], 0, axis, ta));
-    const uint32_t rs1 = uint32_t((axis == 1) ? j : stepsBefore(rw.init[1], rw.delta[1], r1, rw.total[1], 1, axis, ta));
-    const uint32_t rs2 = uint32_t((axis == 2) ? j : stepsBefore(rw.init[2], rw.delta[2], r2, rw.total[2], 2, axis, ta));
-    const int sum = int(rs0 + rs1 + rs2);
-    if (have)
-    {
-      p.count = uint32_t(sum - p_sum);
-      f(p_key, p);
-    }
-    p_key = key;
-    p.k0 = rs0;
-    p.k1 = rs1;
-    p.k2 = rs2;
-    p.t_base = ta;
-    p.first = false;
-    p_sum = sum;
-    have = true;
-  }
-  if (have && with_resume_state)
-  {
-    p.count = uint32_t(manhattan - p_sum) + (include_end ? 1u : 0u);
-    p.end = include_end;
-    f(p_key, p);
+    f(packRegionKey(rc.region[0], rc.region[1], rc.region[2]));
   }
 }
 
@@ -256,50 +209,161 @@ __device__ inline RayFix rayFix(const MapConst &mc, const RayWalk &rw)
   return rf;
 }
 
-/// Fixed-point time of the next step along one axis at a region entry (see Segment).  Returns false when the value
-/// cannot be represented safely (negative or non-finite): the segment is then poisoned.
-__device__ inline bool fixTime(const MapConst &mc, double init, double delta, int total, uint32_t k, double t_base,
-                               uint32_t &f)
+/// Fixed-point time of the next step along one axis at a region entry (see Segment): the axis has taken k steps and the
+/// region is entered at t_base.  An axis without steps left gives kFixFar -- time_next = inf
+/// (ohm/LineWalkCompute.h:299-301) -- and `live` false.  `ok` is cleared when the value cannot be represented safely
+/// (negative or non-finite): the segment is then poisoned.
+__device__ inline uint32_t fixTime(const MapConst &mc, double init, double delta, int total, uint32_t k, double t_base,
+                                   bool &live, bool &ok)
 {
-  if (int(k) >= total)
-  {
-    f = kFixFar;  // no steps left on this axis: time_next = inf (ohm/LineWalkCompute.h:299-301)
-    return true;
-  }
+  live = int(k) < total;
   const double t = (k == 0) ? init : init + delta * double(k);
   const double x = (t - t_base) * mc.fix_scale;
-  const bool ok = x > -1.0;  // (false for NaN; (-1, 0) quantises to 0, still within one unit of the true time)
-  f = !(x >= 1.0) ? 0u : ((x >= double(kFixFar)) ? kFixFar : uint32_t(x));
-  return ok;
+  ok = ok && (!live || x > -1.0);  // (false for NaN; (-1, 0) quantises to 0, still within one unit of the true time)
+  const uint32_t f = !(x >= 1.0) ? 0u : ((x >= double(kFixFar)) ? kFixFar : uint32_t(x));
+  return live ? f : kFixFar;
 }
 
-/// Build the walk kernel's record of one ray-region segment.
-__device__ inline Segment makeSegment(const MapConst &mc, const RayWalk &rw, const RayFix &rf, uint32_t ray,
-                                      const SegmentEntry &en)
+/// The walk kernel's record of the ray-region segment a ray starts when it has taken k0, k1, k2 steps along the axes at
+/// time t_base: everything but the voxel count and the ray word.  kPlain: every region edge is a power of two (see
+/// k_ray_bin).
+template <bool kPlain>
+__device__ inline void segmentHead(const MapConst &mc, const RayWalk &rw, const RayFix &rf, const RegionCursor &rc,
+                                   uint32_t k0, uint32_t k1, uint32_t k2, double t_base, Segment &sg)
 {
-  Segment sg;
   bool ok = !rf.poison;
-  ok = fixTime(mc, rw.init[0], rw.delta[0], rw.total[0], en.k0, en.t_base, sg.f[0]) && ok;
-  ok = fixTime(mc, rw.init[1], rw.delta[1], rw.total[1], en.k1, en.t_base, sg.f[1]) && ok;
-  ok = fixTime(mc, rw.init[2], rw.delta[2], rw.total[2], en.k2, en.t_base, sg.f[2]) && ok;
-  // An axis without steps left never moves: its delta is irrelevant, zero keeps the candidate at kFixFar.
-  sg.e[0] = (int(en.k0) < rw.total[0]) ? rf.e0 : (rf.e0 & kSegNegative);
-  sg.e[1] = (int(en.k1) < rw.total[1]) ? rf.e1 : (rf.e1 & kSegNegative);
-  sg.e[2] = (int(en.k2) < rw.total[2]) ? rf.e2 : (rf.e2 & kSegNegative);
-  if (!ok)
+  bool live0, live1, live2;
+  const uint32_t f0 = fixTime(mc, rw.init[0], rw.delta[0], rw.total[0], k0, t_base, live0, ok);
+  const uint32_t f1 = fixTime(mc, rw.init[1], rw.delta[1], rw.total[1], k1, t_base, live1, ok);
+  const uint32_t f2 = fixTime(mc, rw.init[2], rw.delta[2], rw.total[2], k2, t_base, live2, ok);
+  // A poisoned record is all zeros but for the directions.  An axis without steps left never moves: its delta is
+  // irrelevant, zero keeps the candidate at kFixFar.
+  sg.f[0] = ok ? f0 : 0u;
+  sg.f[1] = ok ? f1 : 0u;
+  sg.f[2] = ok ? f2 : 0u;
+  sg.e[0] = (ok && live0) ? rf.e0 : (rf.e0 & kSegNegative);
+  sg.e[1] = (ok && live1) ? rf.e1 : (rf.e1 & kSegNegative);
+  sg.e[2] = (ok && live2) ? rf.e2 : (rf.e2 & kSegNegative);
+  // The voxel the segment starts in: k steps from the ray's first along the axis' direction (dir = +-1, so g0 + dir * k
+  // without the multiplication: dir >> 1 is 0 or -1, and (k ^ -1) - -1 = -k).
+  auto local = [&](int g0, int dir, uint32_t k, int dim) {
+    const int g = g0 + ((int(k) ^ (dir >> 1)) - (dir >> 1));
+    return kPlain ? (g & (dim - 1)) : localCoord(g, dim);
+  };
+  const int l0 = local(rw.g0[0], rc.dir[0], k0, mc.dim[0]);
+  const int l1 = local(rw.g0[1], rc.dir[1], k1, mc.dim[1]);
+  const int l2 = local(rw.g0[2], rc.dir[2], k2, mc.dim[2]);
+  sg.vox = uint32_t(l0 + l1 * mc.dim[0] + l2 * mc.dim[0] * mc.dim[1]);
+}
+
+/// stepsBefore()'s arithmetic route for the binning pass, which asks for the two other axes at every region crossing.
+/// `fast` holds the tests of that route which depend on the ray and the axis alone -- total != 0, a positive finite
+/// delta, |init| <= 4 delta: forEachBinSegment evaluates them once per ray -- so that only the tests on x are left per
+/// crossing.  Returns false when the count has to come from stepsBefore() itself.  x < 0 <=> floor(x) + 1 <= 0, so one
+/// clamp to [0, total] is stepsBefore's  (x < 0) ? 0 : min(count, total); it also gives the 0 of an axis without steps,
+/// whatever x is there.
+__device__ inline bool stepsBeforeQuick(double init, double rdelta, int total, bool fast, double ta, int &n)
+{
+  const double x = (ta - init) * rdelta;
+  const double whole = floor(x);
+  const double frac = x - whole;
+  n = min(max(int(whole) + 1, 0), total);
+  return fast && frac > 1e-5 && frac < 1.0 - 1e-5 && fabs(x) < 1048576.0;
+}
+
+/// Walk the regions a ray crosses as forEachSegment does and call emit(region key, record) with the walk kernel's
+/// record of every ray-region segment: the fixed-point predictor at the moment the region is entered, the first voxel,
+/// the number of voxels visited in the region and the ray word with its first / end flags.  Every segment carries its
+/// own resume state, so dropping the segments of regions another replica owns does not change what the others do.
+///
+/// A record is built when its region is entered and emitted when the NEXT entry tells how many voxels it holds:
+/// emission trails the enumeration by one.  kPlain: the map is not partitioned and its region edges are powers of two
+/// (see k_ray_bin).
+template <bool kPlain, typename F>
+__device__ inline void forEachBinSegment(const MapConst &mc, const RayWalk &rw, const RayFix &rf, uint32_t ray, F emit)
+{
+  if (!(rw.flags & kRwValid) || !(rw.flags & kRwWalk))
   {
-    sg.f[0] = sg.f[1] = sg.f[2] = 0;
-    sg.e[0] &= kSegNegative;
-    sg.e[1] &= kSegNegative;
-    sg.e[2] &= kSegNegative;
+    return;
   }
-  const int l0 = localCoord(rw.g0[0] + rwDir(rw, 0) * int(en.k0), mc.dim[0]);
-  const int l1 = localCoord(rw.g0[1] + rwDir(rw, 1) * int(en.k1), mc.dim[1]);
-  const int l2 = localCoord(rw.g0[2] + rwDir(rw, 2) * int(en.k2), mc.dim[2]);
-  const uint32_t vi = uint32_t(l0 + l1 * mc.dim[0] + l2 * mc.dim[0] * mc.dim[1]);
-  sg.vox = vi | (en.count << kSegVoxelBits);
-  sg.ray = ray | ((en.first && (rw.flags & kRwExcludeStart)) ? kSegSkipFirst : 0u) | (en.end ? kSegEnd : 0u);
-  return sg;
+  const int manhattan = rw.total[0] + rw.total[1] + rw.total[2];
+  const bool include_end = (rw.flags & kRwIncludeEnd) != 0;
+  if (manhattan == 0 && !include_end)
+  {
+    return;  // no voxel visited, and no region crossing either
+  }
+  const bool all_mine = kPlain || mc.owner_world <= 1u;  // (a map that is not partitioned: no test per segment)
+  auto f = [&](uint64_t key, const Segment &sg) {
+    if (all_mine || ownsRegion(mc, key))
+    {
+      emit(key, sg);
+    }
+  };
+  RegionCursor rc;
+  regionCursorInit(mc, rw, rc);
+  // Reciprocals of the step deltas for the step-count estimates (one division per axis per ray, not per crossing), and
+  // per axis whether stepsBefore's arithmetic route is open to the ray at all.
+  const double r0 = 1.0 / rw.delta[0];
+  const double r1 = 1.0 / rw.delta[1];
+  const double r2 = 1.0 / rw.delta[2];
+  bool fast[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+  {
+    fast[a] = rw.total[a] != 0 && rw.delta[a] > 0 && rw.delta[a] < dInf() && fabs(rw.init[a]) <= 4.0 * rw.delta[a];
+  }
+  // The ray's first segment starts in its origin voxel at time 0.
+  uint64_t p_key = packRegionKey(rc.region[0], rc.region[1], rc.region[2]);
+  Segment p;
+  segmentHead<kPlain>(mc, rw, rf, rc, 0u, 0u, 0u, 0.0, p);
+  p.ray = ray | ((rw.flags & kRwExcludeStart) ? kSegSkipFirst : 0u);
+  int p_sum = 0;
+  int axis, j;
+  double ta;
+    while (regionCursorNext(mc, rw, rc, axis, j, ta))
+  {
+    // Entering a region at the ray's end voxel only produces work when the end voxel is part of the ray.
+    if (stepReachesEnd(rw, axis, j, ta) && !include_end)
+    {
+      continue;
+    }
+    const uint64_t key = packRegionKey(rc.region[0], rc.region[1], rc.region[2]);
+    // Steps taken along each axis when the region is entered: j on the entering axis, stepsBefore() on the others.  All
+    // three quick estimates run in straight-line code (the lanes of a wave enter on different axes); the few counts they
+    // cannot vouch for -- x within 1e-5 of a whole number, degenerate deltas -- come from stepsBefore() itself.
+    int n0, n1, n2;
+    const bool exact0 = !stepsBeforeQuick(rw.init[0], r0, rw.total[0], fast[0], ta, n0) && rw.total[0] != 0 && axis != 0;
+    const bool exact1 = !stepsBeforeQuick(rw.init[1], r1, rw.total[1], fast[1], ta, n1) && rw.total[1] != 0 && axis != 1;
+    const bool exact2 = !stepsBeforeQuick(rw.init[2], r2, rw.total[2], fast[2], ta, n2) && rw.total[2] != 0 && axis != 2;
+    if (exact0 || exact1 || exact2)
+    {
+#pragma unroll 1
+      for (int b = 0; b < 3; ++b)
+      {
+        if (sel3(b, exact0, exact1, exact2))
+        {
+          const int n = stepsBefore(sel3(b, rw.init[0], rw.init[1], rw.init[2]), sel3(b, rw.delta[0], rw.delta[1], rw.delta[2]),
+                                    sel3(b, r0, r1, r2), sel3(b, rw.total[0], rw.total[1], rw.total[2]), b, axis, ta);
+          n0 = (b == 0) ? n : n0;
+          n1 = (b == 1) ? n : n1;
+          n2 = (b == 2) ? n : n2;
+        }
+      }
+    }
+    n0 = (axis == 0) ? j : n0;
+    n1 = (axis == 1) ? j : n1;
+    n2 = (axis == 2) ? j : n2;
+    const int sum = n0 + n1 + n2;
+    p.vox |= uint32_t(sum - p_sum) << kSegVoxelBits;
+    f(p_key, p);
+    p_key = key;
+    segmentHead<kPlain>(mc, rw, rf, rc, uint32_t(n0), uint32_t(n1), uint32_t(n2), ta, p);
+    p.ray = ray;
+    p_sum = sum;
+  }
+  p.vox |= (uint32_t(manhattan - p_sum) + (include_end ? 1u : 0u)) << kSegVoxelBits;
+  p.ray |= include_end ? kSegEnd : 0u;
+  f(p_key, p);
 }
 
 /// Region / voxel of the ray's sample (end) voxel.
@@ -320,7 +384,9 @@ __device__ inline void sampleVoxel(const MapConst &mc, const RayWalk &rw, uint64
 // runs as long as its longest ray: with rays in arrival order (a lidar's beams have unrelated ranges) a third of the
 // lane slots idle.  The workgroup therefore visits its rays by descending extent (counting sort on the ray's Manhattan
 // extent in regions, 64 bins, positions in LDS): the rays of one wave then cross about the same number of regions.
-// The order is irrelevant to the result -- segment records and sample keys carry the ray index.
+// The order is irrelevant to the result -- segment records and sample keys carry the ray index.  (The bins are read out
+// of the RayWalk records, a strided pass over all of them ahead of the loop that loads them whole.  A byte per ray
+// written by k_ray_setup instead was measured: the binning pass got 5 us SLOWER -- profiles/r07_notes.md.)
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t kRayOrderBins = 64;
 
@@ -460,7 +526,7 @@ __global__ void __launch_bounds__(kBinThreads) __attribute__((amdgpu_waves_per_e
     }
     my_visits += (rw.flags & kRwApplySample) ? 1u : 0u;
 
-    forEachSegment(mc, rw, false, [&](uint64_t key, const SegmentEntry &) {
+    forEachSegment(mc, rw, [&](uint64_t key) {
       const uint32_t e = ltabFindOrInsert(tab, key, tab_mask);
       if (e < kLtabSize)
       {
@@ -841,8 +907,13 @@ __global__ void __launch_bounds__(1024)
 // k_ray_bin: scatter segments to region buckets, emit sample sort keys, set the per-region sample bitmask.
 // Three steps per workgroup: count its segments per region in LDS, reserve one contiguous range per region with a
 // single returning atomic, then re-enumerate and scatter through LDS cursors.
+//
+// kPlain: the instantiation for a map that is not partitioned (owner_world <= 1) and whose region edges are all powers
+// of two -- the default map.  Both are known when the batch is launched (BatchRun::launchBin); the kernel then carries
+// neither the ownership test nor the floor-modulo alternative of the local voxel coordinates through its
+// per-segment loop.  The other instantiation takes every map.
 // ---------------------------------------------------------------------------------------------------------------------
-template <uint32_t kTab>
+template <uint32_t kTab, bool kPlain>
 __global__ void __launch_bounds__(kBinThreads)
   k_ray_bin(MapConst mc, RegionTable rt, BatchScratch bs, const RayWalk *__restrict__ walks, uint32_t n_rays,
             Segment *__restrict__ segments, uint32_t segment_capacity, unsigned long long *__restrict__ hit_keys,
@@ -947,7 +1018,7 @@ __global__ void __launch_bounds__(kBinThreads)
     const RayWalk rw = walks[ray];
     emitSample(ray, rw);  // (the ray's record is loaded once for both its sample key and its segments)
     const RayFix rf = rayFix(mc, rw);
-    forEachSegment(mc, rw, true, [&](uint64_t key, const SegmentEntry &entry) {
+    forEachBinSegment<kPlain>(mc, rw, rf, ray, [&](uint64_t key, const Segment &sg) {
       const uint32_t e = ltabFind(tab, key, tab_mask);
       uint32_t pos;
       if (e < kLtabSize)
@@ -965,7 +1036,7 @@ __global__ void __launch_bounds__(kBinThreads)
       }
       if (pos < segment_capacity)
       {
-        segments[pos] = makeSegment(mc, rw, rf, ray, entry);
+        segments[pos] = sg;
       }
     });
   }
