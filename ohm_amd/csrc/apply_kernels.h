@@ -184,7 +184,8 @@ __device__ inline void applyCounts(uint32_t region_index, const MapConst &mc, co
         o.z = n.z ? occMissN(mc, ray_flags, o.z, n.z) : o.z;
         o.w = n.w ? occMissN(mc, ray_flags, o.w, n.w) : o.w;
         // (voxels at their clamp do not move: a settled map's free space needs no log-odds write)
-        const bool moved = o.x != before.x || o.y != before.y || o.z != before.z || o.w != before.w;
+        const bool moved = !sameValue(o.x, before.x) || !sameValue(o.y, before.y) || !sameValue(o.z, before.z) ||
+                           !sameValue(o.w, before.w);
         if (preserve_masked && bits)
         {
           // A masked voxel's log-odds and count belong to applyHits, which may be at work on them right now: only the
@@ -359,10 +360,10 @@ __global__ void __launch_bounds__(256)
         // hands right now)
         float *o1 = occupancy + base + 4 * q;
         uint32_t *c1 = miss_counts + base + 4 * q;
-        if (n.x) { if (o.x != before.x) { o1[0] = o.x; } c1[0] = 0; }
-        if (n.y) { if (o.y != before.y) { o1[1] = o.y; } c1[1] = 0; }
-        if (n.z) { if (o.z != before.z) { o1[2] = o.z; } c1[2] = 0; }
-        if (n.w) { if (o.w != before.w) { o1[3] = o.w; } c1[3] = 0; }
+        if (n.x) { if (!sameValue(o.x, before.x)) { o1[0] = o.x; } c1[0] = 0; }
+        if (n.y) { if (!sameValue(o.y, before.y)) { o1[1] = o.y; } c1[1] = 0; }
+        if (n.z) { if (!sameValue(o.z, before.z)) { o1[2] = o.z; } c1[2] = 0; }
+        if (n.w) { if (!sameValue(o.w, before.w)) { o1[3] = o.w; } c1[3] = 0; }
       }
     }
     return;

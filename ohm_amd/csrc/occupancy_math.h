@@ -21,6 +21,14 @@ __device__ inline float fInf()
   return __int_as_float(0x7f800000);
 }
 
+/// Whether two log-odds are the same stored value.  The write guards of the apply kernels ask this, not ==: the CPU
+/// mapper stores every result, so a -0.0 that receives a zero adjustment (an excluding flag, a saturated voxel, a miss
+/// probability of 0.5) becomes +0.0 -- equal to what was there, and another value.
+__device__ inline bool sameValue(float a, float b)
+{
+  return __float_as_uint(a) == __float_as_uint(b);
+}
+
 /// One miss: ohm/RayMapperOccupancy.cpp:143-163 + ohm/VoxelOccupancyCompute.h:110-120 (null_update == false).
 __device__ inline float occMiss(const MapConst &mc, unsigned ray_flags, float initial)
 {
@@ -53,8 +61,19 @@ __device__ inline float occHit(const MapConst &mc, unsigned ray_flags, float ini
   return (base != inf) ? fminf(base + adj, mc.max_value) : base;
 }
 
+/// A null update (ohm/VoxelOccupancyCompute.h:110-120 with null_update == true): what a ray stopped by
+/// kRfStopOnFirstOccupied gives the voxels behind its stop.  Not the identity: base + 0.0f and the min clamp still run, so
+/// a value below min, a NaN and -inf become min and -0.0 becomes +0.0.
+__device__ inline float occNullMiss(const MapConst &mc, float initial)
+{
+  return (initial != fInf()) ? fmaxf(mc.min_value, initial + 0.0f) : initial;
+}
+
 /// n sequential misses.  The update is a deterministic function of the value alone, so once it reaches a fixed point
-/// (the min clamp) the remaining applications are the identity and can be skipped without changing the result.
+/// (the min clamp) the remaining applications are the identity and can be skipped without changing the result.  The exit
+/// returns the update's OUTPUT: nx == x holds for the same value and for (x, nx) = (-0.0, +0.0), a -0.0 that received a
+/// zero adjustment -- there the CPU mapper has stored +0.0, and +0.0 is a fixed point (the update never tells the two
+/// zeros apart, and +0.0 + 0.0f is +0.0).
 __device__ inline float occMissN(const MapConst &mc, unsigned ray_flags, float x, uint32_t n)
 {
   constexpr unsigned kExcludeFlags = OHMHIP_RF_EXCLUDE_UNOBSERVED | OHMHIP_RF_EXCLUDE_FREE | OHMHIP_RF_EXCLUDE_OCCUPIED;
@@ -75,29 +94,31 @@ __device__ inline float occMissN(const MapConst &mc, unsigned ray_flags, float x
     float nx = fmaxf(mc.min_value, base + first_adj);
     if (nx == x)
     {
-      return x;
+      return nx;
     }
     x = nx;
     for (uint32_t k = 1; k < n; ++k)
     {
       const float adj = (mc.sat_min < x && x < mc.sat_max) ? mc.miss_value : 0.0f;
       nx = fmaxf(mc.min_value, x + adj);
-      if (nx == x)
+      const bool fixed = nx == x;
+      x = nx;
+      if (fixed)
       {
         break;
       }
-      x = nx;
     }
     return x;
   }
   for (uint32_t k = 0; k < n; ++k)
   {
     const float nx = occMiss(mc, ray_flags, x);
-    if (nx == x)
+    const bool fixed = nx == x;
+    x = nx;
+    if (fixed)
     {
       break;
     }
-    x = nx;
   }
   return x;
 }

@@ -581,10 +581,8 @@ __global__ void __launch_bounds__(128)
       {
         atomicMin(&stop_next[ray], position);
       }
-      if (position <= ray_stop)
-      {
-        x = occMiss(mc, ray_flags, x);  // live: at or before the ray's stopping voxel
-      }
+      // live: at or before the ray's stopping voxel; behind it the CPU mapper makes a null update, which still clamps
+      x = (position <= ray_stop) ? occMiss(mc, ray_flags, x) : occNullMiss(mc, x);
     }
     if (kCommit)
     {

@@ -990,7 +990,7 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
           if (n0)
           {
             const float v = occMissN(mc, args.ray_flags, values[j].x, n0);
-            if (v != values[j].x)
+            if (!sameValue(v, values[j].x))
             {
               g_occ[2 * i] = v;
             }
@@ -998,7 +998,7 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
           if (n1)
           {
             const float v = occMissN(mc, args.ray_flags, values[j].y, n1);
-            if (v != values[j].y)
+            if (!sameValue(v, values[j].y))
             {
               g_occ[2 * i + 1] = v;
             }

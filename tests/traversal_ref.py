@@ -253,27 +253,22 @@ Call = namedtuple("Call", "rays flags")
 
 class Occupancy:
     """Log-odds of the voxels a sheet has touched or planted: only `occupied` is used (kRfStopOnFirstOccupied).
-    ohm/VoxelOccupancyCompute.h:44-120 without saturation."""
+    The rule itself is occupancy_ref's; this is that model under the map's default configuration."""
 
     def __init__(self, mp, planted=None):
-        self.mp = mp
+        import occupancy_ref                        # (it imports this module for the walk)
+        self.mp, self.rule = mp, occupancy_ref
+        self.cfg = occupancy_ref.config(mp.hit, mp.miss, mp.threshold, mp.min_value, mp.max_value)
         self.values = dict(planted or {})          # (region, vi) -> float32
 
     def occupied(self, key):
-        v = self.values.get(key, F(np.inf))
-        return v != F(np.inf) and v >= self.mp.threshold
+        return self.rule.occupied(self.cfg, self.values.get(key, F(np.inf)))
 
     def miss(self, key, null_update):
-        v = self.values.get(key, F(np.inf))
-        if null_update:
-            return
-        base = F(0.0) if v == F(np.inf) else v
-        self.values[key] = max(self.mp.min_value, F(base + self.mp.miss))
+        self.values[key] = self.rule.adjust_miss(self.cfg, self.values.get(key, F(np.inf)), 0, null_update)
 
     def hit(self, key):
-        v = self.values.get(key, F(np.inf))
-        base = F(0.0) if v == F(np.inf) else v
-        self.values[key] = min(self.mp.max_value, F(base + self.mp.hit))
+        self.values[key] = self.rule.adjust_hit(self.cfg, self.values.get(key, F(np.inf)))
 
 
 def cpu_adds(call, mp, occupancy=None, mutant=None, last_exit_in=0.0):
