@@ -913,6 +913,59 @@ int ohmhip_transform_samples(const double *transform_times, const double *transf
                              const double *sample_times, const double *local_samples, uint32_t point_count,
                              double max_range, ohmhip_stream_t stream, ohmhip_buffer_t output, uint32_t *ray_elements);
 
+/* RAY PATTERNS.  ohm::RayPattern / RayPatternConical / ClearingPattern (ohm/RayPattern.{h,cpp}, ohm/RayPatternConical.cpp,
+ * ohm/ClearingPattern.{h,cpp}) with the pattern resident in device memory: a fixed fan of rays in the sensor frame, moved
+ * to a pose and integrated -- per application only the pose crosses the link.  A pattern is ray_count (start, end) pairs
+ * of 3 doubles; the host mirrors build it (addPoints / addRays, the conical constructor) and hand it over once.
+ *   POSES.  pose_kind OHMHIP_POSE_QUAT: 7 doubles per pose, translation xyz then rotation x, y, z, w (the layout of
+ *   ohmhip_transform_samples); OHMHIP_POSE_MAT4: 16 doubles per pose, a column-major 4 x 4 matrix m[c][r] = m[4c + r].
+ *   ARITHMETIC (fp64, one rounding per operation, no contraction; tests/ray_pattern_ref.py is the model the device is held
+ *   to bit for bit).  Every pattern point p becomes s = scaling * p per component, then
+ *     QUAT (RayPattern.cpp:58-70, glm's quaternion * vector): u = (q.x, q.y, q.z); uv = cross(u, s); uuv = cross(u, uv);
+ *       out = (s + ((uv * q.w) + uuv) * 2) + translation, cross(a, b) = (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x,
+ *       a.x*b.y - b.x*a.y); the quaternion is used as given, not normalised;
+ *     MAT4 (RayPattern.cpp:72-84, glm's mat4 * vec4): out[r] = (m[0][r]*s.x + m[1][r]*s.y) + (m[2][r]*s.z + m[3][r]).
+ *   (The reference's matrix overload has no scaling argument: scaling == 1 is that overload.)
+ *   OUTPUT: pose major, in pattern order, 6 doubles per ray: a call with K poses yields exactly the K ray sets of K
+ *   single-pose calls, one behind the other. */
+typedef struct ohmhip_pattern_s *ohmhip_pattern_t;
+#define OHMHIP_POSE_QUAT 0
+#define OHMHIP_POSE_MAT4 1
+/* Copies ray_count ray pairs (6 doubles each, host memory) to the device.  ray_count == 0 (ray_pairs may be NULL then)
+ * makes an empty pattern: every use of it succeeds and does nothing. */
+int ohmhip_pattern_create(const double *ray_pairs, size_t ray_count, ohmhip_pattern_t *pattern);
+/* The pattern's output buffers may be read by batches in flight: destroy it after ohmhip_map_sync of the maps it was
+ * applied to (the call itself waits for the device). */
+int ohmhip_pattern_destroy(ohmhip_pattern_t pattern);
+int ohmhip_pattern_ray_count(ohmhip_pattern_t pattern, size_t *ray_count);
+/* RayPattern::buildRays for pose_count poses at once: the rays are built on the device into a buffer of the pattern's
+ * and, with host_out non-NULL, copied to it (pose_count * ray_count * 6 doubles).  Synchronous.  OHMHIP_ERR_CAPACITY when
+ * pose_count * ray_count reaches 2^28 (what one batch takes). */
+int ohmhip_pattern_build_rays(ohmhip_pattern_t pattern, const double *poses, size_t pose_count, int pose_kind,
+                              double scaling, double *host_out);
+/* ClearingPattern::lastRaySet: the rays of the latest ohmhip_pattern_build_rays / ohmhip_map_apply_pattern call on this
+ * pattern, read back from the device.  *elements = number of points (2 per ray; 0 before any call); host_out may be
+ * NULL to ask for the size only.  Waits for the kernel that built them, not for the batch that integrates them. */
+int ohmhip_pattern_last_rays(ohmhip_pattern_t pattern, double *host_out, size_t *elements);
+/* ClearingPattern::apply (ohm/ClearingPattern.h:109-130) for pose_count poses in one device batch, in this order:
+ *  1 rays collected from earlier integrate calls (batch coalescing) are launched: they belong to the unscaled miss value;
+ *  2 this batch's miss value is the fp32 product miss_value * probability_scaling;
+ *  3 the rays are built on the map's stream into one of three buffers the pattern owns, used in turn by
+ *    ohmhip_map_batches_launched -- the rule of ohmhip_map_integrate_rays_device for arrays of batches in flight;
+ *  4 that buffer is a device batch of its own with ray_flags & ~OHMHIP_RF_REVERSE_WALK (ClearingPattern.cpp:40-44),
+ *    ordered behind the kernel by the streams alone: no host synchronisation, nothing staged, never merged with the
+ *    calls that follow;
+ *  5 the miss value is restored, also when the batch fails.
+ * The batch replays its rays one by one in order (OHMHIP_RF_STOP_ON_FIRST_OCCUPIED included), so K poses in one call give
+ * the map K calls with one pose each give -- a later pose's rays see what an earlier pose cleared.  *integrated (optional)
+ * = points of the rays the map's ray filter passed (a NaN pose yields NaN rays, which it drops).  pose_count == 0 or an
+ * empty pattern: OHMHIP_OK, nothing integrated, nothing launched.  OHMHIP_ERR_INVALID_ARG for NULL arguments and an
+ * unknown pose_kind, OHMHIP_ERR_CAPACITY when pose_count * ray_count reaches 2^28.  Flags, map modes and partitioned maps
+ * are served as ohmhip_map_integrate_rays_device serves them. */
+int ohmhip_map_apply_pattern(ohmhip_map_t map, ohmhip_pattern_t pattern, const double *poses, size_t pose_count,
+                             int pose_kind, double scaling, float probability_scaling, unsigned ray_flags,
+                             size_t *integrated);
+
 /* Multi-GPU merge support (no reference equivalent -- ohm is single device).  The resident layer of a
  * map is one allocation of region_stride_bytes per slot: ohm_amd/distributed.py wraps it as a device tensor and runs
  * the RCCL all-reduce of touched-region occupancy deltas on it.  ensure_regions makes regions resident (cleared)

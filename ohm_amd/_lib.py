@@ -193,6 +193,13 @@ _sigs = {
     "ohmhip_map_remove_regions": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ohmhip_transform_samples": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_double, _vp, _vp,
                                            C.POINTER(C.c_uint32)]),
+    "ohmhip_pattern_create": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
+    "ohmhip_pattern_destroy": (C.c_int, [_vp]),
+    "ohmhip_pattern_ray_count": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    "ohmhip_pattern_build_rays": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_double, _vp]),
+    "ohmhip_pattern_last_rays": (C.c_int, [_vp, _vp, C.POINTER(C.c_size_t)]),
+    "ohmhip_map_apply_pattern": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_double, C.c_float, C.c_uint,
+                                           C.POINTER(C.c_size_t)]),
     "ohmhip_map_batch_timings": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_float)]),
     "ohmhip_comm_exchange_side": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "ohmhip_gather_rows": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp]),

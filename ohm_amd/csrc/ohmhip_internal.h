@@ -329,6 +329,19 @@ __host__ __device__ inline uint32_t hashRegionKey(uint64_t key, uint32_t mask)
   h ^= h >> 29;
   return uint32_t(h) & mask;
 }
+
+/// Rays one batch takes (the ray index of the sample key, kHitRayBits - 1 bits): a pattern applied to a batch of poses
+/// must stay below it.
+constexpr size_t kPatternMaxRays = size_t(1) << 28;
+
+/// The device half of ohmhip_map_apply_pattern, defined beside k_pattern_rays (ohmhip_transform.hip): build the rays of
+/// `pose_count` poses (host memory) on `stream` into the pattern's output buffer number `turn` % 3 and record the
+/// pattern's "built" event behind the kernel.  `user` names who will read the buffer (a map): the three buffers are safe
+/// to take in turn only while ONE user counts the turns, so a change of user waits for the device first.  The caller has
+/// checked the arguments and that there is something to build.  *d_rays: pose_count * ray_count * 6 doubles; *built: the
+/// event other streams of the user wait for before they read them.
+int patternBuildOnStream(ohmhip_pattern_t pattern, const void *user, uint64_t turn, hipStream_t stream, const double *poses,
+                         size_t pose_count, int pose_kind, double scaling, const double **d_rays, hipEvent_t *built);
 }  // namespace ohmhip
 
 #endif  // OHMHIP_INTERNAL_H

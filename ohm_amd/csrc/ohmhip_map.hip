@@ -985,3 +985,4 @@ OHMHIP_ABI_CATCH
 #include "cloud_impl.h"
 #include "neighbours_impl.h"
 #include "point_filter_impl.h"
+#include "pattern_impl.h"

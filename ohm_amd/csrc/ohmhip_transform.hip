@@ -13,7 +13,11 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include <algorithm>
 #include <cmath>
+#include <memory>
+
+#include "pattern_kernels.h"
 
 namespace ohmhip
 {
@@ -267,5 +271,216 @@ try
   }
   cleanup();
   return status;
+}
+OHMHIP_ABI_CATCH
+
+// ---- Ray patterns (include/ohmhip.h, RAY PATTERNS) ---------------------------------------------------------------------
+
+/// A ray pattern resident on the device: its points, and the buffers its applications write.
+struct ohmhip_pattern_s
+{
+  /// Where one application's rays go, with the poses that produced them: the pinned block the caller's poses are
+  /// copied to and its device copy.
+  struct Output
+  {
+    double *d_rays = nullptr;
+    size_t ray_bytes = 0;
+    double *d_poses = nullptr;
+    double *h_poses = nullptr;
+    size_t pose_bytes = 0;
+    uint64_t turn = ~uint64_t(0);  ///< the turn that last wrote it
+  };
+  static constexpr int kTurnOutputs = 3;  ///< [0, 3): taken in turn by the batches of a map; [3]: ohmhip_pattern_build_rays
+
+  size_t ray_count = 0;
+  double *d_points = nullptr;
+  Output out[kTurnOutputs + 1];
+  const void *user = nullptr;
+  hipEvent_t built = nullptr;
+  const double *last = nullptr;
+  size_t last_elements = 0;
+
+  ~ohmhip_pattern_s()
+  {
+    (void)hipDeviceSynchronize();  // (batches in flight may still read the outputs)
+    for (Output &o : out)
+    {
+      (void)hipFree(o.d_rays);
+      (void)hipFree(o.d_poses);
+      (void)hipHostFree(o.h_poses);
+    }
+    (void)hipFree(d_points);
+    if (built)
+    {
+      (void)hipEventDestroy(built);
+    }
+  }
+};
+
+namespace
+{
+inline size_t poseDoubles(int pose_kind)
+{
+  return pose_kind == OHMHIP_POSE_QUAT ? 7u : 16u;
+}
+
+/// Build into `o` on `stream`.  The caller has made sure nothing reads `o` any more.
+int patternBuild(ohmhip_pattern_t p, ohmhip_pattern_s::Output &o, hipStream_t stream, const double *poses,
+                 size_t pose_count, int pose_kind, double scaling)
+{
+  const size_t pose_bytes = sizeof(double) * poseDoubles(pose_kind) * pose_count;
+  const size_t ray_bytes = sizeof(double) * 6 * p->ray_count * pose_count;
+  if (o.pose_bytes < pose_bytes)
+  {
+    (void)hipFree(o.d_poses);
+    (void)hipHostFree(o.h_poses);
+    o.d_poses = o.h_poses = nullptr;
+    o.pose_bytes = 0;
+    const size_t want = std::max<size_t>(pose_bytes + pose_bytes / 2, 1024);
+    OHMHIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&o.h_poses), want, hipHostMallocDefault));
+    OHMHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&o.d_poses), want));
+    o.pose_bytes = want;
+  }
+  if (o.ray_bytes < ray_bytes)
+  {
+    (void)hipFree(o.d_rays);
+    o.d_rays = nullptr;
+    o.ray_bytes = 0;
+    OHMHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&o.d_rays), ray_bytes));
+    o.ray_bytes = ray_bytes;
+  }
+  memcpy(o.h_poses, poses, pose_bytes);
+  OHMHIP_CHECK(hipMemcpyAsync(o.d_poses, o.h_poses, pose_bytes, hipMemcpyHostToDevice, stream));
+  const uint32_t points = uint32_t(2 * p->ray_count), n_poses = uint32_t(pose_count);
+  const size_t lanes = size_t(points) * n_poses;  // < 2^29
+  hipLaunchKernelGGL(k_pattern_rays, dim3(uint32_t((lanes + 255) / 256)), dim3(256), 0, stream, p->d_points, points,
+                     o.d_poses, n_poses, pose_kind, scaling, o.d_rays);
+  OHMHIP_CHECK(hipGetLastError());
+  OHMHIP_CHECK(hipEventRecord(p->built, stream));
+  p->last = o.d_rays;
+  p->last_elements = lanes;
+  return OHMHIP_OK;
+}
+}  // namespace
+
+int ohmhip::patternBuildOnStream(ohmhip_pattern_t p, const void *user, uint64_t turn, hipStream_t stream,
+                                 const double *poses, size_t pose_count, int pose_kind, double scaling,
+                                 const double **d_rays, hipEvent_t *built)
+{
+  ohmhip_pattern_s::Output &o = p->out[turn % ohmhip_pattern_s::kTurnOutputs];
+  if (p->user != user)
+  {
+    // Another map's batches may still read what its turns wrote.
+    OHMHIP_CHECK(hipDeviceSynchronize());
+    p->user = user;
+  }
+  else if (o.turn == turn)
+  {
+    // The turn did not advance: the application that took it launched no batch.  Its pose copy may still be queued.
+    OHMHIP_CHECK(hipStreamSynchronize(stream));
+  }
+  o.turn = turn;
+  OHMHIP_CHECK(patternBuild(p, o, stream, poses, pose_count, pose_kind, scaling));
+  *d_rays = o.d_rays;
+  *built = p->built;
+  return OHMHIP_OK;
+}
+
+extern "C" int ohmhip_pattern_create(const double *ray_pairs, size_t ray_count, ohmhip_pattern_t *pattern)
+try
+{
+  if (!pattern || (!ray_pairs && ray_count))
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  *pattern = nullptr;
+  if (ray_count >= kPatternMaxRays)
+  {
+    return OHMHIP_ERR_CAPACITY;
+  }
+  int count = 0;
+  const int derr = ohmhip_device_count(&count);
+  if (derr || count == 0)
+  {
+    return derr ? derr : OHMHIP_ERR_NO_DEVICE;
+  }
+  std::unique_ptr<ohmhip_pattern_s> p(new ohmhip_pattern_s);
+  p->ray_count = ray_count;
+  OHMHIP_CHECK(hipEventCreateWithFlags(&p->built, hipEventDisableTiming));
+  if (ray_count)
+  {
+    OHMHIP_CHECK(hipMalloc(reinterpret_cast<void **>(&p->d_points), sizeof(double) * 6 * ray_count));
+    OHMHIP_CHECK(hipMemcpy(p->d_points, ray_pairs, sizeof(double) * 6 * ray_count, hipMemcpyHostToDevice));
+  }
+  *pattern = p.release();
+  return OHMHIP_OK;
+}
+OHMHIP_ABI_CATCH
+
+extern "C" int ohmhip_pattern_destroy(ohmhip_pattern_t pattern)
+try
+{
+  delete pattern;
+  return OHMHIP_OK;
+}
+OHMHIP_ABI_CATCH
+
+extern "C" int ohmhip_pattern_ray_count(ohmhip_pattern_t pattern, size_t *ray_count)
+try
+{
+  if (!pattern || !ray_count)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  *ray_count = pattern->ray_count;
+  return OHMHIP_OK;
+}
+OHMHIP_ABI_CATCH
+
+extern "C" int ohmhip_pattern_build_rays(ohmhip_pattern_t pattern, const double *poses, size_t pose_count, int pose_kind,
+                                         double scaling, double *host_out)
+try
+{
+  if (!pattern || (!poses && pose_count) || (pose_kind != OHMHIP_POSE_QUAT && pose_kind != OHMHIP_POSE_MAT4))
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  if (pose_count == 0 || pattern->ray_count == 0)
+  {
+    return OHMHIP_OK;
+  }
+  if (pose_count >= kPatternMaxRays || pose_count * pattern->ray_count >= kPatternMaxRays)
+  {
+    return OHMHIP_ERR_CAPACITY;
+  }
+  ohmhip_pattern_s::Output &o = pattern->out[ohmhip_pattern_s::kTurnOutputs];
+  OHMHIP_CHECK(patternBuild(pattern, o, nullptr, poses, pose_count, pose_kind, scaling));
+  if (host_out)
+  {
+    OHMHIP_CHECK(hipMemcpyAsync(host_out, o.d_rays, sizeof(double) * 3 * pattern->last_elements, hipMemcpyDeviceToHost,
+                                nullptr));
+  }
+  return int(hipStreamSynchronize(nullptr));
+}
+OHMHIP_ABI_CATCH
+
+extern "C" int ohmhip_pattern_last_rays(ohmhip_pattern_t pattern, double *host_out, size_t *elements)
+try
+{
+  if (elements)
+  {
+    *elements = 0;
+  }
+  if (!pattern || !elements)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  *elements = pattern->last_elements;
+  if (!host_out || pattern->last_elements == 0)
+  {
+    return OHMHIP_OK;
+  }
+  OHMHIP_CHECK(hipEventSynchronize(pattern->built));
+  return int(hipMemcpy(host_out, pattern->last, sizeof(double) * 3 * pattern->last_elements, hipMemcpyDeviceToHost));
 }
 OHMHIP_ABI_CATCH

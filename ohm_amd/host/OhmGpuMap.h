@@ -2375,6 +2375,210 @@ private:
   int last_status_ = OHMHIP_OK;
 };
 
+/// ohm::RayPattern (ohm/RayPattern.h, .cpp): a fixed set of (start, end) ray pairs relative to the sensor.  The host
+/// assembles it; it then lives in device memory and moving it to a pose is device work (include/ohmhip.h, RAY PATTERNS).
+class RayPattern
+{
+public:
+  RayPattern() = default;
+  virtual ~RayPattern() { dropDevicePattern(); }
+  RayPattern(const RayPattern &) = delete;
+  RayPattern &operator=(const RayPattern &) = delete;
+
+  void addPoints(const dvec3 *points, size_t point_count)
+  {
+    for (size_t i = 0; i < point_count; ++i)
+    {
+      addRay(dvec3{ 0.0, 0.0, 0.0 }, points[i]);
+    }
+  }
+  void addPoint(const dvec3 &point) { addPoints(&point, 1); }
+  void addRays(const dvec3 *ray_pairs, size_t elements)
+  {
+    for (size_t i = 0; i + 1 < elements; i += 2)
+    {
+      addRay(ray_pairs[i], ray_pairs[i + 1]);
+    }
+  }
+  void addRay(const dvec3 &ray_start, const dvec3 &ray_end)
+  {
+    dropDevicePattern();
+    sample_pairs_.push_back(ray_start);
+    sample_pairs_.push_back(ray_end);
+  }
+  size_t rayCount() const { return sample_pairs_.size() / 2; }
+  size_t pointCount() const { return sample_pairs_.size(); }
+  const dvec3 *rayPoints() const { return sample_pairs_.data(); }
+
+  /// RayPattern::buildRays (RayPattern.cpp:58-70), computed on the device.  @return elements in @p rays.
+  size_t buildRays(std::vector<dvec3> *rays, const dvec3 &position, const dquat &rotation, double scaling = 1.0) const
+  {
+    const double pose[7] = { position.x, position.y, position.z, rotation.x, rotation.y, rotation.z, rotation.w };
+    return buildRays(rays, pose, 1, OHMHIP_POSE_QUAT, scaling);
+  }
+  /// ... with a column-major 4 x 4 matrix (glm::dmat4's memory, RayPattern.cpp:72-84).
+  size_t buildRays(std::vector<dvec3> *rays, const double pattern_transform[16]) const
+  {
+    return buildRays(rays, pattern_transform, 1, OHMHIP_POSE_MAT4, 1.0);
+  }
+  /// Extension: @p pose_count poses at once, pose major.
+  size_t buildRays(std::vector<dvec3> *rays, const double *poses, size_t pose_count, int pose_kind, double scaling) const
+  {
+    rays->assign(pose_count * pointCount(), dvec3{ 0.0, 0.0, 0.0 });
+    OHMHIP_GPUAPICHECK(ohmhip_pattern_build_rays(devicePattern(), poses, pose_count, pose_kind, scaling,
+                                                 rays->empty() ? nullptr : &(*rays)[0].x));
+    return rays->size();
+  }
+
+  /// The device copy, made when first needed and dropped when the pattern changes.
+  ohmhip_pattern_t devicePattern() const
+  {
+    if (!handle_)
+    {
+      OHMHIP_GPUAPICHECK(ohmhip_pattern_create(sample_pairs_.empty() ? nullptr : &sample_pairs_[0].x, rayCount(), &handle_));
+    }
+    return handle_;
+  }
+
+private:
+  void dropDevicePattern()
+  {
+    if (handle_)
+    {
+      ohmhip_pattern_destroy(handle_);  // (waits for the device: batches in flight may read its buffers)
+      handle_ = nullptr;
+    }
+  }
+
+  std::vector<dvec3> sample_pairs_;
+  mutable ohmhip_pattern_t handle_ = nullptr;
+};
+
+/// ohm::RayPatternConical (ohm/RayPatternConical.cpp:20-75), the constructor as written there in glm's operation order:
+/// normalise as v * (1 / sqrt(dot)), quaternion * vector as v + ((uv * w) + uuv) * 2, both loop angles accumulated.
+class RayPatternConical : public RayPattern
+{
+public:
+  RayPatternConical(const dvec3 &cone_axis, double cone_angle, double range, double angular_resolution,
+                    double min_range = 0)
+  {
+    const double inv = 1.0 / std::sqrt((cone_axis.x * cone_axis.x + cone_axis.y * cone_axis.y) + cone_axis.z * cone_axis.z);
+    const dvec3 n{ cone_axis.x * inv, cone_axis.y * inv, cone_axis.z * inv };
+    addRay(scaled(n, min_range), scaled(n, range));
+    const dvec3 deflection_base{ n.z, n.x, n.y };
+    const double two_pi = 2 * 3.14159265358979323846;
+    for (double circle_angle = 0; angular_resolution > 0 && circle_angle < two_pi; circle_angle += angular_resolution)
+    {
+      const dvec3 deflection_axis = rotate(angleAxis(circle_angle, n), deflection_base);
+      for (double deflection_angle = angular_resolution; deflection_angle <= 0.5 * cone_angle;
+           deflection_angle += angular_resolution)
+      {
+        const dvec3 ray_dir = rotate(angleAxis(deflection_angle, deflection_axis), n);
+        addRay(scaled(ray_dir, min_range), scaled(ray_dir, range));
+      }
+    }
+  }
+
+private:
+  static dvec3 scaled(const dvec3 &v, double s) { return dvec3{ v.x * s, v.y * s, v.z * s }; }
+  static dvec3 cross(const dvec3 &a, const dvec3 &b)
+  {
+    return dvec3{ a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y };
+  }
+  static dquat angleAxis(double angle, const dvec3 &axis)
+  {
+    const double s = std::sin(angle * 0.5);
+    return dquat{ axis.x * s, axis.y * s, axis.z * s, std::cos(angle * 0.5) };
+  }
+  static dvec3 rotate(const dquat &q, const dvec3 &v)
+  {
+    const dvec3 u{ q.x, q.y, q.z };
+    const dvec3 uv = cross(u, v);
+    const dvec3 uuv = cross(u, uv);
+    return dvec3{ v.x + ((uv.x * q.w) + uuv.x) * 2.0, v.y + ((uv.y * q.w) + uuv.y) * 2.0,
+                  v.z + ((uv.z * q.w) + uuv.z) * 2.0 };
+  }
+};
+
+/// ohm::ClearingPattern (ohm/ClearingPattern.h, .cpp): applies a RayPattern at a pose so that every ray lowers the first
+/// occupied voxel it meets and stops there.  apply() is one library call (ohmhip_map_apply_pattern): rays waiting in the
+/// map's coalescing buffer are launched first, the batch runs with the miss value scaled by probability_scaling, and
+/// GpuMap::missValue() never changes.  applyMany() is an extension: K poses in one device batch, with the result of K
+/// apply() calls.
+class ClearingPattern
+{
+public:
+  static const unsigned kDefaultRayFlags = kRfEndPointAsFree | kRfStopOnFirstOccupied | kRfExcludeFree | kRfExcludeUnobserved;
+
+  ClearingPattern(const RayPattern *pattern, bool take_ownership) : pattern_(pattern), has_ownership_(take_ownership) {}
+  ~ClearingPattern()
+  {
+    if (has_ownership_)
+    {
+      delete pattern_;
+    }
+  }
+  ClearingPattern(const ClearingPattern &) = delete;
+  ClearingPattern &operator=(const ClearingPattern &) = delete;
+
+  const RayPattern *pattern() const { return pattern_; }
+  bool hasPatternOwnership() const { return has_ownership_; }
+  unsigned rayFlags() const { return ray_flags_; }
+  /// ClearingPattern.cpp:40-44: kRfReverseWalk is never set.
+  void setRayFlags(unsigned ray_flags) { ray_flags_ = ray_flags & ~unsigned(kRfReverseWalk); }
+
+  /// @return points integrated (2 per ray the map's ray filter passed); the reference returns nothing.
+  size_t apply(GpuMap *map, const dvec3 &position, const dquat &rotation, float probability_scaling = 1.0f)
+  {
+    const double pose[7] = { position.x, position.y, position.z, rotation.x, rotation.y, rotation.z, rotation.w };
+    return applyMany(map, pose, 1, OHMHIP_POSE_QUAT, probability_scaling);
+  }
+  /// ... with a column-major 4 x 4 matrix (glm::dmat4's memory).
+  size_t apply(GpuMap *map, const double pattern_transform[16], float probability_scaling = 1.0f)
+  {
+    return applyMany(map, pattern_transform, 1, OHMHIP_POSE_MAT4, probability_scaling);
+  }
+  size_t applyMany(GpuMap *map, const double *poses, size_t pose_count, int pose_kind = OHMHIP_POSE_QUAT,
+                   float probability_scaling = 1.0f)
+  {
+    if (!map->syncConfig())  // the host map's values, as before every batch
+    {
+      return 0;
+    }
+    size_t integrated = 0;
+    OHMHIP_GPUAPICHECK(ohmhip_map_apply_pattern(map->handle(), pattern_->devicePattern(), poses, pose_count, pose_kind, 1.0,
+                                                probability_scaling, ray_flags_, &integrated));
+    have_last_ = pose_count > 0 && pattern_->rayCount() > 0;
+    return integrated;
+  }
+
+  /// The rays of the last apply() (or of a buildRays() on the pattern since), read back from the device buffer the batch
+  /// was given.  Valid until the next call.
+  const dvec3 *lastRaySet(size_t *element_count)
+  {
+    last_ray_set_.clear();
+    size_t elements = 0;
+    if (have_last_)
+    {
+      OHMHIP_GPUAPICHECK(ohmhip_pattern_last_rays(pattern_->devicePattern(), nullptr, &elements));
+      last_ray_set_.resize(elements);
+      if (elements)
+      {
+        OHMHIP_GPUAPICHECK(ohmhip_pattern_last_rays(pattern_->devicePattern(), &last_ray_set_[0].x, &elements));
+      }
+    }
+    *element_count = elements;
+    return last_ray_set_.data();
+  }
+
+private:
+  const RayPattern *pattern_;
+  bool has_ownership_;
+  unsigned ray_flags_ = kDefaultRayFlags;
+  bool have_last_ = false;
+  std::vector<dvec3> last_ray_set_;
+};
+
 /// ohm::configureGpu / gpuDevice (ohmgpu/OhmGpu.h:40-66): select the process-wide device.
 inline int configureGpu(int device_index = 0)
 {

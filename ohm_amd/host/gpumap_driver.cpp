@@ -9,6 +9,8 @@
 //   are integrated straight from the device buffer (all rays then start at the origin).
 //   transform: <rays.bin> is a trajectory-and-samples file instead and <out.bin> receives the ray buffer of
 //   ohm::GpuTransformSamples::transform (layouts at the mode below); <resolution> and <batch_rays> are not used.
+//   clearing: RayPattern.Clearing through ohm::ClearingPattern; <batch_rays> and <rays.bin> are not used, three more
+//   arguments give the translation (layout at the mode below).
 //   filter:<clipbounded|cliptobounds|clipray|goodray>: host only, one record per ray (layout at the mode below).
 //   heightmapfill: <rays.bin> is a scene file (voxels written directly) and <out.bin> receives the flood-fill
 //   heightmap of ohm::Heightmap in HeightmapMode::kSimpleFill (layouts at the mode below); <batch_rays> is not used.
@@ -182,6 +184,69 @@ int main(int argc, char **argv)
       return 0;
     }
 
+    if (mode == "clearing")
+    {
+      // RayPattern.Clearing as the reference writes it (tests/ohmtestgpu/GpuRayPatternTests.cpp:28-85): a line of 20 occupied
+      // voxels along x written directly, hit probability 0.51, miss probability 0; a one-ray pattern along y, rotated onto
+      // x by angleAxis(-pi/2, z) and moved to argv 6-8 (the centre of voxel 0), applied 20 times through
+      // ohm::ClearingPattern.  <batch_rays> and <rays.bin> are not used.  out: per application the 2 points of
+      // lastRaySet() (6 doubles), u64 points integrated and the occupancy words of the voxels (0..31, 0, 0) after
+      // syncVoxels(); then the whole occupancy block of region (0, 0, 0) and the map's miss value (float).
+      if (argc < 9)
+      {
+        return 2;
+      }
+      const unsigned voxel_count = 20;
+      ohm::OccupancyMap line_map(resolution);
+      line_map.setHitProbability(0.51f);
+      line_map.setMissProbability(0.0f);
+      const std::array<int16_t, 3> key{ { 0, 0, 0 } };
+      {
+        std::vector<uint8_t> &block = line_map.region(key).voxel_blocks[OHMHIP_LID_OCCUPANCY];
+        std::vector<float> values(line_map.regionVoxelVolume(), std::numeric_limits<float>::infinity());
+        for (unsigned i = 0; i < voxel_count; ++i)
+        {
+          values[i] = line_map.hitValue();
+        }
+        block.resize(sizeof(float) * values.size());
+        std::memcpy(block.data(), values.data(), block.size());
+      }
+      ohm::GpuMap line_gpu_map(&line_map, true);
+      line_gpu_map.uploadRegions(nullptr, 0);
+      ohm::RayPattern line_pattern;
+      line_pattern.addPoint(ohm::dvec3{ 0, line_map.resolution() * voxel_count, 0 });
+      ohm::ClearingPattern clearing(&line_pattern, false);
+      const ohm::dvec3 pattern_translate{ std::atof(argv[6]), std::atof(argv[7]), std::atof(argv[8]) };
+      const double half_angle = (-0.5 * 3.14159265358979323846) * 0.5;  // glm::angleAxis(-0.5 * M_PI, (0, 0, 1))
+      const ohm::dquat rotation{ 0 * std::sin(half_angle), 0 * std::sin(half_angle), 1 * std::sin(half_angle),
+                                 std::cos(half_angle) };
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      for (unsigned i = 0; i < voxel_count; ++i)
+      {
+        const uint64_t integrated = clearing.apply(&line_gpu_map, pattern_translate, rotation);
+        line_gpu_map.syncVoxels();
+        size_t elements = 0;
+        const ohm::dvec3 *ray_set = clearing.lastRaySet(&elements);
+        if (elements != 2)
+        {
+          std::fclose(out);
+          return 7;
+        }
+        std::fwrite(ray_set, sizeof(ohm::dvec3), 2, out);
+        std::fwrite(&integrated, sizeof(integrated), 1, out);
+        std::fwrite(line_map.region(key).voxel_blocks[OHMHIP_LID_OCCUPANCY].data(), sizeof(float), 32, out);
+      }
+      const std::vector<uint8_t> &block = line_map.region(key).voxel_blocks[OHMHIP_LID_OCCUPANCY];
+      std::fwrite(block.data(), 1, block.size(), out);
+      const float miss_value = line_gpu_map.missValue();
+      std::fwrite(&miss_value, sizeof(miss_value), 1, out);
+      std::fclose(out);
+      return 0;
+    }
     if (mode == "heightmapfill")
     {
       // ohm::Heightmap in HeightmapMode::kSimpleFill over a map whose voxels are written directly; <rays.bin> is a scene
