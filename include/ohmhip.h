@@ -966,6 +966,69 @@ int ohmhip_map_apply_pattern(ohmhip_map_t map, ohmhip_pattern_t pattern, const d
                              int pose_kind, double scaling, float probability_scaling, unsigned ray_flags,
                              size_t *integrated);
 
+/* MAP COPY.  ohm::copyMap (ohm/CopyUtil.h:148, ohm/CopyUtil.cpp:58-165) and the rule OccupancyMap::clone is built on
+ * (ohm/OccupancyMap.cpp:953-1004) between two device maps, device to device: one kernel launch per call (k_copy_map),
+ * nothing crosses the host link.  tests/copy_ref.py restates C2 / C3 on the CPU.
+ *  C1 canCopy (CopyUtil.cpp:52-56): dst != src and equal resolution, region voxel dimensions and origin, each compared
+ *     with ==; anything else is OHMHIP_ERR_INVALID_ARG.  The modes may differ (an NDT map's occupancy into a plain map).
+ *  C2 layers: the layers both maps hold (calculateOverlappingLayerSet), narrowed by params->layers (CopyLayerFilter,
+ *     judged on the source layer; 0 = every common layer).  No layer in common before the mask: nothing happens,
+ *     OHMHIP_ERR_NOT_FOUND (the reference returns false, :78-82).  The mask removes every common layer: the regions are
+ *     created in dst, nothing is copied, OHMHIP_OK (:86-100, 117-126).
+ *  C3 regions: a region of src is copied when it passes every filter given.
+ *     (a) keys_xyz: only the listed regions (how the mirrors run arbitrary host CopyChunkFilters); a key src does not
+ *         hold is skipped and counted in keys_absent, a repeated key counts once.
+ *     (b) OHMHIP_COPY_USE_EXTENTS: copyFilterExtents (CopyUtil.cpp:37-45) in its operation order, in double, on the host:
+ *         half = 0.5 * region_spatial_dimensions; lo = centre - half; hi = centre + half; pass = no axis with
+ *         hi < min_extents and no axis with lo > max_extents (touching passes).  centre is MapChunk::region.centre =
+ *         coord * region_dimension WITHOUT the map origin (ohm/MapRegion.cpp:40-42, ohm/MapCoord.h:37-40): on a map
+ *         whose origin is not zero the box is relative to the origin.  Kept as the reference has it.
+ *     (c) OHMHIP_COPY_DIRTY_ONLY, in the place of copyFilterStamp (CopyUtil.cpp:47-50): the regions
+ *         ohmhip_map_dirty_regions lists -- changed since the caller's last ohmhip_map_clear_dirty / syncVoxels.  The
+ *         device map keeps dirty bits, not stamps.  The copy never clears the bit.
+ *  C4 what lands: in every copied region each copied layer of dst equals src's block byte for byte, whether dst held the
+ *     region or not, voxels src holds no data for included.  A tile of a tiled region (LARGE REGIONS) that src lacks reads
+ *     as cleared in dst afterwards, even where dst had data.  Layers only dst has keep what they held; in a region the
+ *     copy creates they read as cleared.
+ *  C5 dst behaves through every entry point like a dst that received the same regions and layers by
+ *     ohmhip_map_read_regions(src) + ohmhip_map_write_regions(dst): the write-back's pre-cleaned copies of the regions
+ *     are void; the NDT replay mask is re-derived from the mean layer, the TSDF replay mask from the TSDF layer with
+ *     DST's truncation distance; a copied occupancy layer marks the region's clearance changed, a copied clearance layer
+ *     marks it unwritten.  Copied regions carry all three dirty bits, as after ohmhip_map_mark_dirty.
+ *  C6 src is read only: it is settled first (rays collected from earlier calls are launched, as every observer does);
+ *     after that no voxel, dirty bit, residency, use stamp or cache counter of it changes.  Regions in its host store
+ *     (SPILL TO HOST) are read where they lie, nothing is re-admitted.
+ *  C7 dst is written: settled, its stream idle; regions it keeps in its host store come back as for
+ *     ohmhip_map_write_regions; its memory limit and spill setting apply exactly as for an ohmhip_map_write_regions of the
+ *     same keys, with the same errors (OHMHIP_ERR_CAPACITY: dst holds what it held, stats->regions_created and
+ *     bytes_copied are 0, regions_passed says what the copy would have moved).
+ *  C8 OHMHIP_ERR_UNSUPPORTED when either map has region ownership or a partition, or dst has replica merge enabled.
+ *     OHMHIP_ERR_INVALID_ARG, before any device work, for null maps, unknown flag bits, a layer mask with bits >=
+ *     OHMHIP_LID_COUNT, keys_xyz non-null with key_count 0 or the reverse, and NaN extents under USE_EXTENTS.
+ *  C9 blocking: the call returns with the copy complete and both maps free to use. */
+#define OHMHIP_COPY_DIRTY_ONLY (1u << 0)
+#define OHMHIP_COPY_USE_EXTENTS (1u << 1)
+typedef struct ohmhip_copy_params
+{
+  unsigned flags;
+  unsigned layers; /* OHMHIP_LAYER_BIT mask of source layers allowed; 0 => every common layer */
+  double min_extents[3], max_extents[3];
+  const int16_t *keys_xyz; /* optional; NULL => every region of src */
+  size_t key_count;
+} ohmhip_copy_params;
+typedef struct ohmhip_copy_stats
+{
+  uint64_t regions_passed;  /* regions of src that passed the filters    */
+  uint64_t regions_created; /* of those, regions dst did not hold before */
+  uint64_t keys_absent;
+  uint64_t bytes_copied;
+  unsigned layers_copied; /* OHMHIP_LAYER_BIT mask */
+} ohmhip_copy_stats;
+/* OHMHIP_OK when C1 holds, OHMHIP_ERR_INVALID_ARG otherwise (null maps included).  No device work. */
+int ohmhip_map_can_copy(ohmhip_map_t dst, ohmhip_map_t src);
+int ohmhip_map_copy(ohmhip_map_t dst, ohmhip_map_t src, const ohmhip_copy_params *params /* NULL: everything */,
+                    ohmhip_copy_stats *stats /* optional */);
+
 /* Multi-GPU merge support (no reference equivalent -- ohm is single device).  The resident layer of a
  * map is one allocation of region_stride_bytes per slot: ohm_amd/distributed.py wraps it as a device tensor and runs
  * the RCCL all-reduce of touched-region occupancy deltas on it.  ensure_regions makes regions resident (cleared)

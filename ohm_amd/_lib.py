@@ -102,6 +102,21 @@ PF_OCCUPANCY_ONLY = 1
 PF_PIECE_POINTS = 1 << 18  # OHMHIP_PF_PIECE_POINTS
 
 
+class CopyParams(C.Structure):
+    """ohmhip_copy_params"""
+    _fields_ = [("flags", C.c_uint), ("layers", C.c_uint), ("min_extents", C.c_double * 3),
+                ("max_extents", C.c_double * 3), ("keys_xyz", C.c_void_p), ("key_count", C.c_size_t)]
+
+
+class CopyStats(C.Structure):
+    """ohmhip_copy_stats"""
+    _fields_ = [("regions_passed", C.c_uint64), ("regions_created", C.c_uint64), ("keys_absent", C.c_uint64),
+                ("bytes_copied", C.c_uint64), ("layers_copied", C.c_uint)]
+
+
+COPY_DIRTY_ONLY, COPY_USE_EXTENTS = 1, 2
+
+
 class MapConfig(C.Structure):
     _fields_ = [("resolution", C.c_double), ("region_dim", C.c_int * 3), ("origin", C.c_double * 3),
                 ("layers", C.c_uint), ("mode", C.c_int), ("hit_value", C.c_float), ("miss_value", C.c_float),
@@ -200,6 +215,8 @@ _sigs = {
     "ohmhip_pattern_last_rays": (C.c_int, [_vp, _vp, C.POINTER(C.c_size_t)]),
     "ohmhip_map_apply_pattern": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_double, C.c_float, C.c_uint,
                                            C.POINTER(C.c_size_t)]),
+    "ohmhip_map_can_copy": (C.c_int, [_vp, _vp]),
+    "ohmhip_map_copy": (C.c_int, [_vp, _vp, C.POINTER(CopyParams), C.POINTER(CopyStats)]),
     "ohmhip_map_batch_timings": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_float)]),
     "ohmhip_comm_exchange_side": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "ohmhip_gather_rows": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp]),

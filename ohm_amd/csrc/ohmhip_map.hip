@@ -19,6 +19,7 @@
 #include "cloud_kernels.h"
 #include "neighbours_kernels.h"
 #include "point_filter_kernels.h"
+#include "copy_kernels.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -986,3 +987,4 @@ OHMHIP_ABI_CATCH
 #include "neighbours_impl.h"
 #include "point_filter_impl.h"
 #include "pattern_impl.h"
+#include "copy_impl.h"

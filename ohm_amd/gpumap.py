@@ -849,6 +849,34 @@ class GpuMap(RayMapper):
         if sync:
             self.wait()
 
+    def lastCopyStats(self):
+        """ohmhip_copy_stats of the last copyMap() into this map (ohm_amd.copyutil), as a dict."""
+        return dict(getattr(self, "_last_copy_stats", {}))
+
+    def _clone_arguments(self):
+        """Constructor arguments, beyond the map and the sizes, that make a map of the same configuration."""
+        return {}
+
+    def clone(self, min_ext=None, max_ext=None):
+        """OccupancyMap::clone (ohm/OccupancyMap.cpp:953-1004) on the device: a new map of the same class, configuration
+        and layers, then the regions that pass the extents rule of copyFilterExtents (every region without extents:
+        +-inf) -- copied device to device by ohmhip_map_copy.  Returns the new GpuMap; its host map holds no chunks
+        until its syncVoxels()."""
+        from . import copyutil
+        src_map = self._map
+        new_map = OccupancyMap(src_map.resolution, src_map.region_voxel_dimensions, layers=tuple(src_map.layers))
+        for name in ("origin", "min_voxel_value", "max_voxel_value", "hit_value", "miss_value",
+                     "occupancy_threshold_value", "saturate_at_min_value", "saturate_at_max_value", "ray_filter"):
+            setattr(new_map, name, getattr(src_map, name))
+        other = type(self)(new_map, True, gpu_mem_size=int(self._cfg.gpu_mem_size),
+                           region_capacity=int(self._cfg.region_capacity), **self._clone_arguments())
+        inf = float("inf")
+        chunk_filter = copyutil.copyFilterExtents((-inf,) * 3 if min_ext is None else min_ext,
+                                                  (inf,) * 3 if max_ext is None else max_ext)
+        if not copyutil.copyMap(other, self, chunk_filter):
+            raise L.OhmHipError(L.ERR_INTERNAL, "GpuMap.clone")
+        return other
+
     def _upload_existing(self):
         """gpumap::enableGpu + GpuLayerCache::upload for regions the CPU map already holds."""
         self.uploadRegions()
@@ -911,6 +939,16 @@ class GpuNdtMap(GpuMap):
         cfg.ndt_reinit_count = self.reinitialise_covariance_point_count
         cfg.ndt_initial_intensity_cov = self.initial_intensity_covariance
 
+    def _clone_arguments(self):
+        return {"ndt_mode": self._ndt_mode}
+
+    def clone(self, min_ext=None, max_ext=None):
+        other = super().clone(min_ext, max_ext)
+        for name in ("sensor_noise", "sample_threshold", "adaptation_rate", "reinitialise_covariance_threshold",
+                     "reinitialise_covariance_point_count", "initial_intensity_covariance"):
+            setattr(other, name, getattr(self, name))  # (taken by the clone's next batch)
+        return other
+
     def setSensorNoise(self, noise):
         """GpuNdtMap::setSensorNoise (ohmgpu/GpuNdtMap.h:63-132): applies from the next batch."""
         self.sensor_noise = float(noise)
@@ -934,6 +972,10 @@ class GpuTsdfMap(GpuMap):
 
     def _fill_config(self, cfg):
         (cfg.tsdf_max_weight, cfg.tsdf_trunc, cfg.tsdf_dropoff, cfg.tsdf_sparsity) = self.tsdf_options
+
+    def _clone_arguments(self):
+        return dict(zip(("max_weight", "default_truncation_distance", "dropoff_epsilon",
+                         "sparsity_compensation_factor"), self.tsdf_options))
 
     # ohmgpu/GpuTsdfMap.h:64-79: the option setters / getters under the reference's names (they apply from the next batch;
     # `tsdf_options` = (max_weight, default_truncation_distance, dropoff_epsilon, sparsity_compensation_factor)).

@@ -875,6 +875,15 @@ public:
   }
 
   ohmhip_map_t handle() const { return handle_; }
+  /// OccupancyMap::clone (ohm/OccupancyMap.cpp:953-1004) on the device: a new map of the same class, configuration and
+  /// layers, which owns its (empty) host map, then the regions that pass the extents rule of copyFilterExtents, copied
+  /// device to device (ohmhip_map_copy).  Without extents: every region.  Null when the copy fails (lastStatus()).
+  std::unique_ptr<GpuMap> clone() const
+  {
+    const double inf = std::numeric_limits<double>::infinity();
+    return clone(dvec3{ -inf, -inf, -inf }, dvec3{ inf, inf, inf });
+  }
+  std::unique_ptr<GpuMap> clone(const dvec3 &min_ext, const dvec3 &max_ext) const;
   /// Push the map's current parameters (threshold, built-in ray filter, ...) to the device, as a batch would: what a
   /// query of the map (RaysQueryGpu) calls first.  @return false when the device refuses them.
   bool syncConfig() { return pushConfigIfChanged(); }
@@ -929,6 +938,8 @@ protected:
   }
   /// Mapper-specific parameters (NDT, TSDF) as they stand now.
   virtual void fillMapperValues(ohmhip_map_config &) const {}
+  /// A map of this class and configuration over `map`, which it owns (clone()).
+  virtual GpuMap *newLike(OccupancyMap *map) const { return new GpuMap(map, false, 2048, size_t(cfg_.gpu_mem_size)); }
 
   /// The reference reads the map's parameters at every launch (ohmgpu/GpuMap.cpp:1036-1191): setters called on the
   /// OccupancyMap / mapper after construction apply from the next batch.
@@ -1051,6 +1062,10 @@ public:
 
 protected:
   void fillMapperValues(ohmhip_map_config &cfg) const override { fill(cfg, const_cast<NdtParams *>(&params_)); }
+  GpuMap *newLike(OccupancyMap *map) const override
+  {
+    return new GpuNdtMap(map, false, 2048, size_t(cfg_.gpu_mem_size), mode_, params_);
+  }
 
 public:
 
@@ -1124,6 +1139,10 @@ public:
 
 protected:
   void fillMapperValues(ohmhip_map_config &cfg) const override { fill(cfg, const_cast<TsdfOptions *>(&options_)); }
+  GpuMap *newLike(OccupancyMap *map) const override
+  {
+    return new GpuTsdfMap(map, false, 2048, size_t(cfg_.gpu_mem_size), options_);
+  }
 
 public:
 
@@ -1143,6 +1162,242 @@ private:
   }
   TsdfOptions options_;
 };
+
+// ---------------------------------------------------------------------------------------------------------------------
+// ohm/CopyUtil.h over ohmhip_map_copy (include/ohmhip.h, MAP COPY): canCopy, copyMap and the filter helpers on two
+// GpuMaps.  The copy runs device to device in one kernel launch.
+
+/// What a CopyChunkFilter sees of a MapChunk: the region coordinate, MapRegion::centre -- coord * region spatial
+/// dimensions, WITHOUT the map origin (ohm/MapRegion.cpp:40-42) --, whether the region changed since the last
+/// syncVoxels(), and the map's region spatial dimensions.
+struct CopyChunk
+{
+  std::array<int16_t, 3> coord;
+  dvec3 centre;
+  bool dirty;
+  dvec3 region_spatial_dimensions;
+};
+
+/// An empty filter is an implied pass (CopyUtil.h:23-28).
+using CopyChunkFilter = std::function<bool(const CopyChunk &)>;
+using CopyLayerFilter = std::function<bool(const std::string &)>;
+
+/// The layer names of ohm/DefaultLayer.cpp by OHMHIP_LID_*.
+inline const char *copyLayerName(int layer_id)
+{
+  static const char *const names[OHMHIP_LID_COUNT] = { "occupancy", "mean",      "covariance",     "traversal", "touch_time",
+                                                       "incident_normal", "intensity", "hit_miss_count", "tsdf",      "clearance" };
+  return (layer_id >= 0 && layer_id < OHMHIP_LID_COUNT) ? names[layer_id] : "";
+}
+
+/// copyFilterExtents (CopyUtil.cpp:37-45) in its operation order.  Used alone it goes down as OHMHIP_COPY_USE_EXTENTS.
+struct CopyFilterExtents
+{
+  dvec3 min_ext, max_ext;
+  bool operator()(const CopyChunk &chunk) const
+  {
+    const double dims[3] = { chunk.region_spatial_dimensions.x, chunk.region_spatial_dimensions.y, chunk.region_spatial_dimensions.z };
+    const double centre[3] = { chunk.centre.x, chunk.centre.y, chunk.centre.z };
+    const double mn[3] = { min_ext.x, min_ext.y, min_ext.z }, mx[3] = { max_ext.x, max_ext.y, max_ext.z };
+    bool below = false, above = false;
+    for (int a = 0; a < 3; ++a)
+    {
+      const double half = 0.5 * dims[a];
+      const double lo = centre[a] - half;
+      const double hi = centre[a] + half;
+      below = below || hi < mn[a];
+      above = above || lo > mx[a];
+    }
+    return !below && !above;
+  }
+};
+
+/// In the place of copyFilterStamp (CopyUtil.cpp:47-50): the device map keeps dirty bits, not stamps.  Used alone it
+/// goes down as OHMHIP_COPY_DIRTY_ONLY.
+struct CopyFilterDirty
+{
+  bool operator()(const CopyChunk &chunk) const { return chunk.dirty; }
+};
+
+inline CopyChunkFilter copyFilterExtents(const dvec3 &min_ext, const dvec3 &max_ext)
+{
+  return CopyFilterExtents{ min_ext, max_ext };
+}
+inline CopyChunkFilter copyFilterDirty() { return CopyFilterDirty{}; }
+
+/// CopyUtil.h:50-57
+inline CopyChunkFilter copyFilterAnd(const CopyChunkFilter &filter_a, const CopyChunkFilter &filter_b)
+{
+  if (!filter_a || !filter_b)
+  {
+    return filter_a ? filter_a : filter_b;
+  }
+  return [filter_a, filter_b](const CopyChunk &chunk) { return filter_a(chunk) && filter_b(chunk); };
+}
+
+/// CopyUtil.h:67-75: an empty operand is an implied pass, so the result is empty.
+inline CopyChunkFilter copyFilterOr(const CopyChunkFilter &filter_a, const CopyChunkFilter &filter_b)
+{
+  if (!filter_a || !filter_b)
+  {
+    return {};
+  }
+  return [filter_a, filter_b](const CopyChunk &chunk) { return filter_a(chunk) || filter_b(chunk); };
+}
+
+/// CopyUtil.h:81-91: the negation of an empty filter passes nothing.
+inline CopyChunkFilter copyFilterNegate(const CopyChunkFilter &filter)
+{
+  if (filter)
+  {
+    return [filter](const CopyChunk &chunk) { return !filter(chunk); };
+  }
+  return [](const CopyChunk &) { return false; };
+}
+
+/// CopyUtil.h:96-101
+inline CopyLayerFilter copyLayersFilter(const std::vector<std::string> &layers)
+{
+  return [layers](const std::string &name) { return std::find(layers.begin(), layers.end(), name) != layers.end(); };
+}
+
+/// CopyUtil.h:107-117
+inline CopyLayerFilter copyFilterNegate(const CopyLayerFilter &filter)
+{
+  if (filter)
+  {
+    return [filter](const std::string &name) { return !filter(name); };
+  }
+  return [](const std::string &) { return false; };
+}
+
+/// ohm::canCopy (CopyUtil.cpp:52-56)
+inline bool canCopy(const GpuMap &dst, const GpuMap &src)
+{
+  return ohmhip_map_can_copy(dst.handle(), src.handle()) == OHMHIP_OK;
+}
+
+/// ohm::copyMap (CopyUtil.cpp:58-165) from src into dst.  False where the reference returns false (canCopy fails, no
+/// layer in common) and when the device call fails (status, when given, says how: OHMHIP_ERR_CAPACITY under dst's
+/// memory limit, OHMHIP_ERR_UNSUPPORTED for partitioned or merging maps).  A filter other than copyFilterExtents /
+/// copyFilterDirty alone is evaluated over src's regions on the host and the surviving keys are passed.
+inline bool copyMap(GpuMap &dst, const GpuMap &src, const CopyChunkFilter &copy_chunk_filter = {},
+                    const CopyLayerFilter &copy_layer_filter = {}, ohmhip_copy_stats *stats = nullptr, int *status = nullptr)
+{
+  int local_status = OHMHIP_OK;
+  int &st = status ? *status : local_status;
+  st = OHMHIP_ERR_INVALID_ARG;
+  if (stats)
+  {
+    std::memset(stats, 0, sizeof(*stats));
+  }
+  if (!canCopy(dst, src))
+  {
+    return false;
+  }
+  const unsigned common = dst.map().layers() & src.map().layers();
+  if (common == 0)
+  {
+    st = OHMHIP_ERR_NOT_FOUND;
+    return false;
+  }
+  ohmhip_copy_params params;
+  std::memset(&params, 0, sizeof(params));
+  if (copy_layer_filter)
+  {
+    for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
+    {
+      if ((common & OHMHIP_LAYER_BIT(l)) && copy_layer_filter(copyLayerName(l)))
+      {
+        params.layers |= OHMHIP_LAYER_BIT(l);
+      }
+    }
+    if (params.layers == 0)
+    {
+      // every common layer is filtered out: the regions are still created (:117-126).  0 means "all" in the C ABI, so
+      // the request is spelt with layers that are not common.
+      params.layers = (OHMHIP_LAYER_BIT(OHMHIP_LID_COUNT) - 1u) & ~common;
+      if (params.layers == 0)
+      {
+        st = OHMHIP_ERR_UNSUPPORTED;
+        return false;
+      }
+    }
+  }
+  std::vector<int16_t> keys;
+  if (const CopyFilterExtents *extents = copy_chunk_filter.target<CopyFilterExtents>())
+  {
+    params.flags = OHMHIP_COPY_USE_EXTENTS;
+    const double mn[3] = { extents->min_ext.x, extents->min_ext.y, extents->min_ext.z };
+    const double mx[3] = { extents->max_ext.x, extents->max_ext.y, extents->max_ext.z };
+    std::copy(mn, mn + 3, params.min_extents);
+    std::copy(mx, mx + 3, params.max_extents);
+  }
+  else if (copy_chunk_filter.target<CopyFilterDirty>())
+  {
+    params.flags = OHMHIP_COPY_DIRTY_ONLY;
+  }
+  else if (copy_chunk_filter)
+  {
+    auto list = [&](bool dirty, std::vector<int16_t> &out) {
+      size_t n = 0;
+      int err = dirty ? ohmhip_map_dirty_regions(src.handle(), nullptr, 0, &n) : ohmhip_map_regions(src.handle(), nullptr, 0, &n);
+      out.resize(3 * n);
+      if (err == OHMHIP_OK && n)
+      {
+        err = dirty ? ohmhip_map_dirty_regions(src.handle(), out.data(), n, &n) : ohmhip_map_regions(src.handle(), out.data(), n, &n);
+        out.resize(3 * n);
+      }
+      return err;
+    };
+    std::vector<int16_t> all, dirty;
+    if ((st = list(false, all)) != OHMHIP_OK || (st = list(true, dirty)) != OHMHIP_OK)
+    {
+      return false;
+    }
+    std::map<std::array<int16_t, 3>, bool> is_dirty;
+    for (size_t i = 0; i + 2 < dirty.size(); i += 3)
+    {
+      is_dirty[{ { dirty[i], dirty[i + 1], dirty[i + 2] } }] = true;
+    }
+    const int *dim = src.map().regionVoxelDimensions();
+    const dvec3 spatial{ dim[0] * src.map().resolution(), dim[1] * src.map().resolution(), dim[2] * src.map().resolution() };
+    for (size_t i = 0; i + 2 < all.size(); i += 3)
+    {
+      CopyChunk chunk;
+      chunk.coord = { { all[i], all[i + 1], all[i + 2] } };
+      chunk.centre = dvec3{ double(all[i]) * spatial.x, double(all[i + 1]) * spatial.y, double(all[i + 2]) * spatial.z };
+      chunk.dirty = is_dirty.count(chunk.coord) != 0;
+      chunk.region_spatial_dimensions = spatial;
+      if (copy_chunk_filter(chunk))
+      {
+        keys.insert(keys.end(), all.begin() + i, all.begin() + i + 3);
+      }
+    }
+    if (keys.empty())
+    {
+      st = OHMHIP_OK;
+      return true;  // (every chunk excluded: CopyUtil.cpp:117-123 visits none)
+    }
+    params.keys_xyz = keys.data();
+    params.key_count = keys.size() / 3;
+  }
+  st = ohmhip_map_copy(dst.handle(), src.handle(), &params, stats);
+  return st == OHMHIP_OK;
+}
+
+inline std::unique_ptr<GpuMap> GpuMap::clone(const dvec3 &min_ext, const dvec3 &max_ext) const
+{
+  std::unique_ptr<OccupancyMap> host_map(new OccupancyMap(*map_));
+  host_map->chunks().clear();
+  std::unique_ptr<GpuMap> other(newLike(host_map.get()));
+  host_map.release();  // (owned by `other`: borrowed_map == false)
+  if (!copyMap(*other, *this, copyFilterExtents(min_ext, max_ext)))
+  {
+    return nullptr;
+  }
+  return other;
+}
 
 /// Quaternion in (x, y, z, w) member order (glm::dquat exposes the same members; its memory order depends on the glm
 /// version, ohmgpu/GpuTransformSamples.cpp:169-174).

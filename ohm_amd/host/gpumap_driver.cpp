@@ -359,6 +359,82 @@ int main(int argc, char **argv)
     }
     std::fclose(in);
 
+    if (mode == "copy")
+    {
+      // Copy.CopySubmapFromGpu (tests/ohmtestgpu/GpuCopyTests.cpp:112-150): the rays into a GpuMap, then -- without a
+      // sync of the source -- ohm::copyMap into a second map with copyFilterExtents [argv 6: box minimum, argv 7: box
+      // maximum on every axis, default 0 and 4.5], and a clone() of the same box.  out.bin = the source's chunks, then
+      // the copy's, then the clone's, each in the layout of the integration modes below.
+      const double box_min = argc > 6 ? std::atof(argv[6]) : 0.0;
+      const double box_max = argc > 7 ? std::atof(argv[7]) : 4.5;
+      ohm::OccupancyMap src_map(resolution), dst_map(resolution);
+      ohm::GpuMap src(&src_map, true), dst(&dst_map, true);
+      if (!ohm::canCopy(dst, src) || ohm::canCopy(src, src))
+      {
+        return 8;
+      }
+      const size_t step = batch_rays ? 2 * batch_rays : rays.size();
+      for (size_t i = 0; i < rays.size(); i += step)
+      {
+        const size_t n = std::min(step, rays.size() - i);
+        if (src.integrateRays(rays.data() + i, n) != n)
+        {
+          return 7;
+        }
+      }
+      const ohm::dvec3 copy_min{ box_min, box_min, box_min }, copy_max{ box_max, box_max, box_max };
+      ohmhip_copy_stats stats;
+      if (!ohm::copyMap(dst, src, ohm::copyFilterExtents(copy_min, copy_max), {}, &stats) ||
+          stats.regions_passed != stats.regions_created || stats.layers_copied != OHMHIP_LAYER_BIT(OHMHIP_LID_OCCUPANCY))
+      {
+        return 8;
+      }
+      // the same box by a host lambda (the keys go down), and a filter that passes nothing
+      ohm::OccupancyMap again_map(resolution);
+      ohm::GpuMap again(&again_map, true);
+      const ohm::CopyChunkFilter box = ohm::copyFilterExtents(copy_min, copy_max);
+      ohmhip_copy_stats again_stats;
+      if (!ohm::copyMap(again, src, [&box](const ohm::CopyChunk &chunk) { return box(chunk); }, {}, &again_stats) ||
+          again_stats.regions_passed != stats.regions_passed || again_stats.bytes_copied != stats.bytes_copied ||
+          !ohm::copyMap(again, src, ohm::copyFilterNegate(ohm::CopyChunkFilter())) ||
+          ohm::copyMap(again, src, {}, ohm::copyFilterNegate(ohm::copyLayersFilter({ "occupancy" }))) != true)
+      {
+        return 8;
+      }
+      std::unique_ptr<ohm::GpuMap> clone = src.clone(copy_min, copy_max);
+      if (!clone)
+      {
+        return 8;
+      }
+      src.syncVoxels();
+      dst.syncVoxels();
+      clone->syncVoxels();
+      std::printf("copied %llu of %zu regions, %llu bytes\n", (unsigned long long)stats.regions_passed, src_map.regionCount(),
+                  (unsigned long long)stats.bytes_copied);
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      for (const ohm::OccupancyMap *m : { &src_map, &dst_map, &clone->map() })
+      {
+        const uint64_t regions = m->regionCount();
+        std::fwrite(&regions, sizeof(regions), 1, out);
+        for (const auto &entry : m->chunks())
+        {
+          std::fwrite(entry.first.data(), sizeof(int16_t), 3, out);
+          const uint32_t layer = OHMHIP_LID_OCCUPANCY;
+          const auto &block = entry.second.voxel_blocks[layer];
+          const uint64_t bytes = block.size();
+          std::fwrite(&layer, sizeof(layer), 1, out);
+          std::fwrite(&bytes, sizeof(bytes), 1, out);
+          std::fwrite(block.data(), 1, bytes, out);
+        }
+      }
+      std::fclose(out);
+      return 0;
+    }
+
     if (mode == "linekeys")
     {
       // ohm::LineKeysQueryGpu over the rays: out.bin = u64 rays, then per ray u64 index, u64 count, and after them all
