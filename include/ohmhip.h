@@ -402,6 +402,12 @@ int ohmhip_map_first_ray_time(ohmhip_map_t map, double *time);
  * count L is free once the count has reached L + 2 and a later integrate call has returned (or after ohmhip_map_sync).
  * Does not flush collected rays. */
 OHMHIP_EXPERIMENTAL int ohmhip_map_batches_launched(ohmhip_map_t map, uint64_t *count);
+/* Which route the map's device batches took through the launch pipeline, since the map was created: *batches = batches
+ * completed, *binned_early = those whose binning pass ran on the front stream beside the previous batch's apply kernels
+ * and stood (a plain occupancy batch that follows one, with OHMHIP_EARLY_BIN=1 in the environment at map creation -- off by default; a pass repeated after a wrong guess does
+ * not count).  Read only: it changes nothing and does not flush collected rays.  For tests and measurements, so that a
+ * fallback to the compute stream cannot pass for the early route. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_pipeline_counts(ohmhip_map_t map, uint64_t *batches, uint64_t *binned_early);
 /* Maps whose regions are cut into tiles (LARGE REGIONS above): rays, among those that passed the filter, with an end in
  * a region the reference still addresses (|region| <= 32767) but whose tile coordinates leave the key's 16-bit fields.
  * Such a ray is not walked and, when it is the sample that lies out there, its sample is dropped -- the one place results

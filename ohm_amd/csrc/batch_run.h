@@ -45,6 +45,7 @@ struct BatchRun
   int attempt = 0;
   uint32_t spec_seg_cap = 0, seg_cap = 0;
   bool speculated = false, bucket_hits = false;
+  bool binned_early = false;  ///< the speculative binning pass went to the front stream (frontHalf)
   BatchInfo info;
   unsigned long long *keys_a = nullptr, *keys_b = nullptr, *events = nullptr;
   const unsigned long long *sorted = nullptr;
@@ -151,7 +152,13 @@ struct BatchRun
     return OHMHIP_OK;
   }
 
-  void launchBin(bool bucket, uint32_t seg_capacity, unsigned long long *hit_keys)
+  /// The sample mask a kernel of the binning / ordering phase sets: a plain occupancy batch's is set by the step that
+  /// orders its sample keys (k_sort_region_hits, k_hit_bounds) and k_ray_bin gets none; NDT, TSDF and stop-flag batches
+  /// have no such step ahead of the walk and keep the update in k_ray_bin (k_tsdf_flag).
+  uint32_t *binMask() const { return occupancy_mode ? nullptr : m->pool.d_hit_mask.get(); }
+
+  /// `stream`: the compute stream, or the front stream for the early launch (frontHalf).
+  void launchBin(bool bucket, uint32_t seg_capacity, unsigned long long *hit_keys, hipStream_t stream)
   {
     // (small batches -- 128-ray workgroups -- run the instantiation with the small LDS table: more workgroups per CU)
     // tev[1], the kernel's own stop event, is what the next batch's set-up pass waits for (see map_state.h: a stop event
@@ -163,9 +170,9 @@ struct BatchRun
     const bool small = bin_tab_mask < kLtabSmall;
     const auto kernel = small ? (plain ? k_ray_bin<kLtabSmall, true> : k_ray_bin<kLtabSmall, false>) :
                                 (plain ? k_ray_bin<kLtabSize, true> : k_ray_bin<kLtabSize, false>);
-    hipExtLaunchKernelGGL(kernel, dim3(bin_blocks), dim3(bin_threads), 0, s, nullptr, tev[1], 0, m->mc, regionTable(m),
-                          batchScratch(m), static_cast<const RayWalk *>(batchWalks(m).ptr), n_rays,
-                          static_cast<Segment *>(m->segments.ptr), seg_capacity, hit_keys, m->pool.d_hit_mask.get(), ray_shift,
+    hipExtLaunchKernelGGL(kernel, dim3(bin_blocks), dim3(bin_threads), 0, stream, nullptr, tev[1], 0, m->mc,
+                          regionTable(m), batchScratch(m), static_cast<const RayWalk *>(batchWalks(m).ptr), n_rays,
+                          static_cast<Segment *>(m->segments.ptr), seg_capacity, hit_keys, binMask(), ray_shift,
                           bucket ? 1 : 0, bin_rays_per_block, bin_tab_mask);
     mark(1);
     m->tev_pre_walk[ring] = 1;
@@ -188,13 +195,13 @@ struct BatchRun
     {
       hipExtLaunchKernelGGL((k_sort_region_hits<kSortRegionHits, kSortThreads>), dim3(2 * m->walk_workgroups),
                             dim3(kSortThreads), 0, s, nullptr, kSortSmallHits ? nullptr : tev[2].handle, 0, regionTable(m),
-                            batchScratch(m), in, out, m->mc.region_voxels, kSortSmallHits);
+                            batchScratch(m), in, out, m->mc.region_voxels, kSortSmallHits, m->pool.d_hit_mask.get());
     }
     if (kSortSmallHits)
     {
       hipExtLaunchKernelGGL((k_sort_region_hits<kSortSmallHits ? kSortSmallHits : 64u, kSortSmallThreads>),
                             dim3(8 * m->walk_workgroups), dim3(kSortSmallThreads), 0, s, nullptr, tev[2], 0,
-                            regionTable(m), batchScratch(m), in, out, m->mc.region_voxels, 0u);
+                            regionTable(m), batchScratch(m), in, out, m->mc.region_voxels, 0u, m->pool.d_hit_mask.get());
     }
     sort_covers = need_dense ? kSortRegionHits : kSortSmallHits;
     mark(2);
@@ -206,10 +213,50 @@ struct BatchRun
     hipExtLaunchKernelGGL((k_sort_region_hits<kSortRegionHits, kSortThreads>), dim3(2 * m->walk_workgroups),
                           dim3(kSortThreads), 0, s, nullptr, tev[2], 0, regionTable(m), batchScratch(m),
                           static_cast<const unsigned long long *>(m->hit_keys_a.ptr),
-                          static_cast<unsigned long long *>(m->hit_keys_b.ptr), m->mc.region_voxels, kSortSmallHits);
+                          static_cast<unsigned long long *>(m->hit_keys_b.ptr), m->mc.region_voxels, kSortSmallHits,
+                          m->pool.d_hit_mask.get());
     sort_covers = kSortRegionHits;
   }
 
+  /// The set-up pass and the plan on the front stream; then, speculatively, the binning pass and the sample sort.
+  ///
+  /// THE EARLY BINNING PASS.  The speculative k_ray_bin of batch N+1 needs nothing batch N's apply kernels produce -- it
+  /// is fp64 / integer issue, they are chains of dependent loads over a few dozen regions on a nearly empty device.  With
+  /// m->early_bin it is therefore launched on the FRONT stream f, behind k_plan(N+1) and behind m->early_bin_event
+  /// (batch N's walk-phase end tev[3]; its end tev[4] where its tail still uses the key buffers), and runs beside
+  /// k_apply_lists(N) / k_batch_cleanup(N).  The compute stream s waits for the pass's stop event tev[1] ahead of the
+  /// sample sort, so everything queued on s afterwards -- this batch's sort and walk, the hipStreamSynchronize(s) of the
+  /// wrong-guess and exhaustion paths and of a buffer that grows, and whatever entry point comes next: reads, uploads,
+  /// merges, copies, patterns -- is ordered behind it as before.  Only this one kernel leaves the compute stream.
+  ///
+  /// Hazards, one line per buffer the pass reads (R) or writes (W): who used it last, what orders the two.
+  ///   segments              W  read by walk / traversal pass (N): done at tev[3](N) = early_bin_event.
+  ///   hit_keys_a            W  read by sort (N) (radix sort + k_hit_bounds), before walk (N): tev[3](N).  A stop-flag batch N
+  ///                            sorts and replays in both key buffers after its walk: early_bin_event is its tev[4].
+  ///   hit_keys_b            -  not touched by the pass (apply (N) reads it as `sorted`; sort (N+1) on s writes it, in order).
+  ///   events                -  not touched (k_flagged_events (N) reads it on s; the walk (N+1) on s writes it, in order).
+  ///   BatchScratch          W  seg_cursor, hit_end (both by atomicAdd); R seg_offset, info, the workgroup lists: the
+  ///     parity of N+1          per-hash / per-slot arrays exist twice.  This copy was last used by batch N-1, whose tev[4]
+  ///                            the set-up pass (N+1) waited for on f (batch_done_event); then written by k_ray_setup /
+  ///                            k_plan (N+1), on f ahead of the pass.
+  ///   BatchScratch          -  batch N's copy: read by apply / cleanup (N); the pass has no pointer into it.  The arrays
+  ///     parity of N            that exist once (voxel_first_hit, dirty, last_use) are not touched by the pass.
+  ///   walks_buf, wg_regions,   R  parity of N+1: written by k_ray_setup (N+1) on f, ahead; batch N's copies (k_apply_hits
+  ///     wg_region_count           reads its RayWalk records) are other allocations.
+  ///   BatchInfo x 3         R  block N+1 (error word): zeroed by k_plan (N) or the memset on f, written by set-up / plan
+  ///                            (N+1) on f.  Block N is read by apply (N), block N+2 zeroed by k_plan (N+1): not the pass's.
+  ///   rt.vals (+ keys)      R  written by k_ray_setup (N+1) on f, ahead; otherwise by pool growth, uploads, removals and
+  ///                            evictions -- host paths that synchronise s first, and s is behind the pass.
+  ///   d_hit_mask            -  NOT touched: a plain occupancy batch's bits are set by k_sort_region_hits / k_hit_bounds
+  ///                            on s, behind k_batch_cleanup (N) which clears batch N's (binMask()).  This was the one
+  ///                            buffer the pass shared with apply (N): set early, a bit would be read by k_apply_lists
+  ///                            (N) and cleared by k_batch_cleanup (N) before walk (N+1) looks for it.
+  ///   d_miss_counts,        -  not touched by the pass (walk / apply only, all on s).
+  ///     interval_counts
+  ///   d_rays                -  not read by the pass (the RayWalk records carry what it needs).
+  /// Buffers that grow (DevBuf::ensure) synchronise s before they free: behind the pass for the same reason.  The next
+  /// set-up pass waits for bin_done_event as before -- on this route the stop event of k_stream_marker, an empty kernel on
+  /// s between the wait for the pass and the sort (see where it is launched); behind the pass on f the order is implicit.
   int frontHalf()
   {
     // The set-up pass goes to the front stream.  It has to wait for the batch that last used this parity's scratch
@@ -268,20 +315,41 @@ struct BatchRun
       plan_done = m->ev[7];
     }
     OHMHIP_CHECK(hipStreamWaitEvent(s, plan_done, 0));
-    if (m->phase_timing)
-    {
-      OHMHIP_CHECK(hipEventRecord(tev[6], s));
-      mark(6);
-    }
     // The host needs the batch summary (segment count, sample distribution, pool state) before it can size and launch
     // the rest -- a round trip during which the device would idle.  In steady state (occupancy, previous batch sorted
     // its samples per region) the binning and the sample sort are launched right away with the buffers of the previous
     // batch; the summary then only confirms the guess, and a wrong guess costs a repeat of the two passes.
     spec_seg_cap = uint32_t(std::min<size_t>(m->segments.bytes / sizeof(Segment), 0xffffffffu));
     speculated = occupancy_mode && m->spec_bucket_ok && attempt == 0 && spec_seg_cap > 0;
+    binned_early = speculated && m->early_bin && m->early_bin_event != nullptr;
+    // With the early route the binning pass starts on the front stream, so its start marker goes there too.
+    hipStream_t bin_stream = binned_early ? f : s;
+    if (binned_early)
+    {
+      OHMHIP_CHECK(hipStreamWaitEvent(f, m->early_bin_event, 0));
+    }
+    if (m->phase_timing)
+    {
+      OHMHIP_CHECK(hipEventRecord(tev[6], bin_stream));
+      mark(6);
+    }
     if (speculated)
     {
-      launchBin(true, spec_seg_cap, static_cast<unsigned long long *>(m->hit_keys_a.ptr));
+      launchBin(true, spec_seg_cap, static_cast<unsigned long long *>(m->hit_keys_a.ptr), bin_stream);
+      if (binned_early)
+      {
+        // From here on everything on the compute stream -- this batch's sort, a synchronisation after a wrong guess,
+        // the next read, upload, merge, copy or pattern -- is ordered behind the binning pass.
+        OHMHIP_CHECK(hipStreamWaitEvent(s, tev[1], 0));
+        // The next batch's set-up pass must not reach the device ahead of the sort: behind k_ray_bin on the same stream
+        // it would start within a microsecond of the pass's end, take the CUs' LDS and make the dense sort's 66 KiB
+        // workgroups queue for it (measured: first sort launch 57 -> 115-147 us).  On the compute stream the hand-over
+        // through bin_done_event gave the sort ~15 us of lead; here an empty kernel on s behind the wait gives the same:
+        // its stop event, tev[7], is what the next set-up pass waits for (bin_done_event), and it reaches the front
+        // stream one hand-over after the sort -- queued on s right behind the marker -- has been dispatched.
+        hipExtLaunchKernelGGL(k_stream_marker, dim3(1), dim3(64), 0, s, nullptr, tev[7], 0);
+        m->bin_done_event = tev[7];
+      }
       launchRegionSort(m->spec_max_region_hits);
     }
     OHMHIP_CHECK(hipEventSynchronize(plan_done));
@@ -361,6 +429,7 @@ struct BatchRun
                            batchScratch(m));
       }
       speculated = false;
+      binned_early = false;  // (the pass that stands is the one binAndOrder launches on the compute stream)
     }
     return OHMHIP_OK;
   }
@@ -441,7 +510,7 @@ struct BatchRun
     }
     if (!speculated)
     {
-      launchBin(bucket_hits, seg_cap, keys_a);
+      launchBin(bucket_hits, seg_cap, keys_a, s);
       if (tsdf_mode)
       {
         hipExtLaunchKernelGGL(k_tsdf_flag, dim3(ray_blocks), dim3(256), 0, s, nullptr, tev[2], 0, m->mc, regionTable(m),
@@ -464,7 +533,7 @@ struct BatchRun
         OHMHIP_CHECK(rocprim::radix_sort_keys<SortConfig>(m->sort_temp.ptr, temp_bytes, keys_a, keys_b, size_t(n_rays),
                                                           kHitRayBits, sortEndBit(info.n_slots), s));
         hipExtLaunchKernelGGL(k_hit_bounds, dim3(ray_blocks), dim3(256), 0, s, nullptr, tev[2], 0, sorted,
-                              batchScratch(m), m->mc.region_voxels);
+                              batchScratch(m), m->mc.region_voxels, m->pool.d_hit_mask.get());
         mark(2);
         m->tev_pre_walk[ring] = 2;
       }
@@ -869,6 +938,12 @@ struct BatchRun
     }
     mark(4);
     m->batch_done_event[m->parity] = tev[4];
+    // What the next batch's early binning pass waits for: the end of the walk phase -- the last reader of the segment
+    // buffer and of hit_keys_a -- or the end of the batch where the tail still works in the key buffers (stop-flag
+    // replay; NDT / TSDF maps never bin early).
+    m->early_bin_event = occupancy_mode ? tev[3] : tev[4];
+    ++m->count_batches;
+    m->count_binned_early += binned_early ? 1u : 0u;
     OHMHIP_CHECK(hipGetLastError());
 
     m->stats = {};

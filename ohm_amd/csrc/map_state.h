@@ -301,8 +301,9 @@ struct ohmhip_map_s
                                       ///< copies must not delay the re-admissions queued on copy_stream
   /// Stream of a batch's set-up pass (k_ray_setup, k_plan).  It reads the rays and the region table only, and writes
   /// per-batch scratch that exists twice (see `parity`), so the set-up of batch N+1 runs beside the sample sort of batch
-  /// N and in the CUs its walk kernel vacates.  It is idle whenever no batch call is in progress: every call waits for
-  /// its own plan summary.
+  /// N and in the CUs its walk kernel vacates.  Every call waits for its own plan summary, so between calls the stream
+  /// holds at most the call's early binning pass (early_bin_event below), which the compute stream waits for: whatever
+  /// is ordered behind the compute stream is ordered behind the front stream too.
   Stream front_stream;
   /// Cross-stream ordering uses the STOP EVENTS of the kernels themselves (hipExtLaunchKernelGGL binds an event to the
   /// kernel's own completion signal: free), never a hipEventRecord behind a kernel -- on gfx950 / ROCm 7.2 a record is a
@@ -310,15 +311,27 @@ struct ohmhip_map_s
   /// profiles/r05_event_probe.txt; round 4 paid eight of them per batch).  The events live in the timing ring below.
   /// (batch_done_event and bin_done_event name events of the timing ring `tev`: aliases, not owned)
   hipEvent_t batch_done_event[2] = { nullptr, nullptr };  ///< per parity: stop event of the last kernel of the batch that last used this scratch copy
-  hipEvent_t bin_done_event = nullptr;  ///< stop event of the latest k_ray_bin
+  hipEvent_t bin_done_event = nullptr;  ///< stop event of the latest k_ray_bin (early route: of the marker behind it)
+  /// What a batch's EARLY binning pass waits for on the front stream (BatchRun::frontHalf, where the hazards are listed):
+  /// the previous batch's walk-phase end, tev[3], when that was a plain occupancy batch -- its apply kernels then run
+  /// beside the pass --, else that batch's end, tev[4]; null before the first batch.  An alias like the two above.
+  hipEvent_t early_bin_event = nullptr;
+  /// OHMHIP_EARLY_BIN=1 (read at map creation): a speculatively launched k_ray_bin goes to the front stream, behind
+  /// early_bin_event, and the compute stream waits for it ahead of the sample sort.  0, the default: it is launched on
+  /// the compute stream, behind the previous batch's last kernel.  (Off by default: 11-16 us of 848 per C1 batch, every
+  /// run below every run without it, but not three times the run-to-run spread in three jobs of four --
+  /// profiles/r08_notes.md.)
+  bool early_bin = false;
+  uint64_t count_batches = 0, count_binned_early = 0;  ///< ohmhip_map_pipeline_counts
   uint32_t parity = 0;  ///< which copy of the doubled per-batch scratch (RayWalk array, per-hash / per-slot counters,
                         ///< chunk list, event counters) the current batch uses
   Event ev[8];
   /// Events of the last kTimingRing batches: [1] binned, [2] samples ordered (the kernel before the walk), [3] walked,
-  /// [4] batch done, [5] plan done -- all stop events of kernels --, and with `phase_timing` [0] set-up pass starts, [6]
-  /// binning starts (records: they cost the batch a few microseconds each).  tev_mask: which of them the batch recorded;
+  /// [4] batch done, [5] plan done, [7] the marker behind an early binning pass (BatchRun::frontHalf) -- all stop events
+  /// of kernels --, and with `phase_timing` [0] set-up pass starts, [6] binning starts (on the stream the pass runs on;
+  /// records: they cost the batch a few microseconds each).  tev_mask: which of [0] .. [6] the batch recorded;
   /// tev_pre_walk: the event that marks the start of the batch's walk phase ([2], or [1] when nothing ran in between).
-  Event tev[kTimingRing][7];
+  Event tev[kTimingRing][8];
   uint8_t tev_mask[kTimingRing] = {};
   uint8_t tev_pre_walk[kTimingRing] = {};
   bool phase_timing = false;  ///< ohmhip_map_set_phase_timing / OHMHIP_PHASE_TIMING=1 / OHMHIP_DEBUG_FLAGS & 256

@@ -251,6 +251,10 @@ try
   {
     m->min_chunk_segments = uint32_t(std::max(64, std::min(int(kMaxChunkSegments), std::atoi(env))));
   }
+  if (const char *env = std::getenv("OHMHIP_EARLY_BIN"))
+  {
+    m->early_bin = std::atoi(env) != 0;
+  }
   // Small regions (16^3: at most an eighth of the tile the full shape serves) are walked by half-size workgroups, two
   // per CU.  Measured with the C1 sweep (scripts/half_probe.py, profiles/r06_notes.md): 16^3 regions 1.40 against 1.55 ms
   // per batch; 16 x 16 x 32 regions 1.23 against 1.20 (a wash); 32 x 32 x 16 regions 1.14 against 0.96 -- those hold
@@ -742,6 +746,24 @@ try
     m->launch_thread->wait();
   }
   *count = m->batch_seq;
+  return OHMHIP_OK;
+}
+OHMHIP_ABI_CATCH
+
+int ohmhip_map_pipeline_counts(ohmhip_map_t m, uint64_t *batches, uint64_t *binned_early)
+try
+{
+  if (!m || !batches || !binned_early)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  // (like ohmhip_map_batches_launched: no flush of collected rays, a launch on the map's own thread is waited for)
+  if (m->launch_busy)
+  {
+    m->launch_thread->wait();
+  }
+  *batches = m->count_batches;
+  *binned_early = m->count_binned_early;
   return OHMHIP_OK;
 }
 OHMHIP_ABI_CATCH

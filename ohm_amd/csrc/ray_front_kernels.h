@@ -908,6 +908,11 @@ __global__ void __launch_bounds__(1024)
 // Three steps per workgroup: count its segments per region in LDS, reserve one contiguous range per region with a
 // single returning atomic, then re-enumerate and scatter through LDS cursors.
 //
+// hit_mask: null for a plain occupancy batch.  There the step that orders the sample keys sets the mask
+// (k_sort_region_hits / k_hit_bounds: one atomic per voxel that receives samples instead of one per ray), and the pass
+// writes nothing the previous batch's apply kernels still use -- which is what lets BatchRun::frontHalf launch it beside
+// them.  NDT, TSDF and stop-flag batches order their samples with their events and keep the mask update here.
+//
 // kPlain: the instantiation for a map that is not partitioned (owner_world <= 1) and whose region edges are all powers
 // of two -- the default map.  Both are known when the batch is launched (BatchRun::launchBin); the kernel then carries
 // neither the ownership test nor the floor-modulo alternative of the local voxel coordinates through its
@@ -996,7 +1001,10 @@ __global__ void __launch_bounds__(kBinThreads)
       if (slot < rt.slot_capacity)
       {
         hk = packHitKey(slot, vi, ray, ray_shift);
-        atomicOr(&hit_mask[size_t(slot) * mask_words + (vi >> 5)], 1u << (vi & 31));
+        if (hit_mask)
+        {
+          atomicOr(&hit_mask[size_t(slot) * mask_words + (vi >> 5)], 1u << (vi & 31));
+        }
       }
     }
     if (!bucket_hits || hk != kHitInvalid)

@@ -3,6 +3,7 @@
 //   k_sort_region_hits  1 workgroup/region order a region's sample keys by (voxel, ray) in LDS
 //                                          (fallback for very dense regions: device-wide radix sort + k_hit_bounds)
 //   k_reset_cursors     1 lane / region    undo a binning pass's cursor movement so that it can be repeated
+//   k_stream_marker     empty              a stop event between two kernels of a stream (BatchRun::frontHalf)
 #ifndef OHMHIP_SAMPLE_SORT_KERNELS_H
 #define OHMHIP_SAMPLE_SORT_KERNELS_H
 
@@ -12,10 +13,11 @@
 namespace ohmhip
 {
 // ---------------------------------------------------------------------------------------------------------------------
-// k_hit_bounds: [begin, end) of each region slot in the sorted hit list.
+// k_hit_bounds: [begin, end) of each region slot in the sorted hit list, and the sample mask bit of every voxel in it.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
-  k_hit_bounds(const unsigned long long *__restrict__ sorted, BatchScratch bs, int region_voxels)
+  k_hit_bounds(const unsigned long long *__restrict__ sorted, BatchScratch bs, int region_voxels,
+               uint32_t *__restrict__ hit_mask)
 {
   const uint32_t n_hits = bs.info->n_hits;
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -31,6 +33,7 @@ __global__ void __launch_bounds__(256)
     const uint32_t slot = hitSlot(sorted[i]);
     const uint32_t vi = hitVoxel(sorted[i]);
     bs.voxel_first_hit[size_t(slot) * size_t(region_voxels) + vi] = i;
+    atomicOr(&hit_mask[size_t(slot) * (uint32_t(region_voxels + 31) >> 5) + (vi >> 5)], 1u << (vi & 31));
   }
   const uint32_t slot = hitSlot(sorted[i]);
   if (i == 0 || hitSlot(sorted[i - 1]) != slot)
@@ -108,9 +111,11 @@ constexpr int kSortSmallThreads = 256;
 template <uint32_t kCap, int kThreads>
 __global__ void __launch_bounds__(kThreads)
   k_sort_region_hits(RegionTable rt, BatchScratch bs, const unsigned long long *__restrict__ keys,
-                     unsigned long long *__restrict__ sorted, int region_voxels, uint32_t min_hits)
+                     unsigned long long *__restrict__ sorted, int region_voxels, uint32_t min_hits,
+                     uint32_t *__restrict__ hit_mask)
 {
   __shared__ unsigned long long l_keys[kCap + kCap / 32];
+  const uint32_t mask_words = uint32_t(region_voxels + 31) >> 5;
   // Grid-stride over the list (its length lives on the device: the launch may be issued before the host knows it).
   const uint32_t n_regions = bs.info->n_hit_regions;
   for (uint32_t list_index = blockIdx.x; list_index < n_regions; list_index += gridDim.x)
@@ -169,20 +174,47 @@ __global__ void __launch_bounds__(kThreads)
       j >>= r;
     }
   }
-  for (uint32_t i = threadIdx.x; i < n; i += kThreads)
+  for (uint32_t base = 0; base < n; base += kThreads)  // (every lane takes every trip: the shuffles below)
   {
-    const unsigned long long key = l_keys[sortSlot(i)];
-    sorted[begin + i] = key;
-    if (i == 0 || hitGroup(l_keys[sortSlot(i - 1)]) != hitGroup(key))
+    const uint32_t i = base + threadIdx.x;
+    uint32_t word = 0xffffffffu, bits = 0;
+    if (i < n)
     {
-      // First sample of its voxel: entry point for ordering misses against this voxel's samples.
+      const unsigned long long key = l_keys[sortSlot(i)];
+      sorted[begin + i] = key;
       const uint32_t vi = hitVoxel(key);
-      bs.voxel_first_hit[size_t(slot) * size_t(region_voxels) + vi] = begin + i;
+      word = vi >> 5;
+      if (i == 0 || hitGroup(l_keys[sortSlot(i - 1)]) != hitGroup(key))
+      {
+        // First sample of its voxel: entry point for ordering misses against this voxel's samples, and the voxel's bit
+        // of the sample mask.
+        bs.voxel_first_hit[size_t(slot) * size_t(region_voxels) + vi] = begin + i;
+        bits = 1u << (vi & 31);
+      }
+    }
+    // The keys are in voxel order, so the lanes of a wave whose voxels share a mask word are neighbours: their bits are
+    // ORed along each such run and the run's last lane sets them with one atomic (one per voxel, from neighbouring lanes
+    // to the same address, cost the two sort launches 32 us per C1 batch).
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1)
+    {
+      const uint32_t up_bits = __shfl_up(bits, d, 64);
+      const uint32_t up_word = __shfl_up(word, d, 64);
+      bits |= (lane >= d && up_word == word) ? up_bits : 0u;
+    }
+    const uint32_t next_word = __shfl_down(word, 1u, 64);
+    if (bits && (lane == 63u || next_word != word))
+    {
+      atomicOr(&hit_mask[size_t(slot) * mask_words + word], bits);
     }
   }
   __syncthreads();  // l_keys is reused by the next region
   }  // regions
 }
+
+/// Nothing: a place in a stream whose stop event another stream can wait for.
+__global__ void k_stream_marker() {}
 
 /// Undo the cursor movement of a k_ray_bin pass over the touched regions (segment cursors back to zero, sample cursors
 /// back to the start of the region's range) so the pass can be repeated with other launch parameters.

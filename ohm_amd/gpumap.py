@@ -458,6 +458,13 @@ class GpuMap(RayMapper):
         L.check(L.lib.ohmhip_map_batches_launched(self._handle, C.byref(n)), "batches_launched")
         return int(n.value)
 
+    def pipelineCounts(self):
+        """(device batches completed, those whose binning pass ran early on the front stream and stood) since the map
+        was created (include/ohmhip.h: ohmhip_map_pipeline_counts).  Read only."""
+        batches, early = C.c_uint64(0), C.c_uint64(0)
+        L.check(L.lib.ohmhip_map_pipeline_counts(self._handle, C.byref(batches), C.byref(early)), "pipeline_counts")
+        return int(batches.value), int(early.value)
+
     def raysBeyondTiles(self):
         """Maps with regions above 32768 voxels: rays cut because a tile coordinate left the key range although the
         reference addresses the region (include/ohmhip.h: ohmhip_map_rays_beyond_tiles).  0 for ordinary regions."""
