@@ -1035,6 +1035,91 @@ int ohmhip_map_can_copy(ohmhip_map_t dst, ohmhip_map_t src);
 int ohmhip_map_copy(ohmhip_map_t dst, ohmhip_map_t src, const ohmhip_copy_params *params /* NULL: everything */,
                     ohmhip_copy_stats *stats /* optional */);
 
+/* MAP COMPARE.  ohm::compare::compareVoxels (ohm/CompareMaps.h:139, ohm/CompareMaps.cpp:334-386), the rule ohmcmp is
+ * built on (utils/ohmcmp/ohmcmp.cpp:356-386), between two device maps: one layer of `eval` held against the same layer
+ * of `ref`, member by member, on the device -- only the result and the two lists cross the host link.
+ * tests/compare_ref.py restates K3 - K5 on the CPU.
+ *  K1 compatibility: both maps must have equal region voxel dimensions, else OHMHIP_ERR_INVALID_ARG (the reference would
+ *     index one map's block with the other's key, CompareMaps.cpp:364-373).  Resolution, origin and mode are not looked
+ *     at, as in compareVoxels.  eval == ref is allowed.  Region ownership or a partition on either map:
+ *     OHMHIP_ERR_UNSUPPORTED (a rank holds only its territory).
+ *  K2 layout (compareLayoutLayer, CompareMaps.cpp:78-144): a layer id has one layout here, so the layouts match exactly
+ *     when both maps hold layer_id.  Without a match result->layout_match = 0, every count is 0 and the call returns
+ *     OHMHIP_OK (:339-344: a result, not an error); member_count is the layer's in either case.  The members, all 4
+ *     bytes and of one type per layer (ohm/DefaultLayer.cpp:85-303): occupancy {occupancy f32}; mean {coord, count u32};
+ *     covariance {P00, P01, P11, P02, P12, P22 f32}; traversal {traversal f32}; touch_time {touch u32}; incident_normal
+ *     {packed_normal u32}; intensity {mean, cov f32}; hit_miss_count {hit_count, miss_count u32}; tsdf {weight,
+ *     distance f32}; clearance {clearance f32}.  A tolerance_members bit at or above the layer's member count:
+ *     OHMHIP_ERR_INVALID_ARG.
+ *  K3 what is visited (CompareMaps.cpp:359-383): every voxel of every region of ref, narrowed by keys_xyz to the listed
+ *     regions; a key ref does not hold is skipped and counted in keys_absent, a repeated key counts once.  Regions only
+ *     eval holds are ignored.  A region eval lacks fails every one of its dx * dy * dz voxels: it counts in
+ *     regions_missing, is listed in missing_regions_xyz, and adds nothing to the mismatch list, member_failed or
+ *     member_max_diff (compareVoxel returns before it logs, :197-205).  A tile of a tiled region (LARGE REGIONS) that one
+ *     map lacks, inside a region that map does hold, reads as the layer's clear word (occupancy +inf, clearance -1,
+ *     zeros otherwise).  regions_compared, regions_missing and keys_absent describe the selection, with or without
+ *     OHMHIP_CMP_CONTINUE.
+ *  K4 one voxel (compareVoxel :207-331, compareDatum :58-75): every member is judged; a voxel passes when all its
+ *     members pass.  Member i without its tolerance_members bit passes when its 4 bytes are equal (:313-318).  With the
+ *     bit: eps = the low 4 bytes of tolerance_bits[i] read as the member's type T; hi, lo = the two values, exchanged
+ *     only when ref > val (:69-72); the member passes when hi == lo || (hi - lo) <= eps (:74), for f32 the subtraction
+ *     and both comparisons in fp32 with subnormals kept, for u32 unsigned.  Hence: a NaN on either side fails under any
+ *     tolerance (eps = +inf and identical NaN bits included) and passes the byte comparison when the bits are equal;
+ *     +0 against -0 passes with a tolerance and fails without; +-inf against itself passes; inf against FLT_MAX fails for
+ *     every finite eps; a NaN or negative eps passes equal values only; a subnormal difference is not zero; FLT_MAX
+ *     against -FLT_MAX overflows to inf.
+ *  K5 order and stopping.  The reference iterates a hash map; this library fixes the order of POINT CLOUDS' ORDER rule:
+ *     regions ascending by (rz, ry, rx), voxels by MapChunk index x + y * dx + z * dx * dy, for tiled regions too.
+ *     With OHMHIP_CMP_CONTINUE everything is compared: mismatch_keys10 receives the first min(mismatch_count,
+ *     mismatch_capacity) failing voxels of the regions both maps hold, in order, as 10-byte key records (int16
+ *     region[3], uint8 voxel[3], and in byte 9 the mask of failing members); missing_regions_xyz the first
+ *     min(missing_count, missing_capacity) regions eval lacks, in order; member_failed[i] counts the voxels whose member
+ *     i failed; member_max_diff[i] is the largest hi - lo of member i over the visited voxels of regions both maps hold
+ *     where neither side is a NaN -- a float's bits in the low word, possibly inf -- and 0 when there is none (a
+ *     difference that is itself a NaN, inf against itself, does not count; a zero of either sign is +0).
+ *     Without the flag (the reference's default, OHM_CMP_FAIL, CompareMaps.h:18-22) the result is the one a sequential
+ *     walk in that order returns at its first failure: voxels_failed 1 or 0, voxels_passed the voxels ahead of it,
+ *     mismatch_count + missing_count <= 1 with that one entry in its list, member_failed the failing voxel's mask as
+ *     0 / 1 (all zero when the failure is a region eval lacks), member_max_diff all zero.
+ *  K6 both maps are only read: each is settled first (collected rays launched, an asynchronous launch finished); after
+ *     that no voxel, dirty bit, residency, use stamp or cache counter of either changes.  Regions in a host store (SPILL
+ *     TO HOST) are read where they lie.  Nothing that determines an output uses an atomic: two calls return identical
+ *     bytes.
+ *  K7 capacities: a capacity of 0 (its array may be NULL) only counts; the totals are always complete.
+ *     OHMHIP_ERR_INVALID_ARG, before any device work, for a null map, params or result, unknown flag bits, layer_id
+ *     outside 0 .. OHMHIP_LID_COUNT - 1, a non-zero capacity with a null array, keys_xyz non-null with key_count 0 or the
+ *     reverse, and the refusals of K1 / K2.  ohmhip_map_compare is blocking. */
+#define OHMHIP_CMP_CONTINUE (1u << 0) /* ohm::compare::kContinue (CompareMaps.h:44) */
+#define OHMHIP_CMP_MAX_MEMBERS 6
+typedef struct ohmhip_compare_params
+{
+  unsigned flags;
+  int layer_id;
+  unsigned tolerance_members;                      /* bit i: member i is compared with a tolerance */
+  uint64_t tolerance_bits[OHMHIP_CMP_MAX_MEMBERS]; /* memberClearValue of the reference's tolerance object */
+  const int16_t *keys_xyz;                         /* optional; NULL => every region of ref */
+  size_t key_count;
+} ohmhip_compare_params;
+typedef struct ohmhip_compare_result
+{
+  uint64_t voxels_passed, voxels_failed; /* VoxelsResult (CompareMaps.h:48-56) */
+  int32_t layout_match;
+  uint32_t member_count;
+  uint64_t regions_compared, regions_missing, keys_absent;
+  uint64_t mismatch_count, missing_count; /* totals, whatever the capacities */
+  uint64_t member_failed[OHMHIP_CMP_MAX_MEMBERS];
+  uint64_t member_max_diff[OHMHIP_CMP_MAX_MEMBERS]; /* float members: the float's bits in the low word */
+} ohmhip_compare_result;
+int ohmhip_map_compare(ohmhip_map_t eval, ohmhip_map_t ref, const ohmhip_compare_params *params,
+                       uint64_t mismatch_capacity, void *mismatch_keys10, uint64_t missing_capacity,
+                       int16_t *missing_regions_xyz, ohmhip_compare_result *result);
+/* The same with the two lists and the result in DEVICE memory, enqueued on ref's stream; ohmhip_map_sync(ref) is the
+ * fence.  params and its key list stay host memory: the work list is laid out on the host. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_compare_device(ohmhip_map_t eval, ohmhip_map_t ref,
+                                                  const ohmhip_compare_params *params, uint64_t mismatch_capacity,
+                                                  void *d_mismatch_keys10, uint64_t missing_capacity,
+                                                  int16_t *d_missing_regions_xyz, ohmhip_compare_result *d_result);
+
 /* Multi-GPU merge support (no reference equivalent -- ohm is single device).  The resident layer of a
  * map is one allocation of region_stride_bytes per slot: ohm_amd/distributed.py wraps it as a device tensor and runs
  * the RCCL all-reduce of touched-region occupancy deltas on it.  ensure_regions makes regions resident (cleared)

@@ -11,6 +11,8 @@ from .gpumap import (GpuMap, GpuNdtMap, GpuTransformSamples, GpuTsdfMap, LineKey
 from .raypattern import ClearingPattern, RayPattern, RayPatternConical  # noqa: F401
 from .copyutil import (canCopy, copyMap, copyFilterExtents, copyFilterDirty, copyFilterAnd, copyFilterOr,  # noqa: F401
                        copyFilterNegate, copyLayersFilter)
+from .compare import (Severity, kContinue, VoxelsResult, Tolerance, VoxelMismatch, configureTolerance,  # noqa: F401
+                      compareLayoutLayer, compareVoxels, occupancy_stats, compare_maps, default_tolerances)
 from .heightmap import Heightmap, HeightmapMode, HeightmapVoxelType, UpAxis, HEIGHTMAP_VOXEL_DTYPE  # noqa: F401
 from .cloud import (CloudMode, VoxelCloud, GPU_KEY_DTYPE, CLOUD_CHUNK_VOXELS, cloud_params, count_cloud,  # noqa: F401
                     extract_cloud, write_ply, save_cloud, save_density_cloud, save_tsdf_cloud, save_clearance_cloud,

@@ -116,6 +116,23 @@ class CopyStats(C.Structure):
 
 COPY_DIRTY_ONLY, COPY_USE_EXTENTS = 1, 2
 
+CMP_CONTINUE = 1
+CMP_MAX_MEMBERS = 6  # OHMHIP_CMP_MAX_MEMBERS
+
+
+class CompareParams(C.Structure):
+    """ohmhip_compare_params"""
+    _fields_ = [("flags", C.c_uint), ("layer_id", C.c_int), ("tolerance_members", C.c_uint),
+                ("tolerance_bits", C.c_uint64 * CMP_MAX_MEMBERS), ("keys_xyz", C.c_void_p), ("key_count", C.c_size_t)]
+
+
+class CompareResult(C.Structure):
+    """ohmhip_compare_result"""
+    _fields_ = [("voxels_passed", C.c_uint64), ("voxels_failed", C.c_uint64), ("layout_match", C.c_int32),
+                ("member_count", C.c_uint32), ("regions_compared", C.c_uint64), ("regions_missing", C.c_uint64),
+                ("keys_absent", C.c_uint64), ("mismatch_count", C.c_uint64), ("missing_count", C.c_uint64),
+                ("member_failed", C.c_uint64 * CMP_MAX_MEMBERS), ("member_max_diff", C.c_uint64 * CMP_MAX_MEMBERS)]
+
 
 class MapConfig(C.Structure):
     _fields_ = [("resolution", C.c_double), ("region_dim", C.c_int * 3), ("origin", C.c_double * 3),
@@ -217,6 +234,9 @@ _sigs = {
                                            C.POINTER(C.c_size_t)]),
     "ohmhip_map_can_copy": (C.c_int, [_vp, _vp]),
     "ohmhip_map_copy": (C.c_int, [_vp, _vp, C.POINTER(CopyParams), C.POINTER(CopyStats)]),
+    "ohmhip_map_compare": (C.c_int, [_vp, _vp, C.POINTER(CompareParams), C.c_uint64, _vp, C.c_uint64, _vp,
+                                     C.POINTER(CompareResult)]),
+    "ohmhip_map_compare_device": (C.c_int, [_vp, _vp, C.POINTER(CompareParams), C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
     "ohmhip_map_batch_timings": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_float)]),
     "ohmhip_comm_exchange_side": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "ohmhip_gather_rows": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp]),

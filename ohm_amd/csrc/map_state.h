@@ -424,6 +424,10 @@ struct ohmhip_map_s
     DevBuf pf_points, pf_status, pf_values, pf_keys, pf_kept;
     ScanScratch pf_scan;
     PinnedBuf<char> pf_staging;
+    /// map compare (compare_kernels.h), on the REFERENCE map: the work list, a record per chunk, per-wave failed
+    /// counts and their scan; device copies of the host variant's lists and result
+    DevBuf compare_chunks, compare_records, compare_keys, compare_missing, compare_result;
+    ScanScratch compare_scan;
   } query;
   /// The clearance layer's bookkeeping (clearance_update.h), by the caller's region key -- so it needs no care when a
   /// region changes slot, leaves the pool or comes back.  An update folds the kDirtyClearance bits into `changed` at a

@@ -20,6 +20,7 @@
 #include "neighbours_kernels.h"
 #include "point_filter_kernels.h"
 #include "copy_kernels.h"
+#include "compare_kernels.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -1010,3 +1011,4 @@ OHMHIP_ABI_CATCH
 #include "point_filter_impl.h"
 #include "pattern_impl.h"
 #include "copy_impl.h"
+#include "compare_impl.h"

@@ -1399,6 +1399,240 @@ inline std::unique_ptr<GpuMap> GpuMap::clone(const dvec3 &min_ext, const dvec3 &
   return other;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// ohm/CompareMaps.h over ohmhip_map_compare (include/ohmhip.h, MAP COMPARE): compareLayoutLayer, compareVoxels and
+// configureTolerance on two GpuMaps.  The comparison runs on the device; the result and the listed mismatches cross over.
+namespace compare
+{
+/// ohm::compare::Severity
+enum class Severity
+{
+  kInfo,
+  kWarning,
+  kError
+};
+
+/// ohm::compare::Flag
+enum Flag : unsigned
+{
+  kZero = 0u,
+  kContinue = OHMHIP_CMP_CONTINUE
+};
+
+/// ohm::compare::VoxelsResult, and beside it what the device call reports: every field of ohmhip_compare_result, the
+/// listed mismatches (voxel[3] = the mask of failing members) and the listed regions the evaluated map lacks.
+struct VoxelsResult
+{
+  size_t voxels_passed = 0;
+  size_t voxels_failed = 0;
+  bool layout_match = false;
+  int status = OHMHIP_OK;
+  ohmhip_compare_result detail{};
+  std::vector<CloudKey> mismatches;
+  std::vector<std::array<int16_t, 3>> missing_regions;
+  explicit operator bool() const { return voxels_failed == 0 && layout_match; }
+};
+
+using Log = std::function<void(Severity, const std::string &)>;
+inline void emptyLog(Severity, const std::string &) {}
+
+/// The members of a layer in voxel order, all 4 bytes (ohm/DefaultLayer.cpp:85-303); is_float[i] says how member i reads.
+struct LayerMembers
+{
+  std::vector<std::string> names;
+  unsigned float_mask = 0;
+};
+
+inline LayerMembers layerMembers(int layer_id)
+{
+  switch (layer_id)
+  {
+  case OHMHIP_LID_OCCUPANCY: return { { "occupancy" }, 0x1u };
+  case OHMHIP_LID_MEAN: return { { "coord", "count" }, 0x0u };
+  case OHMHIP_LID_COVARIANCE: return { { "P00", "P01", "P11", "P02", "P12", "P22" }, 0x3fu };
+  case OHMHIP_LID_TRAVERSAL: return { { "traversal" }, 0x1u };
+  case OHMHIP_LID_TOUCH_TIME: return { { "touch" }, 0x0u };
+  case OHMHIP_LID_INCIDENT: return { { "packed_normal" }, 0x0u };
+  case OHMHIP_LID_INTENSITY: return { { "mean", "cov" }, 0x3u };
+  case OHMHIP_LID_HIT_MISS: return { { "hit_count", "miss_count" }, 0x0u };
+  case OHMHIP_LID_TSDF: return { { "weight", "distance" }, 0x3u };
+  case OHMHIP_LID_CLEARANCE: return { { "clearance" }, 0x1u };
+  default: return {};
+  }
+}
+
+inline int layerIdByName(const std::string &layer_name)
+{
+  for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
+  {
+    if (layer_name == copyLayerName(l))
+    {
+      return l;
+    }
+  }
+  return -1;
+}
+
+/// Stands for the reference's dummy MapLayer: member names with the 64-bit clear values that hold the allowed errors.
+/// The compared member's own type reads the stored bytes (CompareMaps.cpp:248-304).
+struct Tolerance
+{
+  explicit Tolerance(std::string layer) : layer_name(std::move(layer)) {}
+  std::string layer_name;
+  std::vector<std::pair<std::string, uint64_t>> members;
+  int indexOf(const std::string &member_name) const
+  {
+    for (size_t i = 0; i < members.size(); ++i)
+    {
+      if (members[i].first == member_name)
+      {
+        return int(i);
+      }
+    }
+    return -1;
+  }
+};
+
+/// ohm::compare::configureTolerance (CompareMaps.cpp:396-469): the absolute value, its typed bytes in the low end.
+inline void configureTolerance(Tolerance &layer, const char *member_name, float epsilon)
+{
+  epsilon = std::fabs(epsilon);
+  uint64_t e = 0;
+  std::memcpy(&e, &epsilon, sizeof(epsilon));
+  layer.members.emplace_back(member_name, e);
+}
+inline void configureTolerance(Tolerance &layer, const char *member_name, double epsilon)
+{
+  epsilon = std::fabs(epsilon);
+  uint64_t e = 0;
+  std::memcpy(&e, &epsilon, sizeof(epsilon));
+  layer.members.emplace_back(member_name, e);
+}
+inline void configureTolerance(Tolerance &layer, const char *member_name, uint8_t epsilon) { layer.members.emplace_back(member_name, uint64_t(epsilon)); }
+inline void configureTolerance(Tolerance &layer, const char *member_name, uint16_t epsilon) { layer.members.emplace_back(member_name, uint64_t(epsilon)); }
+inline void configureTolerance(Tolerance &layer, const char *member_name, uint32_t epsilon) { layer.members.emplace_back(member_name, uint64_t(epsilon)); }
+inline void configureTolerance(Tolerance &layer, const char *member_name, uint64_t epsilon) { layer.members.emplace_back(member_name, epsilon); }
+inline void configureTolerance(Tolerance &layer, const char *member_name, int8_t epsilon) { layer.members.emplace_back(member_name, uint64_t(std::abs(int(epsilon)))); }
+inline void configureTolerance(Tolerance &layer, const char *member_name, int16_t epsilon) { layer.members.emplace_back(member_name, uint64_t(std::abs(int(epsilon)))); }
+inline void configureTolerance(Tolerance &layer, const char *member_name, int32_t epsilon) { layer.members.emplace_back(member_name, uint64_t(std::llabs(int64_t(epsilon)))); }
+inline void configureTolerance(Tolerance &layer, const char *member_name, int64_t epsilon) { layer.members.emplace_back(member_name, uint64_t(epsilon < 0 ? -uint64_t(epsilon) : uint64_t(epsilon))); }
+
+/// ohm::compare::compareLayoutLayer (CompareMaps.cpp:78-144): a layer has one layout in this library, so what is left to
+/// check is that both maps hold it.
+inline bool compareLayoutLayer(const GpuMap &eval_map, const GpuMap &ref_map, const std::string &layer_name, unsigned flags = 0,
+                               const Log &log = emptyLog)
+{
+  (void)flags;
+  const int layer = layerIdByName(layer_name);
+  bool ok = true;
+  if (layer < 0 || !ref_map.map().hasLayer(layer))
+  {
+    log(Severity::kError, "the reference map holds no layer named " + layer_name);
+    ok = false;
+  }
+  if (layer < 0 || !eval_map.map().hasLayer(layer))
+  {
+    log(Severity::kError, "the evaluated map holds no layer named " + layer_name);
+    ok = false;
+  }
+  return ok;
+}
+
+/// ohm::compare::compareVoxels (CompareMaps.cpp:334-386) on the device.  With a log other than emptyLog the first
+/// max_logged failing voxels of regions both maps hold are fetched (readVoxels) and reported member by member at
+/// Severity::kError; the two lists of the result hold up to max_logged entries either way.
+inline VoxelsResult compareVoxels(GpuMap &eval_map, GpuMap &ref_map, const std::string &layer_name,
+                                  const Tolerance *tolerance = nullptr, unsigned flags = 0, const Log &log = emptyLog,
+                                  size_t max_logged = 1024)
+{
+  VoxelsResult result;
+  if (!compareLayoutLayer(eval_map, ref_map, layer_name, flags, log))
+  {
+    return result;
+  }
+  const int layer = layerIdByName(layer_name);
+  const LayerMembers members = layerMembers(layer);
+  ohmhip_compare_params params;
+  std::memset(&params, 0, sizeof(params));
+  params.flags = flags;
+  params.layer_id = layer;
+  for (size_t i = 0; tolerance && i < members.names.size(); ++i)
+  {
+    const int at = tolerance->indexOf(members.names[i]);
+    if (at != -1)
+    {
+      params.tolerance_members |= 1u << i;
+      params.tolerance_bits[i] = tolerance->members[size_t(at)].second;
+    }
+  }
+  result.mismatches.resize(max_logged);
+  std::vector<int16_t> missing(3 * max_logged);
+  result.status = ohmhip_map_compare(eval_map.handle(), ref_map.handle(), &params, max_logged,
+                                     max_logged ? result.mismatches.data() : nullptr, max_logged,
+                                     max_logged ? missing.data() : nullptr, &result.detail);
+  if (result.status != OHMHIP_OK)
+  {
+    result.mismatches.clear();
+    return result;
+  }
+  result.voxels_passed = size_t(result.detail.voxels_passed);
+  result.voxels_failed = size_t(result.detail.voxels_failed);
+  result.layout_match = result.detail.layout_match != 0;
+  result.mismatches.resize(size_t(std::min<uint64_t>(result.detail.mismatch_count, max_logged)));
+  for (size_t i = 0; i < size_t(std::min<uint64_t>(result.detail.missing_count, max_logged)); ++i)
+  {
+    result.missing_regions.push_back({ { missing[3 * i], missing[3 * i + 1], missing[3 * i + 2] } });
+  }
+  if (log.target<void (*)(Severity, const std::string &)>() &&
+      *log.target<void (*)(Severity, const std::string &)>() == &emptyLog)
+  {
+    return result;
+  }
+  std::vector<CloudKey> where = result.mismatches;
+  for (CloudKey &key : where)
+  {
+    key.voxel[3] = 0;
+  }
+  std::vector<uint8_t> have, expect, present;
+  if (where.empty() || eval_map.readVoxels(layer, where, have, present) != OHMHIP_OK ||
+      ref_map.readVoxels(layer, where, expect, present) != OHMHIP_OK)
+  {
+    return result;
+  }
+  const size_t count = members.names.size();
+  for (size_t n = 0; n < where.size(); ++n)
+  {
+    for (size_t i = 0; i < count; ++i)
+    {
+      if (!((result.mismatches[n].voxel[3] >> i) & 1u))
+      {
+        continue;
+      }
+      uint32_t h, e;
+      std::memcpy(&h, &have[(n * count + i) * 4], 4);
+      std::memcpy(&e, &expect[(n * count + i) * 4], 4);
+      std::string text = layer_name + " voxel (" + std::to_string(where[n].region[0]) + "," + std::to_string(where[n].region[1]) +
+                         "," + std::to_string(where[n].region[2]) + "):(" + std::to_string(where[n].voxel[0]) + "," +
+                         std::to_string(where[n].voxel[1]) + "," + std::to_string(where[n].voxel[2]) + ") differs in " +
+                         members.names[i] + ": eval holds ";
+      if ((members.float_mask >> i) & 1u)
+      {
+        float hf, ef;
+        std::memcpy(&hf, &h, 4);
+        std::memcpy(&ef, &e, 4);
+        text += std::to_string(hf) + ", ref holds " + std::to_string(ef);
+      }
+      else
+      {
+        text += std::to_string(h) + ", ref holds " + std::to_string(e);
+      }
+      log(Severity::kError, text);
+    }
+  }
+  return result;
+}
+}  // namespace compare
+
 /// Quaternion in (x, y, z, w) member order (glm::dquat exposes the same members; its memory order depends on the glm
 /// version, ohmgpu/GpuTransformSamples.cpp:169-174).
 struct dquat

@@ -435,6 +435,67 @@ int main(int argc, char **argv)
       return 0;
     }
 
+    if (mode == "compare")
+    {
+      // ohm::compare::compareVoxels between two GpuMaps: every ray but the last into the reference map, every ray into
+      // the evaluated one.  out.bin = three comparisons of the occupancy layer -- kContinue, stop-at-first, kContinue with
+      // ohmcmp's tolerance --, each as: the ohmhip_compare_result, u64 listed mismatches + their 10-byte keys, u64
+      // listed missing regions + their keys, u64 messages logged.
+      ohm::OccupancyMap ref_map(resolution), eval_map(resolution);
+      ohm::GpuMap ref(&ref_map, true), eval(&eval_map, true);
+      if (rays.size() < 4 || ref.integrateRays(rays.data(), rays.size() - 2) != rays.size() - 2 ||
+          eval.integrateRays(rays.data(), rays.size()) != rays.size())
+      {
+        return 7;
+      }
+      if (!ohm::compare::compareLayoutLayer(eval, ref, "occupancy") || ohm::compare::compareLayoutLayer(eval, ref, "mean") ||
+          ohm::compare::compareVoxels(eval, ref, "mean").layout_match)
+      {
+        return 8;
+      }
+      // ohmcmp's occupancy tolerance: it forgives one more ray where both maps had observed the voxel
+      ohm::compare::Tolerance loose("occupancy");
+      ohm::compare::configureTolerance(loose, "occupancy", 1e2f);
+      ohm::compare::configureTolerance(loose, "count", uint32_t(1));  // (a name the layer lacks is ignored)
+      if (!ohm::compare::compareVoxels(ref, ref, "occupancy"))
+      {
+        return 8;
+      }
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      for (int pass = 0; pass < 3; ++pass)
+      {
+        const unsigned flags = (pass == 1) ? unsigned(ohm::compare::kZero) : unsigned(ohm::compare::kContinue);
+        uint64_t logged = 0;
+        const ohm::compare::VoxelsResult res =
+          ohm::compare::compareVoxels(eval, ref, "occupancy", pass == 2 ? &loose : nullptr, flags,
+                                      [&logged](ohm::compare::Severity severity, const std::string &) {
+                                        logged += severity == ohm::compare::Severity::kError ? 1u : 0u;
+                                      });
+        if (res.status != OHMHIP_OK || (pass < 2 && bool(res)))
+        {
+          std::fclose(out);
+          return 8;
+        }
+        std::fwrite(&res.detail, sizeof(res.detail), 1, out);
+        const uint64_t n_keys = res.mismatches.size(), n_missing = res.missing_regions.size();
+        std::fwrite(&n_keys, sizeof(n_keys), 1, out);
+        std::fwrite(res.mismatches.data(), sizeof(ohm::CloudKey), n_keys, out);
+        std::fwrite(&n_missing, sizeof(n_missing), 1, out);
+        for (const auto &region : res.missing_regions)
+        {
+          std::fwrite(region.data(), sizeof(int16_t), 3, out);
+        }
+        std::fwrite(&logged, sizeof(logged), 1, out);
+        std::printf("compare flags %u: passed %zu failed %zu\n", flags, res.voxels_passed, res.voxels_failed);
+      }
+      std::fclose(out);
+      return 0;
+    }
+
     if (mode == "linekeys")
     {
       // ohm::LineKeysQueryGpu over the rays: out.bin = u64 rays, then per ray u64 index, u64 count, and after them all
