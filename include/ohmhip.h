@@ -408,6 +408,13 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_batches_launched(ohmhip_map_t map, uint64_t *
  * not count).  Read only: it changes nothing and does not flush collected rays.  For tests and measurements, so that a
  * fallback to the compute stream cannot pass for the early route. */
 OHMHIP_EXPERIMENTAL int ohmhip_map_pipeline_counts(ohmhip_map_t map, uint64_t *batches, uint64_t *binned_early);
+/* How the per-region ordering step of plain occupancy batches ordered its regions, since the map was created:
+ * *regions_ranked = regions placed by bucket and ranked inside their buckets, *regions_network = regions whose buckets
+ * were too crowded for that and that ran the bitonic network.  One count per region and launch that ordered it: a
+ * speculated pass that is dropped and repeated counts twice; regions that go through the device-wide sort (more than
+ * 8192 samples in one region) are not counted.  Counted on the device: waits for the batches launched so far, does not
+ * flush collected rays.  For tests and measurements, so that one path cannot pass for the other. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_order_counts(ohmhip_map_t map, uint64_t *regions_ranked, uint64_t *regions_network);
 /* Maps whose regions are cut into tiles (LARGE REGIONS above): rays, among those that passed the filter, with an end in
  * a region the reference still addresses (|region| <= 32767) but whose tile coordinates leave the key's 16-bit fields.
  * Such a ray is not walked and, when it is the sample that lies out there, its sample is dropped -- the one place results

@@ -246,6 +246,7 @@ _sigs = {
     "ohmhip_map_set_phase_timing": (C.c_int, [_vp, C.c_int]),
     "ohmhip_map_batches_launched": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "ohmhip_map_pipeline_counts": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ohmhip_map_order_counts": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ohmhip_map_rays_beyond_tiles": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "ohmhip_map_line_keys": (C.c_int, [_vp, _vp, C.c_size_t, C.c_uint32, _vp, _vp]),
     "ohmhip_map_rays_query": (C.c_int, [_vp, _vp, C.c_size_t, C.c_double, _vp, _vp, _vp, _vp]),

@@ -179,8 +179,15 @@ struct BatchRun
     m->bin_done_event = tev[1];
   }
 
+  /// Workgroups of an ordering launch: `per_cu` for every CU (the kernels stride over the region list).
+  uint32_t sortGrid(uint32_t per_cu) const
+  {
+    const uint32_t grid = per_cu * m->walk_workgroups;
+    return m->sort_workgroups ? std::min(grid, m->sort_workgroups) : grid;
+  }
+
   /// Order the regions' sample lists.  Small regions (nearly all) by 256-thread workgroups, the dense ones by the
-  /// 1024-thread, 66 KiB instantiation -- launched only when some region needs it, and FIRST: it starts the moment the
+  /// 1024-thread, 68 KiB instantiation -- launched only when some region needs it, and FIRST: it starts the moment the
   /// binning pass ends, ahead of the next batch's set-up pass (which reaches the device ~15 us later through its event),
   /// whereas launched second its workgroups queued behind that pass for a CU's LDS and held the walk back by 50-90 us.
   /// `dense` = the densest region's sample count (the previous batch's when the launch is speculative: binAndOrder adds
@@ -193,15 +200,17 @@ struct BatchRun
     const bool need_dense = kSortSmallHits == 0 || dense > kSortSmallHits;
     if (need_dense)
     {
-      hipExtLaunchKernelGGL((k_sort_region_hits<kSortRegionHits, kSortThreads>), dim3(2 * m->walk_workgroups),
+      hipExtLaunchKernelGGL((k_sort_region_hits<kSortRegionHits, kSortThreads>), dim3(sortGrid(2)),
                             dim3(kSortThreads), 0, s, nullptr, kSortSmallHits ? nullptr : tev[2].handle, 0, regionTable(m),
-                            batchScratch(m), in, out, m->mc.region_voxels, kSortSmallHits, m->pool.d_hit_mask.get());
+                            batchScratch(m), in, out, m->mc.region_voxels, kSortSmallHits, m->pool.d_hit_mask.get(),
+                            m->d_order_counts.get());
     }
     if (kSortSmallHits)
     {
       hipExtLaunchKernelGGL((k_sort_region_hits<kSortSmallHits ? kSortSmallHits : 64u, kSortSmallThreads>),
-                            dim3(8 * m->walk_workgroups), dim3(kSortSmallThreads), 0, s, nullptr, tev[2], 0,
-                            regionTable(m), batchScratch(m), in, out, m->mc.region_voxels, 0u, m->pool.d_hit_mask.get());
+                            dim3(sortGrid(8)), dim3(kSortSmallThreads), 0, s, nullptr, tev[2], 0,
+                            regionTable(m), batchScratch(m), in, out, m->mc.region_voxels, 0u, m->pool.d_hit_mask.get(),
+                            m->d_order_counts.get());
     }
     sort_covers = need_dense ? kSortRegionHits : kSortSmallHits;
     mark(2);
@@ -210,11 +219,11 @@ struct BatchRun
 
   void launchDenseSort()
   {
-    hipExtLaunchKernelGGL((k_sort_region_hits<kSortRegionHits, kSortThreads>), dim3(2 * m->walk_workgroups),
+    hipExtLaunchKernelGGL((k_sort_region_hits<kSortRegionHits, kSortThreads>), dim3(sortGrid(2)),
                           dim3(kSortThreads), 0, s, nullptr, tev[2], 0, regionTable(m), batchScratch(m),
                           static_cast<const unsigned long long *>(m->hit_keys_a.ptr),
                           static_cast<unsigned long long *>(m->hit_keys_b.ptr), m->mc.region_voxels, kSortSmallHits,
-                          m->pool.d_hit_mask.get());
+                          m->pool.d_hit_mask.get(), m->d_order_counts.get());
     sort_covers = kSortRegionHits;
   }
 

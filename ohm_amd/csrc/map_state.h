@@ -454,6 +454,8 @@ struct ohmhip_map_s
   bool walk_half = false;
   uint32_t walkSlots() const { return walk_workgroups * (walk_half ? 2u : 1u); }  ///< persistent walk workgroups of a launch
   DevArray<unsigned long long> d_dbg;  ///< 8 debug counters (OHMHIP_DEBUG_FLAGS & 64)
+  DevArray<unsigned long long> d_order_counts;  ///< regions k_sort_region_hits ordered by rank [0], by the network [1]
+  uint32_t sort_workgroups = 0;  ///< OHMHIP_SORT_WORKGROUPS (tests): cap of the grids of k_sort_region_hits, 0 = none
   double first_ray_time = -1.0;  ///< OccupancyMap::firstRayTime() (ohm/OccupancyMap.cpp:343-347)
   uint32_t event_demand = 0;
   uint32_t event_limit = 0;  ///< OHMHIP_EVENT_LIMIT (tests): cap of the NDT / TSDF event list's first sizing

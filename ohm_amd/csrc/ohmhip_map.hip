@@ -207,6 +207,8 @@ try
   OHMHIP_CHECK(m->d_event_count.alloc(8 * sizeof(uint32_t)));
   OHMHIP_CHECK(m->d_dbg.alloc(kDbgWords * sizeof(unsigned long long)));
   (void)hipMemset(m->d_dbg, 0, kDbgWords * sizeof(unsigned long long));
+  OHMHIP_CHECK(m->d_order_counts.alloc(2 * sizeof(unsigned long long)));
+  OHMHIP_CHECK(hipMemset(m->d_order_counts, 0, 2 * sizeof(unsigned long long)));
   OHMHIP_CHECK(m->h_info.alloc(2 * sizeof(BatchInfo), hipHostMallocMapped | hipHostMallocCoherent));
   std::memset(m->h_info, 0, 2 * sizeof(BatchInfo));
   OHMHIP_CHECK(m->h_passed.alloc(64, hipHostMallocMapped | hipHostMallocCoherent));
@@ -227,6 +229,10 @@ try
     {
       m->walk_workgroups = uint32_t(cus);
     }
+  }
+  if (const char *env = std::getenv("OHMHIP_SORT_WORKGROUPS"))
+  {
+    m->sort_workgroups = uint32_t(std::max(0, std::atoi(env)));
   }
   if (const char *env = std::getenv("OHMHIP_CHUNK_SEGMENTS"))
   {
@@ -765,6 +771,27 @@ try
   }
   *batches = m->count_batches;
   *binned_early = m->count_binned_early;
+  return OHMHIP_OK;
+}
+OHMHIP_ABI_CATCH
+
+int ohmhip_map_order_counts(ohmhip_map_t m, uint64_t *regions_ranked, uint64_t *regions_network)
+try
+{
+  if (!m || !regions_ranked || !regions_network)
+  {
+    return OHMHIP_ERR_INVALID_ARG;
+  }
+  // (no flush of collected rays; the counters are the device's: the batches launched so far are waited for)
+  if (m->launch_busy)
+  {
+    m->launch_thread->wait();
+  }
+  OHMHIP_CHECK(hipStreamSynchronize(m->stream));
+  unsigned long long counts[2] = { 0, 0 };
+  OHMHIP_CHECK(hipMemcpy(counts, m->d_order_counts, sizeof(counts), hipMemcpyDeviceToHost));
+  *regions_ranked = counts[0];
+  *regions_network = counts[1];
   return OHMHIP_OK;
 }
 OHMHIP_ABI_CATCH

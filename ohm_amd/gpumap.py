@@ -465,6 +465,14 @@ class GpuMap(RayMapper):
         L.check(L.lib.ohmhip_map_pipeline_counts(self._handle, C.byref(batches), C.byref(early)), "pipeline_counts")
         return int(batches.value), int(early.value)
 
+    def orderCounts(self):
+        """(regions ordered by bucket and rank, regions ordered by the bitonic network) by the per-region ordering step
+        of plain occupancy batches since the map was created (include/ohmhip.h: ohmhip_map_order_counts).  Waits for
+        the batches launched so far."""
+        ranked, network = C.c_uint64(0), C.c_uint64(0)
+        L.check(L.lib.ohmhip_map_order_counts(self._handle, C.byref(ranked), C.byref(network)), "order_counts")
+        return int(ranked.value), int(network.value)
+
     def raysBeyondTiles(self):
         """Maps with regions above 32768 voxels: rays cut because a tile coordinate left the key range although the
         reference addresses the region (include/ohmhip.h: ohmhip_map_rays_beyond_tiles).  0 for ordinary regions."""
