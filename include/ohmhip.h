@@ -1127,6 +1127,74 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_compare_device(ohmhip_map_t eval, ohmhip_map_
                                                   void *d_mismatch_keys10, uint64_t missing_capacity,
                                                   int16_t *d_missing_regions_xyz, ohmhip_compare_result *d_result);
 
+/* VOXEL EDITS.  The Voxel API's writes for many voxels at once, on the device: Voxel<T>::write (ohmhip_map_write_voxels),
+ * ohm::integrateHit(map, key) / ohm::integrateMiss(map, key) (ohm/VoxelOccupancy.h:57-108) and ohm::integrateHit(map,
+ * sample) (ohm/VoxelMean.h:196-203) (ohmhip_map_integrate_voxels).  Keys are 10-byte GpuKey records as
+ * ohmhip_map_read_voxels takes them, in the caller's region coordinates; with points_xyz in their place the key is
+ * OccupancyMap::voxelKey(point), computed on the device.  tests/voxel_edit_ref.py restates E1 - E4 on the CPU.
+ *  E1 order: for every voxel the result is the one obtained by applying that voxel's elements one at a time, in input
+ *     order, with the reference functions; different voxels are independent; two calls are ordered as called.  The map
+ *     is settled first (rays collected from earlier calls are launched, an asynchronous launch is finished, as every
+ *     observer does): an edit between two ohmhip_map_integrate_rays calls lands between them.
+ *  E2 SET (ohmhip_map_write_voxels): the voxel's ohmhip_layer_voxel_bytes(layer_id) bytes become values[i], for any
+ *     layer the map holds; among duplicate keys the last in input order wins.  The bytes are stored as given: no clamp,
+ *     no validation (NaN, -0.0, +-inf and out-of-clamp values are the caller's business, as with
+ *     ohmhip_map_write_regions).
+ *  E3 HIT is occupancyAdjustHit(&v, v, hit_value, +inf, max_value, saturate_at_min ? min_value : lowest(),
+ *     saturate_at_max ? max_value : FLT_MAX, false), MISS is occupancyAdjustMiss with miss_value and min_value in the
+ *     places of hit_value and max_value: the argument lists of VoxelOccupancy.h:63-65 and :94-96, with the values of
+ *     the map's current configuration.  No ray flag and no ray filter applies and no other layer is touched.
+ *  E4 HIT_SAMPLE requires points (with keys: OHMHIP_ERR_INVALID_ARG).  E3's HIT on voxelKey(point); then, on a map with
+ *     the mean layer, updatePosition (VoxelMean.h:158-163): coord' = subVoxelUpdate(coord, count, point -
+ *     voxelCentreGlobal(key), resolution), count' = min(count, 0xfffffffe) + 1 -- the count saturates; it is not the ray
+ *     mapper's wrapping ++count.  Without the mean layer only the occupancy changes (updatePositionSafe).  Covariance,
+ *     intensity, hit / miss count, touch time, incident, traversal and TSDF layers are never touched, on NDT maps too.
+ *  E5 regions: a key whose region the map does not hold creates it, cleared (of a tiled region, LARGE REGIONS, the
+ *     tiles the edit writes to).  Regions in the host store (SPILL TO HOST) come back as for ohmhip_map_write_regions
+ *     of the same keys; the memory limit and the spill setting apply as there, with the same errors.  All regions an
+ *     edit needs are named before the first voxel is written: on OHMHIP_ERR_CAPACITY the map holds exactly what it
+ *     held and the stats are zero.
+ *  E6 bookkeeping: afterwards the map behaves through every entry point like one that received the same voxels by
+ *     ohmhip_map_read_regions, a host edit, ohmhip_map_write_regions and ohmhip_map_mark_dirty.  Every touched region
+ *     carries all three dirty bits; the write-back's pre-cleaned copy of it is void.  On an NDT map a voxel whose mean
+ *     count the edit makes or leaves > 0 has its ordered-replay mask bit set, one whose count becomes 0 has it cleared;
+ *     on a TSDF map a SET on the TSDF layer re-derives the voxel's bit from the map's truncation distance.  The bit is
+ *     updated per voxel, not by a pass over the region.  An occupancy edit marks the region's clearance changed, a SET
+ *     on the clearance layer marks it unwritten.
+ *  E7 a null key (region -32768 x 3) or a point voxelKey() maps to Key::kNull is skipped and counted in null_keys (the
+ *     reference requires isValid() and specifies nothing).  Host arrays: a key with local coordinates outside the
+ *     region dimensions, or a non-finite point, is OHMHIP_ERR_INVALID_ARG before any device work; in _device arrays
+ *     such an element, and one whose op is not 1 .. 3 or is HIT_SAMPLE beside keys, is treated as a null key.
+ *  E8 OHMHIP_ERR_INVALID_ARG, before any device work, for a null map, count > 0x7fffffff, null arrays with count > 0,
+ *     both of keys10 / points_xyz (or neither with count > 0), an op -- with ops == NULL -- or, for host arrays, any
+ *     ops[i] outside 1 .. 3, and a layer_id out of range.  OHMHIP_ERR_UNSUPPORTED for a layer the map lacks, HIT / MISS /
+ *     HIT_SAMPLE on a map without the occupancy layer, a map with region ownership or a partition, and a map with
+ *     replica merge enabled.  count == 0 is OHMHIP_OK and does nothing.
+ *  E9 blocking: every form returns with the edit complete and the stats final.  The _device forms read arrays that must
+ *     be complete when the call is made; all forms make one read-back of the distinct regions the edit names (the
+ *     region table is the host's). */
+#define OHMHIP_EDIT_HIT 1        /* ohm::integrateHit(map, key)     ohm/VoxelOccupancy.h:57-77   */
+#define OHMHIP_EDIT_MISS 2       /* ohm::integrateMiss(map, key)    ohm/VoxelOccupancy.h:88-108  */
+#define OHMHIP_EDIT_HIT_SAMPLE 3 /* ohm::integrateHit(map, sample)  ohm/VoxelMean.h:196-203; points only */
+typedef struct ohmhip_voxel_edit_stats
+{
+  uint64_t applied;         /* elements applied                                                         */
+  uint64_t null_keys;       /* elements skipped: null key, or a point voxelKey() maps to Key::kNull      */
+  uint64_t distinct_voxels; /* voxels written                                                           */
+  uint64_t regions_touched; /* caller's regions holding at least one written voxel                      */
+  uint64_t regions_created; /* of those, regions the map did not hold before                            */
+} ohmhip_voxel_edit_stats;
+int ohmhip_map_write_voxels(ohmhip_map_t map, int layer_id, const void *keys10, size_t count, const void *values,
+                            ohmhip_voxel_edit_stats *stats /* optional */);
+OHMHIP_EXPERIMENTAL int ohmhip_map_write_voxels_device(ohmhip_map_t map, int layer_id, const void *d_keys10, size_t count,
+                                                       const void *d_values, ohmhip_voxel_edit_stats *stats);
+int ohmhip_map_integrate_voxels(ohmhip_map_t map, const uint8_t *ops /* NULL: every element is `op` */, int op,
+                                const void *keys10 /* or NULL */, const double *points_xyz /* or NULL */, size_t count,
+                                ohmhip_voxel_edit_stats *stats /* optional */);
+OHMHIP_EXPERIMENTAL int ohmhip_map_integrate_voxels_device(ohmhip_map_t map, const uint8_t *d_ops, int op,
+                                                           const void *d_keys10, const double *d_points_xyz,
+                                                           size_t count, ohmhip_voxel_edit_stats *stats);
+
 /* Multi-GPU merge support (no reference equivalent -- ohm is single device).  The resident layer of a
  * map is one allocation of region_stride_bytes per slot: ohm_amd/distributed.py wraps it as a device tensor and runs
  * the RCCL all-reduce of touched-region occupancy deltas on it.  ensure_regions makes regions resident (cleared)

@@ -6,7 +6,7 @@ is the thin host-side mirror of the reference's interface used by the tests and 
 from ._lib import OhmHipError, LIB_PATH, EXPORTED_SYMBOLS  # noqa: F401
 from .gpumap import (GpuMap, GpuNdtMap, GpuTransformSamples, GpuTsdfMap, LineKeysQueryGpu, NdtMode, OccupancyMap, RayFlag,  # noqa: F401
                      OccupancyType, RaysQueryGpu, RayMapper, LAYERS, QueryFlag, ClearanceProcess, LineQueryGpu,
-                     MappingProcessResult, Mapper, NearestNeighbours,
+                     MappingProcessResult, Mapper, NearestNeighbours, VoxelEdit, key_range,
                      device_count, device_info, probability_to_value, value_to_probability)
 from .raypattern import ClearingPattern, RayPattern, RayPatternConical  # noqa: F401
 from .copyutil import (canCopy, copyMap, copyFilterExtents, copyFilterDirty, copyFilterAnd, copyFilterOr,  # noqa: F401

@@ -134,6 +134,15 @@ class CompareResult(C.Structure):
                 ("member_failed", C.c_uint64 * CMP_MAX_MEMBERS), ("member_max_diff", C.c_uint64 * CMP_MAX_MEMBERS)]
 
 
+EDIT_HIT, EDIT_MISS, EDIT_HIT_SAMPLE = 1, 2, 3  # OHMHIP_EDIT_*
+
+
+class VoxelEditStats(C.Structure):
+    """ohmhip_voxel_edit_stats"""
+    _fields_ = [("applied", C.c_uint64), ("null_keys", C.c_uint64), ("distinct_voxels", C.c_uint64),
+                ("regions_touched", C.c_uint64), ("regions_created", C.c_uint64)]
+
+
 class MapConfig(C.Structure):
     _fields_ = [("resolution", C.c_double), ("region_dim", C.c_int * 3), ("origin", C.c_double * 3),
                 ("layers", C.c_uint), ("mode", C.c_int), ("hit_value", C.c_float), ("miss_value", C.c_float),
@@ -276,6 +285,11 @@ _sigs = {
     "ohmhip_map_voxel_keys": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "ohmhip_map_read_voxels": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
     "ohmhip_map_read_voxels_device": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
+    "ohmhip_map_write_voxels": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.POINTER(VoxelEditStats)]),
+    "ohmhip_map_write_voxels_device": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.POINTER(VoxelEditStats)]),
+    "ohmhip_map_integrate_voxels": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t, C.POINTER(VoxelEditStats)]),
+    "ohmhip_map_integrate_voxels_device": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t,
+                                                     C.POINTER(VoxelEditStats)]),
     "ohmhip_map_filter_points": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(PointFilterParams), C.c_uint64, _vp, _vp, _vp,
                                            _vp, C.POINTER(C.c_uint64)]),
     "ohmhip_map_filter_points_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.POINTER(PointFilterParams),

@@ -429,6 +429,13 @@ struct ohmhip_map_s
     DevBuf compare_chunks, compare_records, compare_keys, compare_missing, compare_result;
     ScanScratch compare_scan;
   } query;
+  /// Voxel edits by key (voxel_edit_impl.h): device copies of the host forms' arrays; per element the tile key, then
+  /// the sort pair, each before and after its sort; the distinct tiles; rocPRIM's scratch; the counters of the stats.
+  struct EditState
+  {
+    DevBuf keys, points, ops, values;
+    DevBuf keys_a, keys_b, vals_a, vals_b, tiles, temp, counters;
+  } edit;
   /// The clearance layer's bookkeeping (clearance_update.h), by the caller's region key -- so it needs no care when a
   /// region changes slot, leaves the pool or comes back.  An update folds the kDirtyClearance bits into `changed` at a
   /// new epoch; a region is up to date for parameter set P when it was written with P (`params`, 1 + index into

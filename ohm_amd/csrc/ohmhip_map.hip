@@ -21,6 +21,7 @@
 #include "point_filter_kernels.h"
 #include "copy_kernels.h"
 #include "compare_kernels.h"
+#include "voxel_edit_kernels.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -1039,3 +1040,4 @@ OHMHIP_ABI_CATCH
 #include "pattern_impl.h"
 #include "copy_impl.h"
 #include "compare_impl.h"
+#include "voxel_edit_impl.h"

@@ -86,6 +86,29 @@ def _key_records(keys):
 _GPU_KEY = np.dtype([("region", "<i2", (3,)), ("voxel", "u1", (4,))])
 
 
+class VoxelEdit(enum.IntEnum):
+    """OHMHIP_EDIT_*: what GpuMap.integrateVoxels does to a voxel."""
+    kHit = L.EDIT_HIT               # ohm::integrateHit(map, key)
+    kMiss = L.EDIT_MISS             # ohm::integrateMiss(map, key)
+    kHitSample = L.EDIT_HIT_SAMPLE  # ohm::integrateHit(map, sample): points only
+
+
+def key_range(min_key, max_key, region_voxel_dimensions):
+    """The keys of ohm::KeyRange(min_key, max_key, region_voxel_dimensions) as GPU_KEY_DTYPE records, in the order
+    KeyRange::walkNext visits them (ohm/KeyRange.cpp:105-129): x fastest, then y, then z, across region borders."""
+    dims = np.asarray(region_voxel_dimensions, dtype=np.int64)
+    lo = np.asarray(min_key["region"], dtype=np.int64) * dims + np.asarray(min_key["voxel"][:3], dtype=np.int64)
+    hi = np.asarray(max_key["region"], dtype=np.int64) * dims + np.asarray(max_key["voxel"][:3], dtype=np.int64)
+    if np.any(hi < lo):
+        return np.zeros(0, dtype=_GPU_KEY)
+    gz, gy, gx = np.meshgrid(*(np.arange(lo[a], hi[a] + 1) for a in (2, 1, 0)), indexing="ij")
+    g = np.stack([gx.ravel(), gy.ravel(), gz.ravel()], axis=1)
+    keys = np.zeros(g.shape[0], dtype=_GPU_KEY)
+    keys["region"] = np.floor_divide(g, dims).astype(np.int16)
+    keys["voxel"][:, :3] = np.mod(g, dims).astype(np.uint8)
+    return keys
+
+
 class NdtMode(enum.IntEnum):
     """ohm/NdtMode.h"""
     kNone = 0
@@ -821,6 +844,83 @@ class GpuMap(RayMapper):
                              np.where(values < np.float32(self._map.occupancy_threshold_value), OccupancyType.kFree,
                                       OccupancyType.kOccupied), OccupancyType.kUnobserved)
         return np.where(present != 0, types, OccupancyType.kNull).astype(np.int8)
+
+    # -- voxel edits by key (include/ohmhip.h, VOXEL EDITS) -----------------------------------------------------------
+    def _edit_keys(self, keys):
+        return _key_records(keys.view(np.uint8) if isinstance(keys, np.ndarray) and keys.dtype == _GPU_KEY else keys)
+
+    def _edit_done(self, status, stats, what):
+        self._last_edit_stats = {name: int(getattr(stats, name)) for name, _ in L.VoxelEditStats._fields_}
+        L.check(status, what)
+        return self._last_edit_stats["applied"]
+
+    def writeVoxels(self, keys, layer_name, values):
+        """Voxel<T>::write for many voxels (ohmhip_map_write_voxels): the voxels of layer `layer_name` at keys -- in
+        every form readVoxels takes -- become values ((N,) or (N, components), converted to the layer's type; the bytes
+        are stored as given).  Among duplicate keys the last wins; null keys are skipped; regions the map does not hold
+        are created.  Returns the number of elements applied; lastEditStats() has the rest."""
+        self._push_config_if_changed()
+        lid, dtype, comps = LAYERS[layer_name]
+        rec = self._edit_keys(keys)
+        n = rec.shape[0]
+        values = np.ascontiguousarray(values, dtype=dtype).reshape((n, comps) if comps > 1 else n)
+        stats = L.VoxelEditStats()
+        status = L.lib.ohmhip_map_write_voxels(self._handle, lid, rec.ctypes.data if n else None, n,
+                                               values.ctypes.data if n else None, C.byref(stats))
+        return self._edit_done(status, stats, "writeVoxels")
+
+    def integrateVoxels(self, ops, keys=None, points=None):
+        """One VoxelEdit per element (an array, or one value for all) at keys, or at the voxels of points ((N, 3)
+        float64) (ohmhip_map_integrate_voxels): ohm::integrateHit(map, key), ohm::integrateMiss(map, key) and -- points
+        only -- ohm::integrateHit(map, sample), per voxel in input order.  Returns the number of elements applied."""
+        self._push_config_if_changed()
+        if (keys is None) == (points is None):
+            raise ValueError("integrateVoxels takes keys or points")
+        rec = pts = None
+        if keys is not None:
+            rec = self._edit_keys(keys)
+            n = rec.shape[0]
+        else:
+            pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+            n = pts.shape[0]
+        op_array = None
+        op = 0
+        if np.ndim(ops) == 0:
+            op = int(ops)
+        else:
+            op_array = np.ascontiguousarray(ops, dtype=np.uint8).reshape(-1)
+            if op_array.shape[0] != n:
+                raise ValueError("one op per element")
+        stats = L.VoxelEditStats()
+        status = L.lib.ohmhip_map_integrate_voxels(self._handle, op_array.ctypes.data if op_array is not None else None,
+                                                   op, rec.ctypes.data if rec is not None else None,
+                                                   pts.ctypes.data if pts is not None else None, n, C.byref(stats))
+        return self._edit_done(status, stats, "integrateVoxels")
+
+    def integrateHits(self, keys=None, points=None, update_mean=False):
+        """ohm::integrateHit(map, key) at every key / at the voxel of every point; with update_mean (points only)
+        ohm::integrateHit(map, sample): the voxel mean takes the point as well."""
+        if update_mean and points is None:
+            raise ValueError("update_mean needs points")
+        return self.integrateVoxels(VoxelEdit.kHitSample if update_mean else VoxelEdit.kHit, keys, points)
+
+    def integrateMisses(self, keys=None, points=None):
+        """ohm::integrateMiss(map, key) at every key / at the voxel of every point."""
+        return self.integrateVoxels(VoxelEdit.kMiss, keys, points)
+
+    def lastEditStats(self):
+        """ohmhip_voxel_edit_stats of the last edit as a dict (all zero after one that failed)."""
+        return dict(getattr(self, "_last_edit_stats", {name: 0 for name, _ in L.VoxelEditStats._fields_}))
+
+    def keyRange(self, lo, hi):
+        """ohm::KeyRange (ohm/KeyRange.h) of the closed box between two keys (GPU_KEY_DTYPE records) or two points
+        (3 floats each, through voxelKeys): its keys as GPU_KEY_DTYPE records, x fastest, then y, then z -- the order
+        KeyRange::walkNext visits them in (ohm/KeyRange.cpp:105-129).  Empty when max lies below min on any axis."""
+        def as_key(v):
+            if isinstance(v, (np.ndarray, np.void)) and getattr(v, "dtype", None) == _GPU_KEY:
+                return np.asarray(v).reshape(1)[0]
+            return self.voxelKeys(np.asarray(v, dtype=np.float64).reshape(1, 3))[0]
+        return key_range(as_key(lo), as_key(hi), self._map.region_voxel_dimensions)
 
     def filterPoints(self, points, expected_value_tolerance=-1.0, occupancy_only=False, capacity=None):
         """ohmfilter's test of every row of points ((N, 3) float64) on the device (ohmhip_map_filter_points; utils/

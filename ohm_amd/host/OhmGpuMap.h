@@ -874,6 +874,119 @@ public:
     return last_status_;
   }
 
+  // -- voxel edits by key (include/ohmhip.h, VOXEL EDITS) ------------------------------------------------------------
+  /// What integrateVoxels does to a voxel (OHMHIP_EDIT_*).
+  enum class VoxelEdit : uint8_t
+  {
+    kHit = OHMHIP_EDIT_HIT,              ///< ohm::integrateHit(map, key)
+    kMiss = OHMHIP_EDIT_MISS,            ///< ohm::integrateMiss(map, key)
+    kHitSample = OHMHIP_EDIT_HIT_SAMPLE  ///< ohm::integrateHit(map, sample): points only
+  };
+
+  /// Voxel<T>::write for many voxels (ohmhip_map_write_voxels): the ohmhip_layer_voxel_bytes(layer_id) bytes of every
+  /// voxel at `keys` become those of `values`, stored as given; among duplicate keys the last wins, null keys are
+  /// skipped, regions the map does not hold are created.  @return the status (lastStatus() too).
+  int writeVoxels(int layer_id, const std::vector<CloudKey> &keys, const void *values)
+  {
+    last_edit_stats_ = ohmhip_voxel_edit_stats{};
+    if (!gpuOk() || !pushConfigIfChanged())
+    {
+      return last_status_ = OHMHIP_ERR_INVALID_ARG;
+    }
+    return last_status_ = ohmhip_map_write_voxels(handle_, layer_id, keys.empty() ? nullptr : keys.data(), keys.size(),
+                                                  values, &last_edit_stats_);
+  }
+
+  /// One VoxelEdit per element -- `ops`, or `op` for all of them when ops is null -- at `keys`, or at the voxels of
+  /// `points` (exactly one of the two; ohmhip_map_integrate_voxels), per voxel in input order.
+  int integrateVoxels(const VoxelEdit *ops, VoxelEdit op, const CloudKey *keys, const dvec3 *points, size_t count)
+  {
+    static_assert(sizeof(dvec3) == 3 * sizeof(double), "points are read as 3 doubles each");
+    static_assert(sizeof(VoxelEdit) == 1, "ops are read as bytes");
+    last_edit_stats_ = ohmhip_voxel_edit_stats{};
+    if (!gpuOk() || !pushConfigIfChanged())
+    {
+      return last_status_ = OHMHIP_ERR_INVALID_ARG;
+    }
+    return last_status_ = ohmhip_map_integrate_voxels(handle_, reinterpret_cast<const uint8_t *>(ops), int(op), keys,
+                                                      points ? &points[0].x : nullptr, count, &last_edit_stats_);
+  }
+
+  /// ohm::integrateHit(map, key) at every key.
+  int integrateHits(const std::vector<CloudKey> &keys)
+  {
+    return integrateVoxels(nullptr, VoxelEdit::kHit, keys.data(), nullptr, keys.size());
+  }
+  /// ohm::integrateHit at the voxel of every point; with update_mean ohm::integrateHit(map, sample): the voxel mean
+  /// takes the point as well.
+  int integrateHits(const std::vector<dvec3> &points, bool update_mean = false)
+  {
+    return integrateVoxels(nullptr, update_mean ? VoxelEdit::kHitSample : VoxelEdit::kHit, nullptr, points.data(),
+                           points.size());
+  }
+  /// ohm::integrateMiss(map, key) at every key / at the voxel of every point.
+  int integrateMisses(const std::vector<CloudKey> &keys)
+  {
+    return integrateVoxels(nullptr, VoxelEdit::kMiss, keys.data(), nullptr, keys.size());
+  }
+  int integrateMisses(const std::vector<dvec3> &points)
+  {
+    return integrateVoxels(nullptr, VoxelEdit::kMiss, nullptr, points.data(), points.size());
+  }
+  /// The single-voxel conveniences, with the reference's names and meaning (ohm/VoxelOccupancy.h:73-77, 104-108,
+  /// ohm/VoxelMean.h:196-203).
+  int integrateHit(const CloudKey &key) { return integrateVoxels(nullptr, VoxelEdit::kHit, &key, nullptr, 1); }
+  int integrateMiss(const CloudKey &key) { return integrateVoxels(nullptr, VoxelEdit::kMiss, &key, nullptr, 1); }
+  int integrateHit(const dvec3 &sample) { return integrateVoxels(nullptr, VoxelEdit::kHitSample, nullptr, &sample, 1); }
+  /// ohmhip_voxel_edit_stats of the last edit (all zero after one that failed).
+  const ohmhip_voxel_edit_stats &lastEditStats() const { return last_edit_stats_; }
+
+  /// ohm::KeyRange (ohm/KeyRange.h) of the closed box between two keys: its keys x fastest, then y, then z -- the order
+  /// KeyRange::walkNext visits them in (ohm/KeyRange.cpp:105-129).  Empty when max lies below min on any axis.
+  std::vector<CloudKey> keyRange(const CloudKey &min_key, const CloudKey &max_key) const
+  {
+    const int *dim = map_->regionVoxelDimensions();
+    long lo[3], hi[3];
+    for (int a = 0; a < 3; ++a)
+    {
+      lo[a] = long(min_key.region[a]) * dim[a] + min_key.voxel[a];
+      hi[a] = long(max_key.region[a]) * dim[a] + max_key.voxel[a];
+      if (hi[a] < lo[a])
+      {
+        return {};
+      }
+    }
+    std::vector<CloudKey> keys;
+    keys.reserve(size_t(hi[0] - lo[0] + 1) * size_t(hi[1] - lo[1] + 1) * size_t(hi[2] - lo[2] + 1));
+    for (long z = lo[2]; z <= hi[2]; ++z)
+    {
+      for (long y = lo[1]; y <= hi[1]; ++y)
+      {
+        for (long x = lo[0]; x <= hi[0]; ++x)
+        {
+          const long g[3] = { x, y, z };
+          CloudKey k{};
+          for (int a = 0; a < 3; ++a)
+          {
+            long r = g[a] / dim[a];
+            r -= (g[a] - r * dim[a] < 0) ? 1 : 0;
+            k.region[a] = int16_t(r);
+            k.voxel[a] = uint8_t(g[a] - r * dim[a]);
+          }
+          keys.push_back(k);
+        }
+      }
+    }
+    return keys;
+  }
+  /// ... between the voxels of two points (voxelKeys).
+  std::vector<CloudKey> keyRange(const dvec3 &min_point, const dvec3 &max_point)
+  {
+    const dvec3 ends[2] = { min_point, max_point };
+    const std::vector<CloudKey> keys = voxelKeys(ends, 2);
+    return (last_status_ == OHMHIP_OK) ? keyRange(keys[0], keys[1]) : std::vector<CloudKey>();
+  }
+
   ohmhip_map_t handle() const { return handle_; }
   /// OccupancyMap::clone (ohm/OccupancyMap.cpp:953-1004) on the device: a new map of the same class, configuration and
   /// layers, which owns its (empty) host map, then the regions that pass the extents rule of copyFilterExtents, copied
@@ -1018,6 +1131,7 @@ protected:
   double ray_segment_length_ = 0;
   bool grouped_rays_ = false;
   int last_status_ = OHMHIP_OK;
+  ohmhip_voxel_edit_stats last_edit_stats_{};
   size_t last_partial_ = 0;
   unsigned partition_world_ = 1;
   RayFilterFunction ray_filter_;

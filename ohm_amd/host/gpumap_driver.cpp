@@ -359,6 +359,76 @@ int main(int argc, char **argv)
     }
     std::fclose(in);
 
+    if (mode == "voxeledit")
+    {
+      // Voxel edits by key through the host mirror.  <rays.bin> holds the points of an edit script, argv 6 names a raw
+      // file with one op byte per point (1 HIT, 2 MISS, 3 HIT_SAMPLE); <batch_rays> is not used.  On an occupancy + mean
+      // map: GpuMap::integrateVoxels of the script; then the single-voxel conveniences on the first point --
+      // integrateHit(sample), integrateMiss(key), integrateHit(key) --; then integrateMisses(keyRange(p, q)) with p and
+      // q the script's last two points.  out.bin: the map's regions (layout at the top), then the five counters of
+      // lastEditStats() after the script (u64 each), u64 range keys and the keys of keyRange (10 bytes each).
+      if (argc < 7 || rays.size() < 2)
+      {
+        return 2;
+      }
+      std::vector<ohm::GpuMap::VoxelEdit> ops(rays.size());
+      FILE *oin = std::fopen(argv[6], "rb");
+      if (!oin || std::fread(ops.data(), 1, ops.size(), oin) != ops.size())
+      {
+        return 4;
+      }
+      std::fclose(oin);
+      ohm::OccupancyMap edit_map(resolution);
+      edit_map.addLayer(OHMHIP_LID_MEAN);
+      ohm::GpuMap edit_gpu_map(&edit_map, true);
+      if (edit_gpu_map.integrateVoxels(ops.data(), ohm::GpuMap::VoxelEdit::kHit, nullptr, rays.data(), rays.size()) != OHMHIP_OK)
+      {
+        return 8;
+      }
+      const ohmhip_voxel_edit_stats script_stats = edit_gpu_map.lastEditStats();
+      const std::vector<ohm::CloudKey> first = edit_gpu_map.voxelKeys(rays.data(), 1);
+      if (edit_gpu_map.lastStatus() != OHMHIP_OK || edit_gpu_map.integrateHit(rays[0]) != OHMHIP_OK ||
+          edit_gpu_map.integrateMiss(first[0]) != OHMHIP_OK || edit_gpu_map.integrateHit(first[0]) != OHMHIP_OK)
+      {
+        return 8;
+      }
+      const std::vector<ohm::CloudKey> range = edit_gpu_map.keyRange(rays[rays.size() - 2], rays[rays.size() - 1]);
+      if (edit_gpu_map.lastStatus() != OHMHIP_OK || edit_gpu_map.integrateMisses(range) != OHMHIP_OK)
+      {
+        return 8;
+      }
+      edit_gpu_map.syncVoxels();
+      FILE *out = std::fopen(argv[5], "wb");
+      if (!out)
+      {
+        return 6;
+      }
+      const uint64_t regions = edit_map.regionCount();
+      std::fwrite(&regions, sizeof(regions), 1, out);
+      for (const auto &entry : edit_map.chunks())
+      {
+        std::fwrite(entry.first.data(), sizeof(int16_t), 3, out);
+        for (uint32_t layer = 0; layer < uint32_t(OHMHIP_LID_COUNT); ++layer)
+        {
+          if (!edit_map.hasLayer(int(layer)))
+          {
+            continue;
+          }
+          const auto &block = entry.second.voxel_blocks[layer];
+          const uint64_t bytes = block.size();
+          std::fwrite(&layer, sizeof(layer), 1, out);
+          std::fwrite(&bytes, sizeof(bytes), 1, out);
+          std::fwrite(block.data(), 1, bytes, out);
+        }
+      }
+      const uint64_t counters[6] = { script_stats.applied,         script_stats.null_keys,       script_stats.distinct_voxels,
+                                     script_stats.regions_touched, script_stats.regions_created, range.size() };
+      std::fwrite(counters, sizeof(uint64_t), 6, out);
+      std::fwrite(range.data(), sizeof(ohm::CloudKey), range.size(), out);
+      std::fclose(out);
+      return 0;
+    }
+
     if (mode == "copy")
     {
       // Copy.CopySubmapFromGpu (tests/ohmtestgpu/GpuCopyTests.cpp:112-150): the rays into a GpuMap, then -- without a
