@@ -1,9 +1,10 @@
 // copy_impl.h -- ohmhip_map_can_copy / ohmhip_map_copy: ohm::canCopy and ohm::copyMap (ohm/CopyUtil.cpp:52-165) between
 // two device maps, device to device (include/ohmhip.h, MAP COPY).  The source is a read-side subject
 // (read_side.h): settled, then only read -- its regions in the host store where they lie.  The destination is written
-// the way ohmhip_map_write_regions writes it (region_io.h), for all layers at once and with one kernel launch.
+// through write_side.h, for all layers at once and with one kernel launch.
 //
-// Part of ohmhip_map.hip's translation unit (included there, after read_side.h): not a stand-alone header.
+// Part of ohmhip_map.hip's translation unit (included there, after read_side.h and write_side.h): not a stand-alone
+// header.
 #ifndef OHMHIP_COPY_IMPL_H
 #define OHMHIP_COPY_IMPL_H
 
@@ -179,37 +180,26 @@ try
     return OHMHIP_OK;
   }
 
-  // C7: the destination.  Every tile of a passing region is named, as ohmhip_map_write_regions names them for a tiled
-  // map: the ones the source lacks are cleared.
+  // C7: the destination.  Every tile of a passing region is named: the ones the source lacks are cleared.
   OHMHIP_CHECK(hipStreamSynchronize(dst->stream));
   OHMHIP_CHECK(refreshHostRegionTable(dst));
   std::vector<int16_t> tile_keys;
   std::vector<TileRef> tiles;
-  uint64_t created = 0;
   for (const uint64_t order : wanted)
   {
     int16_t r[3];
     regionOfOrder(order, r);
     tilesOfRegion(mc, r, tiles);
-    bool held = false;
     for (const TileRef &t : tiles)
     {
       tile_keys.insert(tile_keys.end(), t.key, t.key + 3);
-      held = held || tileExists(dst, t.key);
     }
-    created += held ? 0u : 1u;
   }
   const size_t n_tiles = tile_keys.size() / 3;
-  for (size_t i = 0; i < n_tiles && !dst->precleaned.empty(); ++i)
-  {
-    dropPrecleanedKey(dst, packRegionKey(&tile_keys[3 * i]));  // (the write-back's copy of a rewritten region is void)
-  }
-  std::vector<uint32_t> slots(n_tiles);
-  OHMHIP_CHECK(appendNamedRegions(dst, tile_keys.data(), n_tiles, slots.data()));
-  st.regions_created = created;
+  WrittenTiles named;
+  OHMHIP_CHECK(nameWrittenTiles(dst, tile_keys.data(), n_tiles, named));
+  st.regions_created = named.created;
 
-  const bool ndt = dst->config.mode == OHMHIP_MODE_NDT_OM || dst->config.mode == OHMHIP_MODE_NDT_TM;
-  const bool tsdf = dst->config.mode == OHMHIP_MODE_TSDF;
   const size_t tile_voxels = size_t(dst->mc.region_voxels);
   const size_t mask_words = (tile_voxels + 31) / 32;
   std::vector<MapCopyJob> jobs;
@@ -227,34 +217,19 @@ try
       MapCopyJob job{};
       job.src = tileLayerBlock(src, home, l);
       job.bytes = uint32_t(tile_voxels * kLayerBytes[l]);
-      job.dst = static_cast<char *>(dst->pool.layers[l].get()) + size_t(slots[i]) * job.bytes;
+      job.dst = static_cast<char *>(dst->pool.layers[l].get()) + size_t(named.slots[i]) * job.bytes;
       job.clear_word = layerClearWord(l);
-      job.mask_kind = (ndt && l == OHMHIP_LID_MEAN) ? kMapCopyMaskMean : (tsdf && l == OHMHIP_LID_TSDF) ? kMapCopyMaskTsdf : kMapCopyMaskNone;
-      job.mask = job.mask_kind ? dst->pool.d_hit_mask.get() + size_t(slots[i]) * mask_words : nullptr;
+      job.mask_kind = replayMaskKind(dst, l);
+      job.mask = job.mask_kind ? dst->pool.d_hit_mask.get() + size_t(named.slots[i]) * mask_words : nullptr;
       jobs.push_back(job);
       st.bytes_copied += job.src ? job.bytes : 0u;
     }
   }
   OHMHIP_CHECK(launchMapCopy(dst, jobs));
   st.layers_copied = layers;
-  // C5: the marks of an upload.  All three dirty bits, as after ohmhip_map_mark_dirty; clearance by the caller's region.
-  {
-    const uint32_t *d_index = nullptr;
-    OHMHIP_CHECK(uploadSlotIndex(dst, slots.data(), slots.size(), dst->stream, false, d_index));
-    orSlotBits(dst, d_index, slots.size(), kDirtySync | kDirtyMerge | kDirtyClearance, dst->stream);
-  }
-  for (size_t i = 0; i < n_tiles; ++i)
-  {
-    const uint64_t tile_key = packRegionKey(&tile_keys[3 * i]);
-    if (layers & OHMHIP_LAYER_BIT(OHMHIP_LID_OCCUPANCY))
-    {
-      clearanceMarkChanged(dst, tile_key);
-    }
-    if (layers & OHMHIP_LAYER_BIT(OHMHIP_LID_CLEARANCE))
-    {
-      clearanceMarkUnwritten(dst, tile_key);
-    }
-  }
+  // C5: the marks of an upload, with all three dirty bits; clearance by the caller's region.
+  OHMHIP_CHECK(markWrittenTiles(dst, tile_keys.data(), named.slots.data(), n_tiles, layers,
+                                kDirtySync | kDirtyMerge | kDirtyClearance, dst->stream));
   OHMHIP_CHECK(hipStreamSynchronize(dst->stream));  // C9: blocking (the slot list above is read until here)
   return hipGetLastError();
 }

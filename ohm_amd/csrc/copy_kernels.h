@@ -1,8 +1,8 @@
 // copy_kernels.h -- k_copy_map: ohmhip_map_copy's one launch (include/ohmhip.h, MAP COPY).  Every
 // (tile, layer) block of every region a copy moves is one job; where the layer is the one the destination's "ordered
-// replay" mask is derived from -- mean on an NDT map, TSDF on a TSDF map -- the wave that moves 64 lanes' worth of
-// voxels also writes their mask words, by the rules of k_rebuild_mask (replay_kernels.h), from the values in its
-// registers: the layer is not read a second time and no launch follows per region.
+// replay" mask is derived from (MapCopyJob::mask_kind), the wave that moves 64 lanes' worth of voxels also writes their
+// mask words, by replayMaskBit (replay_kernels.h) from the values in its registers: the layer is not read a second time
+// and no launch follows per region.
 #ifndef OHMHIP_COPY_KERNELS_H
 #define OHMHIP_COPY_KERNELS_H
 
@@ -10,14 +10,6 @@
 
 namespace ohmhip
 {
-/// Which rule turns a moved voxel into its replay-mask bit.
-enum MapCopyMask : uint32_t
-{
-  kMapCopyMaskNone = 0,  ///< the layer does not define the destination's mask
-  kMapCopyMaskMean = 1,  ///< VoxelMean {coord, count}: count > 0
-  kMapCopyMaskTsdf = 2,  ///< VoxelTsdf {weight, distance}: !tsdfCountable under the DESTINATION's truncation distance
-};
-
 /// One block of one layer.  `src` is a pool slot's block of the source map or a layer block inside a record of its
 /// pinned host store (device visible); null: the source holds no such tile, the destination block takes the layer's
 /// clear value.  Every layer's voxel is a multiple of 4 bytes and every block starts on a 4-byte boundary; the blocks
@@ -26,10 +18,10 @@ struct MapCopyJob
 {
   const char *src;
   char *dst;
-  uint32_t *mask;  ///< the destination slot's mask row (mask_kind != kMapCopyMaskNone)
+  uint32_t *mask;  ///< the destination slot's mask row (mask_kind != kReplayMaskNone)
   uint32_t bytes;
   uint32_t clear_word;
-  uint32_t mask_kind;
+  uint32_t mask_kind;  ///< ReplayMaskKind, under the DESTINATION's truncation distance
   uint32_t pad_;
 };
 
@@ -42,11 +34,6 @@ __device__ inline uint32_t spreadBits16(uint32_t v)
   v = (v | (v << 2)) & 0x33333333u;
   v = (v | (v << 1)) & 0x55555555u;
   return v;
-}
-
-__device__ inline bool mapCopyMaskBit(uint32_t kind, uint32_t word0, uint32_t word1, float tsdf_trunc)
-{
-  return (kind == kMapCopyMaskMean) ? word1 > 0u : !tsdfCountable(__uint_as_float(word0), __uint_as_float(word1), tsdf_trunc);
 }
 
 /// grid: n_jobs * parts workgroups of 256; the `parts` workgroups of a job interleave over it wave by wave, so
@@ -66,7 +53,7 @@ __global__ void __launch_bounds__(256)
   const bool aligned = ((reinterpret_cast<uintptr_t>(job.src) | reinterpret_cast<uintptr_t>(job.dst)) & 15u) == 0;
   const uint32_t cw = job.clear_word;
 
-  if (job.mask_kind == kMapCopyMaskNone)
+  if (job.mask_kind == kReplayMaskNone)
   {
     // 16-byte vectors where both sides allow them, 4-byte words for the rest: the whole block when one side is not
     // 16-byte aligned (a 5 x 3 x 7 region's 4-byte layer is 420 bytes: every other slot), else the tail.
@@ -116,8 +103,8 @@ __global__ void __launch_bounds__(256)
       }
       *reinterpret_cast<uint2 *>(job.dst + size_t(v0) * 8u) = make_uint2(q.x, q.y);
     }
-    const bool f0 = here >= 1u && mapCopyMaskBit(job.mask_kind, q.x, q.y, tsdf_trunc);
-    const bool f1 = here == 2u && mapCopyMaskBit(job.mask_kind, q.z, q.w, tsdf_trunc);
+    const bool f0 = here >= 1u && replayMaskBit(job.mask_kind, q.x, q.y, tsdf_trunc);
+    const bool f1 = here == 2u && replayMaskBit(job.mask_kind, q.z, q.w, tsdf_trunc);
     const unsigned long long b0 = __ballot(f0);
     const unsigned long long b1 = __ballot(f1);
     // Mask word k of the step covers voxels base + 32 k ...: 32 lanes' first voxels, or 16 lanes' two voxels each.

@@ -389,14 +389,14 @@ OHMHIP_ABI_CATCH
 
 namespace
 {
-/// TSDF: the "ordered replay" mask of every region the map holds, re-derived from the stored state (tsdfCountable).
+/// TSDF: the "ordered replay" mask of every region the map holds, re-derived from the stored state (replayMaskBit).
 /// An option change needs it: what the earlier options left in a voxel -- the fractional weights of a drop-off or of a
 /// non-integer max_weight -- stays countable under them (or was replayed throughout) and is not under the next ones.
 /// Resident regions by k_rebuild_mask over the committed slots, regions in the host store in their records, whose mask
 /// row moves back into the pool as it is; write-back copies of resident regions carry the old rows and are dropped.
 int tsdfRebuildMasks(ohmhip_map_t m)
 {
-  const float *tsdf = static_cast<const float *>(m->pool.layers[OHMHIP_LID_TSDF].get());
+  const uint32_t *tsdf = static_cast<const uint32_t *>(m->pool.layers[OHMHIP_LID_TSDF].get());
   if (!tsdf)
   {
     return OHMHIP_OK;
@@ -406,8 +406,8 @@ int tsdfRebuildMasks(ohmhip_map_t m)
   for (uint32_t first = 0; first < m->slots_committed; first += kSlotsPerLaunch)
   {
     const uint32_t n = std::min<uint32_t>(kSlotsPerLaunch, m->slots_committed - first);
-    hipLaunchKernelGGL(k_rebuild_mask, dim3(4, n), dim3(256), 0, m->stream, m->mc, first,
-                       static_cast<const uint32_t *>(nullptr), tsdf, m->pool.d_hit_mask.get());
+    hipLaunchKernelGGL(k_rebuild_mask, dim3(4, n), dim3(256), 0, m->stream, m->mc, first, uint32_t(kReplayMaskTsdf), tsdf,
+                       m->pool.d_hit_mask.get());
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   OHMHIP_CHECK(hipGetLastError());
@@ -419,7 +419,7 @@ int tsdfRebuildMasks(ohmhip_map_t m)
   const uint32_t voxels = uint32_t(m->mc.region_voxels);
   for (auto &entry : m->spilled)
   {
-    const float *state = reinterpret_cast<const float *>(entry.second.record + m->store.layer_offset[OHMHIP_LID_TSDF]);
+    const uint32_t *state = reinterpret_cast<const uint32_t *>(entry.second.record + m->store.layer_offset[OHMHIP_LID_TSDF]);
     uint32_t *mask = reinterpret_cast<uint32_t *>(entry.second.record + m->store.mask_offset);
     for (uint32_t w = 0; w < (voxels + 31u) / 32u; ++w)
     {
@@ -427,7 +427,7 @@ int tsdfRebuildMasks(ohmhip_map_t m)
       for (uint32_t b = 0; b < 32u && w * 32u + b < voxels; ++b)
       {
         const uint32_t vi = w * 32u + b;
-        bits |= tsdfCountable(state[2 * vi], state[2 * vi + 1], m->mc.tsdf_trunc) ? 0u : (1u << b);
+        bits |= replayMaskBit(kReplayMaskTsdf, state[2 * vi], state[2 * vi + 1], m->mc.tsdf_trunc) ? (1u << b) : 0u;
       }
       mask[w] = bits;
     }
@@ -927,6 +927,8 @@ OHMHIP_ABI_CATCH
 
 }  // extern "C"
 
+#include "tiling_impl.h"
+#include "write_side.h"
 #include "region_io.h"
 
 #include "spill_impl.h"
@@ -953,9 +955,7 @@ try
     // (the caller rewrote these slots behind the library's back: no use stamp moved, so the background write-back's
     // copies cannot tell -- all of them are void)
     dropPrecleaned(m);
-    const uint32_t *d_index = nullptr;
-    OHMHIP_CHECK(uploadSlotIndex(m, slots, count, m->stream, false, d_index));
-    orSlotBits(m, d_index, count, kDirtySync | kDirtyMerge | kDirtyClearance, m->stream);
+    OHMHIP_CHECK(markWrittenSlots(m, slots, count, kDirtySync | kDirtyMerge | kDirtyClearance, m->stream));
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   return hipGetLastError();
@@ -1027,7 +1027,6 @@ OHMHIP_ABI_CATCH
 
 #include "merge_impl.h"
 #include "partition_impl.h"
-#include "tiling_impl.h"
 #include "read_side.h"
 #include "query_impl.h"
 #include "clearance_impl.h"

@@ -1,7 +1,8 @@
 // region_io.h -- the entry points that list, read, write, create and remove regions (GpuLayerCache sync / upload,
-// ohmgpu/GpuLayerCache.cpp:172-182, 429-633; MapRegionCache::remove).
+// ohmgpu/GpuLayerCache.cpp:172-182, 429-633; MapRegionCache::remove).  ohmhip_map_write_regions is one of the write-side
+// features: the naming of its regions, its replay mask and its marks are write_side.h's.
 //
-// Part of ohmhip_map.hip's translation unit (included there, in order): not a stand-alone header.
+// Part of ohmhip_map.hip's translation unit (included there after write_side.h): not a stand-alone header.
 #ifndef OHMHIP_REGION_IO_H
 #define OHMHIP_REGION_IO_H
 
@@ -305,12 +306,9 @@ try
     return tiledWriteRegions(m, layer_id, keys_xyz, count, srcs);
   }
   OHMHIP_CHECK(hipStreamSynchronize(m->stream));
-  for (size_t i = 0; i < count && !m->precleaned.empty(); ++i)
-  {
-    // (the write-back's copy of a region that is being rewritten is void)
-    dropPrecleanedKey(m, packRegionKey(keys_xyz + 3 * i));
-  }
-  OHMHIP_CHECK(appendNamedRegions(m, keys_xyz, count, nullptr));  // (an upload edits the region where it lives: in the pool)
+  OHMHIP_CHECK(refreshHostRegionTable(m));
+  WrittenTiles named;  // (an upload edits the region where it lives: in the pool)
+  OHMHIP_CHECK(nameWrittenTiles(m, keys_xyz, count, named));
   const size_t stride = size_t(m->mc.region_voxels) * kLayerBytes[layer_id];
   const size_t burst = 64;
   int err = ensureStage(m, std::max(m->h_stage_bytes, burst * stride));
@@ -323,44 +321,26 @@ try
     const size_t n = std::min(burst, count - base);
     for (size_t k = 0; k < n; ++k)
     {
-      const int16_t *key = keys_xyz + 3 * (base + k);
-      const uint32_t slot = m->region_slots[packRegionKey(key)];
       std::memcpy(static_cast<char *>(m->h_stage.get()) + k * stride, srcs[base + k], stride);
-      OHMHIP_CHECK(hipMemcpyAsync(static_cast<char *>(m->pool.layers[layer_id].get()) + size_t(slot) * stride,
+      OHMHIP_CHECK(hipMemcpyAsync(static_cast<char *>(m->pool.layers[layer_id].get()) + size_t(named.slots[base + k]) * stride,
                                   static_cast<char *>(m->h_stage.get()) + k * stride, stride, hipMemcpyHostToDevice,
                                   m->copy_stream));
     }
     OHMHIP_CHECK(hipStreamSynchronize(m->copy_stream));
   }
-  // NDT / TSDF keep a persistent per-voxel "ordered replay" mask derived from the stored state: rebuild it for the
-  // uploaded regions when the layer that defines it was written.
-  const bool ndt = m->config.mode == OHMHIP_MODE_NDT_OM || m->config.mode == OHMHIP_MODE_NDT_TM;
-  const bool tsdf = m->config.mode == OHMHIP_MODE_TSDF;
-  if ((ndt && layer_id == OHMHIP_LID_MEAN) || (tsdf && layer_id == OHMHIP_LID_TSDF))
+  // The replay mask of the uploaded regions, when the layer that defines it was written (write_side.h).
+  const ReplayMaskKind kind = replayMaskKind(m, layer_id);
+  if (kind != kReplayMaskNone)
   {
     for (size_t i = 0; i < count; ++i)
     {
-      const uint32_t slot = m->region_slots[packRegionKey(keys_xyz + 3 * i)];
-      hipLaunchKernelGGL(k_rebuild_mask, dim3(4), dim3(256), 0, m->stream, m->mc, slot,
-                         ndt ? static_cast<const uint32_t *>(m->pool.layers[OHMHIP_LID_MEAN].get()) : nullptr,
-                         tsdf ? static_cast<const float *>(m->pool.layers[OHMHIP_LID_TSDF].get()) : nullptr, m->pool.d_hit_mask);
+      hipLaunchKernelGGL(k_rebuild_mask, dim3(4), dim3(256), 0, m->stream, m->mc, named.slots[i], uint32_t(kind),
+                         static_cast<const uint32_t *>(m->pool.layers[layer_id].get()), m->pool.d_hit_mask.get());
     }
     OHMHIP_CHECK(hipStreamSynchronize(m->stream));
   }
-  // (an occupancy upload makes the neighbourhood's clearance stale; a clearance upload makes the region's own)
-  for (size_t i = 0; i < count && (layer_id == OHMHIP_LID_OCCUPANCY || layer_id == OHMHIP_LID_CLEARANCE); ++i)
-  {
-    const uint64_t key = packRegionKey(keys_xyz + 3 * i);
-    if (layer_id == OHMHIP_LID_OCCUPANCY)
-    {
-      clearanceMarkChanged(m, key);
-    }
-    else
-    {
-      clearanceMarkUnwritten(m, key);
-    }
-  }
-  return OHMHIP_OK;
+  // (an upload leaves no dirty bits)
+  return markWrittenTiles(m, keys_xyz, named.slots.data(), count, OHMHIP_LAYER_BIT(layer_id), 0u, m->stream);
 }
 OHMHIP_ABI_CATCH
 

@@ -436,7 +436,7 @@ __global__ void __launch_bounds__(256) k_batch_reset(BatchScratch bs, uint32_t n
 /// float rounding of (sdf + trunc * w) / (w + 1) for w <= 1e4 (needs > 2e-3 relative margin; 1 % is used).
 constexpr float kTsdfFreeMargin = 1.01f;
 /// The weights that argument covers.  A map whose max_weight lies above it replays every visit (batch_run.h), and a
-/// stored voxel whose state tsdfCountable() does not cover is flagged for the ordered replay by k_rebuild_mask.
+/// stored voxel whose state tsdfCountable() does not cover is flagged for the ordered replay (replayMaskBit).
 constexpr float kTsdfCountedWeightLimit = 1e4f;
 
 /// The stored states on which n free-space visits are (min(w + float(n), max_weight), trunc), as calculateTsdf gives
@@ -458,6 +458,25 @@ __host__ __device__ inline bool tsdfCountable(float wgt, float dist, float trunc
     return dist == 0.0f;
   }
   return dist == trunc && wgt >= 1.0f && wgt <= kTsdfCountedWeightLimit && wgt == truncf(wgt);
+}
+
+/// The layer a map's persistent "ordered replay" voxel mask is derived from, and by which rule.
+enum ReplayMaskKind : uint32_t
+{
+  kReplayMaskNone = 0,  ///< the layer does not define the map's mask
+  kReplayMaskMean = 1,  ///< NDT maps, VoxelMean {coord, count}: the voxel holds samples (count > 0)
+  kReplayMaskTsdf = 2,  ///< TSDF maps, VoxelTsdf {weight, distance}: a state the counting shortcut does not cover
+};
+
+/// THE mask rule: the replay-mask bit of a voxel whose stored state in the defining layer is the words (word0, word1),
+/// under the truncation distance of the map that holds the mask.  Every writer of the mask calls it: k_rebuild_mask,
+/// k_copy_map, k_edit_apply and the host's pass over store records (tsdfRebuildMasks).  Which layer defines the mask
+/// of which map is the host's replayMaskKind (write_side.h).
+__host__ __device__ inline bool replayMaskBit(uint32_t kind, uint32_t word0, uint32_t word1, float tsdf_trunc)
+{
+  return (kind == kReplayMaskMean)
+           ? word1 > 0u
+           : !tsdfCountable(__builtin_bit_cast(float, word0), __builtin_bit_cast(float, word1), tsdf_trunc);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -709,12 +728,12 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-/// Rebuild the persistent "ordered replay" voxel mask of the regions in slots first_slot + blockIdx.y from their stored
-/// layers (after a CPU upload; for every slot after a TSDF option change): NDT: voxels holding samples
-/// (mean.count > 0); TSDF: every voxel whose state the counting shortcut does not cover (tsdfCountable).
+/// Rebuild the persistent "ordered replay" voxel mask of the regions in slots first_slot + blockIdx.y from the stored
+/// layer that defines it (after a CPU upload; for every slot after a TSDF option change), by replayMaskBit.  `layer`:
+/// the pool's layer of `kind`, two words per voxel.
 __global__ void __launch_bounds__(256)
-  k_rebuild_mask(MapConst mc, uint32_t first_slot, const uint32_t *__restrict__ mean_layer,
-                 const float *__restrict__ tsdf_layer, uint32_t *__restrict__ hit_mask)
+  k_rebuild_mask(MapConst mc, uint32_t first_slot, uint32_t kind, const uint32_t *__restrict__ layer,
+                 uint32_t *__restrict__ hit_mask)
 {
   const uint32_t slot = first_slot + blockIdx.y;
   const uint32_t mask_words = uint32_t(mc.region_voxels + 31) >> 5;
@@ -727,15 +746,7 @@ __global__ void __launch_bounds__(256)
       const uint32_t vi = w * 32 + b;
       if (vi < uint32_t(mc.region_voxels))
       {
-        bool flag = false;
-        if (mean_layer)
-        {
-          flag = mean_layer[2 * (base + vi) + 1] > 0;
-        }
-        if (tsdf_layer)
-        {
-          flag = flag || !tsdfCountable(tsdf_layer[2 * (base + vi)], tsdf_layer[2 * (base + vi) + 1], mc.tsdf_trunc);
-        }
+        const bool flag = replayMaskBit(kind, layer[2 * (base + vi)], layer[2 * (base + vi) + 1], mc.tsdf_trunc);
         bits |= flag ? (1u << b) : 0u;
       }
     }

@@ -1,5 +1,5 @@
 // tiling_impl.h -- regions larger than one LDS tile (include/ohmhip.h, "LARGE REGIONS"; ohm/OccupancyMap.h:287 takes any
-// glm::u8vec3 region size, up to 255 voxels per axis).  Included at the end of ohmhip_map.hip.
+// glm::u8vec3 region size, up to 255 voxels per axis).  Included in ohmhip_map.hip ahead of write_side.h and region_io.h, which cut regions into tiles.
 //
 // Inside the library such a region is a set of equal TILES of at most 32768 voxels (MapConst::dim); the whole pipeline --
 // hash table, pool slots, LDS count tile, 15-bit voxel indices in segment, sample and event keys -- works in tiles and

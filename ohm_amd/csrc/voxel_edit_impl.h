@@ -1,9 +1,10 @@
 // voxel_edit_impl.h -- ohmhip_map_write_voxels / ohmhip_map_integrate_voxels and their _device forms: voxels edited by
-// key where they live, in the pool (include/ohmhip.h, VOXEL EDITS).  The regions an edit names are
-// created or brought back the way ohmhip_map_write_regions does it (region_io.h), and the marks an upload leaves are
-// left per touched region; the voxels are written by voxel_edit_kernels.h.
+// key where they live, in the pool (include/ohmhip.h, VOXEL EDITS).  The tiles an edit names are
+// created or brought back, and the marks of an upload left on them, by write_side.h; the voxels are
+// written by voxel_edit_kernels.h.
 //
-// Part of ohmhip_map.hip's translation unit (included there, after read_side.h): not a stand-alone header.
+// Part of ohmhip_map.hip's translation unit (included there, after read_side.h and write_side.h): not a stand-alone
+// header.
 #ifndef OHMHIP_VOXEL_EDIT_IMPL_H
 #define OHMHIP_VOXEL_EDIT_IMPL_H
 
@@ -110,35 +111,12 @@ int editDevice(ohmhip_map_t m, const EditRequest &rq, ohmhip_voxel_edit_stats &s
   }
   const size_t n_tiles = tiles.size();
   std::vector<int16_t> tile_keys(3 * n_tiles);
-  std::unordered_map<uint64_t, char> regions;  // the caller's region -> whether the map held it
-  std::vector<TileRef> of_region;
-  uint64_t created = 0;
   for (size_t i = 0; i < n_tiles; ++i)
   {
-    int16_t *t = &tile_keys[3 * i];
-    unpackRegionKey(tiles[i], t);
-    if (regions.count(callerRegionKey(m, tiles[i])))
-    {
-      continue;
-    }
-    int16_t r[3];
-    regionOfTile(m->mc, t, r);
-    tilesOfRegion(m->mc, r, of_region);
-    bool held = false;
-    for (const TileRef &o : of_region)
-    {
-      held = held || tileExists(m, o.key);
-    }
-    regions.emplace(callerRegionKey(m, tiles[i]), held ? 1 : 0);
-    created += held ? 0u : 1u;
+    unpackRegionKey(tiles[i], &tile_keys[3 * i]);
   }
-  for (size_t i = 0; i < n_tiles && !m->precleaned.empty(); ++i)
-  {
-    dropPrecleanedKey(m, tiles[i]);  // (the write-back's copy of a region that is being rewritten is void)
-  }
-  // All regions are named before the first voxel is written: on failure the map holds what it held.
-  std::vector<uint32_t> slots(n_tiles);
-  OHMHIP_CHECK(appendNamedRegions(m, tile_keys.data(), n_tiles, slots.data()));
+  WrittenTiles named;  // (only the tiles written to)
+  OHMHIP_CHECK(nameWrittenTiles(m, tile_keys.data(), n_tiles, named));
 
   a.rt = regionTable(m);  // (the pool may have grown)
   a.sort_keys = keys_a;
@@ -158,8 +136,6 @@ int editDevice(ohmhip_map_t m, const EditRequest &rq, ohmhip_voxel_edit_stats &s
     OHMHIP_CHECK(es.temp.ensure(std::max<size_t>(sort_bytes, 16), false, s));
     OHMHIP_CHECK(rocprim::radix_sort_pairs(es.temp.ptr, sort_bytes, keys_a, keys_b, vals_a, vals_b, n, 0, end_bit, s));
   }
-  const bool ndt = m->config.mode == OHMHIP_MODE_NDT_OM || m->config.mode == OHMHIP_MODE_NDT_TM;
-  const bool tsdf = m->config.mode == OHMHIP_MODE_TSDF;
   a.sorted_keys = keys_b;
   a.sorted_vals = vals_b;
   a.layer = static_cast<uint32_t *>(m->pool.layers[rq.layer_id].get());
@@ -168,34 +144,15 @@ int editDevice(ohmhip_map_t m, const EditRequest &rq, ohmhip_voxel_edit_stats &s
   a.occupancy = static_cast<float *>(m->pool.layers[OHMHIP_LID_OCCUPANCY].get());
   a.mean = static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_MEAN].get());
   a.hit_mask = m->pool.d_hit_mask.get();
-  a.mask_kind = kEditMaskNone;
-  if (ndt && a.mean && (!rq.set || rq.layer_id == OHMHIP_LID_MEAN))
-  {
-    a.mask_kind = kEditMaskMean;
-  }
-  else if (tsdf && rq.set && rq.layer_id == OHMHIP_LID_TSDF)
-  {
-    a.mask_kind = kEditMaskTsdf;
-  }
+  // (integrateHit(map, sample) writes the mean)
+  a.mask_kind = replayMaskKind(m, rq.set ? rq.layer_id : int(OHMHIP_LID_MEAN));
   hipLaunchKernelGGL(k_edit_apply, grid, block, 0, s, a);
   OHMHIP_CHECK(hipGetLastError());
-  // E6: the marks of an upload.  All three dirty bits, as after ohmhip_map_mark_dirty; clearance by the caller's region.
-  {
-    const uint32_t *d_index = nullptr;
-    OHMHIP_CHECK(uploadSlotIndex(m, slots.data(), slots.size(), s, false, d_index));
-    orSlotBits(m, d_index, slots.size(), kDirtySync | kDirtyMerge | kDirtyClearance, s);
-  }
-  for (size_t i = 0; i < n_tiles; ++i)
-  {
-    if (!rq.set || rq.layer_id == OHMHIP_LID_OCCUPANCY)
-    {
-      clearanceMarkChanged(m, tiles[i]);
-    }
-    else if (rq.layer_id == OHMHIP_LID_CLEARANCE)
-    {
-      clearanceMarkUnwritten(m, tiles[i]);
-    }
-  }
+  // E6: the marks of an upload, with all three dirty bits; clearance by the caller's region.
+  const unsigned written = rq.set ? OHMHIP_LAYER_BIT(rq.layer_id)
+                                  : OHMHIP_LAYER_BIT(OHMHIP_LID_OCCUPANCY) | OHMHIP_LAYER_BIT(OHMHIP_LID_MEAN);
+  OHMHIP_CHECK(markWrittenTiles(m, tile_keys.data(), named.slots.data(), n_tiles, written,
+                                kDirtySync | kDirtyMerge | kDirtyClearance, s));
   OHMHIP_CHECK(hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, s));
   OHMHIP_CHECK(hipStreamSynchronize(s));  // (the slot list above is read until here)
   OHMHIP_CHECK(hipGetLastError());
@@ -206,8 +163,8 @@ int editDevice(ohmhip_map_t m, const EditRequest &rq, ohmhip_voxel_edit_stats &s
   st.applied = uint64_t(n) - null_keys;
   st.null_keys = null_keys;
   st.distinct_voxels = counters[kEditCountVoxels];
-  st.regions_touched = regions.size();
-  st.regions_created = created;
+  st.regions_touched = named.regions;
+  st.regions_created = named.created;
   return OHMHIP_OK;
 }
 

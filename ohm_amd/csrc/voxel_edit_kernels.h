@@ -8,7 +8,8 @@
 //
 // Between locate and apply a STABLE radix sort (rocprim::radix_sort_pairs) over the significant bits of the key: every
 // voxel's elements end up adjacent and in input order.  No atomic decides an order or a value; the only atomics are the
-// counters of the stats and the OR / AND on the replay mask word, where lanes of different voxels share a word.
+// counters of the stats and the OR / AND on the replay mask word, where lanes of different voxels share a word.  The
+// bit itself is replayMaskBit's (replay_kernels.h), for the kind the host picked (EditArgs::mask_kind).
 #ifndef OHMHIP_VOXEL_EDIT_KERNELS_H
 #define OHMHIP_VOXEL_EDIT_KERNELS_H
 
@@ -21,13 +22,6 @@ namespace ohmhip
 {
 constexpr unsigned long long kEditNullKey = ~0ull;
 constexpr uint32_t kEditVoxelBits = 15;  ///< a tile holds at most 32768 voxels (MapConst::dim)
-
-enum : uint32_t
-{
-  kEditMaskNone = 0,
-  kEditMaskMean = 1,  ///< NDT maps: mean.count > 0 (k_rebuild_mask)
-  kEditMaskTsdf = 2   ///< TSDF maps: !tsdfCountable
-};
 
 enum : uint32_t
 {
@@ -62,7 +56,7 @@ struct EditArgs
   float *occupancy;
   uint32_t *mean;  ///< null: the map has no mean layer (updatePositionSafe does nothing)
   uint32_t *hit_mask;
-  uint32_t mask_kind;
+  uint32_t mask_kind;  ///< ReplayMaskKind of the layer written (SET) or of the mean (HIT_SAMPLE)
 };
 
 /// Element i: whether it names a voxel, and then the voxel's tile, its index in the tile and its key in the caller's
@@ -189,14 +183,9 @@ __global__ void __launch_bounds__(256) k_edit_apply(EditArgs a)
     {
       dst[w] = src[w];
     }
-    if (a.mask_kind == kEditMaskMean)
+    if (a.mask_kind != kReplayMaskNone)
     {
-      flag = src[1] > 0u;
-      flag_known = true;
-    }
-    else if (a.mask_kind == kEditMaskTsdf)
-    {
-      flag = !tsdfCountable(__uint_as_float(src[0]), __uint_as_float(src[1]), mc.tsdf_trunc);
+      flag = replayMaskBit(a.mask_kind, src[0], src[1], mc.tsdf_trunc);
       flag_known = true;
     }
   }
@@ -239,16 +228,16 @@ __global__ void __launch_bounds__(256) k_edit_apply(EditArgs a)
     {
       a.mean[2 * gi] = mcoord;
       a.mean[2 * gi + 1] = mcount;
-      if (a.mask_kind == kEditMaskMean)
+      if (a.mask_kind == kReplayMaskMean)
       {
-        flag = mcount > 0u;
+        flag = replayMaskBit(kReplayMaskMean, mcoord, mcount, mc.tsdf_trunc);
         flag_known = true;
       }
     }
   }
   if (flag_known)
   {
-    // E6: the voxel's bit of the ordered-replay mask, by the rule of k_rebuild_mask
+    // E6: the voxel's bit of the ordered-replay mask (replayMaskBit above)
     const uint32_t mask_words = uint32_t(mc.region_voxels + 31) >> 5;
     uint32_t *word = a.hit_mask + size_t(slot) * mask_words + (voxel >> 5);
     if (flag)
