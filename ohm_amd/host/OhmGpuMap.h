@@ -346,15 +346,47 @@ public:
   }
 };
 
-/// ohm::GpuMap (ohmgpu/GpuMap.h:143-384)
-/// ohm::GpuKey (ohmgpu/GpuKey.h:37-46): the voxel key record the device reads and writes.
-struct CloudKey
+/// Voxel key: region + local coordinates (ohm/Key.h), in the layout of the 10-byte record the device reads and writes
+/// (ohm::GpuKey, ohmgpu/GpuKey.h:37-46), so arrays of keys cross the C ABI as they are.  `voxel` names all four bytes
+/// of the record -- the fourth is 0 except where a call documents a use for it -- and `local` its three coordinates;
+/// both are byte arrays over the same storage.  Equality is that of the voxel: the fourth byte does not take part.
+struct Key
 {
   int16_t region[3];
-  uint8_t voxel[4];
+  union
+  {
+    uint8_t voxel[4];
+    uint8_t local[3];
+  };
+  bool operator==(const Key &o) const
+  {
+    return region[0] == o.region[0] && region[1] == o.region[1] && region[2] == o.region[2] && local[0] == o.local[0] &&
+           local[1] == o.local[1] && local[2] == o.local[2];
+  }
 };
-static_assert(sizeof(CloudKey) == 10, "CloudKey keeps the 10-byte GpuKey layout");
+static_assert(sizeof(Key) == 10, "Key keeps the 10-byte GpuKey layout");
+/// The name the map's own calls use for the record.
+using CloudKey = Key;
 
+/// The keys of the regions a device map holds (ohmhip_map_regions), or of those modified since the last
+/// ohmhip_map_clear_dirty (ohmhip_map_dirty_regions): the count, then the list.  @return the status; `keys` is empty
+/// unless it is OHMHIP_OK.
+inline int fetchRegions(ohmhip_map_t map, bool dirty_only, std::vector<std::array<int16_t, 3>> &keys)
+{
+  const auto call = dirty_only ? &ohmhip_map_dirty_regions : &ohmhip_map_regions;
+  size_t count = 0;
+  keys.clear();
+  int status = call(map, nullptr, 0, &count);
+  if (status == OHMHIP_OK && count)
+  {
+    keys.resize(count);
+    status = call(map, keys.front().data(), count, &count);
+    keys.resize(status == OHMHIP_OK ? count : 0);
+  }
+  return status;
+}
+
+/// ohm::GpuMap (ohmgpu/GpuMap.h:143-384)
 class GpuMap : public RayMapper
 {
 public:
@@ -525,13 +557,9 @@ private:
     {
       return;
     }
-    size_t count = 0;
-    OHMHIP_GPUAPICHECK(ohmhip_map_dirty_regions(handle_, nullptr, 0, &count));
-    std::vector<int16_t> keys(3 * count);
-    if (count)
-    {
-      OHMHIP_GPUAPICHECK(ohmhip_map_dirty_regions(handle_, keys.data(), count, &count));
-    }
+    std::vector<std::array<int16_t, 3>> keys;
+    OHMHIP_GPUAPICHECK(fetchRegions(handle_, true, keys));
+    const size_t count = keys.size();
     const size_t voxels = map_->regionVoxelVolume();
     for (int layer = 0; layer < OHMHIP_LID_COUNT; ++layer)
     {
@@ -546,11 +574,11 @@ private:
       std::vector<void *> dsts(count);
       for (size_t i = 0; i < count; ++i)
       {
-        MapChunk &chunk = map_->region({ { keys[3 * i], keys[3 * i + 1], keys[3 * i + 2] } });
+        MapChunk &chunk = map_->region(keys[i]);
         chunk.voxel_blocks[layer].resize(voxels * ohmhip_layer_voxel_bytes(layer));
         dsts[i] = chunk.voxel_blocks[layer].data();
       }
-      OHMHIP_GPUAPICHECK(ohmhip_map_read_regions(handle_, layer, keys.data(), count, dsts.data()));
+      OHMHIP_GPUAPICHECK(ohmhip_map_read_regions(handle_, layer, keys.front().data(), count, dsts.data()));
     }
     if (!only)
     {
@@ -1453,39 +1481,25 @@ inline bool copyMap(GpuMap &dst, const GpuMap &src, const CopyChunkFilter &copy_
   }
   else if (copy_chunk_filter)
   {
-    auto list = [&](bool dirty, std::vector<int16_t> &out) {
-      size_t n = 0;
-      int err = dirty ? ohmhip_map_dirty_regions(src.handle(), nullptr, 0, &n) : ohmhip_map_regions(src.handle(), nullptr, 0, &n);
-      out.resize(3 * n);
-      if (err == OHMHIP_OK && n)
-      {
-        err = dirty ? ohmhip_map_dirty_regions(src.handle(), out.data(), n, &n) : ohmhip_map_regions(src.handle(), out.data(), n, &n);
-        out.resize(3 * n);
-      }
-      return err;
-    };
-    std::vector<int16_t> all, dirty;
-    if ((st = list(false, all)) != OHMHIP_OK || (st = list(true, dirty)) != OHMHIP_OK)
+    std::vector<std::array<int16_t, 3>> all, dirty;
+    if ((st = fetchRegions(src.handle(), false, all)) != OHMHIP_OK ||
+        (st = fetchRegions(src.handle(), true, dirty)) != OHMHIP_OK)
     {
       return false;
     }
-    std::map<std::array<int16_t, 3>, bool> is_dirty;
-    for (size_t i = 0; i + 2 < dirty.size(); i += 3)
-    {
-      is_dirty[{ { dirty[i], dirty[i + 1], dirty[i + 2] } }] = true;
-    }
+    std::sort(dirty.begin(), dirty.end());
     const int *dim = src.map().regionVoxelDimensions();
     const dvec3 spatial{ dim[0] * src.map().resolution(), dim[1] * src.map().resolution(), dim[2] * src.map().resolution() };
-    for (size_t i = 0; i + 2 < all.size(); i += 3)
+    for (const std::array<int16_t, 3> &coord : all)
     {
       CopyChunk chunk;
-      chunk.coord = { { all[i], all[i + 1], all[i + 2] } };
-      chunk.centre = dvec3{ double(all[i]) * spatial.x, double(all[i + 1]) * spatial.y, double(all[i + 2]) * spatial.z };
-      chunk.dirty = is_dirty.count(chunk.coord) != 0;
+      chunk.coord = coord;
+      chunk.centre = dvec3{ double(coord[0]) * spatial.x, double(coord[1]) * spatial.y, double(coord[2]) * spatial.z };
+      chunk.dirty = std::binary_search(dirty.begin(), dirty.end(), coord);
       chunk.region_spatial_dimensions = spatial;
       if (copy_chunk_filter(chunk))
       {
-        keys.insert(keys.end(), all.begin() + i, all.begin() + i + 3);
+        keys.insert(keys.end(), coord.begin(), coord.end());
       }
     }
     if (keys.empty())
@@ -1786,75 +1800,120 @@ private:
   int last_status_ = OHMHIP_OK;
 };
 
-/// Voxel key as the queries report it: region + local coordinates (ohm/Key.h; the device writes the reference's GpuKey
-/// records, ohmgpu/GpuKey.h:37-46).
-struct Key
-{
-  int16_t region[3];
-  uint8_t local[3];
-  bool operator==(const Key &o) const
-  {
-    return region[0] == o.region[0] && region[1] == o.region[1] && region[2] == o.region[2] && local[0] == o.local[0] &&
-           local[1] == o.local[1] && local[2] == o.local[2];
-  }
-};
-
-/// ohm::LineKeysQueryGpu (ohmgpu/LineKeysQueryGpu.h; the interface of ohm/LineKeysQuery.h:47-101 + ohm/Query.h:51-121):
-/// the voxel keys along a set of query lines, walked on the device with the CPU walk's fp64 semantics
-/// (ohmhip_map_line_keys).  The query needs the map's geometry only; it is given the GpuMap that holds the device
-/// handle.  Results as in the reference: one result per ray, resultIndices() / resultCounts() index
-/// intersectedVoxels().
-class LineKeysQueryGpu
+/// ohm::Query (ohm/Query.h:51-121) over a GpuMap: the map, the query flags, the result arrays every query shares and the
+/// execute / reset protocol.  A query derives from it and provides onExecute() and, if it holds more than the shared
+/// results, onReset(); one that always evaluates on the device names kQfGpuEvaluate in forcedQueryFlags().  The device
+/// calls are synchronous, so the asynchronous forms complete at once (ohm/Query.h:103-121).  The accessors here are
+/// ohm::Query's; a query whose reference class reports another type declares its own of the same name, which hides
+/// them: LineQueryGpu::ranges() are floats kept in an array of its own (through a Query& its ranges() is null), and
+/// NearestNeighbours returns the two shared arrays as vectors.
+class Query
 {
 public:
-  explicit LineKeysQueryGpu(GpuMap &gpu_map, unsigned query_flags = 0)
-    : gpu_map_(&gpu_map)
-    , query_flags_(query_flags)
-  {}
+  virtual ~Query() = default;
+
   void setGpuMap(GpuMap *gpu_map) { gpu_map_ = gpu_map; }
-  unsigned queryFlags() const { return query_flags_; }
+  GpuMap *gpuMap() const { return gpu_map_; }
+  unsigned queryFlags() const { return query_flags_ | forcedQueryFlags(); }
   void setQueryFlags(unsigned flags) { query_flags_ = flags; }
 
-  /// Ray start / end point pairs; @p point_count is twice the number of rays.
-  void setRays(const dvec3 *rays, size_t point_count)
-  {
-    rays_.assign(rays, rays + (point_count & ~size_t(1)));
-  }
-  const dvec3 *rays() const { return rays_.data(); }
-  size_t rayPointCount() const { return rays_.size(); }
-
-  size_t numberOfResults() const { return result_counts_.size(); }
-  const size_t *resultIndices() const { return result_indices_.data(); }
-  const size_t *resultCounts() const { return result_counts_.data(); }
+  size_t numberOfResults() const { return number_of_results_; }
   const Key *intersectedVoxels() const { return intersected_voxels_.data(); }
-  const double *ranges() const { return nullptr; }  // (not reported by this query, as in the reference)
+  /// Null for a query that reports no ranges.
+  const double *ranges() const { return ranges_.empty() ? nullptr : ranges_.data(); }
 
-  /// Synchronous query (ohm/Query.h:93).  @return true on success.
+  /// Synchronous query (ohm/Query.h:93): a soft reset, then onExecute().  @return true on success; false without a
+  /// usable map or when the device refuses, and then there are no results.
   bool execute()
   {
     reset(false);
-    const size_t ray_count = rays_.size() / 2;
     if (!gpu_map_ || !gpu_map_->gpuOk())
     {
       return false;
     }
+    if (!onExecute())
+    {
+      reset(false);
+      return false;
+    }
+    return true;
+  }
+  virtual bool executeAsync() { return execute(); }
+  bool wait(unsigned /*timeout_ms*/ = ~0u) { return true; }
+  /// Drops the results; a hard reset also releases their memory (ohm/Query.h:114) and whatever onReset(true) drops.
+  void reset(bool hard_reset = true)
+  {
+    number_of_results_ = 0;
+    intersected_voxels_.clear();
+    ranges_.clear();
+    if (hard_reset)
+    {
+      std::vector<Key>().swap(intersected_voxels_);
+      std::vector<double>().swap(ranges_);
+    }
+    onReset(hard_reset);
+  }
+
+protected:
+  Query(GpuMap *gpu_map, unsigned query_flags)
+    : gpu_map_(gpu_map)
+    , query_flags_(query_flags)
+  {}
+  /// Fill the results and set number_of_results_; the map is there and valid.
+  virtual bool onExecute() = 0;
+  virtual void onReset(bool /*hard_reset*/) {}
+  /// Bits queryFlags() always reports.
+  virtual unsigned forcedQueryFlags() const { return 0; }
+
+  GpuMap *gpu_map_ = nullptr;
+  unsigned query_flags_ = 0;
+  size_t number_of_results_ = 0;
+  std::vector<Key> intersected_voxels_;
+  std::vector<double> ranges_;
+};
+
+/// Worst case of the number of voxels on the line from a to b, as the reference sizes its key buffer
+/// (ohmgpu/LineKeysQueryGpu.cpp:112-119).
+inline uint32_t maxKeysPerLine(const dvec3 &a, const dvec3 &b, double resolution)
+{
+  const double len = std::sqrt((b.x - a.x) * (b.x - a.x) + (b.y - a.y) * (b.y - a.y) + (b.z - a.z) * (b.z - a.z));
+  return uint32_t(std::ceil(len / resolution * std::sqrt(3.0))) + 4u;
+}
+
+/// ohm::LineKeysQueryGpu (ohmgpu/LineKeysQueryGpu.h; the interface of ohm/LineKeysQuery.h:47-101): the voxel keys along a
+/// set of query lines, walked on the device with the CPU walk's fp64 semantics (ohmhip_map_line_keys).  The query needs
+/// the map's geometry only; it is given the GpuMap that holds the device handle.  Results as in the reference: one
+/// result per ray, resultIndices() / resultCounts() index intersectedVoxels(); no ranges.  A reset keeps the rays.
+class LineKeysQueryGpu : public Query
+{
+public:
+  explicit LineKeysQueryGpu(GpuMap &gpu_map, unsigned query_flags = 0) : Query(&gpu_map, query_flags) {}
+
+  /// Ray start / end point pairs; @p point_count is twice the number of rays.
+  void setRays(const dvec3 *rays, size_t point_count) { rays_.assign(rays, rays + (point_count & ~size_t(1))); }
+  const dvec3 *rays() const { return rays_.data(); }
+  size_t rayPointCount() const { return rays_.size(); }
+
+  const size_t *resultIndices() const { return result_indices_.data(); }
+  const size_t *resultCounts() const { return result_counts_.data(); }
+
+protected:
+  bool onExecute() override
+  {
+    const size_t ray_count = rays_.size() / 2;
     if (ray_count == 0)
     {
       return true;
     }
-    // Worst case keys per line, as the reference sizes its buffer (ohmgpu/LineKeysQueryGpu.cpp:112-119).
-    const double res = gpu_map_->map().resolution();
     uint32_t max_keys = 1;
     for (size_t i = 0; i < ray_count; ++i)
     {
-      const dvec3 &a = rays_[2 * i], &b = rays_[2 * i + 1];
-      const double len = std::sqrt((b.x - a.x) * (b.x - a.x) + (b.y - a.y) * (b.y - a.y) + (b.z - a.z) * (b.z - a.z));
-      max_keys = std::max<uint32_t>(max_keys, uint32_t(std::ceil(len / res * std::sqrt(3.0))) + 4u);
+      max_keys = std::max(max_keys, maxKeysPerLine(rays_[2 * i], rays_[2 * i + 1], gpu_map_->map().resolution()));
     }
-    std::vector<unsigned char> records(ray_count * size_t(max_keys) * 10u);
+    std::vector<Key> records(ray_count * size_t(max_keys));
     std::vector<uint32_t> counts(ray_count);
-    if (ohmhip_map_line_keys(gpu_map_->handle(), reinterpret_cast<const double *>(rays_.data()), ray_count, max_keys,
-                             records.data(), counts.data()) != OHMHIP_OK)
+    if (ohmhip_map_line_keys(gpu_map_->handle(), &rays_[0].x, ray_count, max_keys, records.data(), counts.data()) !=
+        OHMHIP_OK)
     {
       return false;
     }
@@ -1862,41 +1921,23 @@ public:
     result_counts_.resize(ray_count);
     for (size_t i = 0; i < ray_count; ++i)
     {
+      const auto first = records.begin() + i * size_t(max_keys);
       result_indices_[i] = intersected_voxels_.size();
-      const size_t n = std::min<size_t>(counts[i], max_keys);
-      result_counts_[i] = n;
-      for (size_t j = 0; j < n; ++j)
-      {
-        const unsigned char *rec = records.data() + (i * size_t(max_keys) + j) * 10u;
-        Key key;
-        std::memcpy(key.region, rec, 6);
-        std::memcpy(key.local, rec + 6, 3);
-        intersected_voxels_.push_back(key);
-      }
+      result_counts_[i] = std::min<size_t>(counts[i], max_keys);
+      intersected_voxels_.insert(intersected_voxels_.end(), first, first + result_counts_[i]);
     }
+    number_of_results_ = ray_count;
     return true;
   }
-  /// The device call is synchronous: the asynchronous forms complete at once (ohm/Query.h:103-121).
-  bool executeAsync() { return execute(); }
-  bool wait(unsigned /*timeout_ms*/ = ~0u) { return true; }
-  void reset(bool hard_reset = true)
+  void onReset(bool) override
   {
     result_indices_.clear();
     result_counts_.clear();
-    intersected_voxels_.clear();
-    if (hard_reset)
-    {
-      // (hard reset releases memory, ohm/Query.h:114)
-      std::vector<Key>().swap(intersected_voxels_);
-    }
   }
 
 private:
-  GpuMap *gpu_map_ = nullptr;
-  unsigned query_flags_ = 0;
   std::vector<dvec3> rays_;
   std::vector<size_t> result_indices_, result_counts_;
-  std::vector<Key> intersected_voxels_;
 };
 
 /// ohm::OccupancyType (ohm/OccupancyType.h:14-24).
@@ -1911,29 +1952,21 @@ enum OccupancyType : int
 /// ohm::QueryFlag::kQfGpuEvaluate (ohm/QueryFlag.h:42).
 constexpr unsigned kQfGpuEvaluate = 1u << 2u;
 
-/// ohm::RaysQueryGpu (ohmgpu/RaysQueryGpu.h; the interface of ohm/RaysQuery.h + ohm/Query.h:51-121): for each ray, the
-/// range to the first occupied voxel, the unobserved volume crossed, and the state and key of the voxel the ray ends in
-/// -- evaluated on the device against the resident map (ohmhip_map_rays_query), bit-identical to the CPU query
-/// (ohm/RaysQuery.cpp:102-203).  The map's current parameters apply; the map is read, never changed.
-class RaysQueryGpu
+/// ohm::RaysQueryGpu (ohmgpu/RaysQueryGpu.h; the interface of ohm/RaysQuery.h): for each ray, the range to the first
+/// occupied voxel, the unobserved volume crossed, and the state and key of the voxel the ray ends in -- evaluated on the
+/// device against the resident map (ohmhip_map_rays_query), bit-identical to the CPU query (ohm/RaysQuery.cpp:102-203).
+/// The map's current parameters apply; the map is read, never changed.  A hard reset also drops the rays
+/// (ohm/RaysQuery.cpp onReset).
+class RaysQueryGpu : public Query
 {
 public:
-  explicit RaysQueryGpu(GpuMap &gpu_map, unsigned query_flags = 0)
-    : gpu_map_(&gpu_map)
-    , query_flags_(query_flags | kQfGpuEvaluate)
-  {}
-  void setGpuMap(GpuMap *gpu_map) { gpu_map_ = gpu_map; }
-  unsigned queryFlags() const { return query_flags_; }
-  void setQueryFlags(unsigned flags) { query_flags_ = flags | kQfGpuEvaluate; }
+  explicit RaysQueryGpu(GpuMap &gpu_map, unsigned query_flags = 0) : Query(&gpu_map, query_flags) {}
 
   void setVolumeCoefficient(double coefficient) { volume_coefficient_ = coefficient; }
   double volumeCoefficient() const { return volume_coefficient_; }
 
   /// Origin / end point pairs; @p element_count is twice the number of rays (an odd trailing point is dropped).
-  void setRays(const dvec3 *rays, size_t element_count)
-  {
-    rays_.assign(rays, rays + (element_count & ~size_t(1)));
-  }
+  void setRays(const dvec3 *rays, size_t element_count) { rays_.assign(rays, rays + (element_count & ~size_t(1))); }
   void addRays(const dvec3 *rays, size_t element_count)
   {
     rays_.insert(rays_.end(), rays, rays + (element_count & ~size_t(1)));
@@ -1947,52 +1980,40 @@ public:
   const dvec3 *rays() const { return rays_.data(); }
   size_t numberOfRays() const { return rays_.size() / 2; }
 
-  size_t numberOfResults() const { return ranges_.size(); }
-  const double *ranges() const { return ranges_.data(); }
   const double *unobservedVolumes() const { return volumes_.data(); }
   const OccupancyType *terminalOccupancyTypes() const { return types_.data(); }
-  const Key *intersectedVoxels() const { return keys_.data(); }
 
-  /// Synchronous query (ohm/Query.h:93).  @return true on success.
-  bool execute()
+protected:
+  unsigned forcedQueryFlags() const override { return kQfGpuEvaluate; }
+  bool onExecute() override
   {
-    reset(false);
-    if (!gpu_map_ || !gpu_map_->gpuOk() || !gpu_map_->syncConfig())
+    if (!gpu_map_->syncConfig())
     {
       return false;
     }
     const size_t n = rays_.size() / 2;
     std::vector<int8_t> types(n);
-    std::vector<unsigned char> records(n * 10u);
     ranges_.resize(n);
     volumes_.resize(n);
+    intersected_voxels_.resize(n);
     if (ohmhip_map_rays_query(gpu_map_->handle(), reinterpret_cast<const double *>(rays_.data()), rays_.size(),
                               volume_coefficient_, ranges_.data(), volumes_.data(), types.data(),
-                              records.data()) != OHMHIP_OK)
+                              intersected_voxels_.data()) != OHMHIP_OK)
     {
-      reset(false);
       return false;
     }
     types_.resize(n);
-    keys_.resize(n);
     for (size_t i = 0; i < n; ++i)
     {
       types_[i] = OccupancyType(types[i]);
-      std::memcpy(keys_[i].region, records.data() + i * 10u, 6);
-      std::memcpy(keys_[i].local, records.data() + i * 10u + 6, 3);
     }
+    number_of_results_ = n;
     return true;
   }
-  /// The device call is synchronous: the asynchronous forms complete at once (ohm/Query.h:103-121).
-  bool executeAsync() { return execute(); }
-  bool wait(unsigned /*timeout_ms*/ = ~0u) { return true; }
-  /// Drops the results; @p hard_reset also drops the rays (ohm/RaysQuery.cpp onReset).
-  void reset(bool hard_reset = true)
+  void onReset(bool hard_reset) override
   {
-    ranges_.clear();
     volumes_.clear();
     types_.clear();
-    keys_.clear();
     if (hard_reset)
     {
       rays_.clear();
@@ -2000,13 +2021,10 @@ public:
   }
 
 private:
-  GpuMap *gpu_map_ = nullptr;
-  unsigned query_flags_ = kQfGpuEvaluate;
   double volume_coefficient_ = 1.0;
   std::vector<dvec3> rays_;
-  std::vector<double> ranges_, volumes_;
+  std::vector<double> volumes_;
   std::vector<OccupancyType> types_;
-  std::vector<Key> keys_;
 };
 
 /// The other ohm::QueryFlag bits (ohm/QueryFlag.h:35-60).
@@ -2016,11 +2034,6 @@ constexpr unsigned kQfNoCache = 1u << 3u;
 constexpr unsigned kQfReportUnscaledResults = 1u << 4u;
 constexpr unsigned kQfSpecialised = 1u << 16u;
 
-/// ohm::ClearanceProcess (ohmgpu/ClearanceProcess.h): the clearance of every voxel of a set of regions -- the distance
-/// to the nearest obstructing voxel within the search radius, per calculateNearestNeighbour (ohm/private/
-/// VoxelAlgorithms.cpp:22-98), evaluated exactly on the device (ohmhip_map_clearance_regions), not by the reference's
-/// approximate flood fill.  Results are kept here per region: the device map has no clearance layer.  Not provided:
-/// update() (incremental dirty-region processing), stamp-based skipping (force = false recomputes), serialisation.
 /// ohm::MappingProcessResult (ohm/MappingProcess.h:18-24).
 enum MappingProcessResult : int
 {
@@ -2028,6 +2041,25 @@ enum MappingProcessResult : int
   kMprProgressing = 1
 };
 
+/// The parameter block of the clearance calls (ohmhip_map_clearance_*) from a search radius, ohm::QueryFlag bits and the
+/// per-axis scaling.
+inline ohmhip_clearance_params clearanceParams(float search_radius, unsigned query_flags, const float axis_scaling[3])
+{
+  ohmhip_clearance_params p{};
+  p.search_radius = search_radius;
+  for (int a = 0; a < 3; ++a)
+  {
+    p.axis_scaling[a] = axis_scaling[a];
+  }
+  p.flags = query_flags;
+  return p;
+}
+
+/// ohm::ClearanceProcess (ohmgpu/ClearanceProcess.h): the clearance of every voxel of a set of regions -- the distance
+/// to the nearest obstructing voxel within the search radius, per calculateNearestNeighbour (ohm/private/
+/// VoxelAlgorithms.cpp:22-98), evaluated exactly on the device (ohmhip_map_clearance_regions), not by the reference's
+/// approximate flood fill.  calculateForExtents() keeps its results here per region; update() keeps the map's clearance
+/// layer current.  Not provided: stamp-based skipping (force = false recomputes), serialisation.
 class ClearanceProcess
 {
 public:
@@ -2071,10 +2103,11 @@ public:
       return OHMHIP_ERR_INVALID_ARG;
     }
     const auto start = std::chrono::steady_clock::now();
+    const ohmhip_clearance_params p = params();
     for (;;)
     {
       size_t processed = 0, remaining = 0;
-      const int status = ohmhip_map_clearance_update(gpu_map.handle(), params(), max_regions, &processed, &remaining);
+      const int status = ohmhip_map_clearance_update(gpu_map.handle(), &p, max_regions, &processed, &remaining);
       if (status != OHMHIP_OK)
       {
         return status;
@@ -2115,13 +2148,7 @@ public:
     std::vector<RegionKey> present;
     if (!(query_flags_ & kQfInstantiateUnknown))
     {
-      size_t n = 0;
-      if (ohmhip_map_regions(gpu_map.handle(), nullptr, 0, &n) != OHMHIP_OK)
-      {
-        return false;
-      }
-      present.resize(n);
-      if (n && ohmhip_map_regions(gpu_map.handle(), present.front().data(), n, &n) != OHMHIP_OK)
+      if (fetchRegions(gpu_map.handle(), false, present) != OHMHIP_OK)
       {
         return false;
       }
@@ -2150,7 +2177,8 @@ public:
     {
       dsts[i] = blocks[i].data();
     }
-    if (ohmhip_map_clearance_regions(gpu_map.handle(), keys.data(), count, params(), dsts.data()) != OHMHIP_OK)
+    const ohmhip_clearance_params p = params();
+    if (ohmhip_map_clearance_regions(gpu_map.handle(), keys.data(), count, &p, dsts.data()) != OHMHIP_OK)
     {
       return false;
     }
@@ -2159,7 +2187,7 @@ public:
       results_[RegionKey{ keys[3 * i], keys[3 * i + 1], keys[3 * i + 2] }] = std::move(blocks[i]);
     }
     if (m.hasLayer(OHMHIP_LID_CLEARANCE) &&
-        ohmhip_map_clearance_update_regions(gpu_map.handle(), keys.data(), count, params(), force ? 1 : 0, nullptr) !=
+        ohmhip_map_clearance_update_regions(gpu_map.handle(), keys.data(), count, &p, force ? 1 : 0, nullptr) !=
           OHMHIP_OK)
     {
       return false;
@@ -2186,30 +2214,14 @@ public:
   }
 
 private:
-  const ohmhip_clearance_params *params()
-  {
-    params_.search_radius = search_radius_;
-    for (int a = 0; a < 3; ++a)
-    {
-      params_.axis_scaling[a] = axis_scaling_[a];
-    }
-    params_.flags = query_flags_;
-    return &params_;
-  }
+  ohmhip_clearance_params params() const { return clearanceParams(search_radius_, query_flags_, axis_scaling_); }
 
   float search_radius_ = 0.0f;
   unsigned query_flags_ = 0;
   float axis_scaling_[3] = { 1.0f, 1.0f, 1.0f };
-  ohmhip_clearance_params params_{};
   std::map<RegionKey, std::vector<float>> results_;
 };
 
-/// ohm::LineQueryGpu (ohmgpu/LineQueryGpu.{h,cpp}; interface of ohm/LineQuery.h): the voxels a segment passes through
-/// (calculateSegmentKeys, device walk: ohmhip_map_line_keys) and the clearance of each (ohmhip_map_clearance_keys),
-/// with LineQueryGpu::onExecute's post-processing: a voxel in no region of the map, or unobstructed within the radius
-/// (-1), reports defaultRange(); only kQfUnknownAsOccupied is passed to the clearance.  kQfNearestResult keeps the
-/// first voxel, then any later one with range >= 0 && (range < closest || closest < 0) -- the GPU query's rule; the CPU
-/// LineQuery compares range * range < closest (ohm/LineQuery.cpp:75-84) and is not followed.
 /// ohm::Mapper (ohm/Mapper.h): runs its processes (ClearanceProcess) over one GpuMap between integrateRays batches.
 class Mapper
 {
@@ -2259,16 +2271,22 @@ private:
   std::vector<std::unique_ptr<ClearanceProcess>> processes_;
 };
 
-class LineQueryGpu
+/// ohm::LineQueryGpu (ohmgpu/LineQueryGpu.{h,cpp}; interface of ohm/LineQuery.h): the voxels a segment passes through
+/// (calculateSegmentKeys, device walk: ohmhip_map_line_keys) and the clearance of each (ohmhip_map_clearance_keys),
+/// with LineQueryGpu::onExecute's post-processing: a voxel in no region of the map, or unobstructed within the radius
+/// (-1), reports defaultRange(); only kQfUnknownAsOccupied is passed to the clearance.  kQfNearestResult keeps the
+/// first voxel, then any later one with range >= 0 && (range < closest || closest < 0) -- the GPU query's rule; the CPU
+/// LineQuery compares range * range < closest (ohm/LineQuery.cpp:75-84) and is not followed.  ranges() are floats, as
+/// the reference reports them.
+class LineQueryGpu : public Query
 {
 public:
   LineQueryGpu(GpuMap &gpu_map, const dvec3 &start_point, const dvec3 &end_point, float search_radius,
                unsigned query_flags = 0)
-    : gpu_map_(&gpu_map)
+    : Query(&gpu_map, query_flags)
     , start_(start_point)
     , end_(end_point)
     , search_radius_(search_radius)
-    , query_flags_(query_flags | kQfGpuEvaluate)
   {}
 
   void setStartPoint(const dvec3 &p) { start_ = p; }
@@ -2277,8 +2295,6 @@ public:
   void setSearchRadius(float r) { search_radius_ = r; }
   float defaultRange() const { return default_range_; }
   void setDefaultRange(float range) { default_range_ = range; }
-  unsigned queryFlags() const { return query_flags_; }
-  void setQueryFlags(unsigned flags) { query_flags_ = flags | kQfGpuEvaluate; }
   void setAxisScaling(float x, float y, float z)
   {
     axis_scaling_[0] = x;
@@ -2286,67 +2302,49 @@ public:
     axis_scaling_[2] = z;
   }
 
-  size_t numberOfResults() const { return ranges_.size(); }
-  const Key *intersectedVoxels() const { return keys_.data(); }
-  const float *ranges() const { return ranges_.data(); }
+  const float *ranges() const { return float_ranges_.data(); }
 
-  /// Synchronous query (ohm/Query.h:93).  @return true on success.
-  bool execute()
+protected:
+  unsigned forcedQueryFlags() const override { return kQfGpuEvaluate; }
+  bool onExecute() override
   {
-    reset();
-    if (!gpu_map_ || !gpu_map_->gpuOk() || !gpu_map_->syncConfig())
+    if (!gpu_map_->syncConfig())
     {
       return false;
     }
     const double line[6] = { start_.x, start_.y, start_.z, end_.x, end_.y, end_.z };
-    const double dx = end_.x - start_.x, dy = end_.y - start_.y, dz = end_.z - start_.z;
-    const double len = std::sqrt(dx * dx + dy * dy + dz * dz);
-    const uint32_t max_keys = uint32_t(std::ceil(len / gpu_map_->map().resolution() * std::sqrt(3.0))) + 4u;
-    std::vector<unsigned char> records(size_t(max_keys) * 10u);
+    const uint32_t max_keys = maxKeysPerLine(start_, end_, gpu_map_->map().resolution());
+    std::vector<Key> &keys = intersected_voxels_;
+    keys.resize(max_keys);
     uint32_t count = 0;
-    if (ohmhip_map_line_keys(gpu_map_->handle(), line, 1, max_keys, records.data(), &count) != OHMHIP_OK)
+    if (ohmhip_map_line_keys(gpu_map_->handle(), line, 1, max_keys, keys.data(), &count) != OHMHIP_OK)
     {
       return false;
     }
     const size_t n = std::min<size_t>(count, max_keys);
-    std::vector<float> ranges(n);
-    ohmhip_clearance_params p{};
-    p.search_radius = search_radius_;
-    for (int a = 0; a < 3; ++a)
-    {
-      p.axis_scaling[a] = axis_scaling_[a];
-    }
-    p.flags = query_flags_ & kQfUnknownAsOccupied;
-    if (n && ohmhip_map_clearance_keys(gpu_map_->handle(), records.data(), n, &p, ranges.data()) != OHMHIP_OK)
+    keys.resize(n);
+    float_ranges_.resize(n);
+    const ohmhip_clearance_params p = clearanceParams(search_radius_, query_flags_ & kQfUnknownAsOccupied, axis_scaling_);
+    if (n && ohmhip_map_clearance_keys(gpu_map_->handle(), keys.data(), n, &p, float_ranges_.data()) != OHMHIP_OK)
     {
       return false;
     }
-    size_t n_regions = 0;
-    if (ohmhip_map_regions(gpu_map_->handle(), nullptr, 0, &n_regions) != OHMHIP_OK)
-    {
-      return false;
-    }
-    std::vector<std::array<int16_t, 3>> present(n_regions);
-    if (n_regions && ohmhip_map_regions(gpu_map_->handle(), present.front().data(), n_regions, &n_regions) != OHMHIP_OK)
+    std::vector<std::array<int16_t, 3>> present;
+    if (fetchRegions(gpu_map_->handle(), false, present) != OHMHIP_OK)
     {
       return false;
     }
     std::sort(present.begin(), present.end());
-    keys_.resize(n);
-    ranges_.resize(n);
     size_t closest_index = 0;
     float closest = -1.0f;
     for (size_t i = 0; i < n; ++i)
     {
-      std::memcpy(keys_[i].region, records.data() + i * 10u, 6);
-      std::memcpy(keys_[i].local, records.data() + i * 10u + 6, 3);
-      const std::array<int16_t, 3> rk = { keys_[i].region[0], keys_[i].region[1], keys_[i].region[2] };
-      float range = ranges[i];
+      const std::array<int16_t, 3> rk = { keys[i].region[0], keys[i].region[1], keys[i].region[2] };
+      float &range = float_ranges_[i];
       if (!std::binary_search(present.begin(), present.end(), rk) || range < 0)
       {
         range = default_range_;
       }
-      ranges_[i] = range;
       if (i == 0 || (range >= 0 && (range < closest || closest < 0)))
       {
         closest_index = i;
@@ -2355,30 +2353,22 @@ public:
     }
     if ((query_flags_ & kQfNearestResult) && n)
     {
-      keys_[0] = keys_[closest_index];
-      ranges_[0] = ranges_[closest_index];
-      keys_.resize(1);
-      ranges_.resize(1);
+      keys[0] = keys[closest_index];
+      float_ranges_[0] = float_ranges_[closest_index];
+      keys.resize(1);
+      float_ranges_.resize(1);
     }
+    number_of_results_ = keys.size();
     return true;
   }
-  bool executeAsync() { return execute(); }
-  bool wait(unsigned /*timeout_ms*/ = ~0u) { return true; }
-  void reset()
-  {
-    keys_.clear();
-    ranges_.clear();
-  }
+  void onReset(bool) override { float_ranges_.clear(); }
 
 private:
-  GpuMap *gpu_map_ = nullptr;
   dvec3 start_, end_;
   float search_radius_ = 0.0f;
   float default_range_ = -1.0f;
   float axis_scaling_[3] = { 1.0f, 1.0f, 1.0f };
-  unsigned query_flags_ = kQfGpuEvaluate;
-  std::vector<Key> keys_;
-  std::vector<float> ranges_;
+  std::vector<float> float_ranges_;
 };
 
 /// Not in the reference (ohm is single device): the RCCL communicator the library owns (include/ohmhip.h, ohmhip_comm_*).
@@ -2905,76 +2895,46 @@ inline VoxelCloud extractCloud(GpuMap &gpu_map, const CloudOptions &options = Cl
   return cloud;
 }
 
-/// ohm::NearestNeighbours (ohm/NearestNeighbours.h; the interface of ohm/Query.h:51-121) against the device-resident map:
-/// the obstructing voxels within searchRadius() of nearPoint(), in the CPU query's visiting order, or with
-/// kQfNearestResult the closest one (GpuMap::nearestNeighbours).  ranges() are float results widened to double, as the
-/// reference stores them.
-class NearestNeighbours
+/// ohm::NearestNeighbours (ohm/NearestNeighbours.h) against the device-resident map: the obstructing voxels within
+/// searchRadius() of nearPoint(), in the CPU query's visiting order, or with kQfNearestResult the closest one
+/// (GpuMap::nearestNeighbours).  ranges() are float results widened to double, as the reference stores them.  There is
+/// no asynchronous form, as for the reference's CPU query (ohm/NearestNeighbours.cpp:287-290).  lastStatus() is that of
+/// the last device call: an execute() refused for want of a usable map makes none and leaves it as it was.
+class NearestNeighbours : public Query
 {
 public:
   NearestNeighbours(GpuMap &gpu_map, const dvec3 &near_point, float search_radius, unsigned query_flags)
-    : gpu_map_(&gpu_map)
+    : Query(&gpu_map, query_flags)
     , near_point_(near_point)
     , search_radius_(search_radius)
-    , query_flags_(query_flags)
   {}
 
   dvec3 nearPoint() const { return near_point_; }
   void setNearPoint(const dvec3 &point) { near_point_ = point; }
   float searchRadius() const { return search_radius_; }
   void setSearchRadius(float range) { search_radius_ = range; }
-  unsigned queryFlags() const { return query_flags_; }
-  void setQueryFlags(unsigned flags) { query_flags_ = flags; }
 
-  void reset(bool /*hard_reset*/ = true)
-  {
-    intersected_voxels_.clear();
-    ranges_.clear();
-  }
+  bool executeAsync() override { return false; }
 
-  bool execute()
-  {
-    reset();
-    if (!gpu_map_)
-    {
-      return false;
-    }
-    std::vector<uint64_t> counts;
-    std::vector<CloudKey> keys;
-    std::vector<float> ranges;
-    last_status_ = gpu_map_->nearestNeighbours(&near_point_, 1, search_radius_, query_flags_, counts, keys, ranges);
-    if (last_status_ != OHMHIP_OK)
-    {
-      return false;
-    }
-    for (size_t i = 0; i < keys.size(); ++i)
-    {
-      Key k;
-      for (int c = 0; c < 3; ++c)
-      {
-        k.region[c] = keys[i].region[c];
-        k.local[c] = keys[i].voxel[c];
-      }
-      intersected_voxels_.push_back(k);
-      ranges_.push_back(double(ranges[i]));
-    }
-    return true;
-  }
-  bool executeAsync() { return false; }  // as the reference's CPU query (ohm/NearestNeighbours.cpp:287-290)
-  bool wait(unsigned /*timeout_ms*/ = ~0u) { return true; }
-
-  size_t numberOfResults() const { return intersected_voxels_.size(); }
   const std::vector<Key> &intersectedVoxels() const { return intersected_voxels_; }
   const std::vector<double> &ranges() const { return ranges_; }
   int lastStatus() const { return last_status_; }
 
+protected:
+  bool onExecute() override
+  {
+    std::vector<uint64_t> counts;
+    std::vector<float> ranges;
+    last_status_ =
+      gpu_map_->nearestNeighbours(&near_point_, 1, search_radius_, query_flags_, counts, intersected_voxels_, ranges);
+    ranges_.assign(ranges.begin(), ranges.end());
+    number_of_results_ = intersected_voxels_.size();
+    return last_status_ == OHMHIP_OK;
+  }
+
 private:
-  GpuMap *gpu_map_ = nullptr;
   dvec3 near_point_{ 0, 0, 0 };
   float search_radius_ = 0.0f;
-  unsigned query_flags_ = 0;
-  std::vector<Key> intersected_voxels_;
-  std::vector<double> ranges_;
   int last_status_ = OHMHIP_OK;
 };
 

@@ -1,37 +1,22 @@
 """-m gpu: ohm::ClearanceProcess and ohm::LineQueryGpu of the C++ mirror (ohm_amd/host/OhmGpuMap.h), run by
 `gpumap_driver clearance` and `gpumap_driver linequery`, against the clearance restatement (tests/clearance_ref.py) at
 exact equality."""
-import os
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import cpp_driver
+from clearance_ref import QF_UNKNOWN_AS_OCCUPIED, Geometry, clearance_keys, clearance_regions
 from ohm_amd import OccupancyMap, synth
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from clearance_ref import QF_UNKNOWN_AS_OCCUPIED, Geometry, clearance_keys, clearance_regions  # noqa: E402
-from parity import make_oracle  # noqa: E402
-from rays_query_ref import OracleBlocks  # noqa: E402
+from parity import make_oracle
+from rays_query_ref import OracleBlocks
 
 pytestmark = pytest.mark.gpu
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ohm_amd", "lib", "gpumap_driver")
 
 
 def drive(mode, rays, radius, flags, query_lines=0):
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
-    with tempfile.TemporaryDirectory() as tmp:
-        rp, op = os.path.join(tmp, "rays.bin"), os.path.join(tmp, "out.bin")
-        with open(rp, "wb") as f:
-            f.write(struct.pack("<Q", rays.shape[0]))
-            f.write(np.ascontiguousarray(rays, dtype=np.float64).tobytes())
-        res = subprocess.run([DRIVER, mode, "0.1", str(query_lines), rp, op, repr(radius), str(flags)], capture_output=True,
-                             text=True, timeout=600)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        return open(op, "rb").read()
+    return cpp_driver.run(mode, 0.1, query_lines, rays, radius, flags, timeout=600)
 
 
 def oracle_map(rays):

@@ -1,30 +1,18 @@
 """-m gpu: ohm::Mapper + ohm::ClearanceProcess::update of the C++ mirror (ohm_amd/host/OhmGpuMap.h), run by
 `gpumap_driver clearanceupdate`, give the clearance layer the Python path gives, bit for bit."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import cpp_driver
 from ohm_amd import ClearanceProcess, GpuMap, Mapper, MappingProcessResult, OccupancyMap, QueryFlag, synth
 
 pytestmark = pytest.mark.gpu
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ohm_amd", "lib", "gpumap_driver")
 
 
 def drive(rays, batch_rays, radius, flags, budget, dim):
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
-    with tempfile.TemporaryDirectory() as tmp:
-        rp, op = os.path.join(tmp, "rays.bin"), os.path.join(tmp, "out.bin")
-        with open(rp, "wb") as f:
-            f.write(struct.pack("<Q", rays.shape[0]))
-            f.write(np.ascontiguousarray(rays, dtype=np.float64).tobytes())
-        res = subprocess.run([DRIVER, "clearanceupdate", "0.1", str(batch_rays), rp, op, repr(radius), str(flags),
-                              str(budget), str(dim)], capture_output=True, text=True, timeout=600)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        data = open(op, "rb").read()
+    data = cpp_driver.run("clearanceupdate", 0.1, batch_rays, rays, radius, flags, budget, dim, timeout=600)
     (n,) = struct.unpack_from("<Q", data, 0)
     rec = np.dtype([("key", "<i2", 3), ("block", "<f4", dim ** 3)])
     assert len(data) == 8 + n * rec.itemsize

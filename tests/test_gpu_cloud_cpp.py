@@ -1,39 +1,24 @@
 """-m gpu: ohm::extractCloud of the C++ mirror (ohm_amd/host/OhmGpuMap.h), run by `gpumap_driver cloud`: the map
 (occupancy + mean) is built by ohm::GpuMap::integrateRays in small batches -- still collected by batch coalescing when
 the cloud is asked for -- and the three arrays it writes equal the CPU restatement's (tests/cloud_ref.py)."""
-import os
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import cloud_ref as CR
+import cpp_driver
+from heightmap_cases import two_level_scene
 from ohm_amd import OccupancyMap
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import cloud_ref as CR  # noqa: E402
-from heightmap_cases import two_level_scene  # noqa: E402
-from parity import make_oracle  # noqa: E402
+from parity import make_oracle
 
 pytestmark = pytest.mark.gpu
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ohm_amd", "lib", "gpumap_driver")
 
 
 @pytest.mark.parametrize("export_free", [False, True])
 def test_cpp_cloud(gpu, export_free):
     rays = two_level_scene()
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
-    with tempfile.TemporaryDirectory() as tmp:
-        rp, op = os.path.join(tmp, "rays.bin"), os.path.join(tmp, "out.bin")
-        with open(rp, "wb") as f:
-            f.write(struct.pack("<Q", rays.shape[0]))
-            f.write(np.ascontiguousarray(rays, dtype=np.float64).tobytes())
-        res = subprocess.run([DRIVER, "cloud", "0.1", "4096", rp, op, str(int(export_free))], capture_output=True,
-                             text=True, timeout=300)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        data = open(op, "rb").read()
+    data = cpp_driver.run("cloud", 0.1, 4096, rays, int(export_free))
     count, n = struct.unpack_from("<QQ", data, 0)
     assert count == n and len(data) == 16 + n * (24 + 10 + 4)
     positions = np.frombuffer(data, dtype=np.float64, count=3 * n, offset=16).reshape(n, 3)

@@ -3,22 +3,18 @@ ohm_amd/lib/gpumap_driver: every ray but the last into the reference map, every 
 driver writes -- the result, both lists, the number of messages; with kContinue, with stop-at-first and with ohmcmp's
 occupancy tolerance -- must equal what the Python mirror gives for the same rays."""
 import ctypes as C
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import compare_cases as cases
-import ohm_amd
+import cpp_driver
 from ohm_amd import GpuMap, OccupancyMap, Tolerance, compareVoxels, configureTolerance, kContinue
 from ohm_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
 
-DRIVER = os.path.join(os.path.dirname(ohm_amd.LIB_PATH), "gpumap_driver")
 RESOLUTION = 0.1
 
 
@@ -42,17 +38,8 @@ def _results(data, count):
 
 
 def test_cpp_compare_equals_the_python_mirror(gpu):
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
     rays = np.concatenate([cases.fan_rays(1500, 12, reach=2.5), [[0.01, 0.02, 0.03], [1.93, -1.21, 0.77]]])
-    with tempfile.TemporaryDirectory() as tmp:
-        rp, op = os.path.join(tmp, "rays.bin"), os.path.join(tmp, "out.bin")
-        with open(rp, "wb") as f:
-            f.write(struct.pack("<Q", rays.shape[0]))
-            f.write(np.ascontiguousarray(rays, dtype=np.float64).tobytes())
-        res = subprocess.run([DRIVER, "compare", repr(RESOLUTION), "0", rp, op], capture_output=True, text=True, timeout=120)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        with open(op, "rb") as f:
-            cpp = _results(f.read(), 3)
+    cpp = _results(cpp_driver.run("compare", RESOLUTION, 0, rays, timeout=120), 3)
     ref, ev = GpuMap(OccupancyMap(RESOLUTION)), GpuMap(OccupancyMap(RESOLUTION))
     assert ref.integrateRays(rays[:-2]) == len(rays) - 2 and ev.integrateRays(rays) == len(rays)
     loose = Tolerance("occupancy")

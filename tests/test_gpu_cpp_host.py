@@ -4,54 +4,23 @@ Mirrors the batching harness of tests/ohmtestgpu/GpuMapTest.cpp:68-205."""
 import os
 import struct
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-import ohm_amd
-from ohm_amd import LAYERS, synth
+import cpp_driver
+from ohm_amd import synth
 from oracle.oracle import OracleMap
 
 from parity import assert_parity, compare_maps
 
 pytestmark = pytest.mark.gpu
 
-DRIVER = os.path.join(os.path.dirname(ohm_amd.LIB_PATH), "gpumap_driver")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ID_TO_NAME = {v[0]: k for k, v in LAYERS.items()}
 
 
-def run_driver(mode, resolution, batch, rays, n_layers, driver=None):
-    driver = driver or DRIVER
-    assert os.path.exists(driver), "%s missing: run __graft_entry__.build()" % os.path.basename(driver)
-    with tempfile.TemporaryDirectory() as tmp:
-        rp, op = os.path.join(tmp, "rays.bin"), os.path.join(tmp, "out.bin")
-        with open(rp, "wb") as f:
-            f.write(struct.pack("<Q", rays.shape[0]))
-            f.write(np.ascontiguousarray(rays, dtype=np.float64).tobytes())
-        res = subprocess.run([driver, mode, repr(resolution), str(batch), rp, op], capture_output=True, text=True,
-                             timeout=300)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        data = open(op, "rb").read()
-    off = 0
-    (n_regions,) = struct.unpack_from("<Q", data, off)
-    off += 8
-    chunks = {}
-    for _ in range(n_regions):
-        key = struct.unpack_from("<3h", data, off)
-        off += 6
-        layers = {}
-        for _l in range(n_layers):
-            lid, nbytes = struct.unpack_from("<IQ", data, off)
-            off += 12
-            name = ID_TO_NAME[lid]
-            dtype = np.dtype(LAYERS[name][1])
-            layers[name] = np.frombuffer(data, dtype=dtype, count=nbytes // dtype.itemsize, offset=off).copy()
-            off += nbytes
-        chunks[tuple(key)] = layers
-    assert off == len(data)
-    return chunks
+def run_driver(mode, resolution, batch, rays, n_layers, driver=cpp_driver.DRIVER):
+    return cpp_driver.read_region_dump(cpp_driver.run(mode, resolution, batch, rays, driver=driver), n_layers)
 
 
 @pytest.mark.parametrize("mode,layers,res", [("occ", ("occupancy",), 0.1), ("occmean", ("occupancy", "mean"), 0.1),
@@ -79,15 +48,7 @@ def test_cpp_line_keys_query_gpu(gpu):
     """ohm::LineKeysQueryGpu of the C++ mirror (setRays / executeAsync / wait / resultIndices / resultCounts /
     intersectedVoxels, ohm/LineKeysQuery.h:47-101): every ray's keys equal the oracle's CPU walk."""
     lines = synth.random_rays(1500, extent=4.0, seed=77, origin_spread=2.0)
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
-    with tempfile.TemporaryDirectory() as tmp:
-        rp, op = os.path.join(tmp, "rays.bin"), os.path.join(tmp, "out.bin")
-        with open(rp, "wb") as f:
-            f.write(struct.pack("<Q", lines.shape[0]))
-            f.write(np.ascontiguousarray(lines, dtype=np.float64).tobytes())
-        res = subprocess.run([DRIVER, "linekeys", "0.1", "0", rp, op], capture_output=True, text=True, timeout=300)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        data = open(op, "rb").read()
+    data = cpp_driver.run("linekeys", 0.1, 0, lines)
     (n,) = struct.unpack_from("<Q", data, 0)
     assert n == lines.shape[0] // 2
     table = np.frombuffer(data, dtype="<u8", count=2 * n, offset=8).reshape(n, 2)
@@ -128,7 +89,6 @@ def test_cpp_transform_samples_general_trajectory(gpu):
     doubles of the file and writes the output from .x, .y, .z, so the order of the members is part of what is tested."""
     import transform_cases as TC
     from ohm_amd import GpuTransformSamples
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
     for name in ("general_small_stamps", "general_big_stamps"):
         for case in dict(TC.families())[name]:
             ts = GpuTransformSamples()
@@ -136,16 +96,10 @@ def test_cpp_transform_samples_general_trajectory(gpu):
                                     case["local"], case["max_range"])
             expect = ts.read(count)
             ts.close()
-            with tempfile.TemporaryDirectory() as tmp:
-                ip, op = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-                with open(ip, "wb") as f:
-                    f.write(struct.pack("<QQd", case["times"].shape[0], case["local"].shape[0], case["max_range"]))
-                    for key in ("times", "translations", "rotations", "sample_times", "local"):
-                        f.write(np.ascontiguousarray(case[key], dtype="<f8").tobytes())
-                res = subprocess.run([DRIVER, "transform", "0.1", "0", ip, op], capture_output=True, text=True,
-                                     timeout=300)
-                assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-                data = open(op, "rb").read()
+            blob = struct.pack("<QQd", case["times"].shape[0], case["local"].shape[0], case["max_range"])
+            for key in ("times", "translations", "rotations", "sample_times", "local"):
+                blob += np.ascontiguousarray(case[key], dtype="<f8").tobytes()
+            data = cpp_driver.run("transform", 0.1, 0, blob)
             (elements,) = struct.unpack_from("<Q", data, 0)
             assert elements == count > 0 and len(data) == 8 + 24 * elements
             got = np.frombuffer(data, dtype="<f8", offset=8).reshape(-1, 3)

@@ -1,39 +1,24 @@
 """-m gpu: ohm::Heightmap of the C++ mirror (ohm_amd/host/OhmGpuMap.h), run by `gpumap_driver heightmap`: the map
 (occupancy + mean) is built by ohm::GpuMap::integrateRays in small batches -- still collected by batch coalescing when
 the heightmap is asked for -- and the three arrays it writes equal the CPU restatement's (tests/heightmap_ref.py)."""
-import os
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import cpp_driver
+import heightmap_ref as R
+from heightmap_cases import two_level_scene
 from ohm_amd import OccupancyMap
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import heightmap_ref as R  # noqa: E402
-from heightmap_cases import two_level_scene  # noqa: E402
-from parity import make_oracle  # noqa: E402
+from parity import make_oracle
 
 pytestmark = pytest.mark.gpu
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ohm_amd", "lib", "gpumap_driver")
 
 
 @pytest.mark.parametrize("min_clearance,virtual", [(0.0, False), (1.5, True)])
 def test_cpp_heightmap(gpu, min_clearance, virtual):
     rays = two_level_scene()
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
-    with tempfile.TemporaryDirectory() as tmp:
-        rp, op = os.path.join(tmp, "rays.bin"), os.path.join(tmp, "out.bin")
-        with open(rp, "wb") as f:
-            f.write(struct.pack("<Q", rays.shape[0]))
-            f.write(np.ascontiguousarray(rays, dtype=np.float64).tobytes())
-        res = subprocess.run([DRIVER, "heightmap", "0.1", "4096", rp, op, repr(min_clearance), str(int(virtual))],
-                             capture_output=True, text=True, timeout=300)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        data = open(op, "rb").read()
+    data = cpp_driver.run("heightmap", 0.1, 4096, rays, min_clearance, int(virtual))
     ma, mb, populated, cells, has_mean = struct.unpack_from("<IIQQB", data, 0)
     n = ma * mb
     assert has_mean == 1 and len(data) == 25 + n * (4 + 24 + 8)

@@ -2,41 +2,29 @@
 `gpumap_driver heightmapfill`: the scaled multi-level scene is written into the host map voxel by voxel and uploaded,
 kLayeredFill is still refused, and the arrays, the visit log and the stats the fill writes equal the CPU restatement's
 (tests/heightmap_fill_ref.py)."""
-import os
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import heightmap_ref as R  # noqa: E402
-import heightmap_fill_ref as F  # noqa: E402
-from heightmap_fill_cases import scaled_multi_level  # noqa: E402
+import cpp_driver
+import heightmap_fill_ref as F
+import heightmap_ref as R
+from heightmap_fill_cases import scaled_multi_level
 
 pytestmark = pytest.mark.gpu
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ohm_amd", "lib", "gpumap_driver")
 
 
 def test_cpp_heightmap_fill(gpu):
     scene, p = scaled_multi_level()
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
-    with tempfile.TemporaryDirectory() as tmp:
-        sp, op = os.path.join(tmp, "scene.bin"), os.path.join(tmp, "out.bin")
-        with open(sp, "wb") as f:
-            f.write(struct.pack("<3i", *scene.dim))
-            f.write(struct.pack("<6d", *p.reference_pos, p.floor, p.ceiling, p.min_clearance))
-            f.write(struct.pack("<iI", p.up_axis, (1 if p.virtual_surface else 0) | (2 if p.promote_virtual_below else 0)))
-            f.write(struct.pack("<Q", len(scene.chunks)))
-            for key in sorted(scene.chunks):
-                f.write(struct.pack("<3h", *key))
-                f.write(np.ascontiguousarray(scene.chunks[key]["occupancy"], dtype=np.float32).tobytes())
-        res = subprocess.run([DRIVER, "heightmapfill", repr(scene.resolution), "0", sp, op], capture_output=True,
-                             text=True, timeout=300)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        data = open(op, "rb").read()
+    blob = struct.pack("<3i", *scene.dim)
+    blob += struct.pack("<6d", *p.reference_pos, p.floor, p.ceiling, p.min_clearance)
+    blob += struct.pack("<iI", p.up_axis, (1 if p.virtual_surface else 0) | (2 if p.promote_virtual_below else 0))
+    blob += struct.pack("<Q", len(scene.chunks))
+    for key in sorted(scene.chunks):
+        blob += struct.pack("<3h", *key)
+        blob += np.ascontiguousarray(scene.chunks[key]["occupancy"], dtype=np.float32).tobytes()
+    data = cpp_driver.run("heightmapfill", scene.resolution, 0, blob)
     want = F.build_fill(scene.source(), p)
     assert want.revisits > 0 and want.raising_pops > 0 and (want.occupancy == -1.0).any()
     ma, mb = struct.unpack_from("<II", data, 0)

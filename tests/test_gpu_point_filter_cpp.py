@@ -1,31 +1,19 @@
 """-m gpu: the C++14 host mirror's point filter (ohm_amd/host/OhmGpuMap.h: GpuMap::filterPoints), driven by gpumap_driver
 on an occupancy + mean map of ~2 000 rays -- integrated by ohm::GpuMap::integrateRays in batches that batch coalescing
 still holds when the filter is asked -- against the Python mirror on the same rays and points: the same bytes."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import cpp_driver
 from ohm_amd import GPU_KEY_DTYPE, GpuMap, OccupancyMap
 
 pytestmark = pytest.mark.gpu
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ohm_amd", "lib", "gpumap_driver")
 
 
 def run_driver(rays, *args):
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
-    with tempfile.TemporaryDirectory() as tmp:
-        rp, op = os.path.join(tmp, "rays.bin"), os.path.join(tmp, "out.bin")
-        with open(rp, "wb") as f:
-            f.write(struct.pack("<Q", rays.shape[0]))
-            f.write(np.ascontiguousarray(rays, dtype=np.float64).tobytes())
-        res = subprocess.run([DRIVER, "filter", "0.1", "512", rp, op] + [str(a) for a in args], capture_output=True,
-                             text=True, timeout=300)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        return open(op, "rb").read()
+    return cpp_driver.run("filter", 0.1, 512, rays, *args)
 
 
 @pytest.mark.parametrize("args", [(), (0.5, 0), (-1.0, 1)])

@@ -2,24 +2,18 @@
 readVoxels / occupancyTypes and the ohm::NearestNeighbours query class), driven by gpumap_driver on the two-level scene
 -- integrated by ohm::GpuMap::integrateRays in batches that batch coalescing still holds when the first query is asked --
 against the CPU restatement (tests/neighbours_ref.py) over the oracle's map, at exact equality."""
-import os
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import cpp_driver
+import neighbours_ref as NR
+from heightmap_cases import two_level_scene
 from ohm_amd import OccupancyMap
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import neighbours_ref as NR  # noqa: E402
-from heightmap_cases import two_level_scene  # noqa: E402
-from parity import make_oracle  # noqa: E402
+from parity import make_oracle
 
 pytestmark = pytest.mark.gpu
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ohm_amd", "lib", "gpumap_driver")
 LAYERS = ("occupancy", "mean")
 
 
@@ -33,16 +27,7 @@ def scene(gpu):
 
 
 def run_driver(mode, rays, *args):
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
-    with tempfile.TemporaryDirectory() as tmp:
-        rp, op = os.path.join(tmp, "rays.bin"), os.path.join(tmp, "out.bin")
-        with open(rp, "wb") as f:
-            f.write(struct.pack("<Q", rays.shape[0]))
-            f.write(np.ascontiguousarray(rays, dtype=np.float64).tobytes())
-        res = subprocess.run([DRIVER, mode, "0.1", "4096", rp, op] + [str(a) for a in args], capture_output=True,
-                             text=True, timeout=300)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        return open(op, "rb").read()
+    return cpp_driver.run(mode, 0.1, 4096, rays, *args)
 
 
 @pytest.mark.parametrize("flags", [0, 1, 2, 3])

@@ -2,38 +2,26 @@
 RayPattern.Clearing as the reference writes it (tests/ohmtestgpu/GpuRayPatternTests.cpp:28-85).  After each of the 20
 applications the occupancy words equal the CPU oracle's, fed the model's rays; lastRaySet() returns the model's rays."""
 import math
-import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import cpp_driver
+import ray_pattern_ref as R
 from ohm_amd import ClearingPattern, OccupancyMap
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import ray_pattern_ref as R  # noqa: E402
-from parity import make_oracle  # noqa: E402
+from parity import make_oracle
 
 pytestmark = pytest.mark.gpu
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ohm_amd", "lib", "gpumap_driver")
 
 
 def test_cpp_ray_pattern_clearing(gpu):
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
     map_ = OccupancyMap(0.1, (32, 32, 32))
     map_.setHitProbability(0.51)
     map_.setMissProbability(0.0)
     om = make_oracle(map_)
     hit = np.float32(map_.hit_value)
     translate = om.voxel_centre((0, 0, 0), (0, 0, 0))
-    with tempfile.TemporaryDirectory() as tmp:
-        op = os.path.join(tmp, "out.bin")
-        res = subprocess.run([DRIVER, "clearing", "0.1", "0", "-", op] + [repr(float(v)) for v in translate],
-                             capture_output=True, text=True, timeout=300)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        data = open(op, "rb").read()
+    data = cpp_driver.run("clearing", 0.1, 0, None, *[repr(float(v)) for v in translate])
     rec = np.dtype([("rays", "<f8", (2, 3)), ("integrated", "<u8"), ("row", "<f4", 32)])
     assert len(data) == 20 * rec.itemsize + 4 * 32768 + 4
     got = np.frombuffer(data, dtype=rec, count=20)

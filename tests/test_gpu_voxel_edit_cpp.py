@@ -1,56 +1,30 @@
 """-m gpu: the C++14 host mirror's voxel edits (ohm_amd/host/OhmGpuMap.h: GpuMap::integrateVoxels, the single-voxel
 conveniences integrateHit / integrateMiss with the reference's names, keyRange and integrateMisses over it), driven by
 gpumap_driver's `voxeledit` mode on an edit script, against the model of tests/voxel_edit_ref.py at exact equality."""
-import os
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import cpp_driver
 import mean_cases
 import occupancy_cases as OC
 import voxel_edit_ref as V
-from ohm_amd import LAYERS
 
 pytestmark = pytest.mark.gpu
-DRIVER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ohm_amd", "lib", "gpumap_driver")
 GPU_KEY = np.dtype([("region", "<i2", (3,)), ("voxel", "u1", (4,))])
 
 
 def run_driver(points, ops):
-    assert os.path.exists(DRIVER), "gpumap_driver missing: run __graft_entry__.build()"
-    with tempfile.TemporaryDirectory() as tmp:
-        pp, qp, op = (os.path.join(tmp, n) for n in ("points.bin", "ops.bin", "out.bin"))
-        with open(pp, "wb") as f:
-            f.write(struct.pack("<Q", points.shape[0]))
-            f.write(np.ascontiguousarray(points, dtype=np.float64).tobytes())
-        with open(qp, "wb") as f:
-            f.write(np.ascontiguousarray(ops, dtype=np.uint8).tobytes())
-        res = subprocess.run([DRIVER, "voxeledit", "0.1", "0", pp, op, qp], capture_output=True, text=True, timeout=120)
-        assert res.returncode == 0, (res.returncode, res.stdout, res.stderr)
-        return open(op, "rb").read()
+    return cpp_driver.run("voxeledit", 0.1, 0, points, np.ascontiguousarray(ops, dtype=np.uint8).tobytes(), timeout=120)
 
 
 def parse(data, layers):
-    (n_regions,) = struct.unpack_from("<Q", data, 0)
-    at = 8
-    blocks = {}
-    by_id = {LAYERS[n][0]: n for n in layers}
-    for _ in range(n_regions):
-        region = struct.unpack_from("<3h", data, at)
-        at += 6
-        blocks[region] = {}
-        for _ in layers:
-            lid, nbytes = struct.unpack_from("<IQ", data, at)
-            at += 12
-            blocks[region][by_id[lid]] = np.frombuffer(data, dtype=LAYERS[by_id[lid]][1], count=nbytes // 4, offset=at)
-            at += nbytes
-    counters = struct.unpack_from("<6Q", data, at)
-    at += 48
-    keys = np.frombuffer(data, dtype=GPU_KEY, count=counters[5], offset=at)
-    assert at + 10 * counters[5] == len(data)
+    blocks, rest = cpp_driver.read_region_dump(data, len(layers), tail=True)
+    assert all(set(region) == set(layers) for region in blocks.values())
+    counters = struct.unpack_from("<6Q", rest, 0)
+    keys = np.frombuffer(rest, dtype=GPU_KEY, count=counters[5], offset=48)
+    assert 48 + 10 * counters[5] == len(rest)
     return blocks, counters, keys
 
 

@@ -93,7 +93,8 @@ def test_golden_ray_flags():
     from ohm_amd.gpumap import RayFlag
     for name, value in expect.items():
         assert getattr(RayFlag, "kRf" + name) == value
-    cpp = open(os.path.join(root, "ohm_amd", "host", "OhmGpuMap.h")).read()
+    import cpp_driver
+    cpp = cpp_driver.host_mirror_text()
     for name, value in expect.items():
         m = re.search(r"kRf%s\s*=\s*([^,\n]+)" % name, cpp)
         assert m, name

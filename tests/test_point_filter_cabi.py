@@ -7,6 +7,7 @@ import os
 
 import numpy as np
 
+import cpp_driver
 import ohm_amd
 from ohm_amd import GPU_KEY_DTYPE, GpuMap
 from ohm_amd import _lib as L
@@ -81,9 +82,7 @@ def test_refusals_without_a_map():
 def test_mirrors():
     assert callable(GpuMap.filterPoints) and callable(GpuMap.lastFilterKept)
     assert callable(ohm_amd.filter_cloud) and callable(ohm_amd.write_filtered_ply)
-    with open(os.path.join(ROOT, "ohm_amd", "host", "OhmGpuMap.h")) as fh:
-        text = fh.read()
+    text = cpp_driver.host_mirror_text()
     for token in ("int filterPoints(", "ohmhip_map_filter_points(", "ohmhip_point_filter_params", "OHMHIP_PF_OCCUPANCY_ONLY"):
         assert token in text, token
-    with open(os.path.join(ROOT, "ohm_amd", "host", "gpumap_driver.cpp")) as fh:
-        assert 'mode == "filter"' in fh.read()
+    assert '{ "filter", &modeFilterPoints,' in cpp_driver.driver_text()  # the driver's mode table

@@ -7,6 +7,7 @@ import os
 
 import numpy as np
 
+import cpp_driver
 import ohm_amd
 from ohm_amd import GPU_KEY_DTYPE, GpuMap, VoxelEdit
 from ohm_amd import _lib as L
@@ -83,8 +84,7 @@ def test_mirrors():
 
 
 def test_cpp_mirror_declares_the_same_interface():
-    with open(os.path.join(ROOT, "ohm_amd", "host", "OhmGpuMap.h")) as fh:
-        text = fh.read()
+    text = cpp_driver.host_mirror_text()
     for token in ("writeVoxels(", "integrateVoxels(", "integrateHits(", "integrateMisses(", "integrateHit(",
                   "integrateMiss(", "lastEditStats(", "keyRange(", "enum class VoxelEdit"):
         assert token in text, token
