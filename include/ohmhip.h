@@ -591,8 +591,8 @@ int ohmhip_map_clearance_update_regions(ohmhip_map_t map, const int16_t *keys_xy
  *    = voxelKey(pos) IN THE HEIGHTMAP'S OWN GEOMETRY (grid_resolution, regions of region_size voxels with 1 on the up
  *    axis, origin) with the up axis' region and local zeroed.  Occupancy +1.0f (surface) / -1.0f (virtual surface);
  *    HeightmapVoxel (24 bytes, ohmheightmap/HeightmapVoxel.h:68-97): height = float(src_height - dot(voxelCentreGlobal(
- *    hm_key), up)), clearance = float(ground clearance), normal 0, layer 0 (kHvlBaseLayer), flags = 1 (kHvfObservedAbove)
- *    or 0, contributing_samples = min(mean.count, 0xffff) of the ground voxel -- free ones too -- when the source's mean
+ *    hm_key), up)), clearance = float(ground clearance), normal 0 (or SURFACE NORMALS below), layer 0 (kHvlBaseLayer),
+ *    flags = 1 (kHvfObservedAbove) or 0, contributing_samples = min(mean.count, 0xffff) of the ground voxel -- free ones too -- when the source's mean
  *    layer is in use, else 0; heightmap mean (when in use): coord = subVoxelCoord(pos - voxelCentreGlobal(hm_key),
  *    grid_resolution), count = 1.
  *  6 COLLISIONS.  Planar mode overwrites: of the source columns landing in one heightmap cell the one with the LARGEST
@@ -602,10 +602,14 @@ int ohmhip_map_clearance_update_regions(ohmhip_map_t map, const int16_t *keys_xy
  * resolution / 2 on a and b.  Cells nobody wrote hold +inf / zeros, as a cleared chunk does.  source_column (optional):
  * the walk index of the column that wrote the cell, 0xffffffff for none.
  * NOT PROVIDED: the layered fill modes (kLayeredFill*: multi-layer sorting) and with them the virtual-surface filter;
- * blur, mesh, serialisation.  kSimpleFill is a call of its own (the next block); here mode != 0: OHMHIP_ERR_UNSUPPORTED.  Surface normals
- * from an NDT map's covariance are left 0: the reference derives them with an eigen solver chosen at compile time
- * (Eigen, or 20 rounds of glm::qr_decompose, ohm/CovarianceVoxel.cpp:49-144), so there is no single answer to be
- * exact against.
+ * blur, mesh, serialisation.  kSimpleFill is a call of its own (the next block); here mode != 0: OHMHIP_ERR_UNSUPPORTED.
+ * SURFACE NORMALS.  normal_x / y / z are 0 unless OHMHIP_HM_SURFACE_NORMALS is set and the source map has the covariance
+ * layer: then the cell of a kOccupied ground voxel carries covarianceEstimatePrimaryNormal of that voxel's covariance
+ * turned towards up (Heightmap.cpp:815-826), by the rule D1-D6 of COVARIANCE DECOMPOSITION below -- the reference
+ * derives it with an eigen solver chosen at compile time (Eigen, or 20 rounds of glm::qr_decompose, ohm/CovarianceVoxel.
+ * cpp:49-144), so the answer held to is the rule's, not either build's last bits.  Cells of free (virtual) ground
+ * voxels keep zeros; no other field or array changes with the flag; it applies to the flood fill alike.  The covariance
+ * is read once per cell written, not per step of the search.
  * The map is observed as the clearance queries observe it -- collected rays launched, an asynchronous launch settled,
  * regions of the host store from their pinned records, tiled regions in the caller's coordinates -- and nothing of it
  * changes.  OHMHIP_ERR_UNSUPPORTED also for a map without the occupancy layer and for a map with region ownership or a
@@ -615,6 +619,7 @@ int ohmhip_map_clearance_update_regions(ohmhip_map_t map, const int16_t *keys_xy
 #define OHMHIP_HM_GENERATE_VIRTUAL_SURFACE (1u << 0) /* Heightmap::setGenerateVirtualSurface */
 #define OHMHIP_HM_PROMOTE_VIRTUAL_BELOW (1u << 1)    /* Heightmap::setPromoteVirtualBelow */
 #define OHMHIP_HM_IGNORE_VOXEL_MEAN (1u << 2)        /* Heightmap::setIgnoreVoxelMean */
+#define OHMHIP_HM_SURFACE_NORMALS (1u << 3)          /* normals from the covariance layer (SURFACE NORMALS above) */
 typedef struct ohmhip_heightmap_params
 {
   double reference_pos[3];
@@ -844,6 +849,80 @@ int ohmhip_map_read_voxels(ohmhip_map_t map, int layer_id, const void *keys10, s
 /* The same on DEVICE arrays, enqueued on the map's stream; ohmhip_map_sync is the fence. */
 OHMHIP_EXPERIMENTAL int ohmhip_map_read_voxels_device(ohmhip_map_t map, int layer_id, const void *d_keys10, size_t count,
                                                       void *d_values, uint8_t *d_present);
+
+/* COVARIANCE DECOMPOSITION.  What ohm derives from an NDT voxel's covariance -- covarianceEigenDecomposition,
+ * covarianceEstimatePrimaryNormal, covarianceUnitSphereTransformation (ohm/CovarianceVoxel.cpp:147-206) -- computed
+ * where the covariance lies.  The reference picks its eigen solver at compile time (Eigen, or 20 rounds of
+ * glm::qr_decompose), and the two agree only to a perturbation bound around the mathematical object: the spectrum of
+ * C = S S^T.  This library holds to that object by ONE deterministic fp64 rule, the same text compiled for the device
+ * and the host, which tests/covariance_eigen_ref.py restates operation by operation and equals bit for bit (DESIGN.md
+ * 4.14 has its measured distance from an arbitrary-precision decomposition):
+ *  D1 MATRIX.  The six floats p0 .. p5 of CovarianceVoxel widened to fp64; S lower triangular with rows (p0, 0, 0),
+ *     (p1, p2, 0), (p3, p4, p5) (ohm/CovarianceVoxel.h:71-99); C = S S^T with c00 = p0 p0, c01 = p0 p1, c02 = p0 p3,
+ *     c11 = p1 p1 + p2 p2, c12 = p1 p3 + p2 p4, c22 = (p3 p3 + p4 p4) + p5 p5; no fused multiply-add anywhere.
+ *  D2 NON-FINITE.  Any entry of C NaN or +-inf: eigenvalues (1, 1, 1), identity eigenvectors, status
+ *     OHMHIP_COV_NON_FINITE -- the Eigen build when its solver does not report success (CovarianceVoxel.cpp:58-65).
+ *     Only a non-finite float brings it about: FLT_MAX squared is 1.2e77, finite in fp64.
+ *  D3 SOLVER.  Cyclic Jacobi on the upper triangle with V = I, pairs (0,1), (0,2), (1,2) per sweep, at most 16 sweeps
+ *     (no known input rotates in more than 6); a sweep starts only while (|a01| + |a02|) + |a12| != 0.  Per pair
+ *     with apq != 0: g = 100 |apq|; from the fourth sweep on, |app| + g == |app| and |aqq| + g == |aqq| set apq = 0
+ *     and skip; h = aqq - app; t = apq / h when |h| + g == |h|, else theta = (0.5 h) / apq, t = 1 / (|theta| +
+ *     sqrt(theta theta + 1)) negated for theta < 0; c = 1 / sqrt(t t + 1), s = t c, tau = s / (1 + c); app -= t apq,
+ *     aqq += t apq, apq = 0; the third index' two entries and the three rows of V's columns p and q go (x, y) ->
+ *     (x - s (y + x tau), y + s (x - y tau)).  Eigenvalues ascending (the Eigen build's order) by the strict swaps
+ *     (0,1), (1,2), (0,1), so equal values keep the order of their diagonal positions; V's columns move with them.
+ *  D4 ROTATION.  det = (V00 m0 - V01 m1) + V02 m2 with m0 = V11 V22 - V12 V21, m1 = V10 V22 - V12 V20, m2 = V10 V21
+ *     - V11 V20 (Vrc: row r, column c).  det < 0 negates column 0 (a -0.0 that makes is kept), det == 0 gives the
+ *     identity (:66-74, :187-195).
+ *  D5 SCALE.  scale_i = |lambda_i| > 1e-9 ? sqrt(|lambda_i|) : |lambda_i| (:198-203).
+ *  D6 NORMAL.  index = 0; for i = 0 .. 2: lambda_i < lambda_index takes i (preferred_axis 0); column `index` after D4,
+ *     divided by sqrt(length2) when length2 = (x x + y y) + z z > 0.  A heightmap then multiplies it by flip =
+ *     ((nx ux + ny uy) + nz uz) >= 0 ? 1.0 : -1.0 for the up axis normal u, in fp64, and narrows each component to
+ *     float (ohmheightmap/Heightmap.cpp:820-825).
+ * ohmhip_covariance_decompose runs the rule on the host for covariances the caller holds (6 floats each): eigenvalues 3
+ * doubles, eigenvectors 9 doubles column-major after D4, scales 3 (D5), normals 3 (D6, not flipped), status 1 byte;
+ * every output array is optional.  No device is needed.
+ * ohmhip_map_covariance_eigen decomposes the voxels at `count` keys (10-byte GpuKeys, as ohmhip_map_read_voxels takes
+ * them) on the device: per key 3 + 9 doubles and a status byte -- OHMHIP_COV_ABSENT where ohmhip_map_read_voxels would
+ * report present 0 (no such region, a null key; the doubles are zeros then), else OHMHIP_COV_DECOMPOSED or
+ * OHMHIP_COV_NON_FINITE.  A never written voxel of a present region is the zero matrix and decomposes.  Only the results
+ * cross to the host, not the 24-byte covariance layer.  A missing region is never created; the map is observed exactly
+ * as ohmhip_map_read_voxels observes it and nothing of it changes; that call's refusals, with OHMHIP_ERR_UNSUPPORTED for
+ * a map without the covariance layer. */
+#define OHMHIP_COV_ABSENT 0
+#define OHMHIP_COV_DECOMPOSED 1
+#define OHMHIP_COV_NON_FINITE 2
+int ohmhip_covariance_decompose(const float *covariance6, size_t count, double *eigenvalues, double *eigenvectors,
+                                double *scales, double *normals, uint8_t *status);
+int ohmhip_map_covariance_eigen(ohmhip_map_t map, const void *keys10, size_t count, double *eigenvalues,
+                                double *eigenvectors, uint8_t *status);
+/* The same on DEVICE arrays, enqueued on the map's stream; ohmhip_map_sync is the fence. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_covariance_eigen_device(ohmhip_map_t map, const void *d_keys10, size_t count,
+                                                           double *d_eigenvalues, double *d_eigenvectors,
+                                                           uint8_t *d_status);
+/* COVARIANCE ELLIPSOIDS.  ohm2ply --mode covariance (utils/ohm2ply/ohm2ply.cpp:845-1018) without the download: for every
+ * voxel the OHMHIP_CLOUD_OCCUPANCY cloud of the same params selects -- isOccupied only, OHMHIP_CLOUD_USE_EXTENTS
+ * honoured --, in that cloud's fixed order (row i describes the voxel of row i of ohmhip_map_cloud), the position
+ * positionSafe(mean), the rotation axes9 (9 doubles column-major, D4) and scales3 (D5) of covarianceUnitSphereTransformation
+ * -- WITHOUT ohm2ply's display factor sqrt(3) --, the key and the occupancy value.  The selection, count, scan and emit
+ * are the cloud call's own; the decomposition then reads the covariance at the emitted keys.  *count = all matching
+ * voxels; at most capacity rows are written; keys10 and values are optional (the device variant needs d_keys10, zeroes
+ * it past the count, and refuses a capacity above 2^31 - 1 with OHMHIP_ERR_CAPACITY).  The device variant does not
+ * learn the count on the host, so its work and its scratch (25 B a row) grow with capacity, not with the count: rows
+ * past the count are read at the zeroed key and not written.  Pass a capacity near the count
+ * (ohmhip_map_covariance_ellipsoids_count).  OHMHIP_ERR_INVALID_ARG for
+ * OHMHIP_CLOUD_EXPORT_FREE, OHMHIP_CLOUD_IGNORE_VOXEL_MEAN, a mode other than OHMHIP_CLOUD_OCCUPANCY and null positions /
+ * axes / scales with capacity > 0; OHMHIP_ERR_UNSUPPORTED for a map without the occupancy, mean or covariance layer
+ * (ohm2ply refuses such a map, :863-873); every other refusal as for ohmhip_map_cloud.  Nothing of the map changes. */
+int ohmhip_map_covariance_ellipsoids_count(ohmhip_map_t map, const ohmhip_cloud_params *params, uint64_t *count);
+int ohmhip_map_covariance_ellipsoids(ohmhip_map_t map, const ohmhip_cloud_params *params, uint64_t capacity,
+                                     double *positions_xyz, double *axes9, double *scales3, void *keys10, float *values,
+                                     uint64_t *count);
+/* The same into DEVICE arrays (d_count one uint64), enqueued on the map's stream; ohmhip_map_sync is the fence. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_covariance_ellipsoids_device(ohmhip_map_t map, const ohmhip_cloud_params *params,
+                                                                uint64_t capacity, double *d_positions_xyz,
+                                                                double *d_axes9, double *d_scales3, void *d_keys10,
+                                                                float *d_values, uint64_t *d_count);
 
 /* POINT FILTER.  ohmfilter's filterCloud (utils/ohmfilter/ohmfilter.cpp:150-279): of a point cloud, the points that fall
  * in an occupied voxel of the resident map and -- on a map with the NDT layers -- inside that voxel's Gaussian

@@ -16,4 +16,7 @@ from .compare import (Severity, kContinue, VoxelsResult, Tolerance, VoxelMismatc
 from .heightmap import Heightmap, HeightmapMode, HeightmapVoxelType, UpAxis, HEIGHTMAP_VOXEL_DTYPE  # noqa: F401
 from .cloud import (CloudMode, VoxelCloud, GPU_KEY_DTYPE, CLOUD_CHUNK_VOXELS, cloud_params, count_cloud,  # noqa: F401
                     extract_cloud, write_ply, save_cloud, save_density_cloud, save_tsdf_cloud, save_clearance_cloud,
-                    write_filtered_ply, filter_cloud)
+                    write_filtered_ply, filter_cloud, EllipsoidCloud, extract_covariance_ellipsoids, icosphere,
+                    write_ellipsoid_ply, save_covariance_cloud)
+from .covariance import (CovarianceDecomposition, covariance_decompose, covariance_estimate_primary_normal,  # noqa: F401
+                         covariance_unit_sphere_transformation, rotation_to_quaternion, quaternion_to_rotation)

@@ -70,7 +70,7 @@ class HeightmapFillStats(C.Structure):
                 ("generations", C.c_uint32), ("largest_generation", C.c_uint32)]
 
 
-HM_GENERATE_VIRTUAL_SURFACE, HM_PROMOTE_VIRTUAL_BELOW, HM_IGNORE_VOXEL_MEAN = 1, 2, 4
+HM_GENERATE_VIRTUAL_SURFACE, HM_PROMOTE_VIRTUAL_BELOW, HM_IGNORE_VOXEL_MEAN, HM_SURFACE_NORMALS = 1, 2, 4, 8
 
 
 class CloudParams(C.Structure):
@@ -97,6 +97,8 @@ class PointFilterParams(C.Structure):
     """ohmhip_point_filter_params"""
     _fields_ = [("expected_value_tolerance", C.c_double), ("flags", C.c_uint32)]
 
+
+COV_ABSENT, COV_DECOMPOSED, COV_NON_FINITE = range(3)  # OHMHIP_COV_*
 
 PF_OCCUPANCY_ONLY = 1
 PF_PIECE_POINTS = 1 << 18  # OHMHIP_PF_PIECE_POINTS
@@ -285,6 +287,14 @@ _sigs = {
     "ohmhip_map_voxel_keys": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
     "ohmhip_map_read_voxels": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
     "ohmhip_map_read_voxels_device": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, _vp]),
+    "ohmhip_covariance_decompose": (C.c_int, [_vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp]),
+    "ohmhip_map_covariance_eigen": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "ohmhip_map_covariance_eigen_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "ohmhip_map_covariance_ellipsoids_count": (C.c_int, [_vp, C.POINTER(CloudParams), C.POINTER(C.c_uint64)]),
+    "ohmhip_map_covariance_ellipsoids": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, _vp, _vp,
+                                                   C.POINTER(C.c_uint64)]),
+    "ohmhip_map_covariance_ellipsoids_device": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, _vp,
+                                                          _vp, _vp]),
     "ohmhip_map_write_voxels": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.POINTER(VoxelEditStats)]),
     "ohmhip_map_write_voxels_device": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.POINTER(VoxelEditStats)]),
     "ohmhip_map_integrate_voxels": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_size_t, C.POINTER(VoxelEditStats)]),

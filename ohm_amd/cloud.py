@@ -163,3 +163,103 @@ def filter_cloud(file_name, gpu_map, points, timestamps, expected_value_toleranc
     kept = kept.astype(np.int64)
     exported = write_filtered_ply(file_name, points[kept], timestamps[kept])
     return exported, points.shape[0] - exported
+
+
+class EllipsoidCloud(VoxelCloud):
+    """A VoxelCloud whose rows also carry the covariance ellipsoid of their voxel: axes (n, 3, 3) float64 with
+    axes[i, c] the unit axis of scale c (the rotation of covarianceUnitSphereTransformation, column by column) and
+    scales (n, 3) float64, ascending -- one standard deviation, without ohm2ply's display factor."""
+
+    def __init__(self, positions, axes, scales, keys, values, count):
+        super().__init__(positions, keys, values, count, CloudMode.OCCUPANCY)
+        self.axes = axes
+        self.scales = scales
+
+
+def extract_covariance_ellipsoids(gpu_map, extents=None, capacity=None):
+    """ohm2ply --mode covariance without the download (ohmhip_map_covariance_ellipsoids): for every occupied voxel of
+    an NDT map -- the selection and the order of extract_cloud(gpu_map, extents=extents), row for row -- its mean
+    position and the rotation and scale that deform a unit sphere into its covariance's ellipsoid, decomposed on the
+    device by the rule D1-D5 of include/ohmhip.h.  capacity=None: a count call first, then arrays of that size."""
+    p = cloud_params(CloudMode.OCCUPANCY, extents=extents)
+    handle = gpu_map._handle
+    n = C.c_uint64(0)
+    if capacity is None:
+        L.check(L.lib.ohmhip_map_covariance_ellipsoids_count(handle, C.byref(p), C.byref(n)),
+                "ohmhip_map_covariance_ellipsoids_count")
+        capacity = int(n.value)
+    capacity = int(capacity)
+    positions = np.empty((capacity, 3), dtype=np.float64)
+    axes = np.empty((capacity, 3, 3), dtype=np.float64)
+    scales = np.empty((capacity, 3), dtype=np.float64)
+    keys = np.empty(capacity, dtype=GPU_KEY_DTYPE)
+    values = np.empty(capacity, dtype=np.float32)
+    arrays = [a.ctypes.data if capacity else None for a in (positions, axes, scales, keys, values)]
+    L.check(L.lib.ohmhip_map_covariance_ellipsoids(handle, C.byref(p), capacity, *arrays, C.byref(n)),
+            "ohmhip_map_covariance_ellipsoids")
+    held = min(int(n.value), capacity)
+    return EllipsoidCloud(positions[:held], axes[:held], scales[:held], keys[:held], values[:held], n.value)
+
+
+def icosphere(subdivisions=1):
+    """A unit sphere as (vertices (V, 3) float64, faces (F, 3) int32): an icosahedron whose faces are split in four
+    `subdivisions` times, the new vertices pushed onto the sphere.  1: 42 vertices, 80 faces."""
+    t = (1.0 + np.sqrt(5.0)) / 2.0
+    vertices = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+                (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    vertices = [tuple(np.array(v, dtype=np.float64) / np.linalg.norm(v)) for v in vertices]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+             (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10),
+             (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(subdivisions)):
+        midpoint = {}
+
+        def mid(i, j):
+            key = (min(i, j), max(i, j))
+            if key not in midpoint:
+                m = (np.array(vertices[i]) + np.array(vertices[j])) * 0.5
+                vertices.append(tuple(m / np.linalg.norm(m)))
+                midpoint[key] = len(vertices) - 1
+            return midpoint[key]
+
+        split = []
+        for a, b, c in faces:
+            ab, bc, ca = mid(a, b), mid(b, c), mid(c, a)
+            split += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = split
+    return np.array(vertices, dtype=np.float64), np.array(faces, dtype=np.int32)
+
+
+COVARIANCE_DISPLAY_SCALE = float(np.sqrt(3.0))  #: ohm2ply's factor on the scales (utils/ohm2ply/ohm2ply.cpp:845-1018)
+
+
+def write_ellipsoid_ply(file_name, ellipsoids, subdivisions=1, display_scale=COVARIANCE_DISPLAY_SCALE):
+    """Binary little-endian PLY mesh: per ellipsoid one icosphere, each unit vertex u mapped to position + R (scale *
+    display_scale * u); vertices x y z as doubles, faces as uchar-counted int lists.  Returns (vertices, faces)."""
+    sphere, faces = icosphere(subdivisions)
+    n = len(ellipsoids)
+    scaled = sphere[None, :, :] * (ellipsoids.scales * display_scale)[:, None, :]      # (n, V, 3): along the axes
+    # axes[i, c, r]: column c of the rotation -- world = sum_c scaled[c] * axis_c
+    world = np.einsum("nvc,ncr->nvr", scaled, ellipsoids.axes) + ellipsoids.positions[:, None, :]
+    vertices = np.ascontiguousarray(world.reshape(-1, 3), dtype="<f8")
+    index = faces[None, :, :] + (np.arange(n, dtype=np.int64) * sphere.shape[0])[:, None, None]
+    face_records = np.empty(n * faces.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    face_records["n"] = 3
+    face_records["v"] = index.reshape(-1, 3)
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % vertices.shape[0], "property double x",
+              "property double y", "property double z", "element face %d" % face_records.shape[0],
+              "property list uchar int vertex_indices", "end_header"]
+    with open(file_name, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(vertices.tobytes())
+        fh.write(face_records.tobytes())
+    return vertices.shape[0], face_records.shape[0]
+
+
+def save_covariance_cloud(file_name, gpu_map, extents=None, subdivisions=1):
+    """ohm2ply --mode covariance: the ellipsoid of every occupied voxel of an NDT map as a triangle mesh, with ohm2ply's
+    sqrt(3) display factor on the scales.  The sphere is this module's icosphere, not ohm2ply's tessellation: the
+    surfaces agree, the vertex lists do not.  Returns the number of ellipsoids written."""
+    ellipsoids = extract_covariance_ellipsoids(gpu_map, extents=extents)
+    write_ellipsoid_ply(file_name, ellipsoids, subdivisions)
+    return len(ellipsoids)

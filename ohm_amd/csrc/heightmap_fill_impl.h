@@ -54,6 +54,7 @@ int heightmapFillDevice(ohmhip_map_t m, const ohmhip_heightmap_params *p, Height
   f.mean = f.use_mean ? static_cast<const uint2 *>(m->pool.layers[OHMHIP_LID_MEAN].get()) : nullptr;
   f.spill_mean_delta =
     (long long)(m->store.layer_offset[OHMHIP_LID_MEAN]) - (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
+  hmCovarianceView(m, f);
   // F2: voxelKey(reference_pos) clamped into the extents on all three axes (the up axis is geometry.plane already)
   MapConst kc = m->mc;
   kc.tile_split[0] = kc.tile_split[1] = kc.tile_split[2] = 1;

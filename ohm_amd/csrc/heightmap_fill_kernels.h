@@ -210,9 +210,7 @@ __device__ inline long long hmCellRecord(const HeightmapArgs &a, HmCursor &c, co
   uint32_t *vox = a.rec_vox + rec * kHmVoxelWords;
   vox[0] = __float_as_uint(height);
   vox[1] = __float_as_uint(float(clearance));
-  vox[2] = 0u;  // normals: not computed (include/ohmhip.h)
-  vox[3] = 0u;
-  vox[4] = 0u;
+  hmSurfaceNormal(a, c, vi, voxel_type == kOtOccupied, up_vec, vox);
   // layer kHvlBaseLayer (0) | flags << 8 | contributing_samples << 16
   vox[5] = ((have_ground && ground_observed_above) ? 0x100u : 0u) | (samples << 16);
   return (long long)(size_t(cb) * size_t(a.ma) + size_t(ca));

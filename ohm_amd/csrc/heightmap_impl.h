@@ -56,6 +56,7 @@ int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, Heightma
   a.up_positive = up_axis >= 0;
   a.use_mean = m->pool.layers[OHMHIP_LID_MEAN] && !(p->flags & OHMHIP_HM_IGNORE_VOXEL_MEAN);
   e.use_mean = uint8_t(a.use_mean);
+  a.surface_normals = ((p->flags & OHMHIP_HM_SURFACE_NORMALS) && m->pool.layers[OHMHIP_LID_COVARIANCE]) ? 1 : 0;
   a.generate_virtual = (p->flags & OHMHIP_HM_GENERATE_VIRTUAL_SURFACE) ? 1 : 0;
   a.flags = (a.generate_virtual ? kHmVirtualSurfaces : 0u) |
             ((p->flags & OHMHIP_HM_PROMOTE_VIRTUAL_BELOW) ? kHmPromoteVirtualBelow : 0u);
@@ -175,6 +176,14 @@ int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, Heightma
   return OHMHIP_OK;
 }
 
+/// Where the covariance layer lies, for cells that carry surface normals (a.surface_normals from heightmapGeometry).
+void hmCovarianceView(ohmhip_map_t m, HeightmapArgs &a)
+{
+  a.covariance = a.surface_normals ? static_cast<const float *>(m->pool.layers[OHMHIP_LID_COVARIANCE].get()) : nullptr;
+  a.spill_cov_delta = (long long)(m->store.layer_offset[OHMHIP_LID_COVARIANCE]) -
+                      (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
+}
+
 /// The two kernels on the map's stream, results into device arrays.  d_counts: 4 uint64 of the query's own.
 int heightmapDevice(ohmhip_map_t m, HeightmapArgs &a, float *d_occ, void *d_vox, void *d_mean, uint32_t *d_col)
 {
@@ -184,6 +193,7 @@ int heightmapDevice(ohmhip_map_t m, HeightmapArgs &a, float *d_occ, void *d_vox,
   a.mean = a.use_mean ? static_cast<const uint2 *>(m->pool.layers[OHMHIP_LID_MEAN].get()) : nullptr;
   a.spill_mean_delta =
     (long long)(m->store.layer_offset[OHMHIP_LID_MEAN]) - (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
+  hmCovarianceView(m, a);
   const size_t columns = size_t(a.na) * size_t(a.nb);
   const size_t cells = size_t(a.ma) * size_t(a.mb);
   OHMHIP_CHECK(qs.hm_winner.ensure(sizeof(int) * cells, false, s));

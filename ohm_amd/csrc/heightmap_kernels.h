@@ -27,6 +27,7 @@
 #ifndef OHMHIP_HEIGHTMAP_KERNELS_H
 #define OHMHIP_HEIGHTMAP_KERNELS_H
 
+#include "covariance_eigen_device.h"
 #include "ndt_tsdf_device.h"
 #include "query_kernels.h"
 
@@ -48,6 +49,9 @@ struct HeightmapArgs : MapReadView  ///< the source map
   const uint2 *mean;          ///< pool layer or null
   long long spill_mean_delta; ///< bytes from a stored region's occupancy block to its mean block
   int use_mean;               ///< source has the mean layer and ignore_voxel_mean is off
+  const float *covariance;    ///< pool layer or null
+  long long spill_cov_delta;  ///< bytes from a stored region's occupancy block to its covariance block
+  int surface_normals;        ///< OHMHIP_HM_SURFACE_NORMALS and the source has the covariance layer
   int min_g[3], max_g[3];     ///< rule 1: min_ext_key / max_ext_key as global voxel coordinates
   int plane;                  ///< rule 2: the plane key's up coordinate, clamped
   int a, b, up;               ///< heightmapAxisIndices
@@ -345,6 +349,48 @@ __device__ inline uint32_t hmSubVoxelCoord(const double v[3], double resolution)
   return pattern | (1u << 31);
 }
 
+/// Words 2-4 of a cell's HeightmapVoxel (Heightmap.cpp:808-826): zeros, or -- with surface normals on, for an OCCUPIED
+/// ground voxel -- the primary normal of its covariance turned towards up (D6 of include/ohmhip.h).  The cursor sits on
+/// the ground voxel's tile and vi is the voxel's index in it.  The covariance is read here, once per cell written: the
+/// cursor keeps a tile's occupancy block, not where the tile lives, so the tile is looked up once more.
+__device__ inline void hmSurfaceNormal(const HeightmapArgs &a, const HmCursor &c, int vi, bool occupied,
+                                       const double up_vec[3], uint32_t *vox)
+{
+  vox[2] = 0u;
+  vox[3] = 0u;
+  vox[4] = 0u;
+  if (!a.surface_normals || !occupied)
+  {
+    return;
+  }
+  const FoundTile t = mapFindTile(a, c.tx, c.ty, c.tz);
+  const float *cov = nullptr;
+  if (t.slot != kSlotUnassigned)
+  {
+    cov = a.covariance + (size_t(t.slot) * size_t(a.mc.region_voxels) + size_t(vi)) * 6u;
+  }
+  else if (t.stored)
+  {
+    cov = reinterpret_cast<const float *>(reinterpret_cast<const char *>(t.stored) + a.spill_cov_delta) + size_t(vi) * 6u;
+  }
+  if (!cov)
+  {
+    return;
+  }
+  float p[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+  {
+    p[i] = cov[i];
+  }
+  const CovEigen e = covarianceEigen(p);
+  float normal[3];
+  covarianceSurfaceNormal(e, up_vec, normal);
+  vox[2] = __float_as_uint(normal[0]);
+  vox[3] = __float_as_uint(normal[1]);
+  vox[4] = __float_as_uint(normal[2]);
+}
+
 __global__ void __launch_bounds__(256) k_heightmap_columns(HeightmapArgs a)
 {
   const int ia = int(blockIdx.x) * 64 + int(threadIdx.x & 63u);
@@ -463,9 +509,7 @@ __global__ void __launch_bounds__(256) k_heightmap_columns(HeightmapArgs a)
         uint32_t *vox = a.rec_vox + col * kHmVoxelWords;
         vox[0] = __float_as_uint(height);
         vox[1] = __float_as_uint(float(clearance));
-        vox[2] = 0u;  // normals: not computed (include/ohmhip.h)
-        vox[3] = 0u;
-        vox[4] = 0u;
+        hmSurfaceNormal(a, c, vi, voxel_type == kOtOccupied, up_vec, vox);
         // layer kHvlBaseLayer (0) | flags << 8 | contributing_samples << 16
         vox[5] = ((have_ground && ground_observed_above) ? 0x100u : 0u) | (samples << 16);
         atomicMax(&a.winner[size_t(cb) * size_t(a.ma) + size_t(ca)], int(col));

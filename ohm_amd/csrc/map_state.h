@@ -419,6 +419,9 @@ struct ohmhip_map_s
     DevBuf nn_chunks, nn_chunk_begin, nn_near, nn_best, nn_query_counts, nn_query_best, nn_keys, nn_ranges;
     ScanScratch nn_scan, nn_query_scan;
     DevBuf rv_keys, rv_values, rv_present;  ///< voxels read by key: device copies of the host arrays
+    /// covariance decomposition by key (covariance_kernels.h): the voxels read and their present flags; device copies
+    /// of the host variant's result arrays
+    DevBuf cov_voxels, cov_present, cov_values, cov_vectors, cov_status;
     /// point filter (point_filter_kernels.h): per-wave kept counts and their scan; one piece of the host variant's
     /// arrays on the device, and the pinned block its points are staged through (two pieces + the piece's kept count)
     DevBuf pf_points, pf_status, pf_values, pf_keys, pf_kept;

@@ -22,6 +22,7 @@
 #include "copy_kernels.h"
 #include "compare_kernels.h"
 #include "voxel_edit_kernels.h"
+#include "covariance_kernels.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -1040,3 +1041,4 @@ OHMHIP_ABI_CATCH
 #include "copy_impl.h"
 #include "compare_impl.h"
 #include "voxel_edit_impl.h"
+#include "covariance_impl.h"

@@ -845,6 +845,22 @@ class GpuMap(RayMapper):
                                       OccupancyType.kOccupied), OccupancyType.kUnobserved)
         return np.where(present != 0, types, OccupancyType.kNull).astype(np.int8)
 
+    def covarianceEigen(self, keys):
+        """covarianceEigenDecomposition (ohm/CovarianceVoxel.cpp:147-154) of the voxels at keys -- in every form
+        readVoxels takes -- by the rule D1-D4 of include/ohmhip.h, on the device (ohmhip_map_covariance_eigen):
+        (eigenvalues (N, 3) float64 ascending, eigenvectors (N, 3, 3) float64 with eigenvectors[i, c] the column of
+        eigenvalue c, status (N,) uint8: 0 the map holds no such region or the key is null, 1 decomposed, 2 a non-finite
+        covariance).  Only the results cross to the host; the map is read, never changed."""
+        self._push_config_if_changed()
+        rec = _key_records(keys.view(np.uint8) if isinstance(keys, np.ndarray) and keys.dtype == _GPU_KEY else keys)
+        n = rec.shape[0]
+        values = np.zeros((n, 3), dtype=np.float64)
+        vectors = np.zeros((n, 3, 3), dtype=np.float64)
+        status = np.zeros(n, dtype=np.uint8)
+        L.check(L.lib.ohmhip_map_covariance_eigen(self._handle, rec.ctypes.data, n, values.ctypes.data,
+                                                  vectors.ctypes.data, status.ctypes.data), "covarianceEigen")
+        return values, vectors, status
+
     # -- voxel edits by key (include/ohmhip.h, VOXEL EDITS) -----------------------------------------------------------
     def _edit_keys(self, keys):
         return _key_records(keys.view(np.uint8) if isinstance(keys, np.ndarray) and keys.dtype == _GPU_KEY else keys)

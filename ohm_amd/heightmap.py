@@ -65,6 +65,9 @@ class Heightmap:
         self.ignore_voxel_mean = False
         self.generate_virtual_surface = False
         self.promote_virtual_below = False
+        #: surface normals of occupied cells from the source's covariance layer (OHMHIP_HM_SURFACE_NORMALS): what the
+        #: reference always computes on an NDT map; off, normal_x / y / z stay 0
+        self.surface_normals = False
         self.mode = HeightmapMode.kPlanar
         self.keep_visit_log = False
         self.heightmap_origin = (0.0, 0.0, 0.0)
@@ -108,7 +111,8 @@ class Heightmap:
         p.floor, p.ceiling, p.min_clearance = float(self.floor), float(self.ceiling), float(self.min_clearance)
         p.flags = ((L.HM_GENERATE_VIRTUAL_SURFACE if self.generate_virtual_surface else 0) |
                    (L.HM_PROMOTE_VIRTUAL_BELOW if self.promote_virtual_below else 0) |
-                   (L.HM_IGNORE_VOXEL_MEAN if self.ignore_voxel_mean else 0))
+                   (L.HM_IGNORE_VOXEL_MEAN if self.ignore_voxel_mean else 0) |
+                   (L.HM_SURFACE_NORMALS if self.surface_normals else 0))
         return p
 
     def build_heightmap(self, reference_pos, cull_to=None):

@@ -2592,6 +2592,11 @@ public:
   bool promoteVirtualBelow() const { return promote_virtual_below_; }
   void setMode(HeightmapMode mode) { mode_ = mode; }
   HeightmapMode mode() const { return mode_; }
+  /// Surface normals of occupied cells from the source's covariance layer (OHMHIP_HM_SURFACE_NORMALS): what the
+  /// reference always computes on an NDT map (ohmheightmap/Heightmap.cpp:815-826).  Off -- the default -- normal_x / y /
+  /// z stay 0; on a map without the covariance layer the setting changes nothing.
+  void setSurfaceNormals(bool enable) { surface_normals_ = enable; }
+  bool surfaceNormals() const { return surface_normals_; }
   /// The origin of the heightmap's own OccupancyMap (heightmap().setOrigin() in the reference).
   void setHeightmapOrigin(const dvec3 &origin) { origin_ = origin; }
   const dvec3 &heightmapOrigin() const { return origin_; }
@@ -2644,7 +2649,8 @@ public:
     p.min_clearance = min_clearance_;
     p.flags = (generate_virtual_surface_ ? OHMHIP_HM_GENERATE_VIRTUAL_SURFACE : 0u) |
               (promote_virtual_below_ ? OHMHIP_HM_PROMOTE_VIRTUAL_BELOW : 0u) |
-              (ignore_voxel_mean_ ? OHMHIP_HM_IGNORE_VOXEL_MEAN : 0u);
+              (ignore_voxel_mean_ ? OHMHIP_HM_IGNORE_VOXEL_MEAN : 0u) |
+              (surface_normals_ ? OHMHIP_HM_SURFACE_NORMALS : 0u);
     const bool fill = mode_ == HeightmapMode::kSimpleFill;  // the layered modes: refused by the planar call
     last_status_ = fill ? ohmhip_map_heightmap_fill_extents(gpu_map_->handle(), &p, &extents_) :
                           ohmhip_map_heightmap_extents(gpu_map_->handle(), &p, &extents_);
@@ -2803,6 +2809,7 @@ private:
   unsigned region_size_;
   double ceiling_ = 0, floor_ = 0;
   bool ignore_voxel_mean_ = false, generate_virtual_surface_ = false, promote_virtual_below_ = false;
+  bool surface_normals_ = false;
   HeightmapMode mode_ = HeightmapMode::kPlanar;
   dvec3 origin_{ 0, 0, 0 };
   ohmhip_heightmap_extents extents_{};
@@ -2894,6 +2901,249 @@ inline VoxelCloud extractCloud(GpuMap &gpu_map, const CloudOptions &options = Cl
   cloud.values.resize(held);
   return cloud;
 }
+
+/// What ohm derives from an NDT voxel's covariance (ohm/CovarianceVoxel.h:33-67), by the one fp64 rule D1-D6 of
+/// include/ohmhip.h ("COVARIANCE DECOMPOSITION") that the device and the host evaluate alike.  Per voxel: eigenvalues
+/// ascending, eigenvectors as 9 doubles column-major after D4 (a glm::dmat3's storage), and a status byte
+/// (OHMHIP_COV_ABSENT: the map holds no such region or the key is null -- the doubles are zeros --, OHMHIP_COV_DECOMPOSED,
+/// OHMHIP_COV_NON_FINITE).
+struct CovarianceEigen
+{
+  std::vector<double> eigenvalues;   ///< 3 a voxel
+  std::vector<double> eigenvectors;  ///< 9 a voxel
+  std::vector<uint8_t> status;
+  int call_status = OHMHIP_OK;
+  size_t size() const { return status.size(); }
+};
+
+/// covarianceEigenDecomposition (ohm/CovarianceVoxel.cpp:147-154) for covariances the caller holds, 6 floats each
+/// (CovarianceVoxel::trianglar_covariance), on the host (ohmhip_covariance_decompose).
+inline CovarianceEigen covarianceEigenDecomposition(const float *covariance6, size_t count)
+{
+  CovarianceEigen e;
+  e.eigenvalues.assign(3 * count, 0.0);
+  e.eigenvectors.assign(9 * count, 0.0);
+  e.status.assign(count, 0);
+  e.call_status = ohmhip_covariance_decompose(covariance6, count, e.eigenvalues.data(), e.eigenvectors.data(), nullptr,
+                                              nullptr, e.status.data());
+  return e;
+}
+
+/// ... and for the voxels of `gpu_map`'s device map at `keys`, decomposed on the device (ohmhip_map_covariance_eigen):
+/// only the results cross to the host, and the map is read, never changed.
+inline CovarianceEigen covarianceEigenDecomposition(GpuMap &gpu_map, const std::vector<Key> &keys)
+{
+  CovarianceEigen e;
+  e.eigenvalues.assign(3 * keys.size(), 0.0);
+  e.eigenvectors.assign(9 * keys.size(), 0.0);
+  e.status.assign(keys.size(), 0);
+  e.call_status = (gpu_map.gpuOk() && gpu_map.syncConfig()) ?
+                    ohmhip_map_covariance_eigen(gpu_map.handle(), keys.data(), keys.size(), e.eigenvalues.data(),
+                                                e.eigenvectors.data(), e.status.data()) :
+                    int(OHMHIP_ERR_INVALID_ARG);
+  return e;
+}
+
+/// D6 of one decomposition (covarianceEstimatePrimaryNormal with preferred_axis 0, ohm/CovarianceVoxel.cpp:157-177):
+/// the column of the first smallest eigenvalue, divided by its length when that is not zero.
+inline dvec3 covariancePrimaryNormal(const double *eigenvalues, const double *eigenvectors)
+{
+  int index = 0;
+  for (int i = 0; i < 3; ++i)
+  {
+    index = (eigenvalues[i] < eigenvalues[index]) ? i : index;
+  }
+  const double *v = eigenvectors + 3 * index;
+  const double length2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+  if (!(length2 > 0.0))
+  {
+    return dvec3{ v[0], v[1], v[2] };
+  }
+  const double length = std::sqrt(length2);
+  return dvec3{ v[0] / length, v[1] / length, v[2] / length };
+}
+
+/// covarianceEstimatePrimaryNormal over keys: one normal a key (zeros where the status is OHMHIP_COV_ABSENT), not yet
+/// turned towards an up axis.  @return the call's status; `status` (optional) receives the per-voxel bytes.
+inline int covarianceEstimatePrimaryNormal(GpuMap &gpu_map, const std::vector<Key> &keys, std::vector<dvec3> &normals,
+                                           std::vector<uint8_t> *status = nullptr)
+{
+  const CovarianceEigen e = covarianceEigenDecomposition(gpu_map, keys);
+  normals.assign(keys.size(), dvec3{ 0, 0, 0 });
+  for (size_t i = 0; e.call_status == OHMHIP_OK && i < keys.size(); ++i)
+  {
+    if (e.status[i] != OHMHIP_COV_ABSENT)
+    {
+      normals[i] = covariancePrimaryNormal(&e.eigenvalues[3 * i], &e.eigenvectors[9 * i]);
+    }
+  }
+  if (status)
+  {
+    *status = e.status;
+  }
+  return e.call_status;
+}
+
+/// The unit quaternion of a rotation given as 9 doubles column-major, by Shepperd's method: of 1 + m00 + m11 + m22,
+/// 1 + m00 - m11 - m22, 1 - m00 + m11 - m22 and 1 - m00 - m11 + m22 (four times w, x, y, z squared) the largest, the
+/// first among equals, gives its component as sqrt(.) / 2; the other three are the matching sums or differences of
+/// off-diagonal pairs times 0.25 / that component.  The same operations in the same order as ohm_amd.
+/// rotation_to_quaternion.
+inline dquat covarianceRotationQuaternion(const double *c)
+{
+  // m(r, c) = c[3 * c + r]
+  const double m00 = c[0], m10 = c[1], m20 = c[2], m01 = c[3], m11 = c[4], m21 = c[5], m02 = c[6], m12 = c[7], m22 = c[8];
+  const double four[4] = { 1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22 };
+  int k = 0;
+  for (int i = 1; i < 4; ++i)
+  {
+    k = (four[i] > four[k]) ? i : k;
+  }
+  const double big = 0.5 * std::sqrt(four[k] > 0.0 ? four[k] : 0.0);
+  const double f = 0.25 / big;
+  const double wx = m21 - m12, wy = m02 - m20, wz = m10 - m01;
+  const double xy = m01 + m10, xz = m02 + m20, yz = m12 + m21;
+  dquat q{};
+  switch (k)
+  {
+  case 0: q.w = big; q.x = wx * f; q.y = wy * f; q.z = wz * f; break;
+  case 1: q.w = wx * f; q.x = big; q.y = xy * f; q.z = xz * f; break;
+  case 2: q.w = wy * f; q.x = xy * f; q.y = big; q.z = yz * f; break;
+  default: q.w = wz * f; q.x = xz * f; q.y = yz * f; q.z = big; break;
+  }
+  return q;
+}
+
+/// covarianceUnitSphereTransformation (ohm/CovarianceVoxel.cpp:180-206) over keys: the rotation (from the D4 matrix)
+/// and the scale (D5: |lambda| > 1e-9 ? sqrt(|lambda|) : |lambda|) that deform a unit sphere into each voxel's
+/// ellipsoid; zeros where the status is OHMHIP_COV_ABSENT.
+inline int covarianceUnitSphereTransformation(GpuMap &gpu_map, const std::vector<Key> &keys, std::vector<dquat> &rotations,
+                                              std::vector<dvec3> &scales, std::vector<uint8_t> *status = nullptr)
+{
+  const CovarianceEigen e = covarianceEigenDecomposition(gpu_map, keys);
+  rotations.assign(keys.size(), dquat{ 0, 0, 0, 0 });
+  scales.assign(keys.size(), dvec3{ 0, 0, 0 });
+  for (size_t i = 0; e.call_status == OHMHIP_OK && i < keys.size(); ++i)
+  {
+    if (e.status[i] == OHMHIP_COV_ABSENT)
+    {
+      continue;
+    }
+    rotations[i] = covarianceRotationQuaternion(&e.eigenvectors[9 * i]);
+    double s[3];
+    for (int c = 0; c < 3; ++c)
+    {
+      const double eval = std::abs(e.eigenvalues[3 * i + c]);
+      s[c] = (eval > 1e-9) ? std::sqrt(eval) : eval;
+    }
+    scales[i] = dvec3{ s[0], s[1], s[2] };
+  }
+  if (status)
+  {
+    *status = e.status;
+  }
+  return e.call_status;
+}
+
+/// ohm2ply --mode covariance (utils/ohm2ply/ohm2ply.cpp:845-1018) as a query against the device map
+/// (ohmhip_map_covariance_ellipsoids): every occupied voxel of an NDT map, in extractCloud's order for the same
+/// extents, with its mean position, the rotation (9 doubles column-major, D4) and the scale (D5, without ohm2ply's
+/// sqrt(3) display factor) of its covariance's ellipsoid, and its occupancy value.  intersectedVoxels() are the voxels'
+/// keys; there are no ranges.
+class CovarianceEllipsoids : public Query
+{
+public:
+  explicit CovarianceEllipsoids(GpuMap &gpu_map) : Query(&gpu_map, 0) {}
+
+  /// Only regions from regionKey(min_extents) to regionKey(max_extents) (OHMHIP_CLOUD_USE_EXTENTS).
+  void setExtents(const dvec3 &min_extents, const dvec3 &max_extents)
+  {
+    use_extents_ = true;
+    min_extents_ = min_extents;
+    max_extents_ = max_extents;
+  }
+  void clearExtents() { use_extents_ = false; }
+
+  const std::vector<dvec3> &positions() const { return positions_; }
+  const std::vector<double> &axes() const { return axes_; }  ///< 9 a voxel
+  const std::vector<dvec3> &scales() const { return scales_; }
+  const std::vector<float> &values() const { return values_; }
+  int lastStatus() const { return last_status_; }
+
+protected:
+  bool onExecute() override
+  {
+    if (!gpu_map_->syncConfig())
+    {
+      last_status_ = OHMHIP_ERR_INVALID_ARG;
+      return false;
+    }
+    ohmhip_cloud_params p{};
+    p.mode = OHMHIP_CLOUD_OCCUPANCY;
+    p.flags = use_extents_ ? OHMHIP_CLOUD_USE_EXTENTS : 0u;
+    p.surface_distance = std::numeric_limits<float>::infinity();
+    const double lo[3] = { min_extents_.x, min_extents_.y, min_extents_.z };
+    const double hi[3] = { max_extents_.x, max_extents_.y, max_extents_.z };
+    for (int i = 0; i < 3; ++i)
+    {
+      p.min_extents[i] = lo[i];
+      p.max_extents[i] = hi[i];
+    }
+    uint64_t count = 0;
+    last_status_ = ohmhip_map_covariance_ellipsoids_count(gpu_map_->handle(), &p, &count);
+    if (last_status_ != OHMHIP_OK)
+    {
+      return false;
+    }
+    if (count == 0)
+    {
+      return true;
+    }
+    static_assert(sizeof(dvec3) == 3 * sizeof(double), "positions and scales are written as 3 doubles a voxel");
+    const uint64_t capacity = count;
+    positions_.resize(size_t(capacity));
+    axes_.resize(size_t(9 * capacity));
+    scales_.resize(size_t(capacity));
+    values_.resize(size_t(capacity));
+    intersected_voxels_.resize(size_t(capacity));
+    last_status_ = ohmhip_map_covariance_ellipsoids(gpu_map_->handle(), &p, capacity, &positions_[0].x, axes_.data(),
+                                                    &scales_[0].x, intersected_voxels_.data(), values_.data(), &count);
+    if (last_status_ != OHMHIP_OK)
+    {
+      return false;
+    }
+    const size_t held = size_t(std::min(count, capacity));
+    positions_.resize(held);
+    axes_.resize(9 * held);
+    scales_.resize(held);
+    values_.resize(held);
+    intersected_voxels_.resize(held);
+    number_of_results_ = held;
+    return true;
+  }
+  void onReset(bool hard_reset) override
+  {
+    positions_.clear();
+    axes_.clear();
+    scales_.clear();
+    values_.clear();
+    if (hard_reset)
+    {
+      std::vector<dvec3>().swap(positions_);
+      std::vector<double>().swap(axes_);
+      std::vector<dvec3>().swap(scales_);
+      std::vector<float>().swap(values_);
+    }
+  }
+
+private:
+  bool use_extents_ = false;
+  dvec3 min_extents_{ 0, 0, 0 }, max_extents_{ 0, 0, 0 };
+  std::vector<dvec3> positions_, scales_;
+  std::vector<double> axes_;
+  std::vector<float> values_;
+  int last_status_ = OHMHIP_OK;
+};
 
 /// ohm::NearestNeighbours (ohm/NearestNeighbours.h) against the device-resident map: the obstructing voxels within
 /// searchRadius() of nearPoint(), in the CPU query's visiting order, or with kQfNearestResult the closest one

@@ -698,6 +698,72 @@ int modeVoxels(const Args &args)
   return kOk;
 }
 
+/// covariance: the covariance calls of the mirror over a GpuNdtMap (occupancy + mean + covariance) built from the rays
+/// in batches.  The keys are those of every 97th ray's end point, then a key of a region the map does not hold and a
+/// null key.  out: u64 keys, the keys (10-byte records), the covariance voxels readVoxels gives for them (6 f32 each);
+/// of covarianceEigenDecomposition the eigenvalues (3 f64 each), eigenvectors (9 f64 each) and status (u8 each); of
+/// covarianceEstimatePrimaryNormal the normals (3 f64 each); of covarianceUnitSphereTransformation the rotations (x, y, z, w f64 each) and scales (3 f64 each); then what a
+/// CovarianceEllipsoids query reports: u64 results, positions (3 f64 each), axes (9 f64 each), scales (3 f64 each),
+/// keys (10-byte records), values (f32 each); then a planar heightmap with surface normals and virtual surfaces on,
+/// reference position (0, 0, 0), +Z up: u32 ma, u32 mb, the occupancy and HeightmapVoxel arrays.
+int modeCovariance(const Args &args)
+{
+  const std::vector<ohm::dvec3> rays = readRays(args.input);
+  ohm::OccupancyMap map = hostMap(args.resolution, true);
+  ohm::GpuNdtMap gpu(&map, true);
+  check(gpu.gpuOk(), kMapInvalid);
+  check(integrateInBatches(gpu, rays, args.batch_rays) == (rays.size() & ~size_t(1)), kFailedCall);
+  const std::vector<ohm::dvec3> points = everyNinetySeventhEnd(rays);
+  std::vector<ohm::Key> keys = gpu.voxelKeys(points.data(), points.size());
+  check(gpu.lastStatus() == OHMHIP_OK, kFailedCall);
+  ohm::Key absent{};
+  absent.region[0] = absent.region[1] = absent.region[2] = 300;
+  keys.push_back(absent);
+  ohm::Key null_key{};
+  null_key.region[0] = null_key.region[1] = null_key.region[2] = int16_t(-32768);
+  keys.push_back(null_key);
+  std::vector<uint8_t> covariance, present;
+  check(gpu.readVoxels(OHMHIP_LID_COVARIANCE, keys, covariance, present) == OHMHIP_OK, kFailedCall);
+  const ohm::CovarianceEigen eigen = ohm::covarianceEigenDecomposition(gpu, keys);
+  std::vector<ohm::dvec3> normals, scales;
+  std::vector<ohm::dquat> rotations;
+  std::vector<uint8_t> normal_status, sphere_status;
+  check(eigen.call_status == OHMHIP_OK &&
+          ohm::covarianceEstimatePrimaryNormal(gpu, keys, normals, &normal_status) == OHMHIP_OK &&
+          ohm::covarianceUnitSphereTransformation(gpu, keys, rotations, scales, &sphere_status) == OHMHIP_OK &&
+          normal_status == eigen.status && sphere_status == eigen.status,
+        kFailedCall);
+  ohm::CovarianceEllipsoids ellipsoids(gpu);
+  check(ellipsoids.execute() && ellipsoids.lastStatus() == OHMHIP_OK, kFailedCall);
+  ohm::Heightmap heightmap(args.resolution, 0.0, ohm::UpAxis::kZ);
+  heightmap.setOccupancyMap(&gpu);
+  heightmap.setGenerateVirtualSurface(true);
+  check(!heightmap.surfaceNormals(), kUnexpected);
+  heightmap.setSurfaceNormals(true);
+  check(heightmap.buildHeightmap(ohm::dvec3{ 0.0, 0.0, 0.0 }), kFailedCall);
+  OutFile out(args.output);
+  out.value(uint64_t(keys.size()));
+  out.array(keys);
+  out.array(covariance);
+  out.array(eigen.eigenvalues);
+  out.array(eigen.eigenvectors);
+  out.array(eigen.status);
+  out.array(normals);
+  out.array(rotations);
+  out.array(scales);
+  out.value(uint64_t(ellipsoids.numberOfResults()));
+  out.array(ellipsoids.positions());
+  out.array(ellipsoids.axes());
+  out.array(ellipsoids.scales());
+  out.bytes(ellipsoids.intersectedVoxels(), ellipsoids.numberOfResults() * sizeof(ohm::Key));
+  out.array(ellipsoids.values());
+  out.value(uint32_t(heightmap.heightmapCellsA()));
+  out.value(uint32_t(heightmap.heightmapCellsB()));
+  out.array(heightmap.occupancy());
+  out.array(heightmap.heightmapVoxels());
+  return kOk;
+}
+
 /// filter [tolerance: -1] [occupancy only] [offset: 0.35]: GpuMap::filterPoints over a map with occupancy + mean; the
 /// points are every ray's end point and, displaced by offset along x, the same again.  out: u64 points, u64 kept, the
 /// status (u8 each), the kept indices (u64 each), the values (f64 each), the keys (10-byte records).
@@ -1092,6 +1158,7 @@ const Mode kModes[] = {
   { "cloud", &modeCloud, true },
   { "neighbours", &modeNeighbours, true },
   { "voxels", &modeVoxels, true },
+  { "covariance", &modeCovariance, true },
   { "filter", &modeFilterPoints, true },
   { "voxeledit", &modeVoxelEdit, true },
   { "filter:clipbounded", &modeRayFilter, false },
