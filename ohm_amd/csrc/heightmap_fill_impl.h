@@ -1,6 +1,7 @@
-// heightmap_fill_impl.h -- host side of the flood-fill heightmap (heightmap_fill_kernels.h): the planar call's checks
-// and geometry (heightmap_impl.h), the seed, then one round of kernels per generation of the reference's queue with the
-// next generation's size read back through a pinned word (its scan is 32 bit: not read_side.h's countAndScan).
+// heightmap_fill_impl.h -- host side of the flood-fill heightmap (heightmap_fill_kernels.h): the planar call's
+// prologue, source view and staged outputs (heightmap_impl.h), then one round of kernels per generation of the
+// reference's queue with the next generation's size read back through a pinned word (its scan is 32 bit: not
+// read_side.h's countAndScan).
 // Included after heightmap_impl.h in ohmhip_map.hip's translation unit.
 #ifndef OHMHIP_HEIGHTMAP_FILL_IMPL_H
 #define OHMHIP_HEIGHTMAP_FILL_IMPL_H
@@ -42,32 +43,15 @@ int fillQueueReserve(DevBuf &queue, size_t entries, size_t used, hipStream_t s)
 /// The walk, results into device arrays; returns with the stream idle.  The log, 3 uint32 per visit for the first
 /// log_capacity visits, goes to d_log, or to log_staging grown to what the walk produced (the host-array call, whose
 /// capacity may be "everything").
-int heightmapFillDevice(ohmhip_map_t m, const ohmhip_heightmap_params *p, HeightmapArgs &geometry, float *d_occ,
-                        void *d_vox, void *d_mean, uint32_t *d_visit, uint32_t *d_log, DevBuf *log_staging,
-                        uint64_t log_capacity, ohmhip_heightmap_fill_stats &stats)
+int heightmapFillDevice(ohmhip_map_t m, const HeightmapArgs &geometry, const int seed[3], float *d_occ, void *d_vox,
+                        void *d_mean, uint32_t *d_visit, uint32_t *d_log, DevBuf *log_staging, uint64_t log_capacity,
+                        ohmhip_heightmap_fill_stats &stats)
 {
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
   HeightmapFillArgs f{};
   static_cast<HeightmapArgs &>(f) = geometry;
-  OHMHIP_CHECK(mapReadView(m, f));
-  f.mean = f.use_mean ? static_cast<const uint2 *>(m->pool.layers[OHMHIP_LID_MEAN].get()) : nullptr;
-  f.spill_mean_delta =
-    (long long)(m->store.layer_offset[OHMHIP_LID_MEAN]) - (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
-  hmCovarianceView(m, f);
-  // F2: voxelKey(reference_pos) clamped into the extents on all three axes (the up axis is geometry.plane already)
-  MapConst kc = m->mc;
-  kc.tile_split[0] = kc.tile_split[1] = kc.tile_split[2] = 1;
-  int rref[3], lref[3];
-  if (!voxelKey(kc, p->reference_pos, rref, lref))
-  {
-    return OHMHIP_ERR_INTERNAL;  // (heightmapGeometry reports a null key as nothing to build)
-  }
-  int seed[3];
-  for (int c = 0; c < 3; ++c)
-  {
-    seed[c] = std::min(std::max(rref[c] * m->mc.kdim[c] + lref[c], f.min_g[c]), f.max_g[c]);
-  }
+  OHMHIP_CHECK(heightmapSourceView(m, f));
   const size_t cells = size_t(f.ma) * size_t(f.mb);
   const size_t grid_cells = size_t(f.na) * size_t(f.nb);
   f.grid_cells = uint32_t(grid_cells);
@@ -81,8 +65,6 @@ int heightmapFillDevice(ohmhip_map_t m, const ohmhip_heightmap_params *p, Height
   f.cell_visit = static_cast<uint32_t *>(qs.hm_winner.ptr);
   f.counts = static_cast<unsigned long long *>(qs.hm_counts.ptr);
   f.grid = static_cast<int *>(qs.hmf_grid.ptr);
-  const char *env = std::getenv("OHMHIP_HEIGHTMAP_COUNT");  // development: count the voxels inspected (counts[3])
-  f.count_inspected = (env && std::atoi(env) != 0) ? 1 : 0;
   f.out_occ = d_occ;
   f.out_vox = static_cast<uint32_t *>(d_vox);
   f.out_mean = static_cast<uint2 *>(d_mean);
@@ -94,6 +76,7 @@ int heightmapFillDevice(ohmhip_map_t m, const ohmhip_heightmap_params *p, Height
   OHMHIP_CHECK(hipGetLastError());
 
   OHMHIP_CHECK(fillQueueReserve(qs.hmf_queue, 1 << 14, 0, s));
+  // F2: the seed is heightmapGeometry's clamped key of reference_pos
   const uint2 first = make_uint2(uint32_t(seed[f.b] - f.min_g[f.b]) * uint32_t(f.na) + uint32_t(seed[f.a] - f.min_g[f.a]),
                                  uint32_t(seed[f.up] - f.min_g[f.up]));
   OHMHIP_CHECK(hipMemcpyAsync(qs.hmf_queue.ptr, &first, sizeof(first), hipMemcpyHostToDevice, s));
@@ -201,10 +184,8 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  OHMHIP_CHECK(heightmapRefusal(m, params, true));
-  OHMHIP_SETTLE(m);
   HeightmapArgs a;
-  return heightmapGeometry(m, params, a, *extents);
+  return heightmapBegin(m, params, true, a, *extents);
 }
 OHMHIP_ABI_CATCH
 
@@ -217,11 +198,10 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  OHMHIP_CHECK(heightmapRefusal(m, params, true));
-  OHMHIP_SETTLE(m);
   HeightmapArgs a;
   ohmhip_heightmap_extents e;
-  OHMHIP_CHECK(heightmapGeometry(m, params, a, e));
+  int seed[3];
+  OHMHIP_CHECK(heightmapBegin(m, params, true, a, e, seed));
   *stats = ohmhip_heightmap_fill_stats{};
   if (!e.populated)
   {
@@ -234,24 +214,16 @@ try
   {
     visit_log_capacity = 0;
   }
-  float *d_occ;
-  char *d_vox, *d_mean;
-  uint32_t *d_visit;
-  OHMHIP_CHECK(stageOut(qs.hm_out_occ, occupancy, n, s, d_occ));
-  OHMHIP_CHECK(stageOut(qs.hm_out_vox, voxels24, 24 * n, s, d_vox));
-  OHMHIP_CHECK(stageOut(qs.hm_out_mean, mean8, 8 * n, s, d_mean));
-  OHMHIP_CHECK(stageOut(qs.hm_out_col, source_visit, n, s, d_visit));
-  OHMHIP_CHECK(heightmapFillDevice(m, params, a, d_occ, d_vox, d_mean, d_visit, nullptr, &qs.hmf_log,
-                                   visit_log_capacity, *stats));
+  HeightmapStaged d;
+  OHMHIP_CHECK(d.stage(qs, occupancy, voxels24, mean8, source_visit, n, s));
+  OHMHIP_CHECK(heightmapFillDevice(m, a, seed, d.occ, d.vox, d.mean, d.source, nullptr, &qs.hmf_log, visit_log_capacity,
+                                   *stats));
   const uint64_t logged = std::min<uint64_t>(visit_log_capacity, stats->visits);
   if (logged)
   {
     OHMHIP_CHECK(hipMemcpyAsync(visit_log, qs.hmf_log.ptr, sizeof(uint32_t) * 3 * logged, hipMemcpyDeviceToHost, s));
   }
-  OHMHIP_CHECK(copyOut(occupancy, d_occ, n, s));
-  OHMHIP_CHECK(copyOut(voxels24, d_vox, 24 * n, s));
-  OHMHIP_CHECK(copyOut(mean8, d_mean, 8 * n, s));
-  OHMHIP_CHECK(copyOut(source_visit, d_visit, n, s));
+  OHMHIP_CHECK(d.copyBack(occupancy, voxels24, mean8, source_visit, n, s));
   return hipStreamSynchronize(s);
 }
 OHMHIP_ABI_CATCH
@@ -265,17 +237,16 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  OHMHIP_CHECK(heightmapRefusal(m, params, true));
-  OHMHIP_SETTLE(m);
   HeightmapArgs a;
   ohmhip_heightmap_extents e;
-  OHMHIP_CHECK(heightmapGeometry(m, params, a, e));
+  int seed[3];
+  OHMHIP_CHECK(heightmapBegin(m, params, true, a, e, seed));
   *stats = ohmhip_heightmap_fill_stats{};
   if (!e.populated)
   {
     return OHMHIP_OK;
   }
-  return heightmapFillDevice(m, params, a, d_occupancy, d_voxels24, d_mean8, d_source_visit, d_visit_log, nullptr,
+  return heightmapFillDevice(m, a, seed, d_occupancy, d_voxels24, d_mean8, d_source_visit, d_visit_log, nullptr,
                              d_visit_log ? visit_log_capacity : 0, *stats);
 }
 OHMHIP_ABI_CATCH

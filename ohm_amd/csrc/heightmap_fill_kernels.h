@@ -53,169 +53,6 @@ struct HeightmapFillArgs : HeightmapArgs  ///< `winner` is not used; rec_* hold 
   uint32_t log_count;        ///< visits to write to out_log
 };
 
-/// Rule 3, the selection ladder of findNearestSupportingVoxel (:346-419) as the fill walks: kBiasAbove on every visit
-/// but the first, never kIgnoreVirtualAbove.  Returns false when there is no candidate.
-__device__ inline bool hmSupportingVoxelFill(const HeightmapArgs &a, HmCursor &c, const int seed[3], bool bias_above,
-                                             int &candidate)
-{
-  const int min_up = sel3(a.up, a.min_g), max_up = sel3(a.up, a.max_g);
-  const int down_to = a.up_positive ? min_up : max_up;
-  const int up_to = a.up_positive ? max_up : min_up;
-  int below = 0, above = 0;
-  bool virtual_below = false, virtual_above = false;
-  const int offset_below = hmSearch(a, c, seed, down_to, a.voxel_floor, false, below, virtual_below);
-  const int offset_above = hmSearch(a, c, seed, up_to, a.voxel_ceiling, true, above, virtual_above);
-  const bool have_below = offset_below >= 0;
-  const bool have_above = offset_above >= 0;
-  virtual_below = have_below && virtual_below && !(a.flags & kHmPromoteVirtualBelow);
-  bool take_below;
-  if (bias_above && have_below && have_above)
-  {
-    take_below = offset_below < offset_above;  // :367-373 the closer one, the one above on a tie
-  }
-  else if (have_below && virtual_above && !virtual_below)
-  {
-    take_below = true;
-  }
-  else if (have_above && !virtual_above && virtual_below)
-  {
-    take_below = false;
-  }
-  else
-  {
-    take_below = have_below && (!have_above || offset_below <= offset_above ||
-                                (!virtual_above && offset_below + offset_above >= a.clearance_permissive));
-  }
-  candidate = take_below ? below : above;
-  return take_below ? have_below : have_above;
-}
-
-// The functions below are the ground search and the cell value of k_heightmap_columns, statement for statement.  They
-// are written out a second time because that kernel's machine code is held fixed (scripts/kernel_fingerprint.py) and
-// it keeps them in its body; calling its hmSubVoxelCoord from a second place changed how the compiler inlines it there
-// (6232 -> 6253 instructions), hence the copy of that one too.
-
-/// Rule 4, findGround (:422-512) from `candidate` up the column of `walk`.  False when the column has no ground.
-__device__ inline bool hmGround(const HeightmapArgs &a, HmCursor &c, const int walk[3], int candidate,
-                                const double up_vec[3], int &ground_up, double &clearance, bool &ground_observed_above)
-{
-  const int up = a.up;
-  const int min_up = sel3(up, a.min_g), max_up = sel3(up, a.max_g);
-  const int step_dir = a.up_positive ? 1 : -1;
-  bool observed_above = false;
-  double column_height = 1.7976931348623157e308;
-  double column_clearance_height = column_height;
-  int candidate_type = kOtNull;
-  int last_type = kOtNull;
-  int key[3] = { walk[0], walk[1], walk[2] };
-  for (int key_up = candidate; key_up >= min_up && key_up <= max_up; key_up += step_dir)
-  {
-    hmPut(key, up, key_up);
-    const int voxel_type = hmType(a, c, key);
-    const bool last_is_unobserved = last_type == kOtUnobserved || last_type == kOtNull;
-    observed_above = observed_above || (voxel_type != kOtNull && voxel_type != kOtUnobserved);
-    if (voxel_type == kOtOccupied ||
-        (a.generate_virtual && last_is_unobserved && voxel_type == kOtFree && candidate_type == kOtNull))
-    {
-      // sourceVoxelHeight (:167-184): the mean position for occupied voxels, the centre otherwise
-      double pos[3];
-      hmPosition(a, c, key, hmSeek(a, c, key), voxel_type == kOtOccupied, pos);
-      const double height = hmDot(pos, up_vec);
-      if (candidate_type != kOtNull)
-      {
-        column_clearance_height = height;
-        if (column_clearance_height - column_height >= a.min_clearance)
-        {
-          break;
-        }
-      }
-      column_height = column_clearance_height = height;
-      ground_up = key_up;
-      candidate_type = voxel_type;
-      observed_above = false;
-    }
-    last_type = voxel_type;
-  }
-  if (candidate_type == kOtNull)
-  {
-    return false;
-  }
-  clearance = column_clearance_height - column_height;
-  ground_observed_above = observed_above;
-  return true;
-}
-
-/// subVoxelCoord (ohm/VoxelMeanCompute.h:69-92), as hmSubVoxelCoord.
-__device__ inline uint32_t hmFillSubVoxelCoord(const double v[3], double resolution)
-{
-  const int mean_positions = (1 << 10) - 1;
-  const double mean_resolution = resolution / double(mean_positions);
-  const double offset = double(0.5f) * resolution;
-  uint32_t pattern = 0;
-#pragma unroll
-  for (int axis = 0; axis < 3; ++axis)
-  {
-    int pos = pointToRegionCoord(v[axis] + offset, mean_resolution);
-    pos = (pos >= 0 ? (pos < (1 << 10) ? pos : mean_positions) : 0);
-    pattern |= uint32_t(pos) << (10 * axis);
-  }
-  return pattern | (1u << 31);
-}
-
-constexpr long long kHmCellOutside = -2;  ///< hmCellRecord: the cell is not in the dense grid (cannot happen)
-
-/// Rule 5 (Heightmap.cpp:619-671, addSurfaceVoxel :703-835) for ground voxel `ground`: writes the cell's value into
-/// record `rec` of rec_occ / rec_vox / rec_mean and returns the dense index of the heightmap cell; kHmNoCell when the
-/// voxel writes nothing.
-__device__ inline long long hmCellRecord(const HeightmapArgs &a, HmCursor &c, const int ground[3], bool have_candidate,
-                                         bool have_ground, double clearance, bool ground_observed_above,
-                                         const double up_vec[3], size_t rec)
-{
-  const int up = a.up;
-  const int voxel_type = have_candidate ? hmType(a, c, ground) : int(kOtNull);
-  if (!(voxel_type == kOtOccupied || (voxel_type == kOtFree && a.generate_virtual)))
-  {
-    return kHmNoCell;
-  }
-  const int vi = hmSeek(a, c, ground);
-  double pos[3];
-  hmPosition(a, c, ground, vi, voxel_type == kOtOccupied, pos);
-  const double src_height = hmDot(up_vec, pos);
-  hmPut(pos, up, 0.0);
-  int hr[3], hl[3];
-  const bool ok = voxelKey(a.hm, pos, hr, hl);
-  hmPut(hr, up, 0);
-  hmPut(hl, up, 0);
-  const int ca = sel3(a.a, hr) * sel3(a.a, a.hm.kdim) + sel3(a.a, hl) - a.cell0_a;
-  const int cb = sel3(a.b, hr) * sel3(a.b, a.hm.kdim) + sel3(a.b, hl) - a.cell0_b;
-  if (!(ok && ca >= 0 && ca < a.ma && cb >= 0 && cb < a.mb))
-  {
-    return kHmCellOutside;
-  }
-  double centre[3];
-#pragma unroll
-  for (int axis = 0; axis < 3; ++axis)
-  {
-    centre[axis] = voxelCentreAxis(a.hm, axis, hr[axis], hl[axis]);
-  }
-  const float height = float(src_height - hmDot(centre, up_vec));
-  uint32_t samples = 0;
-  if (c.mean)
-  {
-    samples = min(c.mean[vi].y, 0xffffu);
-    const double rel[3] = { pos[0] - centre[0], pos[1] - centre[1], pos[2] - centre[2] };
-    a.rec_mean[rec] = make_uint2(hmFillSubVoxelCoord(rel, a.hm.resolution), 1u);
-  }
-  a.rec_occ[rec] = (voxel_type == kOtOccupied) ? 1.0f : -1.0f;
-  uint32_t *vox = a.rec_vox + rec * kHmVoxelWords;
-  vox[0] = __float_as_uint(height);
-  vox[1] = __float_as_uint(float(clearance));
-  hmSurfaceNormal(a, c, vi, voxel_type == kOtOccupied, up_vec, vox);
-  // layer kHvlBaseLayer (0) | flags << 8 | contributing_samples << 16
-  vox[5] = ((have_ground && ground_observed_above) ? 0x100u : 0u) | (samples << 16);
-  return (long long)(size_t(cb) * size_t(a.ma) + size_t(ca));
-}
-
 /// Neighbour slot k (0 .. 7) of PlaneFillWalker::visit's loops, row_delta on b outer, col_delta on a inner, self skipped.
 __device__ inline void hmFillSlotDelta(int k, int &col_delta, int &row_delta)
 {
@@ -249,15 +86,7 @@ __global__ void __launch_bounds__(64) k_hmfill_columns(HeightmapFillArgs f)
 {
   const uint32_t i = blockIdx.x * 64u + threadIdx.x;
   bool wrote = false;
-  HmCursor c;
-  c.tx = 0x7fffffff;
-  c.ty = c.tz = 0;
-  c.occ = nullptr;
-  c.mean = nullptr;
-  c.rx = 0x7fffffff;
-  c.ry = c.rz = 0;
-  c.region_exists = false;
-  c.inspected = 0;
+  HmCursor c = hmCursorStart();
   if (i < f.gen_count)
   {
     const uint32_t n = f.gen_count;
@@ -273,7 +102,7 @@ __global__ void __launch_bounds__(64) k_hmfill_columns(HeightmapFillArgs f)
     hmPut(walk, f.b, sel3(f.b, f.min_g) + ib);
     hmPut(walk, up, min_up + int(item.y));
     int candidate = 0;
-    const bool have_candidate = hmSupportingVoxelFill(f, c, walk, f.gen_begin + i != 0u, candidate);
+    const bool have_candidate = hmSupportingVoxel(f, c, walk, f.gen_begin + i != 0u, false, candidate);
     double clearance = 0.0;
     int ground_up = 0;
     bool ground_observed_above = false;
@@ -316,15 +145,7 @@ __global__ void __launch_bounds__(64) k_hmfill_columns(HeightmapFillArgs f)
       f.accept[size_t(8) * n] = 0u;
     }
   }
-  const unsigned long long wrote_mask = __ballot(wrote);
-  if (threadIdx.x == 0u && wrote_mask)
-  {
-    atomicAdd(&f.counts[0], (unsigned long long)__popcll(wrote_mask));
-  }
-  if (f.count_inspected && c.inspected)
-  {
-    atomicAdd(&f.counts[3], (unsigned long long)c.inspected);
-  }
+  hmColumnTail(f, c, wrote);
 }
 
 __global__ void __launch_bounds__(256) k_hmfill_replay(HeightmapFillArgs f)

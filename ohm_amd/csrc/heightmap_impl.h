@@ -41,8 +41,11 @@ int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p, bool fill
 }
 
 /// Rules 1 and 2 and the dense grid, on the host in fp64: fills the geometry fields of `a` and `e`.  The map is settled
-/// by the caller.  e.populated == 0: nothing to build.
-int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, HeightmapArgs &a, ohmhip_heightmap_extents &e)
+/// by the caller.  e.populated == 0: nothing to build.  `reference`, when asked for and there is something to build:
+/// voxelKey(reference_pos) as global voxel coordinates, clamped into the extents on all three axes (the fill's seed,
+/// F2; its up coordinate is a.plane).
+int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, HeightmapArgs &a, ohmhip_heightmap_extents &e,
+                      int *reference = nullptr)
 {
   std::memset(&e, 0, sizeof(e));
   a = HeightmapArgs{};
@@ -115,9 +118,16 @@ int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, Heightma
     e.min_local[c] = uint8_t(lmin[c]);
     e.max_region[c] = int16_t(rmax[c]);
     e.max_local[c] = uint8_t(lmax[c]);
+    const int ref = std::min(std::max(rref[c] * mc.kdim[c] + lref[c], a.min_g[c]), a.max_g[c]);
+    if (c == up)
+    {
+      a.plane = ref;  // rule 2
+    }
+    if (reference)
+    {
+      reference[c] = ref;
+    }
   }
-  // rule 2
-  a.plane = std::min(std::max(rref[up] * mc.kdim[up] + lref[up], a.min_g[up]), a.max_g[up]);
   const long long na = (long long)a.max_g[a.a] - a.min_g[a.a] + 1;
   const long long nb = (long long)a.max_g[a.b] - a.min_g[a.b] + 1;
   if (na <= 0 || nb <= 0)
@@ -176,24 +186,60 @@ int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, Heightma
   return OHMHIP_OK;
 }
 
-/// Where the covariance layer lies, for cells that carry surface normals (a.surface_normals from heightmapGeometry).
-void hmCovarianceView(ohmhip_map_t m, HeightmapArgs &a)
+/// What the six entry points do after their own pointer checks: the refusal, the map settled, the geometry.
+/// OHMHIP_OK with e.populated == 0: nothing to build -- the caller zeroes its outputs and answers OHMHIP_OK.
+int heightmapBegin(ohmhip_map_t m, const ohmhip_heightmap_params *p, bool fill, HeightmapArgs &a,
+                   ohmhip_heightmap_extents &e, int *reference = nullptr)
 {
-  a.covariance = a.surface_normals ? static_cast<const float *>(m->pool.layers[OHMHIP_LID_COVARIANCE].get()) : nullptr;
-  a.spill_cov_delta = (long long)(m->store.layer_offset[OHMHIP_LID_COVARIANCE]) -
-                      (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
+  OHMHIP_CHECK(heightmapRefusal(m, p, fill));
+  OHMHIP_SETTLE(m);
+  return heightmapGeometry(m, p, a, e, reference);
 }
+
+/// The source map as the column kernels of both builds see it (a.use_mean and a.surface_normals from
+/// heightmapGeometry): the read view, the mean and covariance layers where in use, the development counter.
+int heightmapSourceView(ohmhip_map_t m, HeightmapArgs &a)
+{
+  OHMHIP_CHECK(mapReadView(m, a));
+  a.mean = layerView(m, OHMHIP_LID_MEAN, a.use_mean);
+  a.covariance = layerView(m, OHMHIP_LID_COVARIANCE, a.surface_normals);
+  const char *env = std::getenv("OHMHIP_HEIGHTMAP_COUNT");  // development: count the voxels inspected (counts[3])
+  a.count_inspected = (env && std::atoi(env) != 0) ? 1 : 0;
+  return OHMHIP_OK;
+}
+
+/// The device copies of the four result arrays of a host-array call (QueryState::hm_out_*): null where the caller
+/// passed none.  `source` is source_column or source_visit.
+struct HeightmapStaged
+{
+  float *occ = nullptr;
+  char *vox = nullptr, *mean = nullptr;
+  uint32_t *source = nullptr;
+
+  int stage(ohmhip_map_s::QueryState &qs, const float *occupancy, const void *voxels24, const void *mean8,
+            const uint32_t *source_host, size_t n, hipStream_t s)
+  {
+    OHMHIP_CHECK(stageOut(qs.hm_out_occ, occupancy, n, s, occ));
+    OHMHIP_CHECK(stageOut(qs.hm_out_vox, voxels24, 24 * n, s, vox));
+    OHMHIP_CHECK(stageOut(qs.hm_out_mean, mean8, 8 * n, s, mean));
+    return stageOut(qs.hm_out_col, source_host, n, s, source);
+  }
+
+  int copyBack(float *occupancy, void *voxels24, void *mean8, uint32_t *source_host, size_t n, hipStream_t s) const
+  {
+    OHMHIP_CHECK(copyOut(occupancy, occ, n, s));
+    OHMHIP_CHECK(copyOut(voxels24, vox, 24 * n, s));
+    OHMHIP_CHECK(copyOut(mean8, mean, 8 * n, s));
+    return copyOut(source_host, source, n, s);
+  }
+};
 
 /// The two kernels on the map's stream, results into device arrays.  d_counts: 4 uint64 of the query's own.
 int heightmapDevice(ohmhip_map_t m, HeightmapArgs &a, float *d_occ, void *d_vox, void *d_mean, uint32_t *d_col)
 {
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
-  OHMHIP_CHECK(mapReadView(m, a));
-  a.mean = a.use_mean ? static_cast<const uint2 *>(m->pool.layers[OHMHIP_LID_MEAN].get()) : nullptr;
-  a.spill_mean_delta =
-    (long long)(m->store.layer_offset[OHMHIP_LID_MEAN]) - (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
-  hmCovarianceView(m, a);
+  OHMHIP_CHECK(heightmapSourceView(m, a));
   const size_t columns = size_t(a.na) * size_t(a.nb);
   const size_t cells = size_t(a.ma) * size_t(a.mb);
   OHMHIP_CHECK(qs.hm_winner.ensure(sizeof(int) * cells, false, s));
@@ -206,8 +252,6 @@ int heightmapDevice(ohmhip_map_t m, HeightmapArgs &a, float *d_occ, void *d_vox,
   a.rec_vox = static_cast<uint32_t *>(qs.hm_rec_vox.ptr);
   a.rec_mean = static_cast<uint2 *>(qs.hm_rec_mean.ptr);
   a.counts = static_cast<unsigned long long *>(qs.hm_counts.ptr);
-  const char *env = std::getenv("OHMHIP_HEIGHTMAP_COUNT");  // development: count the voxels inspected (counts[3])
-  a.count_inspected = (env && std::atoi(env) != 0) ? 1 : 0;
   a.out_occ = d_occ;
   a.out_vox = static_cast<uint32_t *>(d_vox);
   a.out_mean = static_cast<uint2 *>(d_mean);
@@ -231,10 +275,8 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  OHMHIP_CHECK(heightmapRefusal(m, params));
-  OHMHIP_SETTLE(m);
   HeightmapArgs a;
-  return heightmapGeometry(m, params, a, *extents);
+  return heightmapBegin(m, params, false, a, *extents);
 }
 OHMHIP_ABI_CATCH
 
@@ -246,11 +288,9 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  OHMHIP_CHECK(heightmapRefusal(m, params));
-  OHMHIP_SETTLE(m);
   HeightmapArgs a;
   ohmhip_heightmap_extents e;
-  OHMHIP_CHECK(heightmapGeometry(m, params, a, e));
+  OHMHIP_CHECK(heightmapBegin(m, params, false, a, e));
   *populated = 0;
   *cells = 0;
   if (!e.populated)
@@ -258,20 +298,11 @@ try
     return OHMHIP_OK;
   }
   hipStream_t s = m->stream;
-  ohmhip_map_s::QueryState &qs = m->query;
   const size_t n = size_t(a.ma) * size_t(a.mb);
-  float *d_occ;
-  char *d_vox, *d_mean;
-  uint32_t *d_col;
-  OHMHIP_CHECK(stageOut(qs.hm_out_occ, occupancy, n, s, d_occ));
-  OHMHIP_CHECK(stageOut(qs.hm_out_vox, voxels24, 24 * n, s, d_vox));
-  OHMHIP_CHECK(stageOut(qs.hm_out_mean, mean8, 8 * n, s, d_mean));
-  OHMHIP_CHECK(stageOut(qs.hm_out_col, source_column, n, s, d_col));
-  OHMHIP_CHECK(heightmapDevice(m, a, d_occ, d_vox, d_mean, d_col));
-  OHMHIP_CHECK(copyOut(occupancy, d_occ, n, s));
-  OHMHIP_CHECK(copyOut(voxels24, d_vox, 24 * n, s));
-  OHMHIP_CHECK(copyOut(mean8, d_mean, 8 * n, s));
-  OHMHIP_CHECK(copyOut(source_column, d_col, n, s));
+  HeightmapStaged d;
+  OHMHIP_CHECK(d.stage(m->query, occupancy, voxels24, mean8, source_column, n, s));
+  OHMHIP_CHECK(heightmapDevice(m, a, d.occ, d.vox, d.mean, d.source));
+  OHMHIP_CHECK(d.copyBack(occupancy, voxels24, mean8, source_column, n, s));
   unsigned long long counts[4] = { 0, 0, 0, 0 };
   OHMHIP_CHECK(hipMemcpyAsync(counts, a.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
   OHMHIP_CHECK(hipStreamSynchronize(s));
@@ -293,11 +324,9 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  OHMHIP_CHECK(heightmapRefusal(m, params));
-  OHMHIP_SETTLE(m);
   HeightmapArgs a;
   ohmhip_heightmap_extents e;
-  OHMHIP_CHECK(heightmapGeometry(m, params, a, e));
+  OHMHIP_CHECK(heightmapBegin(m, params, false, a, e));
   if (!e.populated)
   {
     return d_counts ? int(hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), m->stream)) : OHMHIP_OK;

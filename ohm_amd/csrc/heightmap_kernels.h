@@ -8,7 +8,9 @@
 //
 // The integer state machines are findNearestSupportingVoxel2 / findNearestSupportingVoxel / findGround of
 // ohmheightmap/private/HeightmapOperations.cpp:186-512 as written (tests/heightmap_ref.py is the same restatement on
-// the CPU, from the same rule list); heights are fp64 in the reference's order (no FMA: -ffp-contract=off).
+// the CPU, from the same rule list); heights are fp64 in the reference's order (no FMA: -ffp-contract=off).  Rules 3-5
+// are stated once, here -- hmSupportingVoxel, hmGround, hmCellRecord -- for this kernel and for k_hmfill_columns
+// (heightmap_fill_kernels.h), which differ in the walk key, the ladder's two flags and what they do with the cell.
 //
 // Shape.  A column is a run of voxels at the stride of one z slice (Z up), of one row (Y up) or of one float (X up).
 // Columns are dealt to lanes in walk order, `a` innermost, 64 x 4 columns per workgroup: with Z or Y up `a` is the
@@ -37,7 +39,7 @@ enum : unsigned
 {
   kHmVirtualSurfaces = 1u << 0,     ///< heightmap::kVirtualSurfaces (private/HeightmapOperations.h:45-63)
   kHmPromoteVirtualBelow = 1u << 2  ///< heightmap::kPromoteVirtualBelow
-  // kBiasAbove is never set in planar mode; kIgnoreVirtualAbove always is (Heightmap.cpp:375)
+  // kBiasAbove and kIgnoreVirtualAbove are hmSupportingVoxel's parameters: each build passes its own
 };
 
 constexpr int kHmNoCell = -1;
@@ -46,11 +48,9 @@ constexpr uint32_t kHmVoxelWords = 6;  ///< HeightmapVoxel: 24 bytes
 struct HeightmapArgs : MapReadView  ///< the source map
 {
   MapConst hm;  ///< heightmap geometry: resolution, region_dim, origin, kdim (1 on the up axis), tile_split 1
-  const uint2 *mean;          ///< pool layer or null
-  long long spill_mean_delta; ///< bytes from a stored region's occupancy block to its mean block
+  LayerView mean;             ///< no layer unless use_mean
   int use_mean;               ///< source has the mean layer and ignore_voxel_mean is off
-  const float *covariance;    ///< pool layer or null
-  long long spill_cov_delta;  ///< bytes from a stored region's occupancy block to its covariance block
+  LayerView covariance;       ///< no layer unless surface_normals
   int surface_normals;        ///< OHMHIP_HM_SURFACE_NORMALS and the source has the covariance layer
   int min_g[3], max_g[3];     ///< rule 1: min_ext_key / max_ext_key as global voxel coordinates
   int plane;                  ///< rule 2: the plane key's up coordinate, clamped
@@ -87,24 +87,28 @@ struct HmCursor
   uint32_t inspected;
 };
 
+/// A cursor that sits on no tile: the first hmSeek resolves.
+__device__ inline HmCursor hmCursorStart()
+{
+  HmCursor c;
+  c.tx = 0x7fffffff;
+  c.ty = c.tz = 0;
+  c.occ = nullptr;
+  c.mean = nullptr;
+  c.rx = 0x7fffffff;
+  c.ry = c.rz = 0;
+  c.region_exists = false;
+  c.inspected = 0;
+  return c;
+}
+
 /// The occupancy and mean blocks of tile (tx, ty, tz); false (and nulls) when the map has no such tile.
 __device__ inline bool hmTile(const HeightmapArgs &a, int tx, int ty, int tz, const float *&occ, const uint2 *&mean)
 {
   const FoundTile t = mapFindTile(a, tx, ty, tz);
-  if (t.slot != kSlotUnassigned)
-  {
-    occ = a.occupancy + size_t(t.slot) * size_t(a.mc.region_voxels);
-    mean = (a.use_mean && a.mean) ? a.mean + size_t(t.slot) * size_t(a.mc.region_voxels) : nullptr;
-    return true;
-  }
-  occ = t.stored;
-  mean = nullptr;
-  if (!occ)
-  {
-    return false;
-  }
-  mean = a.use_mean ? reinterpret_cast<const uint2 *>(reinterpret_cast<const char *>(occ) + a.spill_mean_delta) : nullptr;
-  return true;
+  occ = (t.slot != kSlotUnassigned) ? a.occupancy + size_t(t.slot) * size_t(a.mc.region_voxels) : t.stored;
+  mean = foundTileLayer<uint2>(t, a.mean, size_t(a.mc.region_voxels));
+  return occ != nullptr;
 }
 
 /// Writing component `idx` of a 3-vector with selects (reading it: sel3): a run-time index into a local array would put
@@ -272,9 +276,12 @@ __device__ inline int hmSearch(const HeightmapArgs &a, HmCursor &c, const int se
   return have_virtual ? offset : -1;
 }
 
-/// Rule 3, the selection ladder of findNearestSupportingVoxel (:346-419) without kBiasAbove and with
-/// kIgnoreVirtualAbove.  Returns false when there is no candidate.
-__device__ inline bool hmSupportingVoxel(const HeightmapArgs &a, HmCursor &c, const int seed[3], int &candidate)
+/// Rule 3, the selection ladder of findNearestSupportingVoxel (:346-419), rows in the order of
+/// tests/heightmap_ref.py::supporting_voxel.  The planar build walks without kBiasAbove and with kIgnoreVirtualAbove
+/// (Heightmap.cpp:375); the fill with kBiasAbove on every visit but the first and never kIgnoreVirtualAbove.  Returns
+/// false when there is no candidate.
+__device__ inline bool hmSupportingVoxel(const HeightmapArgs &a, HmCursor &c, const int seed[3], bool bias_above,
+                                         bool ignore_virtual_above, int &candidate)
 {
   const int min_up = sel3(a.up, a.min_g), max_up = sel3(a.up, a.max_g);
   const int down_to = a.up_positive ? min_up : max_up;
@@ -287,7 +294,11 @@ __device__ inline bool hmSupportingVoxel(const HeightmapArgs &a, HmCursor &c, co
   const bool have_above = offset_above >= 0;
   virtual_below = have_below && virtual_below && !(a.flags & kHmPromoteVirtualBelow);
   bool take_below;
-  if (have_below && virtual_above && !virtual_below)
+  if (bias_above && have_below && have_above)
+  {
+    take_below = offset_below < offset_above;  // :367-373 the closer one, the one above on a tie
+  }
+  else if (have_below && virtual_above && !virtual_below)
   {
     take_below = true;
   }
@@ -295,9 +306,9 @@ __device__ inline bool hmSupportingVoxel(const HeightmapArgs &a, HmCursor &c, co
   {
     take_below = false;
   }
-  else if (have_below && virtual_above && virtual_below)
+  else if (ignore_virtual_above && have_below && virtual_above && virtual_below)
   {
-    take_below = true;  // kIgnoreVirtualAbove
+    take_below = true;
   }
   else
   {
@@ -363,16 +374,8 @@ __device__ inline void hmSurfaceNormal(const HeightmapArgs &a, const HmCursor &c
   {
     return;
   }
-  const FoundTile t = mapFindTile(a, c.tx, c.ty, c.tz);
-  const float *cov = nullptr;
-  if (t.slot != kSlotUnassigned)
-  {
-    cov = a.covariance + (size_t(t.slot) * size_t(a.mc.region_voxels) + size_t(vi)) * 6u;
-  }
-  else if (t.stored)
-  {
-    cov = reinterpret_cast<const float *>(reinterpret_cast<const char *>(t.stored) + a.spill_cov_delta) + size_t(vi) * 6u;
-  }
+  const float *cov =
+    foundTileLayer<float>(mapFindTile(a, c.tx, c.ty, c.tz), a.covariance, size_t(a.mc.region_voxels) * 6u);
   if (!cov)
   {
     return;
@@ -381,7 +384,7 @@ __device__ inline void hmSurfaceNormal(const HeightmapArgs &a, const HmCursor &c
 #pragma unroll
   for (int i = 0; i < 6; ++i)
   {
-    p[i] = cov[i];
+    p[i] = cov[size_t(vi) * 6u + i];
   }
   const CovEigen e = covarianceEigen(p);
   float normal[3];
@@ -391,136 +394,114 @@ __device__ inline void hmSurfaceNormal(const HeightmapArgs &a, const HmCursor &c
   vox[4] = __float_as_uint(normal[2]);
 }
 
-__global__ void __launch_bounds__(256) k_heightmap_columns(HeightmapArgs a)
+/// Rule 4, findGround (:422-512) from `candidate` up the column of `walk`.  False when the column has no ground.
+__device__ inline bool hmGround(const HeightmapArgs &a, HmCursor &c, const int walk[3], int candidate,
+                                const double up_vec[3], int &ground_up, double &clearance, bool &ground_observed_above)
 {
-  const int ia = int(blockIdx.x) * 64 + int(threadIdx.x & 63u);
-  const int ib = int(blockIdx.y) * 4 + int(threadIdx.x >> 6);
-  bool wrote = false;
-  HmCursor c;
-  c.tx = 0x7fffffff;
-  c.ty = c.tz = 0;
-  c.occ = nullptr;
-  c.mean = nullptr;
-  c.rx = 0x7fffffff;
-  c.ry = c.rz = 0;
-  c.region_exists = false;
-  c.inspected = 0;
-  if (ia < a.na && ib < a.nb)
+  const int up = a.up;
+  const int min_up = sel3(up, a.min_g), max_up = sel3(up, a.max_g);
+  const int step_dir = a.up_positive ? 1 : -1;
+  bool observed_above = false;
+  double column_height = 1.7976931348623157e308;
+  double column_clearance_height = column_height;
+  int candidate_type = kOtNull;
+  int last_type = kOtNull;
+  int key[3] = { walk[0], walk[1], walk[2] };
+  for (int key_up = candidate; key_up >= min_up && key_up <= max_up; key_up += step_dir)
   {
-    const int up = a.up;
-    double up_vec[3] = { 0.0, 0.0, 0.0 };
-    hmPut(up_vec, up, a.up_positive ? 1.0 : -1.0);
-    int walk[3] = { 0, 0, 0 };
-    hmPut(walk, a.a, sel3(a.a, a.min_g) + ia);
-    hmPut(walk, a.b, sel3(a.b, a.min_g) + ib);
-    hmPut(walk, up, a.plane);
-    const int min_up = sel3(up, a.min_g), max_up = sel3(up, a.max_g);
-    int candidate = 0;
-    const bool have_candidate = hmSupportingVoxel(a, c, walk, candidate);
-
-    // Rule 4, findGround (:422-512)
-    bool have_ground = false;
-    int ground_up = 0;
-    double clearance = 0.0;
-    bool ground_observed_above = false;
-    if (have_candidate)
+    hmPut(key, up, key_up);
+    const int voxel_type = hmType(a, c, key);
+    const bool last_is_unobserved = last_type == kOtUnobserved || last_type == kOtNull;
+    observed_above = observed_above || (voxel_type != kOtNull && voxel_type != kOtUnobserved);
+    if (voxel_type == kOtOccupied ||
+        (a.generate_virtual && last_is_unobserved && voxel_type == kOtFree && candidate_type == kOtNull))
     {
-      const int step_dir = a.up_positive ? 1 : -1;
-      bool observed_above = false;
-      double column_height = 1.7976931348623157e308;
-      double column_clearance_height = column_height;
-      int candidate_type = kOtNull;
-      int last_type = kOtNull;
-      int key[3] = { walk[0], walk[1], walk[2] };
-      for (int key_up = candidate; key_up >= min_up && key_up <= max_up; key_up += step_dir)
-      {
-        hmPut(key, up, key_up);
-        const int voxel_type = hmType(a, c, key);
-        const bool last_is_unobserved = last_type == kOtUnobserved || last_type == kOtNull;
-        observed_above = observed_above || (voxel_type != kOtNull && voxel_type != kOtUnobserved);
-        if (voxel_type == kOtOccupied ||
-            (a.generate_virtual && last_is_unobserved && voxel_type == kOtFree && candidate_type == kOtNull))
-        {
-          // sourceVoxelHeight (:167-184): the mean position for occupied voxels, the centre otherwise
-          double pos[3];
-          hmPosition(a, c, key, hmSeek(a, c, key), voxel_type == kOtOccupied, pos);
-          const double height = hmDot(pos, up_vec);
-          if (candidate_type != kOtNull)
-          {
-            column_clearance_height = height;
-            if (column_clearance_height - column_height >= a.min_clearance)
-            {
-              break;
-            }
-          }
-          column_height = column_clearance_height = height;
-          ground_up = key_up;
-          candidate_type = voxel_type;
-          observed_above = false;
-        }
-        last_type = voxel_type;
-      }
+      // sourceVoxelHeight (:167-184): the mean position for occupied voxels, the centre otherwise
+      double pos[3];
+      hmPosition(a, c, key, hmSeek(a, c, key), voxel_type == kOtOccupied, pos);
+      const double height = hmDot(pos, up_vec);
       if (candidate_type != kOtNull)
       {
-        have_ground = true;
-        clearance = column_clearance_height - column_height;
-        ground_observed_above = observed_above;
-      }
-    }
-
-    // Rule 5 (Heightmap.cpp:619-671, addSurfaceVoxel :703-835)
-    int ground[3] = { walk[0], walk[1], walk[2] };
-    if (have_ground)
-    {
-      hmPut(ground, up, ground_up);
-    }
-    const int voxel_type = have_candidate ? hmType(a, c, ground) : int(kOtNull);
-    if (voxel_type == kOtOccupied || (voxel_type == kOtFree && a.generate_virtual))
-    {
-      const int vi = hmSeek(a, c, ground);
-      double pos[3];
-      hmPosition(a, c, ground, vi, voxel_type == kOtOccupied, pos);
-      const double src_height = hmDot(up_vec, pos);
-      hmPut(pos, up, 0.0);
-      int hr[3], hl[3];
-      const bool ok = voxelKey(a.hm, pos, hr, hl);
-      hmPut(hr, up, 0);
-      hmPut(hl, up, 0);
-      const int ca = sel3(a.a, hr) * sel3(a.a, a.hm.kdim) + sel3(a.a, hl) - a.cell0_a;
-      const int cb = sel3(a.b, hr) * sel3(a.b, a.hm.kdim) + sel3(a.b, hl) - a.cell0_b;
-      if (ok && ca >= 0 && ca < a.ma && cb >= 0 && cb < a.mb)
-      {
-        double centre[3];
-#pragma unroll
-        for (int axis = 0; axis < 3; ++axis)
+        column_clearance_height = height;
+        if (column_clearance_height - column_height >= a.min_clearance)
         {
-          centre[axis] = voxelCentreAxis(a.hm, axis, hr[axis], hl[axis]);
+          break;
         }
-        const size_t col = size_t(ib) * size_t(a.na) + size_t(ia);
-        const float height = float(src_height - hmDot(centre, up_vec));
-        uint32_t samples = 0;
-        if (c.mean)
-        {
-          samples = min(c.mean[vi].y, 0xffffu);
-          const double rel[3] = { pos[0] - centre[0], pos[1] - centre[1], pos[2] - centre[2] };
-          a.rec_mean[col] = make_uint2(hmSubVoxelCoord(rel, a.hm.resolution), 1u);
-        }
-        a.rec_occ[col] = (voxel_type == kOtOccupied) ? 1.0f : -1.0f;
-        uint32_t *vox = a.rec_vox + col * kHmVoxelWords;
-        vox[0] = __float_as_uint(height);
-        vox[1] = __float_as_uint(float(clearance));
-        hmSurfaceNormal(a, c, vi, voxel_type == kOtOccupied, up_vec, vox);
-        // layer kHvlBaseLayer (0) | flags << 8 | contributing_samples << 16
-        vox[5] = ((have_ground && ground_observed_above) ? 0x100u : 0u) | (samples << 16);
-        atomicMax(&a.winner[size_t(cb) * size_t(a.ma) + size_t(ca)], int(col));
-        wrote = true;
       }
-      else
-      {
-        atomicAdd(&a.counts[2], 1ull);
-      }
+      column_height = column_clearance_height = height;
+      ground_up = key_up;
+      candidate_type = voxel_type;
+      observed_above = false;
     }
+    last_type = voxel_type;
   }
+  if (candidate_type == kOtNull)
+  {
+    return false;
+  }
+  clearance = column_clearance_height - column_height;
+  ground_observed_above = observed_above;
+  return true;
+}
+
+constexpr long long kHmCellOutside = -2;  ///< hmCellRecord: the cell is not in the dense grid (cannot happen)
+
+/// Rule 5 (Heightmap.cpp:619-671, addSurfaceVoxel :703-835) for ground voxel `ground`: writes the cell's value into
+/// record `rec` of rec_occ / rec_vox / rec_mean and returns the dense index of the heightmap cell; kHmNoCell when the
+/// voxel writes nothing.
+__device__ inline long long hmCellRecord(const HeightmapArgs &a, HmCursor &c, const int ground[3], bool have_candidate,
+                                         bool have_ground, double clearance, bool ground_observed_above,
+                                         const double up_vec[3], size_t rec)
+{
+  const int up = a.up;
+  const int voxel_type = have_candidate ? hmType(a, c, ground) : int(kOtNull);
+  if (!(voxel_type == kOtOccupied || (voxel_type == kOtFree && a.generate_virtual)))
+  {
+    return kHmNoCell;
+  }
+  const int vi = hmSeek(a, c, ground);
+  double pos[3];
+  hmPosition(a, c, ground, vi, voxel_type == kOtOccupied, pos);
+  const double src_height = hmDot(up_vec, pos);
+  hmPut(pos, up, 0.0);
+  int hr[3], hl[3];
+  const bool ok = voxelKey(a.hm, pos, hr, hl);
+  hmPut(hr, up, 0);
+  hmPut(hl, up, 0);
+  const int ca = sel3(a.a, hr) * sel3(a.a, a.hm.kdim) + sel3(a.a, hl) - a.cell0_a;
+  const int cb = sel3(a.b, hr) * sel3(a.b, a.hm.kdim) + sel3(a.b, hl) - a.cell0_b;
+  if (!(ok && ca >= 0 && ca < a.ma && cb >= 0 && cb < a.mb))
+  {
+    return kHmCellOutside;
+  }
+  double centre[3];
+#pragma unroll
+  for (int axis = 0; axis < 3; ++axis)
+  {
+    centre[axis] = voxelCentreAxis(a.hm, axis, hr[axis], hl[axis]);
+  }
+  const float height = float(src_height - hmDot(centre, up_vec));
+  uint32_t samples = 0;
+  if (c.mean)
+  {
+    samples = min(c.mean[vi].y, 0xffffu);
+    const double rel[3] = { pos[0] - centre[0], pos[1] - centre[1], pos[2] - centre[2] };
+    a.rec_mean[rec] = make_uint2(hmSubVoxelCoord(rel, a.hm.resolution), 1u);
+  }
+  a.rec_occ[rec] = (voxel_type == kOtOccupied) ? 1.0f : -1.0f;
+  uint32_t *vox = a.rec_vox + rec * kHmVoxelWords;
+  vox[0] = __float_as_uint(height);
+  vox[1] = __float_as_uint(float(clearance));
+  hmSurfaceNormal(a, c, vi, voxel_type == kOtOccupied, up_vec, vox);
+  // layer kHvlBaseLayer (0) | flags << 8 | contributing_samples << 16
+  vox[5] = ((have_ground && ground_observed_above) ? 0x100u : 0u) | (samples << 16);
+  return (long long)(size_t(cb) * size_t(a.ma) + size_t(ca));
+}
+
+/// What a column kernel ends on, every lane of the wave present: the wave's count of lanes that wrote a cell into
+/// counts[0], and under OHMHIP_HEIGHTMAP_COUNT the voxels the lane inspected into counts[3].
+__device__ inline void hmColumnTail(const HeightmapArgs &a, const HmCursor &c, bool wrote)
+{
   const unsigned long long wrote_mask = __ballot(wrote);
   if ((threadIdx.x & 63u) == 0u && wrote_mask)
   {
@@ -530,6 +511,49 @@ __global__ void __launch_bounds__(256) k_heightmap_columns(HeightmapArgs a)
   {
     atomicAdd(&a.counts[3], (unsigned long long)c.inspected);
   }
+}
+
+__global__ void __launch_bounds__(256) k_heightmap_columns(HeightmapArgs a)
+{
+  const int ia = int(blockIdx.x) * 64 + int(threadIdx.x & 63u);
+  const int ib = int(blockIdx.y) * 4 + int(threadIdx.x >> 6);
+  bool wrote = false;
+  HmCursor c = hmCursorStart();
+  if (ia < a.na && ib < a.nb)
+  {
+    const int up = a.up;
+    double up_vec[3] = { 0.0, 0.0, 0.0 };
+    hmPut(up_vec, up, a.up_positive ? 1.0 : -1.0);
+    int walk[3] = { 0, 0, 0 };
+    hmPut(walk, a.a, sel3(a.a, a.min_g) + ia);
+    hmPut(walk, a.b, sel3(a.b, a.min_g) + ib);
+    hmPut(walk, up, a.plane);
+    int candidate = 0;
+    const bool have_candidate = hmSupportingVoxel(a, c, walk, false, true, candidate);
+    double clearance = 0.0;
+    int ground_up = 0;
+    bool ground_observed_above = false;
+    const bool have_ground =
+      have_candidate && hmGround(a, c, walk, candidate, up_vec, ground_up, clearance, ground_observed_above);
+    int ground[3] = { walk[0], walk[1], walk[2] };
+    if (have_ground)
+    {
+      hmPut(ground, up, ground_up);
+    }
+    const size_t col = size_t(ib) * size_t(a.na) + size_t(ia);
+    const long long cell =
+      hmCellRecord(a, c, ground, have_candidate, have_ground, clearance, ground_observed_above, up_vec, col);
+    if (cell >= 0)
+    {
+      atomicMax(&a.winner[cell], int(col));
+      wrote = true;
+    }
+    else if (cell == kHmCellOutside)
+    {
+      atomicAdd(&a.counts[2], 1ull);
+    }
+  }
+  hmColumnTail(a, c, wrote);
 }
 
 /// Rule 6: the winners write; every other cell is cleared (occupancy +inf, zeros).

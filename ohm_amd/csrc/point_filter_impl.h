@@ -44,14 +44,8 @@ int pointFilterView(ohmhip_map_t m, const ohmhip_point_filter_params *p, PointFi
   const bool layers = m->pool.layers[OHMHIP_LID_MEAN] && m->pool.layers[OHMHIP_LID_COVARIANCE];
   a.test = (!(p->flags & OHMHIP_PF_OCCUPANCY_ONLY) && layers && p->expected_value_tolerance >= 0) ? 1 : 0;
   a.limit = 3.0 + p->expected_value_tolerance;
-  if (a.test)
-  {
-    a.mean = static_cast<const uint2 *>(m->pool.layers[OHMHIP_LID_MEAN].get());
-    a.covariance = static_cast<const float *>(m->pool.layers[OHMHIP_LID_COVARIANCE].get());
-    a.stored_mean = (long long)(m->store.layer_offset[OHMHIP_LID_MEAN]) - (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
-    a.stored_covariance =
-      (long long)(m->store.layer_offset[OHMHIP_LID_COVARIANCE]) - (long long)(m->store.layer_offset[OHMHIP_LID_OCCUPANCY]);
-  }
+  a.mean = layerView(m, OHMHIP_LID_MEAN, a.test);
+  a.covariance = layerView(m, OHMHIP_LID_COVARIANCE, a.test);
   return OHMHIP_OK;
 }
 

@@ -13,9 +13,10 @@
 // order and its exclusive scan is every wave's first slot of the kept indices.  The tile of a point is resolved as
 // k_read_voxels resolves it -- region hash, then the host store -- and lanes of a wave that fall in the same tile share
 // one probe (waveMatch): the points of a scan are spatially coherent.  The one probe serves all three layers: a pool
-// slot addresses three pool blocks, a store record holds its layers at fixed offsets from the occupancy block.  The mean
-// and covariance voxels are loaded only by lanes whose voxel is occupied.  Counting is __popcll(__ballot(kept)),
-// ranking __popcll(ballot & lanes below).  No atomics: two calls return identical bytes.
+// slot addresses three pool blocks, a store record holds its layers at fixed offsets from the occupancy block
+// (LayerView / foundTileLayer, query_kernels.h).  The mean and covariance voxels are loaded only by lanes whose voxel is
+// occupied.  Counting is __popcll(__ballot(kept)), ranking __popcll(ballot & lanes below).  No atomics: two calls return
+// identical bytes.
 #ifndef OHMHIP_POINT_FILTER_KERNELS_H
 #define OHMHIP_POINT_FILTER_KERNELS_H
 
@@ -32,10 +33,8 @@ enum : uint8_t
 
 struct PointFilterArgs : MapReadView
 {
-  const uint2 *mean;          ///< pool layer [slot][tile voxel]; null: no covariance test
-  const float *covariance;    ///< pool layer [slot][tile voxel][6]
-  long long stored_mean;      ///< bytes from a store record's occupancy block to its mean block
-  long long stored_covariance;
+  LayerView mean;             ///< [tile voxel]; no layer: no covariance test
+  LayerView covariance;       ///< [tile voxel][6]
   int test;                   ///< the covariance test runs
   double limit;               ///< 3.0 + expected_value_tolerance, fp64
   const double *points;       ///< point i at points[i * stride]
@@ -152,10 +151,9 @@ __global__ void __launch_bounds__(256) k_pf_classify(PointFilterArgs a)
       status = kPfKept;
       if (a.test)
       {
-        const char *record = reinterpret_cast<const char *>(t.stored);
-        const uint2 *mean_at = resident ? a.mean + pool_voxel : reinterpret_cast<const uint2 *>(record + a.stored_mean) + voxel;
-        const float *cov_at = resident ? a.covariance + 6u * pool_voxel :
-                                         reinterpret_cast<const float *>(record + a.stored_covariance) + 6u * voxel;
+        // (a.test: both views hold a layer, and the tile was found)
+        const uint2 *mean_at = foundTileLayer<uint2>(t, a.mean, size_t(mc.region_voxels)) + voxel;
+        const float *cov_at = foundTileLayer<float>(t, a.covariance, 6u * size_t(mc.region_voxels)) + 6u * voxel;
         const uint32_t coord = mean_at->x;
         // (24-byte voxels: 8-byte aligned)
         const float2 c01 = reinterpret_cast<const float2 *>(cov_at)[0];

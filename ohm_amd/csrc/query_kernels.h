@@ -1,5 +1,6 @@
-// query_kernels.h -- the read side of the device-resident map: what every reader shares (MapReadView, mapFindTile, the
-// caller's GpuKeyOut), LineKeysQueryGpu and RaysQueryGpu, read-only ray casts against the occupancy layer.
+// query_kernels.h -- the read side of the device-resident map: what every reader shares (MapReadView, mapFindTile,
+// LayerView for a second layer of a found tile, the caller's GpuKeyOut), LineKeysQueryGpu and RaysQueryGpu, read-only ray
+// casts against the occupancy layer.
 //
 //   k_line_keys         1 lane / line    the keys of every voxel on a line, in walk order
 //   k_rays_query        1 lane / ray     the CPU query's walk (ohm/RaysQuery.cpp:102-203 onExecute) over the pool
@@ -100,6 +101,29 @@ __device__ inline FoundTile mapFindTile(const MapReadView &v, int tx, int ty, in
     }
   }
   return t;
+}
+
+/// A second layer of the map for a kernel that finds tiles itself (the occupancy layer is MapReadView's): filled by
+/// layerView() on the host.
+struct LayerView
+{
+  const char *pool;        ///< pool layer: [slot][tile voxel]; null: the map lacks the layer, or the kernel does not read it
+  long long stored_delta;  ///< bytes from a store record's occupancy block to this layer's block
+};
+
+/// Tile `t`'s block of layer `l`, `tile_elements` elements of T; null when the map has no such tile or the view no layer.
+template <typename T>
+__device__ inline const T *foundTileLayer(const FoundTile &t, const LayerView &l, size_t tile_elements)
+{
+  if (!l.pool)
+  {
+    return nullptr;
+  }
+  if (t.slot != kSlotUnassigned)
+  {
+    return reinterpret_cast<const T *>(l.pool) + size_t(t.slot) * tile_elements;
+  }
+  return t.stored ? reinterpret_cast<const T *>(reinterpret_cast<const char *>(t.stored) + l.stored_delta) : nullptr;
 }
 
 /// The occupancy block of tile (tx, ty, tz); null when the map has no such tile.

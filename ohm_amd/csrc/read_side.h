@@ -1,7 +1,8 @@
 // read_side.h -- what the host code of the read-only features shares (query_impl.h, clearance_impl.h,
 // clearance_update.h, heightmap_impl.h, heightmap_fill_impl.h, cloud_impl.h, neighbours_impl.h, point_filter_impl.h):
 // the refusal every one of them makes, where a tile's data lives, the caller's region order, a tile cut into chunks, the
-// map as the read-side kernels see it, count per wave then scan, and the optional host outputs.  Included in
+// map as the read-side kernels see it (and a second layer beside it), count per wave then scan, and the optional host
+// outputs.  Included in
 // ohmhip_map.hip's translation unit after tiling_impl.h and ahead of the read-side parts.  DESIGN.md 5a says what a new
 // feature calls, and in what order.
 #ifndef OHMHIP_READ_SIDE_H
@@ -65,6 +66,19 @@ char *tileLayerBlock(ohmhip_map_t m, const TileHome &home, int layer)
            size_t(home.slot) * size_t(m->mc.region_voxels) * kLayerBytes[layer];
   }
   return home.stored ? home.stored->record + m->store.layer_offset[layer] : nullptr;
+}
+
+/// Layer `layer` beside the occupancy layer of a MapReadView, for kernels that find tiles themselves (foundTileLayer);
+/// `in_use` false, or a map without the layer: a view with no layer.
+LayerView layerView(ohmhip_map_t m, int layer, bool in_use = true)
+{
+  if (!in_use || !m->pool.layers[layer])
+  {
+    return LayerView{ nullptr, 0 };
+  }
+  const size_t *at = m->store.layer_offset;
+  return LayerView{ static_cast<const char *>(m->pool.layers[layer].get()),
+                    (long long)(at[layer]) - (long long)(at[OHMHIP_LID_OCCUPANCY]) };
 }
 
 /// (rz, ry, rx) of a caller's region, biased: ascending == the order clouds, neighbour queries and clearance updates

@@ -16,7 +16,8 @@ from ohm_amd import _lib as L
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import heightmap_ref as R  # noqa: E402
 import heightmap_fill_ref as F  # noqa: E402
-from heightmap_fill_cases import (FLAT_HOLES, flat_cases, flat_floor, mean_scene, scaled_multi_level)  # noqa: E402
+from heightmap_fill_cases import (FLAT_HOLES, HIT, INF32, MISS, flat_cases, flat_floor, mean_scene,  # noqa: E402
+                                  scaled_multi_level)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,14 +34,14 @@ def device_map(scene, one_by_one=False, **kw):
     return map_, gm
 
 
-def fill_heightmap(gm, p, keep_log=True):
+def fill_heightmap(gm, p, keep_log=True, mode=HeightmapMode.kSimpleFill):
     hm = Heightmap(p.grid_resolution, p.min_clearance, UpAxis(p.up_axis), p.region_size)
     hm.floor, hm.ceiling = p.floor, p.ceiling
     hm.generate_virtual_surface = p.virtual_surface
     hm.promote_virtual_below = p.promote_virtual_below
     hm.ignore_voxel_mean = p.ignore_voxel_mean
     hm.heightmap_origin = p.origin
-    hm.mode = HeightmapMode.kSimpleFill
+    hm.mode = mode
     hm.keep_visit_log = keep_log
     hm.set_occupancy_map(gm)
     built = hm.build_heightmap(p.reference_pos, (p.cull_min, p.cull_max))
@@ -147,6 +148,53 @@ def test_generation_wider_than_a_workgroup(gpu):
     p = R.Params(0.5, 0.0, reference_pos=(0.1, 0.1, 0.7), floor=1.5, ceiling=1.5)
     hm, want = check(scene, p, "130 x 130")
     assert want.largest_generation > 256 and want.cells == 130 * 130
+
+
+# -- the two builds' flags of the selection ladder ---------------------------------------------------------------------------
+
+def test_ladder_flags_of_the_two_builds(gpu):
+    """Both builds run one ladder on the device: the planar one with kIgnoreVirtualAbove, the fill with kBiasAbove on
+    every visit but the first.  Two planted columns of one 16^3 region of 1 m voxels tell the flag sets apart, one per
+    row that differs, so flags exchanged between the two call sites fail here.  Column A is free with occupied voxels
+    at z = 4 and z = 10, column B unobserved at z = 0 .. 4 and z = 9 and free elsewhere; an ordinary floor at z = 8
+    around them, the plane and the seed on it, so the fill reaches both from z = 8 and not as its first visit."""
+    col_a, col_b, seed_xy, level = (3, 3), (12, 12), (8, 8), 8
+    scene = flat_floor(n=16, dim=(16, 16, 16), resolution=1.0, level=level, first=0)
+    for z in range(16):
+        scene.put(col_a + (z,), HIT if z in (4, 10) else MISS)
+        scene.put(col_b + (z,), INF32 if (z <= 4 or z == 9) else MISS)
+    assert len(scene.chunks) == 1
+    p = R.Params(1.0, 0.0, reference_pos=scene.centre(seed_xy + (level,)), virtual_surface=True)
+    src = scene.source()
+    min_key, max_key = R.extents(src, p)
+    assert max(1, R.point_to_region_coord(p.min_clearance, src.resolution) - 1) == 1  # clearance_permissive
+
+    def candidate_z(column, flags):
+        return R.supporting_voxel(src, list(column) + [level], p.up_axis, min_key, max_key, 0, 0, 1, flags)[2]
+
+    planar_flags, fill_flags = R.F_VIRTUAL | R.F_IGNORE_VIRTUAL_ABOVE, R.F_VIRTUAL | R.F_BIAS_ABOVE
+    # the precondition: the restatements disagree on both columns, A on the bias row, B on the ignore-virtual-above row
+    assert (candidate_z(col_a, planar_flags), candidate_z(col_a, fill_flags)) == (4, 10)
+    assert (candidate_z(col_b, planar_flags), candidate_z(col_b, fill_flags)) == (4, 9)
+    assert candidate_z(seed_xy, planar_flags) == candidate_z(seed_xy, fill_flags) == level
+
+    _, gm = device_map(scene)
+    hm, want = check(scene, p, "ladder, fill", gm)
+    assert want.log[0].tolist() == list(seed_xy) + [level - min_key[2]]
+    planar_want = R.build_heightmap(src, p)
+    planar, built = fill_heightmap(gm, p, keep_log=False, mode=HeightmapMode.kPlanar)
+    assert built and (planar_want.na, planar_want.nb, planar_want.ma, planar_want.mb) == (want.na, want.nb, want.ma, want.mb)
+    assert np.array_equal(planar.occupancy.view(np.uint32), planar_want.occupancy.view(np.uint32))
+    assert np.array_equal(bits(planar.voxels), bits(planar_want.voxels))
+    assert np.array_equal(planar.source_column, planar_want.source_column)
+    assert planar.populated_count == planar_want.populated
+    # ... and what the builds hold in the two cells is what the candidates lead to (the grid is the map's: cell = column)
+    def rise(result, column):
+        return float(result.voxels["height"][column[1], column[0]]) - float(result.voxels["height"][seed_xy[1], seed_xy[0]])
+
+    assert (rise(planar_want, col_a), rise(want, col_a)) == (4.0 - level, 10.0 - level)
+    assert (rise(planar_want, col_b), rise(want, col_b)) == (5.0 - level, 10.0 - level)  # virtual: the free voxel above
+    assert planar_want.occupancy[col_b[1], col_b[0]] == want.occupancy[col_b[1], col_b[0]] == -1.0
 
 
 # -- mean layer and a coarser grid --------------------------------------------------------------------------------------------
