@@ -601,8 +601,8 @@ int ohmhip_map_clearance_update_regions(ohmhip_map_t map, const int16_t *keys_xy
  * voxelKey of the heightmap for voxelCentreGlobal(min_ext_key) - resolution / 2 and voxelCentreGlobal(max_ext_key) +
  * resolution / 2 on a and b.  Cells nobody wrote hold +inf / zeros, as a cleared chunk does.  source_column (optional):
  * the walk index of the column that wrote the cell, 0xffffffff for none.
- * NOT PROVIDED: the layered fill modes (kLayeredFill*: multi-layer sorting) and with them the virtual-surface filter;
- * blur, mesh, serialisation.  kSimpleFill is a call of its own (the next block); here mode != 0: OHMHIP_ERR_UNSUPPORTED.
+ * NOT PROVIDED: blur, mesh, serialisation.  kSimpleFill and the layered fill modes (kLayeredFill*: multi-layer sorting,
+ * the virtual-surface filter) are calls of their own (the next two blocks); here mode != 0: OHMHIP_ERR_UNSUPPORTED.
  * SURFACE NORMALS.  normal_x / y / z are 0 unless OHMHIP_HM_SURFACE_NORMALS is set and the source map has the covariance
  * layer: then the cell of a kOccupied ground voxel carries covarianceEstimatePrimaryNormal of that voxel's covariance
  * turned towards up (Heightmap.cpp:815-826), by the rule D1-D6 of COVARIANCE DECOMPOSITION below -- the reference
@@ -628,7 +628,7 @@ typedef struct ohmhip_heightmap_params
   double origin[3];
   uint8_t region_size;             /* 0 = 128 (Heightmap::kDefaultRegionSize) */
   int8_t up_axis;                  /* ohm::UpAxis: -3 (kNegZ) .. 2 (kZ) */
-  uint8_t mode;                    /* ohm::HeightmapMode: 0 planar, 1 simple fill (ohmhip_map_heightmap_fill); 2, 3 refused */
+  uint8_t mode;                    /* ohm::HeightmapMode: 0 planar, 1 simple fill (ohmhip_map_heightmap_fill); 2, 3 layered (ohmhip_map_heightmap_layered) */
   double floor, ceiling, min_clearance;
   unsigned flags;                  /* OHMHIP_HM_* */
 } ohmhip_heightmap_params;
@@ -693,7 +693,7 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_heightmap_device(ohmhip_map_t map, const ohmh
  * h, the first visit_log_capacity visits (a smaller capacity is not an error; stats.visits is the full count).
  * stats.revisits: accepted offers to a cell that already held a height.
  * mode 1 builds; mode 0 is OHMHIP_ERR_INVALID_ARG (the planar call); modes 2 and 3 (kLayeredFillUnordered, kLayeredFill:
- * multi-layer sorting, the virtual-surface filter) are NOT PROVIDED: OHMHIP_ERR_UNSUPPORTED.  Every other refusal, and
+ * the next block, ohmhip_map_heightmap_layered) are OHMHIP_ERR_UNSUPPORTED here.  Every other refusal, and
  * how the map is observed, is the planar call's; OHMHIP_ERR_CAPACITY also when the visits exceed 2^32 - 1 or one
  * generation 2^31 / 9 keys.  Nothing of the map changes. */
 typedef struct ohmhip_heightmap_fill_stats
@@ -715,6 +715,93 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_heightmap_fill_device(ohmhip_map_t map, const
                                                          float *d_occupancy, void *d_voxels24, void *d_mean8,
                                                          uint32_t *d_source_visit, uint32_t *d_visit_log,
                                                          uint64_t visit_log_capacity, ohmhip_heightmap_fill_stats *stats);
+
+/* HEIGHTMAP, LAYERED.  ohm::Heightmap::buildHeightmap in HeightmapMode::kLayeredFillUnordered (2) and kLayeredFill (3):
+ * buildHeightmapT<PlaneFillLayeredWalker> (ohmheightmap/Heightmap.cpp:391-402, 522-700; PlaneFillLayeredWalker.cpp),
+ * addSurfaceVoxel's multi-layer branch (Heightmap.cpp:703-835) and filterVirtualVoxels / finaliseLayeredHeightmap /
+ * BaseLayerCandidate::isOtherCandidateBetter / DstVoxel::haveRecordedHeight (private/HeightmapOperations.cpp:32-62,
+ * 135-165, 515-773).  A column of the heightmap holds every surface found over its cell -- the floor under a platform
+ * and the platform -- stacked along the RAW up axis of the heightmap's own key space: slot k of a column is the voxel at
+ * the cell's key moved k steps along that axis.  Equal to the CPU algorithm for every slot and every field.  Rules 1, 3,
+ * 4 and 5 are those of HEIGHTMAP, F1-F3 those of the flood fill; new or different:
+ *  L1 EXTENTS, SEED.  F1 and F2.  PlaneFillLayeredWalker::begin (PlaneFillLayeredWalker.cpp:27-51) clamps the seed into
+ *    the range on all axes and touches nothing: the seed is never "touched", so a neighbour may queue its column again.
+ *  L2 A VISIT.  F3 unchanged: kVirtualSurfaces / kPromoteVirtualBelow only on the first visit, kBiasAbove added on every
+ *    later one, never kIgnoreVirtualAbove (Heightmap.cpp:397-400, :674); then findGround.  ground_key = the ground
+ *    found, else the walk key; hg its height offset.
+ *  L3 NEIGHBOURS (onVisitWalker, Heightmap.cpp:60-70; visit, PlaneFillLayeredWalker.cpp:68-102).  F4's loop order.  A
+ *    neighbour's key is ground_key moved sideways, so it is offered hg.  With a candidate (kAddUnvisitedNeighbours) the
+ *    offer is accepted when (cell, hg) has never been touched; with a null candidate (kAddUnvisitedColumnNeighbours)
+ *    when the cell has never been touched at any height.  An accepted offer touches (cell, hg) -- a node (height, next)
+ *    at the head of the cell's list, :129-158 -- and is appended to the FIFO.  A pop changes nothing; there is no
+ *    "lower" rule.
+ *  L4 BASE CANDIDATE (Heightmap.cpp:623-624).  ground.isValid() && (ground.clearance > 0 || ground.observed_above).
+ *  L5 ADDING TO A COLUMN (addSurfaceVoxel, :731-831), in visit order.  The cell key, position, occupancy value and voxel
+ *    fields are rule 5's.  Slot 0 empty: write there.  Else haveRecordedHeight (HeightmapOperations.cpp:32-62) walks the
+ *    slots in use from 0: |double(float height_k) + dot(centre_k, up) - src_height| < 1e-3 * grid_resolution for any slot
+ *    makes the add a REPEAT, dropped.  Else all slots in use are walked keeping the nearest height difference below and
+ *    above exactly as written (:754-776); the insert slot is the first empty one; the add is dropped as TOO CLOSE when
+ *    either nearest difference is in (0, min_clearance] -- as written for real and virtual voxels alike.  Else height =
+ *    float(src_height - dot(centre(slot), up)), layer = base candidate ? kHvlBaseLayer (0) : kHvlExtended (1), the mean
+ *    coord taken against the slot's centre (DstVoxel::setPosition), and in ordered mode the column is noted as
+ *    multi-layered.  populated counts the adds that stood.
+ *  L6 VIRTUAL-SURFACE FILTER (kLayeredFill with virtual_surface_filter_threshold > 0; Heightmap.cpp:665-683,
+ *    filterVirtualVoxels :515-600).  A map from each ground_key that added a voxel to its slot and type; the first entry
+ *    for a key stands.  A virtual entry with fewer than threshold of its 26 neighbours IN THE SOURCE MAP'S KEY SPACE in
+ *    that map, any type counting, becomes layer kHvlInvalid (2) with occupancy -inf
+ *    (kHeightmapVirtualSurfaceFilteredValue).  The count depends on the set alone, not on the hash map's order.
+ *  L7 FINALISE (kLayeredFill only; finaliseLayeredHeightmap :603-773).  A column not noted as multi-layered: an invalid
+ *    voxel is cleared, anything else becomes kHvlBaseLayer.  A multi-layered column is sorted by (absolute height, slot)
+ *    ascending, invalid voxels at +inf; the absolute height is getVoxelHeight of the slot the voxel sat in (dot(up,
+ *    centre) + double(height)).  The sorted voxels are rewritten from slot 0, each height made relative to its new
+ *    slot's centre in one float rounding, every layer kHvlExtended, invalid entries cleared.  The best base candidate
+ *    (layer kHvlBaseLayer before the sort) then becomes kHvlBaseLayer by isOtherCandidateBetter (:135-165) walked in
+ *    sorted order: first clearance > 0 or kHvfObservedAbove, then the distance of the absolute height to seed_height =
+ *    dot(up, reference_pos), strict <, so the earlier candidate wins a tie.  kLayeredFillUnordered skips L6 and L7: its
+ *    columns keep insertion order and may hold several base-layer voxels.
+ * The reference's own tests run these modes with min_clearance = -1; a negative min_clearance stays an invalid argument
+ * here and 0 builds the same heightmap (tests/test_heightmap_layered_ref.py).
+ * Results: layer_capacity dense planes of mb x ma cells, slot-major [slot][ib][ia], a fastest.  Empty slots hold +inf /
+ * zeros / 0xffffffff, as a cleared chunk does.  layer_count (nullable): slots in use per cell.  source_visit
+ * (nullable): the sequence number of the visit that added the slot's voxel.  A column that needs more slots than
+ * layer_capacity is not an error: the planes beyond the capacity are not returned and stats.layers says what a complete
+ * call needs -- visit_log_capacity's convention.  mean8, source_visit and visit_log as in the fill call.
+ * base.mode 2 or 3 builds; 0 and 1 are OHMHIP_ERR_INVALID_ARG (they have calls of their own); any other mode is
+ * OHMHIP_ERR_UNSUPPORTED; layer_capacity 0, reserved != 0, a null occupancy, voxels24 or stats OHMHIP_ERR_INVALID_ARG.
+ * Every other refusal, and how the map is observed, is the fill call's; OHMHIP_ERR_CAPACITY also for more than 255
+ * slots in one column.  One host round trip per generation, as for the fill.  Nothing of the map changes. */
+typedef struct ohmhip_heightmap_layered_params
+{
+  ohmhip_heightmap_params base;               /* base.mode: 2 kLayeredFillUnordered, 3 kLayeredFill */
+  uint32_t virtual_surface_filter_threshold;  /* Heightmap::setVirtualSurfaceFilterThreshold; 0 = off; ordered mode only */
+  uint32_t reserved;                          /* 0 */
+} ohmhip_heightmap_layered_params;
+typedef struct ohmhip_heightmap_layered_stats
+{
+  uint64_t visits;               /* keys visited, the seed included */
+  uint64_t populated;            /* adds that stood (L5) */
+  uint64_t cells;                /* columns holding >= 1 voxel at the end */
+  uint64_t voxels;               /* voxels at the end */
+  uint64_t repeats, too_close;   /* adds refused as a repeat / as too near */
+  uint64_t filtered;             /* virtual voxels removed by L6 */
+  uint64_t multi_layer_columns;  /* columns L5 noted as multi-layered (ordered mode) */
+  uint32_t layers;               /* largest slot count of any column, before removal */
+  uint32_t generations, largest_generation;
+} ohmhip_heightmap_layered_stats;
+int ohmhip_map_heightmap_layered_extents(ohmhip_map_t map, const ohmhip_heightmap_layered_params *params,
+                                         ohmhip_heightmap_extents *extents);
+int ohmhip_map_heightmap_layered(ohmhip_map_t map, const ohmhip_heightmap_layered_params *params, uint32_t layer_capacity,
+                                 float *occupancy, void *voxels24, void *mean8, uint32_t *source_visit,
+                                 uint8_t *layer_count, uint32_t *visit_log, uint64_t visit_log_capacity,
+                                 ohmhip_heightmap_layered_stats *stats);
+/* The same into DEVICE arrays; stats is a host struct.  Returns with the map's stream idle. */
+OHMHIP_EXPERIMENTAL int ohmhip_map_heightmap_layered_device(ohmhip_map_t map,
+                                                            const ohmhip_heightmap_layered_params *params,
+                                                            uint32_t layer_capacity, float *d_occupancy,
+                                                            void *d_voxels24, void *d_mean8, uint32_t *d_source_visit,
+                                                            uint8_t *d_layer_count, uint32_t *d_visit_log,
+                                                            uint64_t visit_log_capacity,
+                                                            ohmhip_heightmap_layered_stats *stats);
 
 /* POINT CLOUDS.  The voxels of the map that pass a test, as points, compacted on the device: what ohmtools::saveCloud,
  * saveDensityCloud, saveTsdfCloud and saveClearanceCloud (ohmtools/OhmCloud.cpp, driven by ohm2ply) collect on the host

@@ -14,6 +14,7 @@ from .copyutil import (canCopy, copyMap, copyFilterExtents, copyFilterDirty, cop
 from .compare import (Severity, kContinue, VoxelsResult, Tolerance, VoxelMismatch, configureTolerance,  # noqa: F401
                       compareLayoutLayer, compareVoxels, occupancy_stats, compare_maps, default_tolerances)
 from .heightmap import Heightmap, HeightmapMode, HeightmapVoxelType, UpAxis, HEIGHTMAP_VOXEL_DTYPE  # noqa: F401
+from .heightmap import LayeredHeightmap  # noqa: F401
 from .cloud import (CloudMode, VoxelCloud, GPU_KEY_DTYPE, CLOUD_CHUNK_VOXELS, cloud_params, count_cloud,  # noqa: F401
                     extract_cloud, write_ply, save_cloud, save_density_cloud, save_tsdf_cloud, save_clearance_cloud,
                     write_filtered_ply, filter_cloud, EllipsoidCloud, extract_covariance_ellipsoids, icosphere,

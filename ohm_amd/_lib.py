@@ -70,6 +70,19 @@ class HeightmapFillStats(C.Structure):
                 ("generations", C.c_uint32), ("largest_generation", C.c_uint32)]
 
 
+class HeightmapLayeredParams(C.Structure):
+    """ohmhip_heightmap_layered_params"""
+    _fields_ = [("base", HeightmapParams), ("virtual_surface_filter_threshold", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HeightmapLayeredStats(C.Structure):
+    """ohmhip_heightmap_layered_stats"""
+    _fields_ = [("visits", C.c_uint64), ("populated", C.c_uint64), ("cells", C.c_uint64), ("voxels", C.c_uint64),
+                ("repeats", C.c_uint64), ("too_close", C.c_uint64), ("filtered", C.c_uint64),
+                ("multi_layer_columns", C.c_uint64), ("layers", C.c_uint32), ("generations", C.c_uint32),
+                ("largest_generation", C.c_uint32)]
+
+
 HM_GENERATE_VIRTUAL_SURFACE, HM_PROMOTE_VIRTUAL_BELOW, HM_IGNORE_VOXEL_MEAN, HM_SURFACE_NORMALS = 1, 2, 4, 8
 
 
@@ -277,6 +290,12 @@ _sigs = {
                                             C.POINTER(HeightmapFillStats)]),
     "ohmhip_map_heightmap_fill_device": (C.c_int, [_vp, C.POINTER(HeightmapParams), _vp, _vp, _vp, _vp, _vp, C.c_uint64,
                                                    C.POINTER(HeightmapFillStats)]),
+    "ohmhip_map_heightmap_layered_extents": (C.c_int, [_vp, C.POINTER(HeightmapLayeredParams),
+                                                       C.POINTER(HeightmapExtents)]),
+    "ohmhip_map_heightmap_layered": (C.c_int, [_vp, C.POINTER(HeightmapLayeredParams), C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, C.c_uint64, C.POINTER(HeightmapLayeredStats)]),
+    "ohmhip_map_heightmap_layered_device": (C.c_int, [_vp, C.POINTER(HeightmapLayeredParams), C.c_uint32, _vp, _vp, _vp,
+                                                      _vp, _vp, _vp, C.c_uint64, C.POINTER(HeightmapLayeredStats)]),
     "ohmhip_map_cloud_count": (C.c_int, [_vp, C.POINTER(CloudParams), C.POINTER(C.c_uint64)]),
     "ohmhip_map_cloud": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "ohmhip_map_cloud_device": (C.c_int, [_vp, C.POINTER(CloudParams), C.c_uint64, _vp, _vp, _vp, _vp]),

@@ -185,7 +185,7 @@ try
     return OHMHIP_ERR_INVALID_ARG;
   }
   HeightmapArgs a;
-  return heightmapBegin(m, params, true, a, *extents);
+  return heightmapBegin(m, params, kHmBuildFill, a, *extents);
 }
 OHMHIP_ABI_CATCH
 
@@ -201,7 +201,7 @@ try
   HeightmapArgs a;
   ohmhip_heightmap_extents e;
   int seed[3];
-  OHMHIP_CHECK(heightmapBegin(m, params, true, a, e, seed));
+  OHMHIP_CHECK(heightmapBegin(m, params, kHmBuildFill, a, e, seed));
   *stats = ohmhip_heightmap_fill_stats{};
   if (!e.populated)
   {
@@ -240,7 +240,7 @@ try
   HeightmapArgs a;
   ohmhip_heightmap_extents e;
   int seed[3];
-  OHMHIP_CHECK(heightmapBegin(m, params, true, a, e, seed));
+  OHMHIP_CHECK(heightmapBegin(m, params, kHmBuildFill, a, e, seed));
   *stats = ohmhip_heightmap_fill_stats{};
   if (!e.populated)
   {

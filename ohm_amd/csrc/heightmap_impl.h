@@ -6,9 +6,17 @@
 
 namespace
 {
-/// What every heightmap entry point checks before any device work.  `fill`: the flood-fill entry points
-/// (heightmap_fill_impl.h), which build mode 1 and send mode 0 to the planar ones.
-int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p, bool fill = false)
+/// Which build an entry point belongs to: the value is the first ohm::HeightmapMode it builds.
+enum HeightmapBuild
+{
+  kHmBuildPlanar = 0,
+  kHmBuildFill = 1,    ///< heightmap_fill_impl.h
+  kHmBuildLayered = 2  ///< heightmap_layered_impl.h: modes 2 and 3
+};
+
+/// What every heightmap entry point checks before any device work.  A mode that has entry points of its own before
+/// these is an invalid argument here; any other mode the build does not cover is not supported.
+int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p, HeightmapBuild build = kHmBuildPlanar)
 {
   if (!p)
   {
@@ -25,13 +33,13 @@ int heightmapRefusal(ohmhip_map_t m, const ohmhip_heightmap_params *p, bool fill
       return OHMHIP_ERR_INVALID_ARG;
     }
   }
-  if (fill && p->mode == 0)
+  if (int(p->mode) < int(build))
   {
-    return OHMHIP_ERR_INVALID_ARG;  // planar: ohmhip_map_heightmap
+    return OHMHIP_ERR_INVALID_ARG;  // planar: ohmhip_map_heightmap; simple fill: ohmhip_map_heightmap_fill
   }
-  if (p->mode != (fill ? 1 : 0))
+  if (int(p->mode) != int(build) && !(build == kHmBuildLayered && p->mode == 3))
   {
-    return OHMHIP_ERR_UNSUPPORTED;  // the flood-fill modes here; the layered ones everywhere
+    return OHMHIP_ERR_UNSUPPORTED;
   }
   if (!m)
   {
@@ -186,12 +194,13 @@ int heightmapGeometry(ohmhip_map_t m, const ohmhip_heightmap_params *p, Heightma
   return OHMHIP_OK;
 }
 
-/// What the six entry points do after their own pointer checks: the refusal, the map settled, the geometry.
+/// What the planar and the fill entry points do after their own pointer checks: the refusal, the map settled, the
+/// geometry (the layered ones: heightmapLayeredBegin).
 /// OHMHIP_OK with e.populated == 0: nothing to build -- the caller zeroes its outputs and answers OHMHIP_OK.
-int heightmapBegin(ohmhip_map_t m, const ohmhip_heightmap_params *p, bool fill, HeightmapArgs &a,
+int heightmapBegin(ohmhip_map_t m, const ohmhip_heightmap_params *p, HeightmapBuild build, HeightmapArgs &a,
                    ohmhip_heightmap_extents &e, int *reference = nullptr)
 {
-  OHMHIP_CHECK(heightmapRefusal(m, p, fill));
+  OHMHIP_CHECK(heightmapRefusal(m, p, build));
   OHMHIP_SETTLE(m);
   return heightmapGeometry(m, p, a, e, reference);
 }
@@ -276,7 +285,7 @@ try
     return OHMHIP_ERR_INVALID_ARG;
   }
   HeightmapArgs a;
-  return heightmapBegin(m, params, false, a, *extents);
+  return heightmapBegin(m, params, kHmBuildPlanar, a, *extents);
 }
 OHMHIP_ABI_CATCH
 
@@ -290,7 +299,7 @@ try
   }
   HeightmapArgs a;
   ohmhip_heightmap_extents e;
-  OHMHIP_CHECK(heightmapBegin(m, params, false, a, e));
+  OHMHIP_CHECK(heightmapBegin(m, params, kHmBuildPlanar, a, e));
   *populated = 0;
   *cells = 0;
   if (!e.populated)
@@ -326,7 +335,7 @@ try
   }
   HeightmapArgs a;
   ohmhip_heightmap_extents e;
-  OHMHIP_CHECK(heightmapBegin(m, params, false, a, e));
+  OHMHIP_CHECK(heightmapBegin(m, params, kHmBuildPlanar, a, e));
   if (!e.populated)
   {
     return d_counts ? int(hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), m->stream)) : OHMHIP_OK;

@@ -410,6 +410,13 @@ struct ohmhip_map_s
     /// scan, sort and scan scratch, the log's device copy; the pinned word the next generation's size is read through
     DevBuf hmf_grid, hmf_queue, hmf_ground, hmf_rec_cell, hmf_keys_a, hmf_keys_b, hmf_accept, hmf_accept_at, hmf_temp, hmf_log;
     PinnedBuf<uint32_t> hmf_next;
+    /// layered heightmaps (heightmap_layered_kernels.h), beside the fill's: per key of a generation its flags and
+    /// src_height; the touched lists' heads, nodes and the two device words; per heightmap cell the slot count, the
+    /// applied stamp and the multi-layer note; the slot planes; the sorted ground keys; layer_count's device copy; the
+    /// pinned pair the next generation's size and the slots asked for are read through
+    DevBuf hml_flags, hml_height, hml_head, hml_nodes, hml_words, hml_cell_state, hml_occ, hml_vox, hml_mean, hml_visit,
+      hml_ground, hml_ground_sorted, hml_out_count;
+    PinnedBuf<uint32_t> hml_next;
     /// point clouds (cloud_kernels.h): the work list, per-wave counts and their scan; device copies of the host arrays
     DevBuf cloud_chunks, cloud_pos, cloud_keys, cloud_values;
     ScanScratch cloud_scan;

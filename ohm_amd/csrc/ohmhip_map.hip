@@ -16,6 +16,7 @@
 #include "clearance_kernels.h"
 #include "heightmap_kernels.h"
 #include "heightmap_fill_kernels.h"
+#include "heightmap_layered_kernels.h"
 #include "cloud_kernels.h"
 #include "neighbours_kernels.h"
 #include "point_filter_kernels.h"
@@ -1034,6 +1035,7 @@ OHMHIP_ABI_CATCH
 #include "clearance_update.h"
 #include "heightmap_impl.h"
 #include "heightmap_fill_impl.h"
+#include "heightmap_layered_impl.h"
 #include "cloud_impl.h"
 #include "neighbours_impl.h"
 #include "point_filter_impl.h"

@@ -1,6 +1,7 @@
 """ohm::Heightmap (ohmheightmap/Heightmap.h) in planar and simple-fill mode, built on the device from the resident map of
 a GpuMap (ohmhip_map_heightmap, ohmhip_map_heightmap_fill: include/ohmhip.h, "HEIGHTMAP").  Only the results cross to
-the host: three dense (mb, ma) arrays over the heightmap cells the source's extents cover."""
+the host: three dense (mb, ma) arrays over the heightmap cells the source's extents cover.  LayeredHeightmap builds the
+two layered modes (ohmhip_map_heightmap_layered): the same arrays with a leading slot axis."""
 import ctypes as C
 import enum
 
@@ -28,7 +29,8 @@ class HeightmapVoxelType(enum.IntEnum):
 
 
 class HeightmapMode(enum.IntEnum):
-    """ohm::HeightmapMode (ohmheightmap/HeightmapMode.h); kPlanar and kSimpleFill are built on the device."""
+    """ohm::HeightmapMode (ohmheightmap/HeightmapMode.h); Heightmap builds kPlanar and kSimpleFill, LayeredHeightmap the
+    two layered modes."""
     kPlanar = 0
     kSimpleFill = 1
     kLayeredFillUnordered = 2
@@ -225,6 +227,116 @@ class Heightmap:
         if occ == np.float32(np.inf):
             return HeightmapVoxelType.kUnknown, centre, None
         voxel = self.voxels[cb, ca]
+        n = self.up_axis_normal()
+        pos = tuple(centre[c] + n[c] * float(voxel["height"]) for c in range(3))
+        if occ == 0:
+            return HeightmapVoxelType.kVacant, pos, voxel
+        return (HeightmapVoxelType.kSurface if occ > 0 else HeightmapVoxelType.kVirtualSurface), pos, voxel
+
+
+#: HeightmapVoxelLayer (ohmheightmap/HeightmapVoxel.h:17-28)
+kHvlBaseLayer, kHvlExtended, kHvlInvalid = 0, 1, 2
+
+
+class LayeredHeightmap(Heightmap):
+    """Heightmap in HeightmapMode.kLayeredFill (the default here) or kLayeredFillUnordered: rules L1-L7 of
+    include/ohmhip.h.  After build_heightmap(): occupancy, voxels, mean and source_visit as (slots, mb, ma) arrays --
+    slot k of a column is the heightmap voxel at the cell's key moved k steps along the raw up axis, empty slots hold
+    +inf / zeros / 0xffffffff --, layer_count (mb, ma) uint8, layered_stats (the _lib.HeightmapLayeredStats of the build)
+    and, with keep_visit_log set, visit_log.  slots is at least 1 and otherwise what the tallest column needed.
+    Modes kPlanar and kSimpleFill are the parent's."""
+
+    kInitialLayerCapacity = 4
+
+    def __init__(self, grid_resolution, min_clearance, up_axis=UpAxis.kZ, region_size=0):
+        super().__init__(grid_resolution, min_clearance, up_axis, region_size)
+        self.mode = HeightmapMode.kLayeredFill
+        self._virtual_surface_filter_threshold = 0
+
+    @property
+    def virtual_surface_filter_threshold(self):
+        """Heightmap::virtualSurfaceFilterThreshold: 0 is off; applied in kLayeredFill only."""
+        return self._virtual_surface_filter_threshold
+
+    @virtual_surface_filter_threshold.setter
+    def virtual_surface_filter_threshold(self, value):
+        value = int(value)
+        if not 0 <= value <= 0xFFFFFFFF:
+            raise ValueError("virtual_surface_filter_threshold is an unsigned 32 bit count")
+        self._virtual_surface_filter_threshold = value
+
+    def _clear(self):
+        super()._clear()
+        self.layer_count = self.layered_stats = None
+
+    def layered_params(self, reference_pos, cull_to=None):
+        p = L.HeightmapLayeredParams()
+        p.base = self.params(reference_pos, cull_to)
+        p.virtual_surface_filter_threshold = self._virtual_surface_filter_threshold
+        return p
+
+    def build_heightmap(self, reference_pos, cull_to=None):
+        if self.mode not in (HeightmapMode.kLayeredFill, HeightmapMode.kLayeredFillUnordered):
+            return super().build_heightmap(reference_pos, cull_to)
+        self._clear()
+        if self._gpu_map is None:
+            return False
+        handle = self._gpu_map._handle
+        p = self.layered_params(reference_pos, cull_to)
+        e = L.HeightmapExtents()
+        L.check(L.lib.ohmhip_map_heightmap_layered_extents(handle, C.byref(p), C.byref(e)),
+                "ohmhip_map_heightmap_layered_extents")
+        self.extents = e
+        if not e.populated:
+            return False
+        plane = (int(e.mb), int(e.ma))
+        stats = L.HeightmapLayeredStats()
+        # the slots and the visits are known after the walk: what was too small is fetched by a second build
+        slots = self.kInitialLayerCapacity
+        capacity = 4 * int(e.na) * int(e.nb) if self.keep_visit_log else 0
+        while True:
+            shape = (slots,) + plane
+            occupancy = np.empty(shape, dtype=np.float32)
+            voxels = np.empty(shape, dtype=HEIGHTMAP_VOXEL_DTYPE)
+            mean = np.empty(shape + (2,), dtype=np.uint32) if e.use_mean else None
+            source_visit = np.empty(shape, dtype=np.uint32)
+            layer_count = np.empty(plane, dtype=np.uint8)
+            log = np.empty((capacity, 3), dtype=np.uint32) if capacity else None
+            L.check(L.lib.ohmhip_map_heightmap_layered(handle, C.byref(p), slots, occupancy.ctypes.data,
+                                                       voxels.ctypes.data,
+                                                       mean.ctypes.data if mean is not None else None,
+                                                       source_visit.ctypes.data, layer_count.ctypes.data,
+                                                       log.ctypes.data if log is not None else None, capacity,
+                                                       C.byref(stats)), "ohmhip_map_heightmap_layered")
+            if int(stats.layers) <= slots and (log is None or int(stats.visits) <= capacity):
+                break
+            slots = max(slots, int(stats.layers))
+            capacity = max(capacity, int(stats.visits)) if log is not None else 0
+        keep = max(1, int(stats.layers))
+        self.occupancy, self.voxels = occupancy[:keep].copy(), voxels[:keep].copy()
+        self.mean = mean[:keep].copy() if mean is not None else None
+        self.source_visit, self.layer_count = source_visit[:keep].copy(), layer_count
+        self.layered_stats = stats
+        self.visit_log = log[:int(stats.visits)].copy() if log is not None else None
+        self.populated_count = int(stats.populated)
+        self.cell_count = int(stats.cells)
+        return self.populated_count != 0
+
+    def get_heightmap_voxel_info(self, key):
+        """Heightmap::getHeightmapVoxelInfo: the key's up-axis coordinate (region * 1 + local) is the slot."""
+        if self.occupancy is None or self.occupancy.ndim != 3:
+            return super().get_heightmap_voxel_info(key)
+        cell = self.cell_of_key(key)
+        up = self.up_axis_index()
+        slot = int(key[0][up]) + int(key[1][up])
+        if cell is None or not 0 <= slot < self.occupancy.shape[0]:
+            return HeightmapVoxelType.kUnknown, None, None
+        ca, cb = cell
+        centre = self.voxel_centre(key)
+        occ = self.occupancy[slot, cb, ca]
+        if occ == np.float32(np.inf):
+            return HeightmapVoxelType.kUnknown, centre, None
+        voxel = self.voxels[slot, cb, ca]
         n = self.up_axis_normal()
         pos = tuple(centre[c] + n[c] * float(voxel["height"]) for c in range(3))
         if occ == 0:

@@ -2560,13 +2560,14 @@ struct VoxelMean
 
 /// ohm::Heightmap (ohmheightmap/Heightmap.h) in planar and simple-fill mode, built on the device from the resident map
 /// of a GpuMap (ohmhip_map_heightmap, ohmhip_map_heightmap_fill: include/ohmhip.h, "HEIGHTMAP"), equal to the CPU
-/// algorithm for every cell and field; the layered fill modes are refused (OHMHIP_ERR_UNSUPPORTED).  Only the
-/// results cross to the host: the heightmap's layers as dense arrays of heightmapCellsA() x heightmapCellsB() cells, a
-/// fastest, over the cell range the source's extents cover (extents()).
+/// algorithm for every cell and field; the layered fill modes are refused here (OHMHIP_ERR_UNSUPPORTED): they are
+/// LayeredHeightmap's.  Only the results cross to the host: the heightmap's layers as dense arrays of heightmapCellsA()
+/// x heightmapCellsB() cells, a fastest, over the cell range the source's extents cover (extents()).
 class Heightmap
 {
 public:
   static constexpr unsigned kDefaultRegionSize = 128;
+  virtual ~Heightmap() = default;
 
   Heightmap(double grid_resolution, double min_clearance, UpAxis up_axis = UpAxis::kZ, unsigned region_size = 0)
     : grid_resolution_(grid_resolution)
@@ -2614,43 +2615,15 @@ public:
   }
 
   /// Heightmap::buildHeightmap (ohmheightmap/Heightmap.cpp:335-412).  @return true when any cell was populated.
-  bool buildHeightmap(const dvec3 &reference_pos, const Aabb &cull_to = Aabb(dvec3{ 0, 0, 0 }, dvec3{ 0, 0, 0 }))
+  virtual bool buildHeightmap(const dvec3 &reference_pos,
+                              const Aabb &cull_to = Aabb(dvec3{ 0, 0, 0 }, dvec3{ 0, 0, 0 }))
   {
-    occupancy_.clear();
-    voxels_.clear();
-    mean_.clear();
-    source_visit_.clear();
-    visit_log_.clear();
-    fill_stats_ = ohmhip_heightmap_fill_stats{};
-    populated_ = cells_ = 0;
-    extents_ = ohmhip_heightmap_extents{};
+    clearResults();
     if (!gpu_map_ || !gpu_map_->gpuOk() || !gpu_map_->syncConfig())
     {
       return false;
     }
-    ohmhip_heightmap_params p{};
-    const double ref[3] = { reference_pos.x, reference_pos.y, reference_pos.z };
-    const double lo[3] = { cull_to.minExtents().x, cull_to.minExtents().y, cull_to.minExtents().z };
-    const double hi[3] = { cull_to.maxExtents().x, cull_to.maxExtents().y, cull_to.maxExtents().z };
-    const double origin[3] = { origin_.x, origin_.y, origin_.z };
-    for (int i = 0; i < 3; ++i)
-    {
-      p.reference_pos[i] = ref[i];
-      p.cull_min[i] = lo[i];
-      p.cull_max[i] = hi[i];
-      p.origin[i] = origin[i];
-    }
-    p.grid_resolution = grid_resolution_;
-    p.region_size = uint8_t(region_size_ == kDefaultRegionSize ? 0 : region_size_);
-    p.up_axis = int8_t(up_axis_);
-    p.mode = uint8_t(mode_);
-    p.floor = floor_;
-    p.ceiling = ceiling_;
-    p.min_clearance = min_clearance_;
-    p.flags = (generate_virtual_surface_ ? OHMHIP_HM_GENERATE_VIRTUAL_SURFACE : 0u) |
-              (promote_virtual_below_ ? OHMHIP_HM_PROMOTE_VIRTUAL_BELOW : 0u) |
-              (ignore_voxel_mean_ ? OHMHIP_HM_IGNORE_VOXEL_MEAN : 0u) |
-              (surface_normals_ ? OHMHIP_HM_SURFACE_NORMALS : 0u);
+    const ohmhip_heightmap_params p = params(reference_pos, cull_to);
     const bool fill = mode_ == HeightmapMode::kSimpleFill;  // the layered modes: refused by the planar call
     last_status_ = fill ? ohmhip_map_heightmap_fill_extents(gpu_map_->handle(), &p, &extents_) :
                           ohmhip_map_heightmap_extents(gpu_map_->handle(), &p, &extents_);
@@ -2682,6 +2655,35 @@ public:
     populated_ = populated;
     cells_ = cells;
     return populated != 0;
+  }
+
+  /// The settings as the C ABI takes them.
+  ohmhip_heightmap_params params(const dvec3 &reference_pos, const Aabb &cull_to) const
+  {
+    ohmhip_heightmap_params p{};
+    const double ref[3] = { reference_pos.x, reference_pos.y, reference_pos.z };
+    const double lo[3] = { cull_to.minExtents().x, cull_to.minExtents().y, cull_to.minExtents().z };
+    const double hi[3] = { cull_to.maxExtents().x, cull_to.maxExtents().y, cull_to.maxExtents().z };
+    const double origin[3] = { origin_.x, origin_.y, origin_.z };
+    for (int i = 0; i < 3; ++i)
+    {
+      p.reference_pos[i] = ref[i];
+      p.cull_min[i] = lo[i];
+      p.cull_max[i] = hi[i];
+      p.origin[i] = origin[i];
+    }
+    p.grid_resolution = grid_resolution_;
+    p.region_size = uint8_t(region_size_ == kDefaultRegionSize ? 0 : region_size_);
+    p.up_axis = int8_t(up_axis_);
+    p.mode = uint8_t(mode_);
+    p.floor = floor_;
+    p.ceiling = ceiling_;
+    p.min_clearance = min_clearance_;
+    p.flags = (generate_virtual_surface_ ? OHMHIP_HM_GENERATE_VIRTUAL_SURFACE : 0u) |
+              (promote_virtual_below_ ? OHMHIP_HM_PROMOTE_VIRTUAL_BELOW : 0u) |
+              (ignore_voxel_mean_ ? OHMHIP_HM_IGNORE_VOXEL_MEAN : 0u) |
+              (surface_normals_ ? OHMHIP_HM_SURFACE_NORMALS : 0u);
+    return p;
   }
 
   int lastStatus() const { return last_status_; }
@@ -2723,7 +2725,16 @@ public:
   }
 
   /// Heightmap::getHeightmapVoxelInfo (ohmheightmap/Heightmap.cpp:415-461) for a key of the heightmap.
-  HeightmapVoxelType getHeightmapVoxelInfo(const Key &key, dvec3 *pos, HeightmapVoxel *voxel_info = nullptr) const
+  virtual HeightmapVoxelType getHeightmapVoxelInfo(const Key &key, dvec3 *pos,
+                                                   HeightmapVoxel *voxel_info = nullptr) const
+  {
+    return voxelInfoAt(key, 0, pos, voxel_info);
+  }
+
+protected:
+  /// getHeightmapVoxelInfo for the voxel `slot` steps up the raw up axis from the key's cell: plane `slot` of the
+  /// arrays (0 in every mode but the layered ones).
+  HeightmapVoxelType voxelInfoAt(const Key &key, size_t slot, dvec3 *pos, HeightmapVoxel *voxel_info) const
   {
     if (!extents_.populated || occupancy_.empty())
     {
@@ -2736,11 +2747,16 @@ public:
     {
       return HeightmapVoxelType::kUnknown;
     }
+    const size_t plane = size_t(extents_.ma) * size_t(extents_.mb);
+    if ((slot + 1) * plane > occupancy_.size())
+    {
+      return HeightmapVoxelType::kUnknown;
+    }
     Key flat = key;
-    flat.region[upAxisIndex()] = 0;
+    flat.region[upAxisIndex()] = int16_t(slot);
     flat.local[upAxisIndex()] = 0;
     const dvec3 centre = voxelCentreGlobal(flat);
-    const size_t cell = size_t(cb) * extents_.ma + size_t(ca);
+    const size_t cell = slot * plane + size_t(cb) * extents_.ma + size_t(ca);
     const float occupancy = occupancy_[cell];
     if (pos)
     {
@@ -2768,7 +2784,18 @@ public:
     return occupancy > 0 ? HeightmapVoxelType::kSurface : HeightmapVoxelType::kVirtualSurface;
   }
 
-private:
+  void clearResults()
+  {
+    occupancy_.clear();
+    voxels_.clear();
+    mean_.clear();
+    source_visit_.clear();
+    visit_log_.clear();
+    fill_stats_ = ohmhip_heightmap_fill_stats{};
+    populated_ = cells_ = 0;
+    extents_ = ohmhip_heightmap_extents{};
+  }
+
   /// ohmhip_map_heightmap_fill into the arrays sized by buildHeightmap.  The number of visits is known after the walk:
   /// a log too small for it is fetched by a second build.
   bool buildFill(const ohmhip_heightmap_params &p, size_t n)
@@ -2821,6 +2848,116 @@ private:
   bool keep_visit_log_ = false;
   uint64_t populated_ = 0, cells_ = 0;
   int last_status_ = OHMHIP_OK;
+};
+
+/// ohm::Heightmap in HeightmapMode::kLayeredFill (the default here) and kLayeredFillUnordered, built on the device
+/// (ohmhip_map_heightmap_layered: include/ohmhip.h, "HEIGHTMAP, LAYERED", rules L1-L7).  The arrays of the parent gain a
+/// leading slot axis: layerSlots() planes of heightmapCellsB() x heightmapCellsA() cells, slot k of a column the
+/// heightmap voxel at the cell's key moved k steps along the raw up axis; empty slots hold +inf / zeros / 0xffffffff.
+/// kPlanar and kSimpleFill are the parent's builds.
+class LayeredHeightmap : public Heightmap
+{
+public:
+  static constexpr uint32_t kInitialLayerCapacity = 4;
+
+  LayeredHeightmap(double grid_resolution, double min_clearance, UpAxis up_axis = UpAxis::kZ, unsigned region_size = 0)
+    : Heightmap(grid_resolution, min_clearance, up_axis, region_size)
+  {
+    setMode(HeightmapMode::kLayeredFill);
+  }
+
+  /// Heightmap::setVirtualSurfaceFilterThreshold: 0 is off; applied in kLayeredFill only.
+  void setVirtualSurfaceFilterThreshold(unsigned threshold) { filter_threshold_ = threshold; }
+  unsigned virtualSurfaceFilterThreshold() const { return filter_threshold_; }
+
+  bool buildHeightmap(const dvec3 &reference_pos,
+                      const Aabb &cull_to = Aabb(dvec3{ 0, 0, 0 }, dvec3{ 0, 0, 0 })) override
+  {
+    if (mode() != HeightmapMode::kLayeredFill && mode() != HeightmapMode::kLayeredFillUnordered)
+    {
+      layer_count_.clear();
+      layered_stats_ = ohmhip_heightmap_layered_stats{};
+      return Heightmap::buildHeightmap(reference_pos, cull_to);
+    }
+    clearResults();
+    layer_count_.clear();
+    layered_stats_ = ohmhip_heightmap_layered_stats{};
+    if (!gpu_map_ || !gpu_map_->gpuOk() || !gpu_map_->syncConfig())
+    {
+      return false;
+    }
+    ohmhip_heightmap_layered_params p{};
+    p.base = params(reference_pos, cull_to);
+    p.virtual_surface_filter_threshold = filter_threshold_;
+    last_status_ = ohmhip_map_heightmap_layered_extents(gpu_map_->handle(), &p, &extents_);
+    if (last_status_ != OHMHIP_OK || !extents_.populated)
+    {
+      return false;
+    }
+    const size_t plane = size_t(extents_.ma) * size_t(extents_.mb);
+    layer_count_.resize(plane);
+    // the slots and the visits are known after the walk: what was too small is fetched by a second build
+    uint32_t slots = kInitialLayerCapacity;
+    uint64_t capacity = keep_visit_log_ ? 4ull * extents_.na * extents_.nb : 0;
+    for (;;)
+    {
+      occupancy_.resize(slots * plane);
+      voxels_.resize(slots * plane);
+      mean_.resize(extents_.use_mean ? slots * plane : 0);
+      source_visit_.resize(slots * plane);
+      visit_log_.resize(size_t(3 * capacity));
+      last_status_ = ohmhip_map_heightmap_layered(gpu_map_->handle(), &p, slots, occupancy_.data(), voxels_.data(),
+                                                  extents_.use_mean ? mean_.data() : nullptr, source_visit_.data(),
+                                                  layer_count_.data(), capacity ? visit_log_.data() : nullptr,
+                                                  capacity, &layered_stats_);
+      if (last_status_ != OHMHIP_OK)
+      {
+        clearResults();
+        layer_count_.clear();
+        return false;
+      }
+      if (layered_stats_.layers <= slots && (!capacity || layered_stats_.visits <= capacity))
+      {
+        break;
+      }
+      slots = std::max(slots, layered_stats_.layers);
+      capacity = capacity ? std::max(capacity, layered_stats_.visits) : 0;
+    }
+    slots_ = std::max<uint32_t>(1u, layered_stats_.layers);
+    occupancy_.resize(slots_ * plane);
+    voxels_.resize(slots_ * plane);
+    mean_.resize(extents_.use_mean ? slots_ * plane : 0);
+    source_visit_.resize(slots_ * plane);
+    visit_log_.resize(capacity ? size_t(3 * layered_stats_.visits) : 0);
+    populated_ = layered_stats_.populated;
+    cells_ = layered_stats_.cells;
+    return populated_ != 0;
+  }
+
+  /// Planes of the result arrays after a layered build: at least 1, else what the tallest column needed.
+  uint32_t layerSlots() const { return slots_; }
+  /// Slots in use per cell.
+  const std::vector<uint8_t> &layerCounts() const { return layer_count_; }
+  const ohmhip_heightmap_layered_stats &layeredStats() const { return layered_stats_; }
+
+  /// The key's up-axis coordinate is the slot.
+  HeightmapVoxelType getHeightmapVoxelInfo(const Key &key, dvec3 *pos,
+                                           HeightmapVoxel *voxel_info = nullptr) const override
+  {
+    const long slot = long(key.region[upAxisIndex()]) + long(key.local[upAxisIndex()]);
+    const bool layered = mode() == HeightmapMode::kLayeredFill || mode() == HeightmapMode::kLayeredFillUnordered;
+    if (layered && slot < 0)
+    {
+      return HeightmapVoxelType::kUnknown;
+    }
+    return voxelInfoAt(key, layered ? size_t(slot) : 0, pos, voxel_info);
+  }
+
+private:
+  unsigned filter_threshold_ = 0;
+  uint32_t slots_ = 0;
+  std::vector<uint8_t> layer_count_;
+  ohmhip_heightmap_layered_stats layered_stats_{};
 };
 
 /// What a point cloud is made of (include/ohmhip.h, "POINT CLOUDS").

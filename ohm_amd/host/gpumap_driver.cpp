@@ -593,6 +593,85 @@ int modeHeightmapFill(const Args &args)
   return kOk;
 }
 
+/// heightmaplayered: ohm::LayeredHeightmap over a map whose voxels are written directly; <rays.bin> is a scene file
+/// (<batch_rays> is not used).  in: heightmapfill's header, then u32 mode (2, 3) and u32 virtual-surface filter
+/// threshold before the u64 region count and the regions.  out: u32 ma, u32 mb, u32 slots, u32 0, the
+/// ohmhip_heightmap_layered_stats, u64 surface and u64 virtual voxels as getHeightmapVoxelInfo names them over every
+/// slot, then the occupancy, HeightmapVoxel and source visit planes, the layer counts and the log.
+int modeHeightmapLayered(const Args &args)
+{
+  InFile in(args.input);
+  const std::vector<int32_t> dims = in.array<int32_t>(3);
+  const std::vector<double> numbers = in.array<double>(6);
+  const int32_t up_axis = in.value<int32_t>();
+  const uint32_t flags = in.value<uint32_t>();
+  const uint32_t mode = in.value<uint32_t>();
+  const uint32_t threshold = in.value<uint32_t>();
+  const uint64_t regions = in.value<uint64_t>();
+  ohm::OccupancyMap source_map(args.resolution, dims[0], dims[1], dims[2]);
+  for (uint64_t i = 0; i < regions; ++i)
+  {
+    const auto key = in.value<std::array<int16_t, 3>>();
+    std::vector<uint8_t> &block = source_map.region(key).voxel_blocks[OHMHIP_LID_OCCUPANCY];
+    block.resize(sizeof(float) * source_map.regionVoxelVolume());
+    in.bytes(block.data(), block.size());
+  }
+  ohm::GpuMap gpu_map(&source_map, true);
+  gpu_map.uploadRegions(nullptr, 0);
+  ohm::LayeredHeightmap layered(args.resolution, numbers[5], ohm::UpAxis(up_axis));
+  check(layered.mode() == ohm::HeightmapMode::kLayeredFill, kUnexpected);
+  layered.setMode(ohm::HeightmapMode(mode));
+  layered.setVirtualSurfaceFilterThreshold(threshold);
+  ohm::Heightmap &heightmap = layered;  // built through the base class
+  heightmap.setOccupancyMap(&gpu_map);
+  heightmap.setFloor(numbers[3]);
+  heightmap.setCeiling(numbers[4]);
+  heightmap.setGenerateVirtualSurface((flags & 1u) != 0);
+  heightmap.setPromoteVirtualBelow((flags & 2u) != 0);
+  heightmap.setKeepVisitLog(true);
+  const ohm::dvec3 reference{ numbers[0], numbers[1], numbers[2] };
+  check(heightmap.buildHeightmap(reference), kFailedCall);
+  uint64_t types[2] = { 0, 0 };
+  const ohmhip_heightmap_extents &e = heightmap.extents();
+  const int axis_a = heightmap.surfaceAxisIndexA(), axis_b = heightmap.surfaceAxisIndexB();
+  const long region_size = long(ohm::Heightmap::kDefaultRegionSize);
+  for (uint32_t slot = 0; slot <= layered.layerSlots(); ++slot)  // one past the last plane: kUnknown
+  {
+    for (uint32_t cb = 0; cb < e.mb; ++cb)
+    {
+      for (uint32_t ca = 0; ca < e.ma; ++ca)
+      {
+        ohm::Key key{};
+        const long ga = long(e.first_region[0]) * region_size + e.first_local[0] + long(ca);
+        const long gb = long(e.first_region[1]) * region_size + e.first_local[1] + long(cb);
+        key.region[axis_a] = int16_t(ga >= 0 ? ga / region_size : -((-ga + region_size - 1) / region_size));
+        key.local[axis_a] = uint8_t(ga - long(key.region[axis_a]) * region_size);
+        key.region[axis_b] = int16_t(gb >= 0 ? gb / region_size : -((-gb + region_size - 1) / region_size));
+        key.local[axis_b] = uint8_t(gb - long(key.region[axis_b]) * region_size);
+        key.region[heightmap.upAxisIndex()] = int16_t(slot);
+        ohm::dvec3 pos{};
+        const ohm::HeightmapVoxelType type = heightmap.getHeightmapVoxelInfo(key, &pos);
+        check(slot < layered.layerSlots() || type == ohm::HeightmapVoxelType::kUnknown, kUnexpected);
+        types[0] += type == ohm::HeightmapVoxelType::kSurface;
+        types[1] += type == ohm::HeightmapVoxelType::kVirtualSurface;
+      }
+    }
+  }
+  OutFile out(args.output);
+  out.value(uint32_t(heightmap.heightmapCellsA()));
+  out.value(uint32_t(heightmap.heightmapCellsB()));
+  out.value(uint32_t(layered.layerSlots()));
+  out.value(uint32_t(0));
+  out.value(layered.layeredStats());
+  out.value(types);
+  out.array(heightmap.occupancy());
+  out.array(heightmap.heightmapVoxels());
+  out.array(heightmap.sourceVisits());
+  out.array(layered.layerCounts());
+  out.array(heightmap.visitLog());
+  return kOk;
+}
+
 /// heightmap [min clearance] [flags: bit 0 turns virtual surfaces on]: ohm::Heightmap over a map with occupancy + mean.
 /// Reference position (0, 0, 0), +Z up, grid resolution = the map's.  out: u32 ma, u32 mb, u64 populated, u64 cells, u8
 /// has mean, then the occupancy, HeightmapVoxel and (if any) VoxelMean arrays.
@@ -1155,6 +1234,7 @@ const Mode kModes[] = {
   { "clearanceupdate", &modeClearanceUpdate, true },
   { "heightmap", &modeHeightmap, true },
   { "heightmapfill", &modeHeightmapFill, true },
+  { "heightmaplayered", &modeHeightmapLayered, true },
   { "cloud", &modeCloud, true },
   { "neighbours", &modeNeighbours, true },
   { "voxels", &modeVoxels, true },
