@@ -123,6 +123,47 @@ __device__ inline float occMissN(const MapConst &mc, unsigned ray_flags, float x
   return x;
 }
 
+/// The constants of a miss, by value: what a function that is not inlined into its kernel is handed in registers.
+struct MissConst
+{
+  float miss_value, min_value, sat_min, sat_max;
+};
+
+/// occMissN() for a batch without exclusion flags, written for a whole wave: the walk's lean direct apply calls it for
+/// every lane of a tile word, whatever the lane's n.  The first application is occMissN()'s plain path without its
+/// branches (same operations, same order: bit identical); the repeat loop -- only voxels that are not yet at the clamp
+/// need it -- is entered when some lane of the wave has n > 1 and a value the first miss moved.  n == 0 returns x itself,
+/// bit for bit, so the caller's sameValue() write guard also covers "nothing to apply".
+__device__ inline float occMissNPlainWave(const MissConst mc, float x, uint32_t n)
+{
+  const bool unobserved = x == fInf();
+  const float base = unobserved ? 0.0f : x;
+  // (& and |: the compiler turns && and || into branches around the comparisons)
+  const bool first_moves = unobserved | ((mc.sat_min < x) & (x < mc.sat_max));
+  const float first_adj = first_moves ? mc.miss_value : 0.0f;
+  float nx = fmaxf(mc.min_value, base + first_adj);
+  const bool repeat = (n > 1u) & !(nx == x);
+  if (__ballot(repeat))
+  {
+    if (repeat)
+    {
+      float cur = nx;
+      for (uint32_t k = 1; k < n; ++k)
+      {
+        const float adj = (mc.sat_min < cur && cur < mc.sat_max) ? mc.miss_value : 0.0f;
+        nx = fmaxf(mc.min_value, cur + adj);
+        const bool fixed = nx == cur;
+        cur = nx;
+        if (fixed)
+        {
+          break;
+        }
+      }
+    }
+  }
+  return n ? nx : x;
+}
+
 /// ohm/VoxelMeanCompute.h:134-152 with Vec3 = dvec3, coord_real = double (as the CPU mappers instantiate it).
 __device__ inline uint32_t subVoxelUpdate(uint32_t coord, uint32_t point_count, const double v[3], double resolution)
 {

@@ -7,12 +7,15 @@
 //
 // k_region_walk is register bound and fragile.  Cross-compiled for gfx950 at -O3, its six instantiations sit at
 // 128 VGPRs and spill (VGPR spills / scratch bytes; <kSpecial, kTrace, geometry>):
-//   <0,0,Full> 37 / 148   <0,0,Half> 43 / 148   <1,0,Full> 38 / 152   <1,0,Half> 45 / 152
-//   <0,1,Full> 45 / 156   <0,1,Half> 56 / 156
+//   <0,0,Full> 36 / 128   <0,0,Half> 40 / 144   <1,0,Full> 37 / 128   <1,0,Half> 41 / 144
+//   <0,1,Full> 38 / 128   <0,1,Half> 51 / 144
+// (37 / 148, 43 / 148, 38 / 152, 45 / 152, 45 / 156, 56 / 156 before round 14.)
 // Moving the prologue's count-tile initialisation loop, unchanged, into a __device__ inline function took the production
 // <0,0,Full> instantiation from 37 to 90 spilled VGPRs.  So the body of the kernel is left as one piece of text, and ANY
 // edit to it, or to a function it inlines, is checked with scripts/kernel_fingerprint.py against the parent commit
-// before it goes near a GPU: the figures above must not get worse.
+// before it goes near a GPU: the figures above must not get worse.  Code that is new to the kernel and runs once per
+// chunk goes into a __noinline__ function (scanOrderBins, applyFullTile, flushFullTile below): written into the body,
+// the three of round 14 gave 98 spilled VGPRs, the ordering's scan alone 51 (profiles/r14_notes.md).
 #ifndef OHMHIP_WALK_KERNEL_H
 #define OHMHIP_WALK_KERNEL_H
 
@@ -55,6 +58,10 @@ constexpr uint32_t kMaxChunkSegments = OHMHIP_MAX_CHUNK_SEGMENTS;  ///< bounded 
 constexpr uint32_t kTraceChunks = 4096;  ///< debug trace: records kept per launch
 constexpr uint32_t kTraceWords = 32;     ///< debug trace: u64 words per record
 constexpr uint32_t kLengthClasses = 128;      ///< segment length histogram bins (lengths above the last bin share it)
+/// Copies of every length class's counter, chosen by lane index: the segments of a chunk fall into a few dozen classes,
+/// and the lanes of a wave that add to ONE counter are served one after the other.
+constexpr uint32_t kOrderCopies = 8;
+constexpr uint32_t kOrderBins = kLengthClasses * kOrderCopies;
 
 /// Physical position of the count tile's logical word `w` (two voxels per word, voxel order).  A word's LDS bank is its
 /// index modulo 32, which in voxel order is (x / 2, y & 1): lanes whose rays advance in step through a region -- a
@@ -317,6 +324,199 @@ struct WalkGeometry
 };
 using WalkFull = WalkGeometry<kWalkThreads, 1 << kHitVoxelBits, kLdsHits, kMaxChunkSegments, kQueueCap, 1>;
 using WalkHalf = WalkGeometry<kWalkThreads / 2, (1 << kHitVoxelBits) / 2, kLdsHits / 2, kMaxChunkSegments / 2, 96, 4>;
+/// The parts of a chunk's fixed cost that are written for the common shape -- a region that fills the tile -- live in
+/// functions of their own which the kernel CALLS: inlined, each of them took the kernel's register allocation from 37
+/// spilled VGPRs to 50 .. 120 (see the head of this file), and a call per chunk costs a few hundred cycles.  They reach
+/// LDS through pointers that keep its address space, and make their wave-uniform arguments scalar again, which the
+/// calling convention hands over in vector registers.
+using LdsWord = __attribute__((address_space(3))) uint32_t;
+using GlobalWord = __attribute__((address_space(1))) uint32_t;
+using GlobalByte = __attribute__((address_space(1))) char;
+using GlobalFloat = __attribute__((address_space(1))) float;
+// (the compiler's own vector types: float2 / uint4 are classes whose assignment wants the generic address space)
+typedef float Float2 __attribute__((ext_vector_type(2)));
+typedef uint32_t Quad __attribute__((ext_vector_type(4)));
+using GlobalFloat2 = __attribute__((address_space(1))) Float2;
+using LdsQuad = __attribute__((address_space(3))) Quad;
+
+/// atomicAdd(), result unused, on a pointer that says it is global memory.
+__device__ inline void addGlobal(GlobalWord *address, uint32_t value)
+{
+  __hip_atomic_fetch_add(address, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <typename T>
+__device__ inline T *uniformPointer(T *p)
+{
+  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(v));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(v >> 32));
+  return reinterpret_cast<T *>(((unsigned long long)hi << 32) | lo);
+}
+
+__device__ inline float uniformFloat(float v)
+{
+  return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
+}
+
+/// Exclusive scan over the segment ordering's counters (one wave): lane l owns kOrderBins / 64 consecutive ones.
+__device__ __noinline__ void scanOrderBins(LdsWord *bins, uint32_t lane)
+{
+  constexpr uint32_t kQuads = kOrderBins / 256u;
+  LdsQuad *mine = reinterpret_cast<LdsQuad *>(bins) + lane * kQuads;
+  Quad c[kQuads];
+  uint32_t total = 0;
+#pragma unroll
+  for (uint32_t q = 0; q < kQuads; ++q)
+  {
+    c[q] = mine[q];
+    total += c[q].x + c[q].y + c[q].z + c[q].w;
+  }
+  uint32_t incl = total;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1)
+  {
+    const uint32_t up = __shfl_up(incl, d);
+    incl += (int(lane) >= d) ? up : 0u;
+  }
+  uint32_t run = incl - total;
+#pragma unroll
+  for (uint32_t q = 0; q < kQuads; ++q)
+  {
+    Quad e;
+    e.x = run;
+    e.y = e.x + c[q].x;
+    e.z = e.y + c[q].y;
+    e.w = e.z + c[q].z;
+    run = e.w + c[q].w;
+    mine[q] = e;
+  }
+}
+
+/// The direct apply of a single-chunk region in the common case: a plain occupancy batch without exclusion flags on a
+/// region that fills the tile (an even voxel count, every thread's words exist).  The passes are bound by instruction
+/// issue -- 16 waves run their whole instruction stream whichever lanes need it -- and the general form in the kernel
+/// spends most of its stream on conditions that are the same for every word.  Same loads, same arithmetic, same stores.
+/// `g_counts`: where voxels which also receive samples hand their count to k_apply_hits; null when the kernel replays
+/// the samples itself.  `stamps`: null, or the trace record's two words for the ends of the passes.
+template <typename G>
+__device__ __noinline__ void applyFullTile(const LdsWord *tile, float *occupancy, uint32_t *g_counts, MissConst mc,
+                                           unsigned long long *stamps)
+{
+  constexpr uint32_t kWordsPerThread = uint32_t(G::kTileVoxels) / 2u / uint32_t(G::kThreads) / 2u;
+  // (byte offsets from the region's first voxel: a word's two voxels are one float2)
+  GlobalByte *occ_bytes = (GlobalByte *)uniformPointer(occupancy);
+  GlobalWord *counts = (GlobalWord *)uniformPointer(g_counts);
+  stamps = uniformPointer(stamps);
+  mc.miss_value = uniformFloat(mc.miss_value);
+  mc.min_value = uniformFloat(mc.min_value);
+  mc.sat_min = uniformFloat(mc.sat_min);
+  mc.sat_max = uniformFloat(mc.sat_max);
+  for (uint32_t half = 0; half < 2u; ++half)
+  {
+    const uint32_t first = threadIdx.x + half * kWordsPerThread * uint32_t(G::kThreads);
+    uint32_t words[kWordsPerThread];
+    Float2 values[kWordsPerThread];
+    // The LDS reads of the pass in one burst, one wait.
+#pragma unroll
+    for (uint32_t j = 0; j < kWordsPerThread; ++j)
+    {
+      words[j] = tile[tileWord(first + j * uint32_t(G::kThreads))];
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kWordsPerThread; ++j)
+    {
+      const uint32_t i = first + j * uint32_t(G::kThreads);
+      // 0xffff over every entry whose voxel also receives samples: those keep their count for the ordered replay
+      // (k_apply_hits, or the kernel's own); the others are applied here.
+      const uint32_t sampled = ((words[j] >> 15) & 0x00010001u) * 0xffffu;
+      const uint32_t kept = words[j] & sampled & (kTileCountMask | (kTileCountMask << 16));
+      words[j] &= ~sampled;
+      if (counts && __ballot(kept != 0u))
+      {
+        if (kept & 0xffffu)
+        {
+          addGlobal(&counts[2 * i], kept & 0xffffu);
+        }
+        if (kept >> 16)
+        {
+          addGlobal(&counts[2 * i + 1], kept >> 16);
+        }
+      }
+      values[j] = Float2(0.0f);
+      if (words[j])
+      {
+        values[j] = *(const GlobalFloat2 *)(occ_bytes + i * 8u);
+      }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kWordsPerThread; ++j)
+    {
+      const uint32_t i = first + j * uint32_t(G::kThreads);
+      if (__ballot(words[j] != 0u))
+      {
+        // (a voxel at its clamp -- most of a settled map's free space -- does not move: nothing to write; neither does
+        // one without a count, which gets its own value back)
+        const float v0 = occMissNPlainWave(mc, values[j].x, words[j] & 0xffffu);
+        if (!sameValue(v0, values[j].x))
+        {
+          *(GlobalFloat *)(occ_bytes + i * 8u) = v0;
+        }
+        const float v1 = occMissNPlainWave(mc, values[j].y, words[j] >> 16);
+        if (!sameValue(v1, values[j].y))
+        {
+          *(GlobalFloat *)(occ_bytes + i * 8u + 4u) = v1;
+        }
+      }
+    }
+    if (stamps && threadIdx.x == 0)
+    {
+      stamps[half] = wall_clock64();
+    }
+  }
+}
+
+/// The tile flush of a multi-chunk region that fills the tile: every thread's words exist, so their LDS reads go out in
+/// bursts with one wait each, and a word in which no lane of the wave holds a count is passed over on the wave's ballot.
+/// `skip_masked` (NDT / TSDF): entries of masked voxels are not flushed.
+template <typename G>
+__device__ __noinline__ void flushFullTile(const LdsWord *tile, uint32_t *g_counts, uint32_t skip_masked)
+{
+  constexpr uint32_t kBurst = 8;
+  constexpr uint32_t kWords = uint32_t(G::kTileVoxels) / 2u / uint32_t(G::kThreads);
+  static_assert(kWords % kBurst == 0u, "the tile flush reads whole bursts");
+  GlobalWord *counts = (GlobalWord *)uniformPointer(g_counts);
+  skip_masked = __builtin_amdgcn_readfirstlane(skip_masked);
+  for (uint32_t burst = 0; burst < kWords / kBurst; ++burst)
+  {
+    const uint32_t first = threadIdx.x + burst * kBurst * uint32_t(G::kThreads);
+    uint32_t words[kBurst];
+#pragma unroll
+    for (uint32_t j = 0; j < kBurst; ++j)
+    {
+      words[j] = tile[tileWord(first + j * uint32_t(G::kThreads))];
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kBurst; ++j)
+    {
+      const uint32_t i = first + j * uint32_t(G::kThreads);
+      const uint32_t masked = skip_masked ? ((words[j] >> 15) & 0x00010001u) * 0xffffu : 0u;
+      const uint32_t n = words[j] & ~masked & (kTileCountMask | (kTileCountMask << 16));
+      if (__ballot(n != 0u))
+      {
+        if (n & 0xffffu)
+        {
+          addGlobal(&counts[2 * i], n & 0xffffu);
+        }
+        if (n >> 16)
+        {
+          addGlobal(&counts[2 * i + 1], n >> 16);
+        }
+      }
+    }
+  }
+}
+
 /// kSpecial: the batch contains rays whose end voxel is part of the walk (clipped / kRfEndPointAsFree / TSDF) or
 /// kRfExcludeOrigin.  The common case (kSpecial == false) keeps those predicates out of the hot loop: every iteration
 /// of an active lane is a miss.
@@ -328,8 +528,8 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const MapConst &mc = args.mc;
   // Layout: [count tile: ceil(region_voxels / 2) words][queues][staged sample keys][interval counters][cursor]
-  // [length histogram][segment order: u16 per segment].  The tile sits at offset 0 so the per-visit atomic needs no
-  // base add.
+  // [kLengthClasses reserved words][idle words][bucket index][segment order: u16 per segment].  The tile sits at
+  // offset 0 so the per-visit atomic needs no base add.
   const uint32_t count_words = uint32_t(mc.region_voxels + 1) >> 1;
   const uint32_t mask_words = uint32_t(mc.region_voxels + 31) >> 5;
   uint32_t *l_counts = lds;
@@ -339,10 +539,15 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
   // l_cursor[0]: segment cursor, [1]: a fetched chunk's index, [2..5]: its record, [6..7]: its samples, [8..9]: its
   // region key; [12..21]: a second record (start-up only)
   uint32_t *l_cursor = l_intervals + G::kLdsHits / 2;
-  uint32_t *l_hist = l_cursor + kWalkCursorWords;
-  uint32_t *l_idle = l_hist + kLengthClasses;  // [64] scratch words: where a lane with nothing to visit aims its LDS add
+  // (kLengthClasses words behind the cursor are reserved and unused: the class counters live in l_bins)
+  uint32_t *l_idle = l_cursor + kWalkCursorWords + kLengthClasses;  // [64] scratch words: where a lane with nothing to visit aims its LDS add
   uint16_t *l_index = reinterpret_cast<uint16_t *>(l_idle + 64);  // [kIndexBuckets + 2] first staged sample per bucket
   uint16_t *l_order = l_index + kIndexBuckets + 2;
+  // The segment ordering's counters, [kLengthClasses descending][kOrderCopies], share the queues' words: no wave touches
+  // its queue between the barrier behind a chunk's final queue flush and the barrier in front of the next walk loop.
+  uint32_t *l_bins = reinterpret_cast<uint32_t *>(l_queues);
+  static_assert(kOrderBins <= 2u * uint32_t(G::kWaves) * uint32_t(G::kQueueCap), "the class counters alias the queues");
+  static_assert(kOrderBins % 256u == 0u, "the scan gives each of 64 lanes whole uint4s");
 
   // Persistent workgroups: the launch has one workgroup per CU and each takes chunks from a device-wide cursor until
   // none are left.  A static blockIdx -> chunk binding leaves the hardware's round-robin of workgroups over the 8 XCDs
@@ -474,15 +679,16 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
     }
     const uint32_t *g_mask = args.hit_mask + size_t(chunk.slot) * mask_words;
     const uint32_t my_mask = pf_mask;
-    uint32_t lens[kSegPerThread];
+    uint32_t bins[kSegPerThread];  // the segment's counter: its length class, longest first, and the lane's copy
 #pragma unroll
     for (int j = 0; j < kSegPerThread; ++j)
     {
-      lens[j] = min(pf_vox[j] >> kSegVoxelBits, kLengthClasses - 1u);
+      bins[j] = (kLengthClasses - 1u - min(pf_vox[j] >> kSegVoxelBits, kLengthClasses - 1u)) * kOrderCopies +
+                (threadIdx.x & (kOrderCopies - 1u));
     }
-    if (threadIdx.x < kLengthClasses)
+    for (uint32_t b = threadIdx.x; b < kOrderBins; b += uint32_t(G::kThreads))
     {
-      l_hist[threadIdx.x] = 0;
+      l_bins[b] = 0;
     }
     if (threadIdx.x == 0)
     {
@@ -547,12 +753,14 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
     // Longest segments first (counting sort on the voxel count, indices in LDS): lanes refilled together get segments
     // of similar length and so retire together, and the workgroup drains on its SHORTEST segments instead of waiting
     // for a few long stragglers.  The order inside a length class is arbitrary; integer counting does not care.
+    // Every class has kOrderCopies counters and a lane adds to the copy of its own index, in the count and in the
+    // placement alike, so at most 64 / kOrderCopies lanes of a wave meet on one address.
 #pragma unroll
     for (int j = 0; j < kSegPerThread; ++j)
     {
       if (threadIdx.x + uint32_t(j) * uint32_t(G::kThreads) < n_seg)
       {
-        atomicAdd(&l_hist[lens[j]], 1u);
+        atomicAdd(&l_bins[bins[j]], 1u);
       }
     }
     if (lds_resolve && n_region_hits)
@@ -606,20 +814,8 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
     }
     if (threadIdx.x < 64)
     {
-      // Exclusive scan over the classes in DESCENDING length order: lane l owns classes 127 - 2l and 126 - 2l.
-      const uint32_t hi_class = kLengthClasses - 1u - 2u * threadIdx.x;
-      const uint32_t a = l_hist[hi_class];
-      const uint32_t b = l_hist[hi_class - 1u];
-      uint32_t incl = a + b;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1)
-      {
-        const uint32_t up = __shfl_up(incl, d);
-        incl += (int(threadIdx.x) >= d) ? up : 0u;
-      }
-      const uint32_t excl = incl - (a + b);
-      l_hist[hi_class] = excl;
-      l_hist[hi_class - 1u] = excl + a;
+      // Exclusive scan over the counters, which lie in DESCENDING length order: longest first.
+      scanOrderBins((LdsWord *)l_bins, threadIdx.x);
     }
     __syncthreads();
 #pragma unroll
@@ -628,7 +824,7 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
       const uint32_t i = threadIdx.x + uint32_t(j) * uint32_t(G::kThreads);
       if (i < n_seg)
       {
-        l_order[atomicAdd(&l_hist[lens[j]], 1u)] = uint16_t(i);
+        l_order[atomicAdd(&l_bins[bins[j]], 1u)] = uint16_t(i);
       }
     }
     __syncthreads();
@@ -937,6 +1133,19 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
       // in two halves, which keeps the kernel's register peak below the walk loop's budget.
       constexpr uint32_t kWordsPerThread = uint32_t(G::kTileVoxels) / 2u / uint32_t(G::kThreads) / 2u;
       const bool even_voxels = (mc.region_voxels & 1) == 0;
+      // The common case has a body of its own (applyFullTile).
+      constexpr unsigned kExcludeFlags =
+        OHMHIP_RF_EXCLUDE_UNOBSERVED | OHMHIP_RF_EXCLUDE_FREE | OHMHIP_RF_EXCLUDE_OCCUPIED;
+      if (!defer_all && !(args.ray_flags & kExcludeFlags) && mc.region_voxels == G::kTileVoxels)
+      {
+        const MissConst miss = { mc.miss_value, mc.min_value, mc.sat_min, mc.sat_max };
+        applyFullTile<G>((const LdsWord *)l_counts, g_occ, inline_hits ? nullptr : g_counts, miss,
+                         (kTrace && chunk_index < kTraceChunks) ?
+                           args.dbg_counters + 16 + size_t(chunk_index) * kTraceWords + 25 :
+                           nullptr);
+      }
+      else
+      {
       for (uint32_t half = 0; half < 2u; ++half)
       {
       uint32_t words[kWordsPerThread];
@@ -1010,6 +1219,7 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
         args.dbg_counters[16 + size_t(chunk_index) * kTraceWords + 25 + half] = wall_clock64();
       }
       }  // halves
+      }  // general form
       if (inline_hits)
       {
         // Ordered replay of the region's samples, one lane per voxel with samples (the head of its run in the sorted
@@ -1111,7 +1321,12 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
     }
     // Flush the tile: integer adds, so the merge across chunks of one region is order independent.  (NDT / TSDF:
     // entries of masked voxels are skipped -- their visits travel as events.)
-    for (uint32_t i = threadIdx.x; i < count_words; i += uint32_t(G::kThreads))
+    const bool full_tile = mc.region_voxels == G::kTileVoxels;
+    if (full_tile)
+    {
+      flushFullTile<G>((const LdsWord *)l_counts, g_counts, uint32_t(defer_all));
+    }
+    for (uint32_t i = threadIdx.x; !full_tile && i < count_words; i += uint32_t(G::kThreads))
     {
       const uint32_t w = l_counts[tileWord(i)];
       if (w & (kTileCountMask | (kTileCountMask << 16)))
