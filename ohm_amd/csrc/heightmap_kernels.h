@@ -9,8 +9,9 @@
 // The integer state machines are findNearestSupportingVoxel2 / findNearestSupportingVoxel / findGround of
 // ohmheightmap/private/HeightmapOperations.cpp:186-512 as written (tests/heightmap_ref.py is the same restatement on
 // the CPU, from the same rule list); heights are fp64 in the reference's order (no FMA: -ffp-contract=off).  Rules 3-5
-// are stated once, here -- hmSupportingVoxel, hmGround, hmCellRecord -- for this kernel and for k_hmfill_columns
-// (heightmap_fill_kernels.h), which differ in the walk key, the ladder's two flags and what they do with the cell.
+// are stated once, here -- hmSupportingVoxel, hmGround, hmCellRecord -- for this kernel and for hmWalkColumn of the fill
+// and the layered builds (heightmap_walk_kernels.h), which differ in the walk key, the ladder's two flags and what they
+// do with the cell.
 //
 // Shape.  A column is a run of voxels at the stride of one z slice (Z up), of one row (Y up) or of one float (X up).
 // Columns are dealt to lanes in walk order, `a` innermost, 64 x 4 columns per workgroup: with Z or Y up `a` is the

@@ -1,7 +1,7 @@
 // heightmap_layered_impl.h -- host side of the layered heightmaps (heightmap_layered_kernels.h): the fill call's
-// prologue, source view, queue and generation loop (heightmap_fill_impl.h) with the touched lists' node pool growing
+// prologue and source view, the generation walk (heightmap_walk_impl.h) with the touched lists' node pool growing
 // beside the queue and the slot planes growing by doubling when a column asks for more; then L6, L7 and the results.
-// Included after heightmap_fill_impl.h in ohmhip_map.hip's translation unit.
+// Included after heightmap_walk_impl.h in ohmhip_map.hip's translation unit.
 #ifndef OHMHIP_HEIGHTMAP_LAYERED_IMPL_H
 #define OHMHIP_HEIGHTMAP_LAYERED_IMPL_H
 
@@ -12,43 +12,19 @@ static_assert(sizeof(HeightmapLayeredArgs) <= 4096, "kernel arguments are passed
 constexpr uint32_t kHmlInitialSlots = 2;
 constexpr uint32_t kHmlMostSlots = 255;  ///< of one column: beyond it OHMHIP_ERR_CAPACITY
 
-/// What the three layered entry points check before any device work, after their own pointers.
-int heightmapLayeredRefusal(ohmhip_map_t m, const ohmhip_heightmap_layered_params *p)
+/// What the three layered entry points do after their own pointer checks: the layered parameters' own check, then
+/// heightmapBegin.
+int heightmapLayeredBegin(ohmhip_map_t m, const ohmhip_heightmap_layered_params *p, HeightmapArgs &a,
+                          ohmhip_heightmap_extents &e, int *reference = nullptr)
 {
   if (!p || p->reserved != 0)
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
-  return heightmapRefusal(m, &p->base, kHmBuildLayered);
+  return heightmapBegin(m, &p->base, kHmBuildLayered, a, e, reference);
 }
 
-int heightmapLayeredBegin(ohmhip_map_t m, const ohmhip_heightmap_layered_params *p, HeightmapArgs &a,
-                          ohmhip_heightmap_extents &e, int *reference = nullptr)
-{
-  OHMHIP_CHECK(heightmapLayeredRefusal(m, p));
-  OHMHIP_SETTLE(m);
-  return heightmapGeometry(m, &p->base, a, e, reference);
-}
-
-/// The slot planes [slots][cells] of `bytes_per_cell` each: a new block for `slots`, the first `used` planes copied.
-int layeredPlaneReserve(DevBuf &plane, size_t bytes_per_cell, size_t cells, uint32_t slots, uint32_t used, hipStream_t s)
-{
-  const size_t want = bytes_per_cell * cells * slots;
-  if (want <= plane.bytes)
-  {
-    return OHMHIP_OK;
-  }
-  DevBuf grown;
-  OHMHIP_CHECK(grown.ensure(want, false, s));
-  if (used)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(grown.ptr, plane.ptr, bytes_per_cell * cells * used, hipMemcpyDeviceToDevice, s));
-    OHMHIP_CHECK(hipStreamSynchronize(s));
-  }
-  plane = std::move(grown);
-  return OHMHIP_OK;
-}
-
+/// The slot planes [slots][cells]: new blocks for exactly `slots`, the first `used` planes copied.
 int layeredPlanes(ohmhip_map_s::QueryState &qs, HeightmapLayeredArgs &f, uint32_t slots, uint32_t used, hipStream_t s)
 {
   const size_t cells = f.hm_cells;
@@ -56,11 +32,14 @@ int layeredPlanes(ohmhip_map_s::QueryState &qs, HeightmapLayeredArgs &f, uint32_
   {
     return OHMHIP_ERR_CAPACITY;
   }
-  OHMHIP_CHECK(layeredPlaneReserve(qs.hml_occ, sizeof(float), cells, slots, used, s));
-  OHMHIP_CHECK(layeredPlaneReserve(qs.hml_vox, sizeof(uint32_t) * kHmVoxelWords, cells, slots, used, s));
-  OHMHIP_CHECK(layeredPlaneReserve(qs.hml_mean, sizeof(uint2), cells, slots, used, s));
-  OHMHIP_CHECK(layeredPlaneReserve(qs.hml_visit, sizeof(uint32_t), cells, slots, used, s));
-  OHMHIP_CHECK(layeredPlaneReserve(qs.hml_ground, sizeof(unsigned long long), cells, slots, used, s));
+  const auto reserve = [&](DevBuf &plane, size_t bytes_per_cell) {
+    return growAndKeep(plane, bytes_per_cell * cells * slots, bytes_per_cell * cells * used, 0, s);
+  };
+  OHMHIP_CHECK(reserve(qs.hml_occ, sizeof(float)));
+  OHMHIP_CHECK(reserve(qs.hml_vox, sizeof(uint32_t) * kHmVoxelWords));
+  OHMHIP_CHECK(reserve(qs.hml_mean, sizeof(uint2)));
+  OHMHIP_CHECK(reserve(qs.hml_visit, sizeof(uint32_t)));
+  OHMHIP_CHECK(reserve(qs.hml_ground, sizeof(unsigned long long)));
   f.slot_capacity = slots;
   f.sl_occ = static_cast<float *>(qs.hml_occ.ptr);
   f.sl_vox = static_cast<uint32_t *>(qs.hml_vox.ptr);
@@ -70,18 +49,58 @@ int layeredPlanes(ohmhip_map_s::QueryState &qs, HeightmapLayeredArgs &f, uint32_
   return OHMHIP_OK;
 }
 
-int layeredSort(ohmhip_map_s::QueryState &qs, unsigned long long *in, unsigned long long *out, size_t count,
-                unsigned end_bit, hipStream_t s)
+/// The layered builds' steps of the walk: the node pool, flags and heights per generation, two event kernels, and
+/// after the synchronise the planes regrown and the adds run again while a column asks for more.
+struct HeightmapLayeredBuild
 {
-  size_t sort_bytes = 0;
-  OHMHIP_CHECK(rocprim::radix_sort_keys<SortConfig>(nullptr, sort_bytes, in, out, count, 0, end_bit, s));
-  OHMHIP_CHECK(qs.hmf_temp.ensure(sort_bytes, false, s));
-  size_t temp_bytes = qs.hmf_temp.bytes;
-  return rocprim::radix_sort_keys<SortConfig>(qs.hmf_temp.ptr, temp_bytes, in, out, count, 0, end_bit, s);
-}
+  HeightmapLayeredArgs f{};
+  unsigned id_bits = 0;
+  static constexpr auto columns = k_hml_columns;
+
+  int generation(ohmhip_map_s::QueryState &qs, size_t begin, size_t count, uint32_t number, hipStream_t s)
+  {
+    // an accepted offer takes one node
+    OHMHIP_CHECK(walkQueueReserve(qs.hml_nodes, begin + 9 * count, begin + count, s));
+    OHMHIP_CHECK(ensureAs(qs.hml_flags, count, s, f.key_flags));
+    OHMHIP_CHECK(ensureAs(qs.hml_height, count, s, f.src_height));
+    f.nodes = static_cast<uint2 *>(qs.hml_nodes.ptr);
+    f.node_capacity = uint32_t(std::min<size_t>(qs.hml_nodes.bytes / sizeof(uint2), 0xffffffffu));
+    f.stamp = number;
+    return OHMHIP_OK;
+  }
+
+  int adds(size_t count, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_hml_adds, dim3(uint32_t((9 * count + 255) / 256)), dim3(256), 0, s, f);
+    return hipGetLastError();
+  }
+
+  int events(size_t count, hipStream_t s)
+  {
+    hipLaunchKernelGGL(k_hml_offers, dim3(uint32_t((9 * count + 255) / 256)), dim3(256), 0, s, f);
+    OHMHIP_CHECK(hipGetLastError());
+    return adds(count, s);
+  }
+
+  int settle(ohmhip_map_s::QueryState &qs, uint32_t *next, size_t count, hipStream_t s)
+  {
+    OHMHIP_CHECK(hipMemcpyAsync(next + 1, f.words + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    OHMHIP_CHECK(hipStreamSynchronize(s));
+    while (next[1] > f.slot_capacity)
+    {
+      // a column asked for more slots: its adds are not applied yet, every other cell's are
+      OHMHIP_CHECK(layeredPlanes(qs, f, std::max(next[1], 2 * f.slot_capacity), f.slot_capacity, s));
+      OHMHIP_CHECK(hipMemsetAsync(f.words + 1, 0, sizeof(uint32_t), s));
+      OHMHIP_CHECK(adds(count, s));
+      OHMHIP_CHECK(hipMemcpyAsync(next + 1, f.words + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      OHMHIP_CHECK(hipStreamSynchronize(s));
+    }
+    return OHMHIP_OK;
+  }
+};
 
 /// The walk and what follows it, results into device arrays of layer_capacity planes; returns with the stream idle.
-/// The log as in heightmapFillDevice.
+/// The log as in heightmapWalkFinish.
 int heightmapLayeredDevice(ohmhip_map_t m, const ohmhip_heightmap_layered_params &params, const HeightmapArgs &geometry,
                            const int seed[3], uint32_t layer_capacity, float *d_occ, void *d_vox, void *d_mean,
                            uint32_t *d_visit, uint8_t *d_count, uint32_t *d_log, DevBuf *log_staging,
@@ -89,7 +108,8 @@ int heightmapLayeredDevice(ohmhip_map_t m, const ohmhip_heightmap_layered_params
 {
   hipStream_t s = m->stream;
   ohmhip_map_s::QueryState &qs = m->query;
-  HeightmapLayeredArgs f{};
+  HeightmapLayeredBuild build;
+  HeightmapLayeredArgs &f = build.f;
   static_cast<HeightmapArgs &>(f) = geometry;
   OHMHIP_CHECK(heightmapSourceView(m, f));
   const size_t cells = size_t(f.ma) * size_t(f.mb);
@@ -100,6 +120,7 @@ int heightmapLayeredDevice(ohmhip_map_t m, const ohmhip_heightmap_layered_params
   }
   f.grid_cells = uint32_t(grid_cells);
   f.hm_cells = uint32_t(cells);
+  build.id_bits = bitsFor((unsigned long long)grid_cells + cells + 1ull);
   f.ordered = (params.base.mode == 3) ? 1 : 0;
   f.filter_threshold = f.ordered ? params.virtual_surface_filter_threshold : 0u;
   f.epsilon = 1e-3 * params.base.grid_resolution;
@@ -110,20 +131,12 @@ int heightmapLayeredDevice(ohmhip_map_t m, const ohmhip_heightmap_layered_params
     f.seed_height = (up_vec[0] * r[0] + up_vec[1] * r[1]) + up_vec[2] * r[2];  // glm::dot(up, reference_pos)
   }
   f.layer_capacity = layer_capacity;
-  OHMHIP_CHECK(qs.hm_counts.ensure(sizeof(unsigned long long) * kHmlCountWords, false, s));
-  OHMHIP_CHECK(qs.hml_head.ensure(sizeof(uint32_t) * grid_cells, false, s));
-  OHMHIP_CHECK(qs.hml_cell_state.ensure(sizeof(uint32_t) * 3 * cells, false, s));
-  OHMHIP_CHECK(qs.hml_words.ensure(sizeof(uint32_t) * 2, false, s));
-  if (!qs.hml_next.ptr)
-  {
-    OHMHIP_CHECK(qs.hml_next.alloc(sizeof(uint32_t) * 2, hipHostMallocDefault));
-  }
-  f.counts = static_cast<unsigned long long *>(qs.hm_counts.ptr);
-  f.touched_head = static_cast<uint32_t *>(qs.hml_head.ptr);
-  f.slot_count = static_cast<uint32_t *>(qs.hml_cell_state.ptr);
+  OHMHIP_CHECK(ensureAs(qs.hm_counts, kHmlCountWords, s, f.counts));
+  OHMHIP_CHECK(ensureAs(qs.hml_head, grid_cells, s, f.touched_head));
+  OHMHIP_CHECK(ensureAs(qs.hml_cell_state, 3 * cells, s, f.slot_count));
+  OHMHIP_CHECK(ensureAs(qs.hml_words, 2, s, f.words));
   f.applied = f.slot_count + cells;
   f.multi = f.applied + cells;
-  f.words = static_cast<uint32_t *>(qs.hml_words.ptr);
   f.out_occ = d_occ;
   f.out_vox = static_cast<uint32_t *>(d_vox);
   f.out_mean = static_cast<uint2 *>(d_mean);
@@ -134,125 +147,26 @@ int heightmapLayeredDevice(ohmhip_map_t m, const ohmhip_heightmap_layered_params
   hipLaunchKernelGGL(k_hml_clear, dim3(uint32_t((std::max(std::max(cells, grid_cells), size_t(kHmlCountWords)) + 255) / 256)),
                      dim3(256), 0, s, f);
   OHMHIP_CHECK(hipGetLastError());
+  OHMHIP_CHECK(walkQueueReserve(qs.hml_nodes, 1 << 14, 0, s));
 
-  OHMHIP_CHECK(fillQueueReserve(qs.hmf_queue, 1 << 14, 0, s));
-  OHMHIP_CHECK(fillQueueReserve(qs.hml_nodes, 1 << 14, 0, s));
-  // L1: the seed is heightmapGeometry's clamped key of reference_pos
-  const uint2 first = make_uint2(uint32_t(seed[f.b] - f.min_g[f.b]) * uint32_t(f.na) + uint32_t(seed[f.a] - f.min_g[f.a]),
-                                 uint32_t(seed[f.up] - f.min_g[f.up]));
-  OHMHIP_CHECK(hipMemcpyAsync(qs.hmf_queue.ptr, &first, sizeof(first), hipMemcpyHostToDevice, s));
-  OHMHIP_CHECK(hipStreamSynchronize(s));  // `first` is pageable
-
-  const unsigned id_bits = bitsFor((unsigned long long)grid_cells + cells + 1ull);
-  size_t begin = 0, count = 1;
-  stats = ohmhip_heightmap_layered_stats{};
-  while (count)
-  {
-    if (begin + count > 0xffffffffull || 9 * count >= (1ull << 31))
-    {
-      return OHMHIP_ERR_CAPACITY;
-    }
-    ++stats.generations;
-    stats.largest_generation = std::max(stats.largest_generation, uint32_t(count));
-    // every key may be accepted by all 8 neighbours; an accepted offer takes one node
-    OHMHIP_CHECK(fillQueueReserve(qs.hmf_queue, begin + 9 * count, begin + count, s));
-    OHMHIP_CHECK(fillQueueReserve(qs.hml_nodes, begin + 9 * count, begin + count, s));
-    OHMHIP_CHECK(qs.hm_rec_occ.ensure(sizeof(float) * count, false, s));
-    OHMHIP_CHECK(qs.hm_rec_vox.ensure(sizeof(uint32_t) * kHmVoxelWords * count, false, s));
-    OHMHIP_CHECK(qs.hm_rec_mean.ensure(sizeof(uint2) * count, false, s));
-    OHMHIP_CHECK(qs.hmf_ground.ensure(sizeof(uint32_t) * count, false, s));
-    OHMHIP_CHECK(qs.hmf_rec_cell.ensure(sizeof(uint32_t) * count, false, s));
-    OHMHIP_CHECK(qs.hml_flags.ensure(sizeof(uint32_t) * count, false, s));
-    OHMHIP_CHECK(qs.hml_height.ensure(sizeof(double) * count, false, s));
-    OHMHIP_CHECK(qs.hmf_keys_a.ensure(sizeof(unsigned long long) * 9 * count, false, s));
-    OHMHIP_CHECK(qs.hmf_keys_b.ensure(sizeof(unsigned long long) * 9 * count, false, s));
-    OHMHIP_CHECK(qs.hmf_accept.ensure(sizeof(uint32_t) * (8 * count + 1), false, s));
-    OHMHIP_CHECK(qs.hmf_accept_at.ensure(sizeof(uint32_t) * (8 * count + 1), false, s));
-    f.queue = static_cast<uint2 *>(qs.hmf_queue.ptr);
-    f.nodes = static_cast<uint2 *>(qs.hml_nodes.ptr);
-    f.node_capacity = uint32_t(std::min<size_t>(qs.hml_nodes.bytes / sizeof(uint2), 0xffffffffu));
-    f.gen_begin = uint32_t(begin);
-    f.gen_count = uint32_t(count);
-    f.seed_generation = (begin == 0) ? 1 : 0;
-    f.stamp = stats.generations;
-    f.index_bits = bitsFor(count);
-    f.rec_occ = static_cast<float *>(qs.hm_rec_occ.ptr);
-    f.rec_vox = static_cast<uint32_t *>(qs.hm_rec_vox.ptr);
-    f.rec_mean = static_cast<uint2 *>(qs.hm_rec_mean.ptr);
-    f.ground_h = static_cast<uint32_t *>(qs.hmf_ground.ptr);
-    f.rec_cell = static_cast<uint32_t *>(qs.hmf_rec_cell.ptr);
-    f.key_flags = static_cast<uint32_t *>(qs.hml_flags.ptr);
-    f.src_height = static_cast<double *>(qs.hml_height.ptr);
-    f.keys = static_cast<unsigned long long *>(qs.hmf_keys_a.ptr);
-    f.sorted = static_cast<const unsigned long long *>(qs.hmf_keys_b.ptr);
-    f.accept = static_cast<uint32_t *>(qs.hmf_accept.ptr);
-    f.accept_at = static_cast<const uint32_t *>(qs.hmf_accept_at.ptr);
-    uint32_t *accept_at = static_cast<uint32_t *>(qs.hmf_accept_at.ptr);
-
-    hipLaunchKernelGGL(k_hml_columns, dim3(uint32_t((count + 63) / 64)), dim3(64), 0, s, f);
-    OHMHIP_CHECK(hipGetLastError());
-    OHMHIP_CHECK(layeredSort(qs, f.keys, static_cast<unsigned long long *>(qs.hmf_keys_b.ptr), 9 * count,
-                             f.index_bits + id_bits, s));
-    const dim3 event_blocks(uint32_t((9 * count + 255) / 256));
-    hipLaunchKernelGGL(k_hml_offers, event_blocks, dim3(256), 0, s, f);
-    OHMHIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_hml_adds, event_blocks, dim3(256), 0, s, f);
-    OHMHIP_CHECK(hipGetLastError());
-    size_t scan_bytes = 0;
-    OHMHIP_CHECK(rocprim::exclusive_scan(nullptr, scan_bytes, f.accept, accept_at, 0u, 8 * count + 1,
-                                         rocprim::plus<uint32_t>(), s));
-    OHMHIP_CHECK(qs.hmf_temp.ensure(scan_bytes, false, s));
-    scan_bytes = qs.hmf_temp.bytes;
-    OHMHIP_CHECK(rocprim::exclusive_scan(qs.hmf_temp.ptr, scan_bytes, f.accept, accept_at, 0u, 8 * count + 1,
-                                         rocprim::plus<uint32_t>(), s));
-    hipLaunchKernelGGL(k_hmfill_append, dim3(uint32_t((8 * count + 255) / 256)), dim3(256), 0, s,
-                       static_cast<const HeightmapFillArgs &>(f));
-    OHMHIP_CHECK(hipGetLastError());
-    OHMHIP_CHECK(hipMemcpyAsync(qs.hml_next.ptr, accept_at + 8 * count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OHMHIP_CHECK(hipMemcpyAsync(qs.hml_next.ptr + 1, f.words + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    OHMHIP_CHECK(hipStreamSynchronize(s));
-    while (qs.hml_next.ptr[1] > f.slot_capacity)
-    {
-      // a column asked for more slots: its adds are not applied yet, every other cell's are
-      const uint32_t asked = qs.hml_next.ptr[1];
-      OHMHIP_CHECK(layeredPlanes(qs, f, std::max(asked, 2 * f.slot_capacity), f.slot_capacity, s));
-      OHMHIP_CHECK(hipMemsetAsync(f.words + 1, 0, sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_hml_adds, event_blocks, dim3(256), 0, s, f);
-      OHMHIP_CHECK(hipGetLastError());
-      OHMHIP_CHECK(hipMemcpyAsync(qs.hml_next.ptr + 1, f.words + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      OHMHIP_CHECK(hipStreamSynchronize(s));
-    }
-    begin += count;
-    count = qs.hml_next.ptr[0];
-  }
+  OHMHIP_CHECK(heightmapWalk(m, build, seed, stats));
   if (f.filter_threshold)
   {
     // L6
     const size_t slots = size_t(f.slot_capacity) * cells;
-    OHMHIP_CHECK(qs.hmf_keys_a.ensure(sizeof(unsigned long long) * slots, false, s));
-    OHMHIP_CHECK(qs.hml_ground_sorted.ensure(sizeof(unsigned long long) * slots, false, s));
-    f.keys = static_cast<unsigned long long *>(qs.hmf_keys_a.ptr);
-    f.ground_sorted = static_cast<const unsigned long long *>(qs.hml_ground_sorted.ptr);
+    unsigned long long *ground_sorted = nullptr;
+    OHMHIP_CHECK(ensureAs(qs.hm_walk.keys_a, slots, s, f.keys));
+    OHMHIP_CHECK(ensureAs(qs.hml_ground_sorted, slots, s, ground_sorted));
+    f.ground_sorted = ground_sorted;
     hipLaunchKernelGGL(k_hml_keys, dim3(uint32_t((slots + 255) / 256)), dim3(256), 0, s, f);
     OHMHIP_CHECK(hipGetLastError());
-    OHMHIP_CHECK(layeredSort(qs, f.keys, static_cast<unsigned long long *>(qs.hml_ground_sorted.ptr), slots, 64, s));
+    OHMHIP_CHECK(heightmapSort(qs.hm_walk.temp, f.keys, ground_sorted, slots, 64, s));
     hipLaunchKernelGGL(k_hml_filter, dim3(uint32_t((slots + 255) / 256)), dim3(256), 0, s, f);
     OHMHIP_CHECK(hipGetLastError());
   }
-  const uint64_t logged = std::min<uint64_t>(log_capacity, begin);
-  if (log_staging && logged)
-  {
-    OHMHIP_CHECK(log_staging->ensure(sizeof(uint32_t) * 3 * logged, false, s));
-    f.out_log = static_cast<uint32_t *>(log_staging->ptr);
-  }
-  f.log_count = f.out_log ? uint32_t(logged) : 0u;
-  const size_t finish = std::max(cells, size_t(f.log_count));
-  hipLaunchKernelGGL(k_hml_finish, dim3(uint32_t((finish + 255) / 256)), dim3(256), 0, s, f);
-  OHMHIP_CHECK(hipGetLastError());
   unsigned long long counts[kHmlCountWords] = {};
-  OHMHIP_CHECK(hipMemcpyAsync(counts, f.counts, sizeof(counts), hipMemcpyDeviceToHost, s));
-  OHMHIP_CHECK(hipStreamSynchronize(s));
-  stats.visits = begin;
+  // (also INTERNAL: a node beyond the pool, which holds one per queue entry)
+  const int status = heightmapWalkFinish(m, f, k_hml_finish, "layered", log_staging, log_capacity, stats, counts);
   stats.populated = counts[0];
   stats.cells = counts[kHmlCells];
   stats.voxels = counts[kHmlVoxels];
@@ -261,16 +175,7 @@ int heightmapLayeredDevice(ohmhip_map_t m, const ohmhip_heightmap_layered_params
   stats.filtered = counts[kHmlFiltered];
   stats.multi_layer_columns = counts[kHmlMultiColumns];
   stats.layers = uint32_t(counts[kHmlLayers]);
-  if (f.count_inspected)
-  {
-    std::fprintf(stderr, "ohmhip heightmap layered: %llu voxels inspected, %zu visits, %u generations\n", counts[3],
-                 begin, stats.generations);
-  }
-  if (counts[2])
-  {
-    return OHMHIP_ERR_INTERNAL;  // (a visit's cell outside the grid, a node beyond the pool: cannot happen)
-  }
-  return (stats.layers > kHmlMostSlots) ? OHMHIP_ERR_CAPACITY : OHMHIP_OK;
+  return (status == OHMHIP_OK && stats.layers > kHmlMostSlots) ? OHMHIP_ERR_CAPACITY : status;
 }
 }  // namespace
 
@@ -315,25 +220,15 @@ try
   {
     return OHMHIP_ERR_CAPACITY;
   }
-  const size_t n = size_t(layer_capacity) * cells;
-  if (!visit_log)
-  {
-    visit_log_capacity = 0;
-  }
-  HeightmapStaged d;
-  OHMHIP_CHECK(d.stage(qs, occupancy, voxels24, mean8, source_visit, n, s));
-  uint8_t *d_count = nullptr;
-  OHMHIP_CHECK(stageOut(qs.hml_out_count, layer_count, cells, s, d_count));
-  OHMHIP_CHECK(heightmapLayeredDevice(m, *params, a, seed, layer_capacity, d.occ, d.vox, d.mean, d.source, d_count,
-                                      nullptr, &qs.hmf_log, visit_log_capacity, *stats));
-  const uint64_t logged = std::min<uint64_t>(visit_log_capacity, stats->visits);
-  if (logged)
-  {
-    OHMHIP_CHECK(hipMemcpyAsync(visit_log, qs.hmf_log.ptr, sizeof(uint32_t) * 3 * logged, hipMemcpyDeviceToHost, s));
-  }
-  OHMHIP_CHECK(d.copyBack(occupancy, voxels24, mean8, source_visit, n, s));
-  OHMHIP_CHECK(copyOut(layer_count, d_count, cells, s));
-  return hipStreamSynchronize(s);
+  return heightmapWalkToHost(m, occupancy, voxels24, mean8, source_visit, size_t(layer_capacity) * cells, visit_log,
+                             visit_log_capacity, *stats, [&](const HeightmapStaged &d, DevBuf *log, uint64_t capacity) {
+                               uint8_t *d_count = nullptr;
+                               OHMHIP_CHECK(stageOut(qs.hml_out_count, layer_count, cells, s, d_count));
+                               OHMHIP_CHECK(heightmapLayeredDevice(m, *params, a, seed, layer_capacity, d.occ, d.vox,
+                                                                   d.mean, d.source, d_count, nullptr, log, capacity,
+                                                                   *stats));
+                               return copyOut(layer_count, d_count, cells, s);
+                             });
 }
 OHMHIP_ABI_CATCH
 

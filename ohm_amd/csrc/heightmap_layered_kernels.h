@@ -2,25 +2,24 @@
 // kLayeredFillUnordered) built on the device from the resident map, read only.  Rules L1-L7 of include/ohmhip.h
 // ("HEIGHTMAP, LAYERED").
 //
-// The walk is the fill's (heightmap_fill_kernels.h): the queue is one device array, a generation a range of it, one
-// round of kernels per generation.  What differs is what a generation's keys share:
+// The walk -- queue, generations, the round of kernels per generation -- is heightmap_walk_kernels.h's.  The layered
+// builds' own is what a generation's keys share:
 //
-//   k_hml_columns  1 lane / key of the generation   L2, L4: supporting voxel, ground, the cell record (the device
-//                                                   functions of heightmap_kernels.h, unchanged); the key's 8 offers
-//                                                   keyed (grid cell, key index), its add keyed (heightmap cell, key index)
-//   (radix sort)                                    offers and adds in one array: grid cells first, heightmap cells behind
+//   k_hml_columns  1 lane / key of the generation   L2, L4: the walk's column evaluation; the key's flags and fp64
+//                                                   src_height; its add keyed (heightmap cell, key index) as its event
+//                                                   of its own, sorted behind the offers' grid cells
 //   k_hml_offers   1 lane / sorted event            L3: the first offer of a grid cell replays the cell's offers in order
 //                                                   against the cell's touched list -- a head per cell, (height, next)
 //                                                   nodes in one pool -- and flags the accepted ones
 //   k_hml_adds     1 lane / sorted event            L5: the first add of a heightmap cell applies the cell's adds in order
 //                                                   to the column's slots
-//   (exclusive scan), k_hmfill_append               the fill's: accepted offers become the next generation
 //
-// Exactness.  The fill's argument carries over to two independent per-cell orders.  A touched list is read and written
-// only by offers to its grid cell, and key i of a generation makes at most one offer to a cell; a column of slots is read
-// and written only by adds to its heightmap cell, and key i makes at most one add.  In the reference key i makes its
-// offers, then its add, then key i + 1 follows: the events of one cell ordered by i are in the reference's order, and
-// neither decision reads what the other writes.  Generations run in order on one stream, so lists and slots carry over.
+// Exactness.  The fill's argument (heightmap_fill_kernels.h) carries over to two independent per-cell orders.  A touched
+// list is read and written only by offers to its grid cell, and key i of a generation makes at most one offer to a cell;
+// a column of slots is read and written only by adds to its heightmap cell, and key i makes at most one add.  In the
+// reference key i makes its offers, then its add, then key i + 1 follows: the events of one cell ordered by i are in the
+// reference's order, and neither decision reads what the other writes.  Generations run in order on one stream, so lists
+// and slots carry over.
 //
 // The slots are planes [slot][cell] of the walk's own, not the caller's: a column may need more slots than the caller
 // asked for, and L7 permutes them.  When the adds of one cell could outgrow the planes the cell's lane applies none of
@@ -35,7 +34,7 @@
 #ifndef OHMHIP_HEIGHTMAP_LAYERED_KERNELS_H
 #define OHMHIP_HEIGHTMAP_LAYERED_KERNELS_H
 
-#include "heightmap_fill_kernels.h"
+#include "heightmap_walk_kernels.h"
 
 namespace ohmhip
 {
@@ -64,9 +63,8 @@ enum : int  ///< counts[] beyond HeightmapArgs' [0] populated [2] outside [3] in
   kHmlCountWords = 12
 };
 
-/// `grid`, `cell_visit` and `out_visit` of the fill are not used.  Event ids: a grid cell, grid_cells + a heightmap cell,
-/// grid_cells + hm_cells for "no event".
-struct HeightmapLayeredArgs : HeightmapFillArgs
+/// Event ids: a grid cell, grid_cells + a heightmap cell, grid_cells + hm_cells for "no event".
+struct HeightmapLayeredArgs : HeightmapWalkArgs
 {
   uint32_t hm_cells;           ///< ma * mb
   uint32_t stamp;              ///< 1 + the generation's number
@@ -145,64 +143,21 @@ __global__ void __launch_bounds__(64) k_hml_columns(HeightmapLayeredArgs f)
   HmCursor c = hmCursorStart();
   if (i < f.gen_count)
   {
-    const uint32_t n = f.gen_count;
-    const uint2 item = f.queue[size_t(f.gen_begin) + i];
-    const int ia = int(item.x % uint32_t(f.na));
-    const int ib = int(item.x / uint32_t(f.na));
-    const int up = f.up;
-    double up_vec[3] = { 0.0, 0.0, 0.0 };
-    hmPut(up_vec, up, f.up_positive ? 1.0 : -1.0);
-    const int min_up = sel3(up, f.min_g);
-    int walk[3] = { 0, 0, 0 };
-    hmPut(walk, f.a, sel3(f.a, f.min_g) + ia);
-    hmPut(walk, f.b, sel3(f.b, f.min_g) + ib);
-    hmPut(walk, up, min_up + int(item.y));
-    int candidate = 0;
-    const bool have_candidate = hmSupportingVoxel(f, c, walk, f.gen_begin + i != 0u, false, candidate);
-    double clearance = 0.0;
-    int ground_up = 0;
-    bool ground_observed_above = false;
-    const bool have_ground =
-      have_candidate && hmGround(f, c, walk, candidate, up_vec, ground_up, clearance, ground_observed_above);
-    int ground[3] = { walk[0], walk[1], walk[2] };
-    if (have_ground)
-    {
-      hmPut(ground, up, ground_up);
-    }
-    f.ground_h[i] = uint32_t(sel3(up, ground) - min_up);
-    f.key_flags[i] = (have_candidate ? 0u : uint32_t(kHmlNullCandidate)) |
-                     ((have_ground && (clearance > 0.0 || ground_observed_above)) ? uint32_t(kHmlBaseCandidate) : 0u);
-    const long long cell =
-      hmCellRecord(f, c, ground, have_candidate, have_ground, clearance, ground_observed_above, up_vec, size_t(i));
-    f.rec_cell[i] = (cell >= 0) ? uint32_t(cell) : kHmFillNoCell;
-    if (cell >= 0)
+    const HmWalkColumn col = hmWalkColumn(f, c, i);
+    f.key_flags[i] =
+      (col.have_candidate ? 0u : uint32_t(kHmlNullCandidate)) |
+      ((col.have_ground && (col.clearance > 0.0 || col.ground_observed_above)) ? uint32_t(kHmlBaseCandidate) : 0u);
+    if (col.cell >= 0)
     {
       // rule 5's src_height once more, in fp64: hmCellRecord keeps it as the float relative to slot 0
       double pos[3];
-      hmPosition(f, c, ground, hmSeek(f, c, ground), f.rec_occ[i] > 0.0f, pos);
-      f.src_height[i] = hmDot(up_vec, pos);
-    }
-    else if (cell == kHmCellOutside)
-    {
-      atomicAdd(&f.counts[2], 1ull);
+      hmPosition(f, c, col.ground, hmSeek(f, c, col.ground), f.rec_occ[i] > 0.0f, pos);
+      f.src_height[i] = hmDot(col.up_vec, pos);
     }
     const unsigned long long none = ((unsigned long long)f.grid_cells + f.hm_cells) << f.index_bits;
-    f.keys[i] = (cell >= 0) ? ((((unsigned long long)f.grid_cells + (unsigned long long)cell) << f.index_bits) | i) : none;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-    {
-      int col_delta, row_delta;
-      hmFillSlotDelta(k, col_delta, row_delta);
-      const int na = ia + col_delta, nb = ib + row_delta;
-      const bool on_grid = na >= 0 && na < f.na && nb >= 0 && nb < f.nb;
-      const unsigned long long to = (unsigned long long)(uint32_t(nb) * uint32_t(f.na) + uint32_t(na));
-      f.keys[size_t(1 + k) * n + i] = on_grid ? ((to << f.index_bits) | i) : none;
-      f.accept[size_t(8) * i + uint32_t(k)] = 0u;
-    }
-    if (i == 0u)
-    {
-      f.accept[size_t(8) * n] = 0u;
-    }
+    const unsigned long long add = (unsigned long long)f.grid_cells + (unsigned long long)col.cell;
+    f.keys[i] = (col.cell >= 0) ? ((add << f.index_bits) | i) : none;
+    hmWalkOffers(f, i, col.ia, col.ib, none);
   }
   hmColumnTail(f, c, false);
 }
@@ -218,12 +173,11 @@ __global__ void __launch_bounds__(256) k_hml_offers(HeightmapLayeredArgs f)
   }
   const unsigned long long index_mask = (1ull << f.index_bits) - 1ull;
   const unsigned long long id = f.sorted[p] >> f.index_bits;
-  if (id >= f.grid_cells || (p != 0 && (f.sorted[p - 1] >> f.index_bits) == id))
+  if (id >= f.grid_cells || !hmWalkFirstOf(f, p, id))
   {
     return;
   }
   const uint32_t cell = uint32_t(id);
-  const int ca = int(cell % uint32_t(f.na)), cb = int(cell / uint32_t(f.na));
   uint32_t head = f.touched_head[cell];
   for (size_t q = p; q < events; ++q)
   {
@@ -258,10 +212,7 @@ __global__ void __launch_bounds__(256) k_hml_offers(HeightmapLayeredArgs f)
       }
       f.nodes[node] = make_uint2(offered, head);
       head = node + 1u;
-      const uint32_t from = f.queue[size_t(f.gen_begin) + i].x;
-      const int col_delta = ca - int(from % uint32_t(f.na)), row_delta = cb - int(from / uint32_t(f.na));
-      const int at = (row_delta + 1) * 3 + (col_delta + 1);
-      f.accept[size_t(8) * i + uint32_t(at > 4 ? at - 1 : at)] = 1u;
+      f.accept[size_t(8) * i + hmWalkSlotOf(f, cell, f.queue[size_t(f.gen_begin) + i].x)] = 1u;
     }
   }
   f.touched_head[cell] = head;
@@ -279,7 +230,7 @@ __global__ void __launch_bounds__(256) k_hml_adds(HeightmapLayeredArgs f)
   const unsigned long long index_mask = (1ull << f.index_bits) - 1ull;
   const unsigned long long id = f.sorted[p] >> f.index_bits;
   const unsigned long long first_cell = f.grid_cells;
-  if (id < first_cell || id >= first_cell + f.hm_cells || (p != 0 && (f.sorted[p - 1] >> f.index_bits) == id))
+  if (id < first_cell || id >= first_cell + f.hm_cells || !hmWalkFirstOf(f, p, id))
   {
     return;
   }
@@ -584,17 +535,7 @@ __global__ void __launch_bounds__(256) k_hml_finish(HeightmapLayeredArgs f)
     for (uint32_t k = kept; k < f.layer_capacity; ++k)
     {
       const size_t to = size_t(k) * cells + cell;
-      f.out_occ[to] = __int_as_float(0x7f800000);
-      uint32_t *vox = f.out_vox + to * kHmVoxelWords;
-#pragma unroll
-      for (uint32_t w = 0; w < kHmVoxelWords; ++w)
-      {
-        vox[w] = 0u;
-      }
-      if (f.out_mean)
-      {
-        f.out_mean[to] = make_uint2(0u, 0u);
-      }
+      hmWalkClearCell(f, to);
       if (f.out_source)
       {
         f.out_source[to] = 0xffffffffu;
@@ -614,13 +555,7 @@ __global__ void __launch_bounds__(256) k_hml_finish(HeightmapLayeredArgs f)
   {
     atomicAdd(&f.counts[kHmlCells], (unsigned long long)__popcll(mask));
   }
-  if (f.out_log && cell < size_t(f.log_count))
-  {
-    const uint2 item = f.queue[cell];
-    f.out_log[3 * cell + 0] = item.x % uint32_t(f.na);
-    f.out_log[3 * cell + 1] = item.x / uint32_t(f.na);
-    f.out_log[3 * cell + 2] = item.y;
-  }
+  hmWalkLogEntry(f, cell);
 }
 }  // namespace ohmhip
 

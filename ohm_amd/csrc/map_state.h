@@ -405,18 +405,21 @@ struct ohmhip_map_s
     DevBuf clear_regions, clear_keys, clear_out, clear_mask;  ///< clearance queries (clearance_kernels.h)
     /// heightmap (heightmap_kernels.h): per-cell winner, per-column records, counters; device copies of the host arrays
     DevBuf hm_winner, hm_rec_occ, hm_rec_vox, hm_rec_mean, hm_counts, hm_out_occ, hm_out_vox, hm_out_mean, hm_out_col;
-    /// flood-fill heightmap (heightmap_fill_kernels.h): the visit grid, the queue of every visit, per key of a
-    /// generation its ground height and heightmap cell, the cell events unsorted / sorted, the accept flags and their
-    /// scan, sort and scan scratch, the log's device copy; the pinned word the next generation's size is read through
-    DevBuf hmf_grid, hmf_queue, hmf_ground, hmf_rec_cell, hmf_keys_a, hmf_keys_b, hmf_accept, hmf_accept_at, hmf_temp, hmf_log;
-    PinnedBuf<uint32_t> hmf_next;
-    /// layered heightmaps (heightmap_layered_kernels.h), beside the fill's: per key of a generation its flags and
-    /// src_height; the touched lists' heads, nodes and the two device words; per heightmap cell the slot count, the
-    /// applied stamp and the multi-layer note; the slot planes; the sorted ground keys; layer_count's device copy; the
-    /// pinned pair the next generation's size and the slots asked for are read through
+    /// the generation walk of the fill and layered heightmaps (heightmap_walk_impl.h): the queue of every visit, per key
+    /// of a generation its ground height and heightmap cell, the events unsorted / sorted, the accept flags and their
+    /// scan, sort and scan scratch, the log's device copy; the pinned pair read back per generation: [0] the next
+    /// generation's size, [1] the build's own
+    struct HeightmapWalk
+    {
+      DevBuf queue, ground, rec_cell, keys_a, keys_b, accept, accept_at, temp, log;
+      PinnedBuf<uint32_t> next;
+    } hm_walk;
+    DevBuf hmf_grid;  ///< flood-fill heightmap (heightmap_fill_kernels.h): the visit grid
+    /// layered heightmaps (heightmap_layered_kernels.h): per key of a generation its flags and src_height; the touched
+    /// lists' heads, nodes and the two device words; per heightmap cell the slot count, the applied stamp and the
+    /// multi-layer note; the slot planes; the sorted ground keys; layer_count's device copy
     DevBuf hml_flags, hml_height, hml_head, hml_nodes, hml_words, hml_cell_state, hml_occ, hml_vox, hml_mean, hml_visit,
       hml_ground, hml_ground_sorted, hml_out_count;
-    PinnedBuf<uint32_t> hml_next;
     /// point clouds (cloud_kernels.h): the work list, per-wave counts and their scan; device copies of the host arrays
     DevBuf cloud_chunks, cloud_pos, cloud_keys, cloud_values;
     ScanScratch cloud_scan;

@@ -15,6 +15,7 @@
 #include "query_kernels.h"
 #include "clearance_kernels.h"
 #include "heightmap_kernels.h"
+#include "heightmap_walk_kernels.h"
 #include "heightmap_fill_kernels.h"
 #include "heightmap_layered_kernels.h"
 #include "cloud_kernels.h"
@@ -1034,6 +1035,7 @@ OHMHIP_ABI_CATCH
 #include "clearance_impl.h"
 #include "clearance_update.h"
 #include "heightmap_impl.h"
+#include "heightmap_walk_impl.h"
 #include "heightmap_fill_impl.h"
 #include "heightmap_layered_impl.h"
 #include "cloud_impl.h"

@@ -1,6 +1,7 @@
 """Scenes of the layered heightmap tests (CPU restatement and device) -- TEST INFRASTRUCTURE.  Built on the flood fill's
 scenes (tests/heightmap_fill_cases.py: Scene, the multi-level scene, the mean scene).
 
+staircase()       hand-made: six steps of three columns, each a voxel higher than the last
 two_storey()      hand-made: a ground floor of 12 x 12 columns over four 8^3 regions, an upper floor over part of it
                   that reaches two map corners, a ramp between them, and columns without a floor voxel ("holes": a
                   virtual surface, or nothing) at chosen places.  Every column of interest lies on or beside the region
@@ -44,6 +45,17 @@ def two_storey(observed_top=True, mean=False):
     return s
 
 
+def staircase(steps=6):
+    """Steps of 3 columns each, one voxel higher per column of x, with a free voxel above each; they straddle the region
+    boundaries at x = 0 and y = 0."""
+    s = Scene(1.0, (8, 8, 8), False)
+    for i in range(steps):
+        for y in (-1, 0, 1):
+            s.put((i - 3, y, FLOOR + i), HIT)
+            s.put((i - 3, y, FLOOR + i + 1), MISS)
+    return s
+
+
 def _params(seed_level=FLOOR, **kw):
     """The seed over column (-5, 4) at the height of the centre of global voxel z = seed_level (region 0 spans -4 .. 4)."""
     return dict(dict(grid_resolution=1.0, min_clearance=0.0, reference_pos=(-8.5, 0.5, seed_level - 3.5)), **kw)
@@ -70,6 +82,11 @@ HAND_MADE = (
 def hand_made_cases():
     for name, scene_kw, params_kw, mode, threshold, quirks in HAND_MADE:
         yield name, two_storey(**scene_kw), Params(**params_kw), mode, threshold, quirks
+    # one heightmap cell over the whole staircase: a column of six voxels, a step per generation; generation 1 alone
+    # makes five adds to it (plane_growth())
+    stairs = staircase()
+    yield ("six-storeys", stairs, Params(6.0, 0.0, reference_pos=stairs.centre((-3, 0, FLOOR)), origin=(5.0, 5.0, 0.0)),
+           MODE_ORDERED, 0, ("multi_layer_columns", "repeats"))
     # every up axis: the scene turned, the seed with it
     base = two_storey()
     kw = _params(virtual_surface=True, ceiling=2.0)
@@ -90,6 +107,28 @@ def quirk_counts(res):
     counts["virtual_kept"] = int((res.occupancy == -1.0).sum())
     counts["mean_in_upper_slot"] = int((res.mean[1:, :, :, 1] != 0).sum()) if res.mean is not None else 0
     return counts
+
+
+def plane_growth(res, initial=2):
+    """How the device's slot planes must grow on this walk: [(capacity before, slots asked for)] for every generation
+    after which they do.  A heightmap cell asks for the voxels its column held before the generation plus every add the
+    generation makes to it, stood or not; the planes start at `initial` slots and grow to max(asked, 2 * capacity)."""
+    ends = []
+    for size in res.generation_sizes:
+        ends.append(size + (ends[-1] if ends else 0))
+    asked = [{} for _ in ends]
+    generation = 0
+    for visit, cell, held in res.add_trace:  # in visit order
+        while visit >= ends[generation]:
+            generation += 1
+        asked[generation][cell] = asked[generation].get(cell, held) + 1
+    capacity, grown = initial, []
+    for cells in asked:
+        most = max(cells.values(), default=0)
+        if most > capacity:
+            grown.append((capacity, most))
+            capacity = max(most, 2 * capacity)
+    return grown
 
 
 def layered_cases():

@@ -47,6 +47,7 @@ class _Walk(F._Walk):
         self.multi = set()  # multi_layer_keys
         self.by_ground = {}  # src_to_heightmap_keys: ground key -> (cell, the _Slot)
         self.log = []
+        self.add_trace = []  # per add, stood or not: (visit, heightmap cell, voxels the column held)
         self.populated = self.repeats = self.too_close = self.filtered = 0
         # how often the walk met what the hand-made cases exist for (tests assert on these, the device has no such count)
         self.quirks = dict.fromkeys(("column_rule_refusals", "too_close_real", "permuted_columns", "base_not_nearest",
@@ -116,6 +117,7 @@ class _Walk(F._Walk):
     def add(self, add):
         """addSurfaceVoxel (Heightmap.cpp:703-835) in a multi-layered mode."""
         column = self.columns.setdefault(add["cell"], [])
+        self.add_trace.append((add["visit"], add["cell"], len(column)))
         key = (add["hr"], add["hl"])
         src_height = add["src_height"]
         if column:
@@ -245,6 +247,7 @@ class _Walk(F._Walk):
         res.generations = len(generation_sizes)
         res.largest_generation = max(generation_sizes)
         res.generation_sizes = list(generation_sizes)
+        res.add_trace = list(self.add_trace)
         res.quirks = dict(self.quirks)
         return res
 

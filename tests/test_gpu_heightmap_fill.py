@@ -148,6 +148,7 @@ def test_generation_wider_than_a_workgroup(gpu):
     p = R.Params(0.5, 0.0, reference_pos=(0.1, 0.1, 0.7), floor=1.5, ceiling=1.5)
     hm, want = check(scene, p, "130 x 130")
     assert want.largest_generation > 256 and want.cells == 130 * 130
+    assert len(want.log) > (1 << 14)  # the queue outgrows its first block mid-walk, with entries to keep
 
 
 # -- the two builds' flags of the selection ladder ---------------------------------------------------------------------------

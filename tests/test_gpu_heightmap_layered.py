@@ -153,6 +153,7 @@ def test_generation_wider_than_a_workgroup(gpu):
     p = R.Params(0.5, 0.0, reference_pos=(0.1, 0.1, 0.7), floor=1.5, ceiling=1.5)
     hm, want = check(scene, p, LC.MODE_ORDERED, 0, ("repeats",), "130 x 130")
     assert want.largest_generation > 256 and want.cells == 130 * 130 and want.layers == 1
+    assert len(want.log) > (1 << 14)  # the queue and the node pool outgrow their first blocks mid-walk, with entries to keep
 
 
 # -- mean layer and a coarser grid --------------------------------------------------------------------------------------------
