@@ -203,14 +203,14 @@ struct BatchRun
       hipExtLaunchKernelGGL((k_sort_region_hits<kSortRegionHits, kSortThreads>), dim3(sortGrid(2)),
                             dim3(kSortThreads), 0, s, nullptr, kSortSmallHits ? nullptr : tev[2].handle, 0, regionTable(m),
                             batchScratch(m), in, out, m->mc.region_voxels, kSortSmallHits, m->pool.d_hit_mask.get(),
-                            m->d_order_counts.get());
+                            m->d_order_counts.get(), walkLdsHits());
     }
     if (kSortSmallHits)
     {
       hipExtLaunchKernelGGL((k_sort_region_hits<kSortSmallHits ? kSortSmallHits : 64u, kSortSmallThreads>),
                             dim3(sortGrid(8)), dim3(kSortSmallThreads), 0, s, nullptr, tev[2], 0,
                             regionTable(m), batchScratch(m), in, out, m->mc.region_voxels, 0u, m->pool.d_hit_mask.get(),
-                            m->d_order_counts.get());
+                            m->d_order_counts.get(), walkLdsHits());
     }
     sort_covers = need_dense ? kSortRegionHits : kSortSmallHits;
     mark(2);
@@ -223,7 +223,7 @@ struct BatchRun
                           dim3(kSortThreads), 0, s, nullptr, tev[2], 0, regionTable(m), batchScratch(m),
                           static_cast<const unsigned long long *>(m->hit_keys_a.ptr),
                           static_cast<unsigned long long *>(m->hit_keys_b.ptr), m->mc.region_voxels, kSortSmallHits,
-                          m->pool.d_hit_mask.get(), m->d_order_counts.get());
+                          m->pool.d_hit_mask.get(), m->d_order_counts.get(), walkLdsHits());
     sort_covers = kSortRegionHits;
   }
 

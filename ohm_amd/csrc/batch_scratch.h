@@ -26,7 +26,9 @@ struct BatchScratch
   uint32_t *dirty;         ///< [slot_capacity]
   uint32_t *last_use;      ///< [2 x slot_capacity] use history per slot (touchRegionUse; spill to host)
   uint32_t stamp;          ///< this batch's stamp
-  uint32_t *voxel_first_hit;  ///< [slot_capacity * region_voxels] index of a voxel's first sample in the sorted list
+  /// [slot_capacity * region_voxels] index of a voxel's first sample in the sorted list; written, and read, only for
+  /// regions with more samples than the walk stages in LDS (k_sort_region_hits, resolveFlaggedMiss)
+  uint32_t *voxel_first_hit;
   BatchInfo *info;
   struct WgRegion *wg_regions;  ///< [workgroups * kLtabSize] regions each binning workgroup feeds (k_ray_setup -> bin)
   uint32_t *wg_region_count;    ///< [workgroups]

@@ -51,8 +51,8 @@ __global__ void __launch_bounds__(256)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // k_sort_region_hits: one workgroup per touched region orders the region's samples by (voxel, ray) in LDS and records
-// each voxel's first sample.  Replaces a device-wide radix sort of all sample keys plus k_hit_bounds when no region holds
-// more than kSortRegionHits samples.
+// each voxel's first sample where the walk can ask for it.  Replaces a device-wide radix sort of all sample keys plus
+// k_hit_bounds when no region holds more than kSortRegionHits samples.
 //
 // RANKED ORDERING.  A batch of a moving sensor puts about one sample into a sampled voxel and three into the 32 voxels
 // that share a word of the sample mask, so a region's keys are placed by counting and only finished by comparing:
@@ -195,11 +195,13 @@ static_assert(kSortRegionHits <= (1u << (64 - kHitSlotShift)), "a key's final po
 /// CU) busy between its barriers, so regions of at most kSortSmallHits samples -- nearly all of them -- go to a
 /// 256-thread, 19 KiB one that runs eight per CU.  Both move kCap / kThreads = 8 staged keys per lane.
 /// `order_counts`: [0] regions ordered by rank, [1] regions ordered by the network (ohmhip_map_order_counts).
+/// `walk_lds_hits`: samples of a region the batch's walk shape stages in LDS (G::kLdsHits of k_region_walk).
 template <uint32_t kCap, int kThreads>
 __global__ void __launch_bounds__(kThreads, 8)
   k_sort_region_hits(RegionTable rt, BatchScratch bs, const unsigned long long *__restrict__ keys,
                      unsigned long long *__restrict__ sorted, int region_voxels, uint32_t min_hits,
-                     uint32_t *__restrict__ hit_mask, unsigned long long *__restrict__ order_counts)
+                     uint32_t *__restrict__ hit_mask, unsigned long long *__restrict__ order_counts,
+                     uint32_t walk_lds_hits)
 {
   constexpr uint32_t kPerLane = (kCap + uint32_t(kThreads) - 1u) / uint32_t(kThreads);
   constexpr uint32_t kWaves = uint32_t(kThreads) / 64u;
@@ -388,9 +390,14 @@ __global__ void __launch_bounds__(kThreads, 8)
       word = vi >> 5;
       if (i == 0 || hitGroup(l_keys[sortSlot(i - 1)]) != hitGroup(key))
       {
-        // First sample of its voxel: entry point for ordering misses against this voxel's samples, and the voxel's bit
-        // of the sample mask.
-        bs.voxel_first_hit[size_t(slot) * size_t(region_voxels) + vi] = begin + i;
+        // First sample of its voxel: the voxel's bit of the sample mask, and the entry point for ordering misses
+        // against this voxel's samples.  Only resolveFlaggedMiss reads the entry, and only for a region whose samples
+        // the walk cannot stage in LDS (more than `walk_lds_hits`): every other region's misses are ordered against the
+        // staged keys, and its scattered stores -- one cache line per sampled voxel -- would be written for nobody.
+        if (n > walk_lds_hits)
+        {
+          bs.voxel_first_hit[size_t(slot) * size_t(region_voxels) + vi] = begin + i;
+        }
         bits = 1u << (vi & 31);
       }
     }

@@ -7,15 +7,19 @@
 //
 // k_region_walk is register bound and fragile.  Cross-compiled for gfx950 at -O3, its six instantiations sit at
 // 128 VGPRs and spill (VGPR spills / scratch bytes; <kSpecial, kTrace, geometry>):
-//   <0,0,Full> 36 / 128   <0,0,Half> 40 / 144   <1,0,Full> 37 / 128   <1,0,Half> 41 / 144
-//   <0,1,Full> 38 / 128   <0,1,Half> 51 / 144
-// (37 / 148, 43 / 148, 38 / 152, 45 / 152, 45 / 156, 56 / 156 before round 14.)
+//   <0,0,Full> 11 / 48   <0,0,Half> 8 / 32   <1,0,Full> 11 / 48   <1,0,Half> 16 / 48
+//   <0,1,Full> 17 / 48   <0,1,Half> 16 / 48
+// (36 / 128, 40 / 144, 37 / 128, 41 / 144, 38 / 128, 51 / 144 before round 16, whose tile initialisation for a region
+// that fills the tile is a function -- initFullTile -- and whose general form no longer starts at a mask word the
+// compiler knows to be the thread's own: the lane-dependent addresses and predicates it used to hoist out of the chunk
+// loop, spill, and reload in every chunk are gone; profiles/r16_notes.md.  37 / 148, 43 / 148, 38 / 152, 45 / 152,
+// 45 / 156, 56 / 156 before round 14.)
 // Moving the prologue's count-tile initialisation loop, unchanged, into a __device__ inline function took the production
 // <0,0,Full> instantiation from 37 to 90 spilled VGPRs.  So the body of the kernel is left as one piece of text, and ANY
 // edit to it, or to a function it inlines, is checked with scripts/kernel_fingerprint.py against the parent commit
 // before it goes near a GPU: the figures above must not get worse.  Code that is new to the kernel and runs once per
-// chunk goes into a __noinline__ function (scanOrderBins, applyFullTile, flushFullTile below): written into the body,
-// the three of round 14 gave 98 spilled VGPRs, the ordering's scan alone 51 (profiles/r14_notes.md).
+// chunk goes into a __noinline__ function (scanOrderBins, applyFullTile, flushFullTile, initFullTile below): written
+// into the body, the three of round 14 gave 98 spilled VGPRs, the ordering's scan alone 51 (profiles/r14_notes.md).
 #ifndef OHMHIP_WALK_KERNEL_H
 #define OHMHIP_WALK_KERNEL_H
 
@@ -517,6 +521,44 @@ __device__ __noinline__ void flushFullTile(const LdsWord *tile, uint32_t *g_coun
   }
 }
 
+/// The count tile's initialisation for a region that fills the tile, without flag_all: every thread owns whole mask
+/// words (one in both shapes), every 4-word group of its 16 tile words exists, and the mask word is the one the thread
+/// prefetched.  Entries start at zero count with the voxel's mask flag in the top bit, at the positions tileWord() gives
+/// them, exactly as the general form in the kernel writes them.  Everything that depends on the lane -- the store
+/// addresses, the row's swizzle -- is computed here from `tid`, so the kernel keeps nothing of it alive across its chunk
+/// loop.  The swizzle's low two bits permute the words inside a 4-word group: physical word r holds logical word
+/// r ^ (swizzle & 3).  That is a swap of neighbouring 2-bit fields (bit 0) and of neighbouring 4-bit groups (bit 1) of
+/// the mask word, applied to the word once; sixteen fixed-shift decodes follow (field to the top, arithmetic shift down
+/// to bits 16 / 15, one mask).
+template <typename G>
+__device__ __noinline__ void initFullTile(LdsWord *tile, uint32_t mask_word, uint32_t tid)
+{
+  static_assert(uint32_t(G::kTileVoxels) == 32u * uint32_t(G::kThreads), "one mask word per thread");
+  const uint32_t w = tid;
+  const uint32_t swizzle = ((w >> 1) ^ (w >> 6)) & 31u;  // tileWord(w * 16) ^ (w * 16)
+  uint32_t m = mask_word;
+  uint32_t d = (m ^ (m >> 2)) & 0x33333333u & (0u - (swizzle & 1u));
+  m ^= d ^ (d << 2);
+  d = (m ^ (m >> 4)) & 0x0f0f0f0fu & (0u - ((swizzle >> 1) & 1u));
+  m ^= d ^ (d << 4);
+  // The swizzle's high bits permute the 4-word groups of the row: logical group g lies at g ^ (swizzle >> 2).
+  LdsQuad *groups = reinterpret_cast<LdsQuad *>(tile);
+  const uint32_t group = swizzle >> 2;
+#pragma unroll
+  for (uint32_t q = 0; q < 4; ++q)
+  {
+    Quad v;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r)
+    {
+      // field q * 4 + r: its low bit to bit 15, its high bit to bit 31
+      const uint32_t top = m << (30u - (q * 4u + r) * 2u);
+      v[r] = uint32_t(int32_t(top) >> 15) & 0x80008000u;
+    }
+    groups[(w * 4u + q) ^ group] = v;
+  }
+}
+
 /// kSpecial: the batch contains rays whose end voxel is part of the walk (clipped / kRfEndPointAsFree / TSDF) or
 /// kRfExcludeOrigin.  The common case (kSpecial == false) keeps those predicates out of the hot loop: every iteration
 /// of an active lane is a miss.
@@ -706,8 +748,16 @@ __global__ void __launch_bounds__(G::kThreads, G::kMinWavesPerEu) k_region_walk(
     }
     // Tile entries start at zero count with the voxel's mask flag in the top bit: one mask word covers 16 tile words,
     // half a row of the tile, which tileWord() maps onto half a row again: the 4-word groups permuted by the high bits
-    // of the row's XOR constant, the words inside a group by its low two bits.
-    for (uint32_t w = threadIdx.x; w < mask_words; w += uint32_t(G::kThreads))
+    // of the row's XOR constant, the words inside a group by its low two bits.  The common case has a body of its own
+    // (initFullTile).
+    // (The general form starts behind the last mask word when initFullTile served the region.  Written as an else
+    // branch around the unchanged loop, the call took five of the six instantiations above the parent's spill counts.)
+    const bool full_init = !args.flag_all && mc.region_voxels == G::kTileVoxels;
+    if (full_init)
+    {
+      initFullTile<G>((LdsWord *)l_counts, my_mask, threadIdx.x);
+    }
+    for (uint32_t w = full_init ? mask_words : threadIdx.x; w < mask_words; w += uint32_t(G::kThreads))
     {
       const uint32_t mword = args.flag_all ? 0xffffffffu : ((w == threadIdx.x) ? my_mask : g_mask[w]);
       const uint32_t swizzle = tileWord(w * 16u) ^ (w * 16u);
