@@ -254,10 +254,58 @@ int ohmhip_map_integrate_rays(ohmhip_map_t map, const double *rays, size_t eleme
  * passed: `rays` holds the accepted (possibly moved) origin / sample pairs and filter_flags[ray] the RayFilterFlag bits
  * the filter set (ohm/RayFilter.h:21-29: 1 invalid, 2 clipped start, 4 clipped end).  The map's built-in filter is not applied to
  * such a batch; a clipped end makes the end voxel part of the ray and suppresses the sample, as in the CPU mappers
- * (ohm/RayMapperOccupancy.cpp:209-223, ohm/RayMapperNdt.cpp:251-269). */
+ * (ohm/RayMapperOccupancy.cpp:209-223, ohm/RayMapperNdt.cpp:251-269).  Hand over accepted rays only: a ray whose flags
+ * carry kRffInvalid is neither integrated nor counted in *integrated. */
 int ohmhip_map_integrate_rays_filtered(ohmhip_map_t map, const double *rays, size_t element_count,
                                        const float *intensities, const double *timestamps, unsigned ray_flags,
                                        const unsigned char *filter_flags, size_t *integrated);
+/* GpuMap::setRayFilter with the STOCK filters of ohm/RayFilter.cpp, evaluated on the device: a chain of up to
+ * OHMHIP_MAX_RAY_FILTER_STAGES stages the map owns.  While a chain is set it stands in place of the built-in filter
+ * (ohmhip_map_config::ray_filter) for every batch the map integrates -- host pointers, device pointers, collected calls,
+ * ohmhip_map_apply_pattern -- as GpuMap::effectiveRayFilter does (ohmgpu/GpuMap.cpp:348-369, 736-746); batches of
+ * ohmhip_map_integrate_rays_filtered are the caller's and are not filtered again; ohmhip_map_rays_query and
+ * ohmhip_map_line_keys keep the built-in filter (the reference reads OccupancyMap::rayFilter() there).
+ *   GOOD            goodRayFilter(range)   RayFilter.cpp:12-34     range <= 0: no range test
+ *   CLIP            clipRayFilter(range)   RayFilter.cpp:37-57
+ *   CLIP_BOUNDED    clipBounded(box)       RayFilter.cpp:60-77, Aabb::clipLine / rayIntersect / contains (ohm/Aabb.h)
+ *   CLIP_TO_BOUNDS  clipToBounds(box)      RayFilter.cpp:80-86
+ * Stage i sees the ray as stage i - 1 left it, RayFilterFlag bits are OR-ed, the first stage that returns false ends the
+ * chain (`a(...) && b(...)` in a lambda).  A rejected ray counts as not integrated; kRffClippedEnd makes the end voxel
+ * part of the ray and suppresses the sample, as for a caller-filtered batch.  Aabb::contains is the reference's
+ * `!any(max < p) && !any(min > p)`: a NaN coordinate counts as contained.  NaN in `range` or a box is accepted (the
+ * reference has no check; its comparisons decide).  The time base of the touch-time layer still comes from the first
+ * stamp of the call as submitted.  The caller's arrays are never written: moved rays live in scratch of the map's.
+ * set: count == 0 clears the chain.  OHMHIP_ERR_INVALID_ARG for a kind outside 1..4, count above the maximum, NULL
+ * stages with count > 0, a non-zero `reserved`.  Rays waiting in the coalescing buffer are launched first, so calls that
+ * reported a count were filtered by the chain that counted them.  Not available on a partitioned / owner-computes map
+ * (OHMHIP_ERR_UNSUPPORTED, whichever is set second): routed rays would be filtered twice. */
+enum ohmhip_ray_filter_stage_kind
+{
+  OHMHIP_RFS_GOOD = 1,
+  OHMHIP_RFS_CLIP = 2,
+  OHMHIP_RFS_CLIP_BOUNDED = 3,
+  OHMHIP_RFS_CLIP_TO_BOUNDS = 4
+};
+#define OHMHIP_MAX_RAY_FILTER_STAGES 4
+typedef struct ohmhip_ray_filter_stage
+{
+  int kind;          /* ohmhip_ray_filter_stage_kind */
+  int reserved;      /* 0 */
+  double range;      /* GOOD, CLIP */
+  double box_min[3]; /* CLIP_BOUNDED, CLIP_TO_BOUNDS */
+  double box_max[3];
+} ohmhip_ray_filter_stage;
+int ohmhip_map_set_ray_filter_stages(ohmhip_map_t map, const ohmhip_ray_filter_stage *stages, unsigned count);
+/* The chain as set: *count stages (0: none), the first min(*count, capacity) of them in `out` (may be NULL). */
+int ohmhip_map_ray_filter_stages(ohmhip_map_t map, ohmhip_ray_filter_stage *out, unsigned capacity, unsigned *count);
+/* What the chain does to a batch, without touching the map: for EVERY input ray the ray as the chain leaves it
+ * (rays_out, element_count dvec3) and its RayFilterFlag byte (flags_out, one per ray; a rejected ray carries
+ * kRffInvalid = 1 and the points as the rejecting stage left them); *passed = rays kept.  Runs the device pass.  With no
+ * chain set rays come back as given, flags 0.  Outputs may be NULL.  The _device form takes device pointers. */
+int ohmhip_map_apply_ray_filter(ohmhip_map_t map, const double *rays, size_t element_count, double *rays_out,
+                                unsigned char *flags_out, size_t *passed);
+int ohmhip_map_apply_ray_filter_device(ohmhip_map_t map, const double *d_rays, size_t element_count, double *d_rays_out,
+                                       unsigned char *d_flags_out, size_t *passed);
 /* Small host batches (the reference tools present 4096 rays per call, ohmapp/OhmAppGpu.cpp:187-207) would cost a full
  * pipeline pass each.  Consecutive host-pointer batches with the same flags and the same optional arrays are therefore
  * collected in the pinned staging block and run as ONE device batch once min_rays have accumulated -- or as soon as

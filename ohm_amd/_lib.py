@@ -171,6 +171,16 @@ class MapConfig(C.Structure):
                 ("region_capacity", C.c_uint32)]
 
 
+RFS_GOOD, RFS_CLIP, RFS_CLIP_BOUNDED, RFS_CLIP_TO_BOUNDS = 1, 2, 3, 4  # OHMHIP_RFS_*
+MAX_RAY_FILTER_STAGES = 4  # OHMHIP_MAX_RAY_FILTER_STAGES
+
+
+class RayFilterStage(C.Structure):
+    """ohmhip_ray_filter_stage"""
+    _fields_ = [("kind", C.c_int), ("reserved", C.c_int), ("range", C.c_double), ("box_min", C.c_double * 3),
+                ("box_max", C.c_double * 3)]
+
+
 class MergeStats(C.Structure):
     _fields_ = [("regions_local", C.c_uint32), ("regions_union", C.c_uint32), ("regions_shared", C.c_uint32),
                 ("payload_bytes", C.c_uint64), ("key_bytes", C.c_uint64), ("ms_total", C.c_float)]
@@ -329,6 +339,10 @@ _sigs = {
     "ohmhip_map_mark_dirty": (C.c_int, [_vp, _vp, C.c_size_t]),
     "ohmhip_map_integrate_rays_filtered": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_uint, _vp,
                                                     C.POINTER(C.c_size_t)]),
+    "ohmhip_map_set_ray_filter_stages": (C.c_int, [_vp, C.POINTER(RayFilterStage), C.c_uint]),
+    "ohmhip_map_ray_filter_stages": (C.c_int, [_vp, C.POINTER(RayFilterStage), C.c_uint, C.POINTER(C.c_uint)]),
+    "ohmhip_map_apply_ray_filter": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t)]),
+    "ohmhip_map_apply_ray_filter_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t)]),
     "ohmhip_map_update_config": (C.c_int, [_vp, C.POINTER(MapConfig)]),
     "ohmhip_map_set_batch_coalescing": (C.c_int, [_vp, C.c_size_t]),
     "ohmhip_map_set_async_launch": (C.c_int, [_vp, C.c_int]),

@@ -58,6 +58,9 @@ struct BatchRun
   /// room; k_pad_events); the true count is on its way to the host and is looked at once the replay has been launched.
   bool events_speculated = false;
   uint32_t spec_events = 0;
+  /// The map has a ray-filter chain and the caller did not filter the batch: the rays as presented.  d_rays then points
+  /// at this parity's copy of the map's chain scratch, which k_ray_filter fills ahead of the set-up pass (frontHalf).
+  const double *unfiltered_rays = nullptr;
 
   /// Samples of a region the walk kernel's shape stages in LDS (WalkFull / WalkHalf).
   uint32_t walkLdsHits() const { return uint32_t(m->walk_half ? WalkHalf::kLdsHits : WalkFull::kLdsHits); }
@@ -79,6 +82,21 @@ struct BatchRun
     // The other copy of the doubled per-batch scratch.
     m->parity ^= 1u;
     ray_blocks = (n_rays + 255) / 256;
+    if (m->ray_chain.count && !m->mc.batch_filter_flags)
+    {
+      // The chain's pass writes the moved rays and the flag bytes into the map's scratch -- never into the caller's
+      // array -- and every kernel of the batch from the set-up pass on reads those.  The source stays as presented, so
+      // a repeated attempt (pool growth, spill) and a batch presented again as halves filter the same rays again.
+      // (integrateRaysDevice puts batch_filter_flags back when the call ends.)
+      for (int p = 0; p < 2; ++p)
+      {
+        OHMHIP_CHECK(m->ray_chain.rays[p].ensure(size_t(n_rays) * 48, false, s));
+        OHMHIP_CHECK(m->ray_chain.flags[p].ensure(size_t(n_rays), false, s));
+      }
+      unfiltered_rays = d_rays;
+      d_rays = static_cast<const double *>(m->ray_chain.rays[m->parity].ptr);
+      m->mc.batch_filter_flags = static_cast<const unsigned char *>(m->ray_chain.flags[m->parity].ptr);
+    }
     // Binning launch shape: 1024 rays per 512-thread workgroup for large batches; small batches use smaller workgroups
     // with as many rays as threads so they still cover the CUs.
     bin_rays_per_block = m->bin_rays_per_block;
@@ -295,6 +313,14 @@ struct BatchRun
     {
       OHMHIP_CHECK(hipEventRecord(tev[0], f));
       mark(0);
+    }
+    if (unfiltered_rays)
+    {
+      // Behind the wait for the batch that last read this parity's chain scratch (batch_done_event above).
+      hipLaunchKernelGGL(k_ray_filter, dim3(ray_blocks), dim3(256), 0, f,
+                         static_cast<const ohmhip_ray_filter_stage *>(m->ray_chain.d_stages.ptr), m->ray_chain.count,
+                         unfiltered_rays, n_rays, const_cast<double *>(d_rays),
+                         const_cast<unsigned char *>(m->mc.batch_filter_flags), static_cast<uint32_t *>(nullptr));
     }
     if (bin_tab_mask < kLtabSmall)
     {

@@ -528,6 +528,20 @@ struct ohmhip_map_s
   /// Host-pointer batches smaller than this are collected and run as one device batch (0: every host batch is launched
   /// by the call that presents it).  On by default: the reference tools present 4096 rays per call.
   size_t coalesce_min_rays = size_t(1) << 16;
+  /// The ray-filter chain (ohmhip_map_set_ray_filter_stages; ray_filter_chain.h, ray_filter_kernels.h): while count > 0 it
+  /// stands in place of the built-in filter for every batch the caller has not filtered.  It does not ride in MapConst:
+  /// k_ray_filter and k_count_passed get the device copy through arguments of their own.
+  struct RayFilterChain
+  {
+    ohmhip_ray_filter_stage stages[OHMHIP_MAX_RAY_FILTER_STAGES] = {};  ///< host copy: the staging threads' count
+    uint32_t count = 0;
+    DevBuf d_stages;  ///< device copy, rewritten only with nothing pending or in flight on the front / copy streams
+    /// Per batch parity: the rays as the chain leaves them and their flag bytes.  Readers are the batch's set-up pass and
+    /// its apply / replay kernels (sample points), so a copy is free again when the batch after the next starts -- the
+    /// rule of the other doubled per-batch scratch (BatchRun::frontHalf waits for batch_done_event[parity]).
+    DevBuf rays[2], flags[2];
+    DevBuf q_rays, q_out, q_flags, q_passed;  ///< ohmhip_map_apply_ray_filter: its own buffers, like the other queries
+  } ray_chain;
 
   // host mirror of the region table
   std::unordered_map<uint64_t, uint32_t> region_slots;

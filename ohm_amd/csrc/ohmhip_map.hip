@@ -6,6 +6,7 @@
 #include "apply_kernels.h"
 #include "batch_scratch.h"
 #include "pool_kernels.h"
+#include "ray_filter_kernels.h"
 #include "ray_front_kernels.h"
 #include "region_table.h"
 #include "sample_sort_kernels.h"
@@ -678,6 +679,12 @@ try
     OHMHIP_CHECK(m->walks_buf[p].ensure(sizeof(RayWalk) * n, false, s));
     OHMHIP_CHECK(m->wg_regions[p].ensure(sizeof(WgRegion) * size_t(std::min<size_t>(blocks, (n + kBinRaysPerBlock - 1) / kBinRaysPerBlock * 8)) * kLtabSize, false, s));
     OHMHIP_CHECK(m->wg_region_count[p].ensure(sizeof(uint32_t) * size_t(blocks), false, s));
+    if (m->ray_chain.count)
+    {
+      // (a map with a ray-filter chain: the pass's output; a chain set later sizes it from walks_buf, ray_filter_impl.h)
+      OHMHIP_CHECK(m->ray_chain.rays[p].ensure(n * 48, false, s));
+      OHMHIP_CHECK(m->ray_chain.flags[p].ensure(n, false, s));
+    }
   }
   const bool occupancy = m->config.mode == OHMHIP_MODE_OCCUPANCY;
   // 16 events per ray -- the threshold above which sizeBuffers() grows the list on measured demand only -- and never more
@@ -972,6 +979,10 @@ try
   {
     return OHMHIP_ERR_INVALID_ARG;
   }
+  if (world_size > 1 && m->ray_chain.count)
+  {
+    return OHMHIP_ERR_UNSUPPORTED;  // a ray-filter chain and routed rays do not combine (ohmhip_map_set_ray_filter_stages)
+  }
   ohmhip_map_sync(m);
   if (m->slots_committed != 0)
   {
@@ -1030,6 +1041,7 @@ OHMHIP_ABI_CATCH
 
 #include "merge_impl.h"
 #include "partition_impl.h"
+#include "ray_filter_impl.h"
 #include "read_side.h"
 #include "query_impl.h"
 #include "clearance_impl.h"

@@ -250,6 +250,10 @@ try
       }
     }
   }
+  if (on && m->ray_chain.count)
+  {
+    return OHMHIP_ERR_UNSUPPORTED;  // a ray-filter chain and routed rays do not combine (ohmhip_map_set_ray_filter_stages)
+  }
   OHMHIP_CHECK(ohmhip_map_sync(m));
   if (m->slots_committed != 0 || !m->spilled.empty())
   {

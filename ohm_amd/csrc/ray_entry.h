@@ -209,7 +209,8 @@ try
     MapConst count_mc = m->mc;
     count_mc.batch_filter_flags = nullptr;
     hipLaunchKernelGGL(k_count_passed, dim3(1), dim3(1024), 0, cs, count_mc, static_cast<const double *>(staged),
-                       uint32_t(n_rays), ray_flags, m->h_passed.dev);
+                       uint32_t(n_rays), ray_flags, m->h_passed.dev,
+                       static_cast<const ohmhip_ray_filter_stage *>(m->ray_chain.d_stages.ptr), m->ray_chain.count);
     OHMHIP_CHECK(hipEventRecord(m->ev_passed, cs));
     OHMHIP_CHECK(hipEventSynchronize(m->ev_passed));  // (also: the caller's arrays have been copied)
     *integrated = size_t(*m->h_passed) * 2;
@@ -278,13 +279,30 @@ int validateBatchRequest(ohmhip_map_t m, unsigned ray_flags)
 /// Rays of a host batch the map's ray filter accepts: what the device counts as integrated (k_ray_setup, kRwPassed),
 /// computed on the host with the same arithmetic (walk_device.h: filterRay) so that a call can report it without
 /// waiting for the device -- or for a batch that has not even been launched yet.
-size_t hostFilterCount(const MapConst &mc, const double *rays, size_t n_rays, bool caller_filtered)
+/// With a ray-filter chain set the verdict is the chain's: the same function the device pass runs (ray_filter_chain.h).
+size_t hostFilterCount(const MapConst &mc, const ohmhip_map_s::RayFilterChain &chain, const double *rays, size_t n_rays,
+                       bool caller_filtered)
 {
-  if (caller_filtered || mc.filter_mode == OHMHIP_FILTER_NONE)
+  if (caller_filtered)
   {
     return n_rays;
   }
   size_t passed = 0;
+  if (chain.count)
+  {
+    for (size_t i = 0; i < n_rays; ++i)
+    {
+      double start[3] = { rays[6 * i], rays[6 * i + 1], rays[6 * i + 2] };
+      double end[3] = { rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5] };
+      unsigned filter_flags;
+      passed += rayFilterChain(chain.stages, chain.count, start, end, &filter_flags) ? 1u : 0u;
+    }
+    return passed;
+  }
+  if (mc.filter_mode == OHMHIP_FILTER_NONE)
+  {
+    return n_rays;
+  }
   for (size_t i = 0; i < n_rays; ++i)
   {
     const double *r = rays + 6 * i;
@@ -331,11 +349,13 @@ size_t copyRaysCountInRange(double *dst, const double *rays, size_t n_rays, doub
 
 /// Copy rays [first, last) of a host block into the pinned block at `dst` and count the rays the filter accepts in the
 /// same sweep: the range is cut into pieces that stay in the core's L2 between the copy and the count.
-size_t stageRayRange(const MapConst &mc, char *dst, const double *rays, size_t first, size_t last, bool caller_filtered)
+size_t stageRayRange(const MapConst &mc, const ohmhip_map_s::RayFilterChain &chain, char *dst, const double *rays,
+                     size_t first, size_t last, bool caller_filtered)
 {
   static constexpr size_t kPiece = 4096;  // rays per copy+count piece (192 KiB)
   const double range2 = mc.filter_range * mc.filter_range;
-  if (!caller_filtered && mc.filter_mode == OHMHIP_FILTER_GOOD && mc.filter_range > 0 && std::isfinite(range2))
+  if (!caller_filtered && !chain.count && mc.filter_mode == OHMHIP_FILTER_GOOD && mc.filter_range > 0 &&
+      std::isfinite(range2))
   {
     return copyRaysCountInRange(reinterpret_cast<double *>(dst + first * 48), rays + first * 6, last - first, range2);
   }
@@ -344,7 +364,7 @@ size_t stageRayRange(const MapConst &mc, char *dst, const double *rays, size_t f
   {
     const size_t n = std::min<size_t>(kPiece, last - at);
     std::memcpy(dst + at * 48, rays + at * 6, n * 48);
-    passed += hostFilterCount(mc, rays + at * 6, n, caller_filtered);
+    passed += hostFilterCount(mc, chain, rays + at * 6, n, caller_filtered);
   }
   return passed;
 }
@@ -370,15 +390,15 @@ size_t stageRaysAndCount(ohmhip_map_t m, char *dst, const double *rays, size_t n
   const unsigned n_workers = unsigned(std::min<size_t>(kStageThreads, n_rays / kStagePerThread));
   if (n_workers <= 1)
   {
-    return stageRayRange(mc, dst, rays, 0, n_rays, caller_filtered);
+    return stageRayRange(mc, m->ray_chain, dst, rays, 0, n_rays, caller_filtered);
   }
   const size_t n_pieces = (n_rays + kUploadPiece - 1) / kUploadPiece;
   std::atomic<size_t> next(0), passed(0);
   auto work = [&](unsigned) {
     for (size_t p = next.fetch_add(1); p < n_pieces; p = next.fetch_add(1))
     {
-      passed.fetch_add(stageRayRange(mc, dst, rays, p * kUploadPiece, std::min(n_rays, (p + 1) * kUploadPiece),
-                                     caller_filtered));
+      passed.fetch_add(stageRayRange(mc, m->ray_chain, dst, rays, p * kUploadPiece,
+                                     std::min(n_rays, (p + 1) * kUploadPiece), caller_filtered));
     }
   };
   StagePool &pool = stagePool(m);
@@ -406,8 +426,8 @@ int stageRaysAndUpload(ohmhip_map_t m, ohmhip_map_s::RaySlot &sl, const double *
   }
   std::atomic<size_t> next(0), passed(0);
   auto stage_piece = [&](size_t p) {
-    passed.fetch_add(stageRayRange(mc, dst, rays, p * kUploadPiece, std::min(n_rays, (p + 1) * kUploadPiece),
-                                   caller_filtered));
+    passed.fetch_add(stageRayRange(mc, m->ray_chain, dst, rays, p * kUploadPiece,
+                                   std::min(n_rays, (p + 1) * kUploadPiece), caller_filtered));
     done[p].store(1, std::memory_order_release);
   };
   auto work = [&](unsigned) {
@@ -542,6 +562,12 @@ int integrateRaysHost(ohmhip_map_t m, const double *rays, size_t element_count, 
   if (filter_flags)
   {
     std::memcpy(slotFilterFlags(sl) + m->pending_rays, filter_flags, n_rays);
+    // A ray the caller flagged kRffInvalid all the same is not integrated by the device (walk_device.h: filterRay): the
+    // host's count says so too.
+    for (size_t i = 0; i < n_rays; ++i)
+    {
+      passed -= (filter_flags[i] & kRffInvalid) ? 1u : 0u;
+    }
   }
   m->pending_flags = ray_flags;
   m->pending_fflags = filter_flags != nullptr;

@@ -16,6 +16,7 @@
 #define OHMHIP_RAY_FRONT_KERNELS_H
 
 #include "batch_scratch.h"
+#include "ray_filter_chain.h"
 #include "region_table.h"
 #include "walk_device.h"
 
@@ -1052,9 +1053,11 @@ __global__ void __launch_bounds__(kBinThreads)
 
 /// The number of rays of [rays, rays + n) the map's ray filter passes: what an integrate call reports for its own
 /// rays when they only run later, with a collected batch (one workgroup; the count goes straight to pinned memory).
+/// With a ray-filter chain set (n_stages > 0) the verdict is the chain's (ray_filter_chain.h), as k_ray_filter will
+/// give it when the batch runs.
 __global__ void __launch_bounds__(1024)
   k_count_passed(MapConst mc, const double *__restrict__ rays, uint32_t n_rays, unsigned ray_flags,
-                 uint32_t *__restrict__ host_count)
+                 uint32_t *__restrict__ host_count, const ohmhip_ray_filter_stage *__restrict__ stages, uint32_t n_stages)
 {
   __shared__ uint32_t s_ok;
   if (threadIdx.x == 0)
@@ -1072,6 +1075,12 @@ __global__ void __launch_bounds__(1024)
     {
       start[a] = rays[size_t(ray) * 6 + a];
       end[a] = rays[size_t(ray) * 6 + 3 + a];
+    }
+    if (n_stages)
+    {
+      unsigned filter_flags;
+      my_ok += rayFilterChain(stages, n_stages, start, end, &filter_flags) ? 1u : 0u;
+      continue;
     }
     setupRay(mc, start, end, ray_flags, rw, ray);
     my_ok += (rw.flags & kRwPassed) ? 1u : 0u;

@@ -257,8 +257,10 @@ __device__ inline bool filterRay(const MapConst &mc, const double start[3], doub
   {
     // Filtered (and possibly moved) by the caller's RayFilterFunction: only the flag is consumed here -- kRffClippedEnd
     // makes the end voxel part of the ray and suppresses the sample (ohm/RayMapperOccupancy.cpp:209-223).
-    clipped_end = (mc.batch_filter_flags[ray] & 4u) != 0;  // kRffClippedEnd, ohm/RayFilter.h:21-29
-    return true;
+    // kRffInvalid: a ray the map's device filter chain rejected (k_ray_filter writes this array then) is not passed.
+    const unsigned filter_flags = mc.batch_filter_flags[ray];
+    clipped_end = (filter_flags & 4u) != 0;  // kRffClippedEnd, ohm/RayFilter.h:21-29
+    return (filter_flags & 1u) == 0;
   }
   if (mc.filter_mode == OHMHIP_FILTER_NONE)
   {

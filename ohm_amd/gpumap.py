@@ -20,6 +20,7 @@ import time
 import numpy as np
 
 from . import _lib as L
+from . import rayfilter as _rayfilter
 
 
 class RayFlag(enum.IntFlag):
@@ -363,17 +364,64 @@ class GpuMap(RayMapper):
     # GpuMap::setRayFilter / rayFilter / effectiveRayFilter / clearRayFilter (ohmgpu/GpuMap.cpp:348-369).  A filter is a
     # callable of the vectorised form described in ohm_amd/rayfilter.py; without one the map's built-in filter
     # (OccupancyMap.ray_filter) runs on the device.
+    # A rayfilter.DeviceRayFilter (RF.on_device(...): a chain of the stock filters) is set on the device instead: the map
+    # evaluates it for every batch -- integrateRays, integrateRaysDevice, collected calls, patterns -- with no host pass
+    # (include/ohmhip.h: ohmhip_map_set_ray_filter_stages).  Not on a partitioned map; RaysQueryGpu keeps the built-in
+    # filter.
     def setRayFilter(self, ray_filter):
+        if isinstance(ray_filter, _rayfilter.DeviceRayFilter):
+            self._set_device_chain(ray_filter.stages)
+            self._device_ray_filter = ray_filter
+            self._ray_filter = None
+            return
+        if getattr(self, "_device_ray_filter", None) is not None:
+            self._set_device_chain(())
+        self._device_ray_filter = None
         self._ray_filter = ray_filter
 
+    def _set_device_chain(self, stages):
+        records = (L.RayFilterStage * max(len(stages), 1))()
+        for record, stage in zip(records, stages):
+            record.kind, record.reserved, record.range = stage.kind, 0, stage.range
+            record.box_min[:] = [float(v) for v in stage.box.min]
+            record.box_max[:] = [float(v) for v in stage.box.max]
+        L.check(L.lib.ohmhip_map_set_ray_filter_stages(self._handle, records if stages else None, len(stages)),
+                "set_ray_filter_stages")
+
     def rayFilter(self):
-        return getattr(self, "_ray_filter", None)
+        device = getattr(self, "_device_ray_filter", None)
+        return device if device is not None else getattr(self, "_ray_filter", None)
 
     def effectiveRayFilter(self):
         return self.rayFilter()
 
     def clearRayFilter(self):
+        if getattr(self, "_device_ray_filter", None) is not None:
+            self._set_device_chain(())
+        self._device_ray_filter = None
         self._ray_filter = None
+
+    def applyRayFilterDevice(self, d_rays_ptr, element_count, d_rays_out_ptr=None, d_flags_out_ptr=None):
+        """applyRayFilter on arrays resident in HBM: raw device pointers to element_count dvec3 in and out and to one
+        flag byte per ray (the outputs may be None).  Returns the number of rays kept."""
+        done = C.c_size_t(0)
+        L.check(L.lib.ohmhip_map_apply_ray_filter_device(self._handle, d_rays_ptr, element_count, d_rays_out_ptr,
+                                                         d_flags_out_ptr, C.byref(done)), "apply_ray_filter_device")
+        return int(done.value)
+
+    def applyRayFilter(self, rays):
+        """What the device chain does to `rays` ((2N, 3) origin / sample pairs) without touching the map: (keep, rays as
+        the chain leaves them, RayFilterFlag bytes), every ray reported (ohmhip_map_apply_ray_filter)."""
+        done = C.c_size_t(0)
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 3)
+        n = rays.shape[0] // 2
+        out = np.empty((2 * n, 3), dtype=np.float64)
+        flags = np.empty(n, dtype=np.uint8)
+        L.check(L.lib.ohmhip_map_apply_ray_filter(self._handle, rays.ctypes.data, rays.shape[0], out.ctypes.data,
+                                                  flags.ctypes.data, C.byref(done)), "apply_ray_filter")
+        keep = (flags & 1) == 0
+        assert int(keep.sum()) == int(done.value)
+        return keep, out, flags
 
     def integrateRays(self, rays, intensities=None, timestamps=None, ray_update_flags=RayFlag.kRfDefault):
         """rays: (2N, 3) float64 origin/sample pairs.  Returns number of POINTS integrated (2 per ray), 0 on failure
@@ -388,7 +436,8 @@ class GpuMap(RayMapper):
         ints = None if intensities is None else np.ascontiguousarray(intensities, dtype=np.float32)
         ts = None if timestamps is None else np.ascontiguousarray(timestamps, dtype=np.float64)
         done = C.c_size_t(0)
-        if self.rayFilter() is not None:
+        host_filter = getattr(self, "_ray_filter", None)  # (a DeviceRayFilter is the device's: nothing to do here)
+        if host_filter is not None:
             # The reference runs the RayFilterFunction per ray on the host before upload (ohmgpu/GpuMap.cpp:736-746):
             # rejected rays are dropped, the others go on with their (possibly moved) end points and filter flags.
             if ts is not None and len(ts) and not getattr(self, "_time_base_checked", False):
@@ -398,7 +447,7 @@ class GpuMap(RayMapper):
                 if self.firstRayTime() < 0:
                     self.setFirstRayTime(ts[0])
                 self._time_base_checked = True
-            keep, starts, ends, fflags = self.rayFilter()(rays[0::2].copy(), rays[1::2].copy())
+            keep, starts, ends, fflags = host_filter(rays[0::2].copy(), rays[1::2].copy())
             keep = np.asarray(keep, dtype=bool)
             n_keep = int(keep.sum())
             if n_keep == 0:

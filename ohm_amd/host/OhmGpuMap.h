@@ -230,6 +230,77 @@ inline bool clipToBounds(dvec3 * /*start*/, dvec3 *end, unsigned *filter_flags, 
   return true;
 }
 
+/// A chain of up to OHMHIP_MAX_RAY_FILTER_STAGES of the stock filters above for GpuMap::setRayFilter: evaluated on the
+/// DEVICE for every batch the map integrates, in place of the map's built-in filter (include/ohmhip.h:
+/// ohmhip_map_set_ray_filter_stages).  Stage i sees the ray as stage i - 1 left it, flags are OR-ed, the first stage that
+/// rejects ends the chain -- `a(...) && b(...)` in a RayFilterFunction lambda.  Calling it runs the same chain on the
+/// host (Aabb::contains above has the reference's form already: a NaN coordinate counts as contained); a rejected ray
+/// carries kRffInvalid.
+class DeviceRayFilter
+{
+public:
+  DeviceRayFilter &goodRay(double max_range = 0.0) { return add(OHMHIP_RFS_GOOD, max_range, nullptr); }
+  DeviceRayFilter &clipRay(double max_length) { return add(OHMHIP_RFS_CLIP, max_length, nullptr); }
+  DeviceRayFilter &clipBounded(const Aabb &box) { return add(OHMHIP_RFS_CLIP_BOUNDED, 0.0, &box); }
+  DeviceRayFilter &clipToBounds(const Aabb &box) { return add(OHMHIP_RFS_CLIP_TO_BOUNDS, 0.0, &box); }
+  /// False once more stages were added than the device takes (setRayFilter then fails).
+  bool valid() const { return !overflow_; }
+  const std::vector<ohmhip_ray_filter_stage> &stages() const { return stages_; }
+
+  bool operator()(dvec3 *start, dvec3 *end, unsigned *filter_flags) const
+  {
+    for (const ohmhip_ray_filter_stage &st : stages_)
+    {
+      const Aabb box(dvec3{ st.box_min[0], st.box_min[1], st.box_min[2] }, dvec3{ st.box_max[0], st.box_max[1], st.box_max[2] });
+      bool keep = true;
+      switch (st.kind)
+      {
+      case OHMHIP_RFS_GOOD:
+        keep = goodRayFilter(start, end, filter_flags, st.range);
+        break;
+      case OHMHIP_RFS_CLIP:
+        keep = clipRayFilter(start, end, filter_flags, st.range);
+        break;
+      case OHMHIP_RFS_CLIP_BOUNDED:
+        keep = ohm::clipBounded(start, end, filter_flags, box);
+        break;
+      default:
+        keep = ohm::clipToBounds(start, end, filter_flags, box);
+        break;
+      }
+      if (!keep)
+      {
+        *filter_flags |= kRffInvalid;
+        return false;
+      }
+    }
+    return true;
+  }
+
+private:
+  DeviceRayFilter &add(int kind, double range, const Aabb *box)
+  {
+    if (stages_.size() >= OHMHIP_MAX_RAY_FILTER_STAGES)
+    {
+      overflow_ = true;
+      return *this;
+    }
+    ohmhip_ray_filter_stage st = {};
+    st.kind = kind;
+    st.range = range;
+    if (box)
+    {
+      const dvec3 &lo = box->minExtents(), &hi = box->maxExtents();
+      st.box_min[0] = lo.x, st.box_min[1] = lo.y, st.box_min[2] = lo.z;
+      st.box_max[0] = hi.x, st.box_max[1] = hi.y, st.box_max[2] = hi.z;
+    }
+    stages_.push_back(st);
+    return *this;
+  }
+  std::vector<ohmhip_ray_filter_stage> stages_;
+  bool overflow_ = false;
+};
+
 /// ohm/MapProbability.h:20-36 (float)
 inline float probabilityToValue(float probability) { return std::log(probability / (1.0f - probability)); }
 inline float valueToProbability(float value)
@@ -433,10 +504,53 @@ public:
   /// ohmgpu/GpuMap.cpp:348-369.  With a filter set, integrateRays() runs it per ray on the host, as the reference does
   /// (GpuMap.cpp:736-746), and hands the surviving rays and their RayFilterFlag bits to the device; without one the
   /// map's built-in filter (OccupancyMap::setRayFilter(mode, range)) runs on the device.
-  void setRayFilter(const RayFilterFunction &ray_filter) { ray_filter_ = ray_filter; }
+  void setRayFilter(const RayFilterFunction &ray_filter)
+  {
+    clearDeviceRayFilter();
+    ray_filter_ = ray_filter;
+  }
+  /// A chain of the stock filters, evaluated on the device for every batch -- host pointers, device buffers, collected
+  /// calls -- with no host pass (ohmhip_map_set_ray_filter_stages).  Returns false (lastStatus()) when the chain is
+  /// refused: too many stages, a partitioned map.  rayFilter() is empty while a device chain is set.
+  bool setRayFilter(const DeviceRayFilter &ray_filter)
+  {
+    if (!gpuOk() || !ray_filter.valid())
+    {
+      last_status_ = OHMHIP_ERR_INVALID_ARG;
+      return false;
+    }
+    const std::vector<ohmhip_ray_filter_stage> &stages = ray_filter.stages();
+    last_status_ = ohmhip_map_set_ray_filter_stages(handle_, stages.data(), unsigned(stages.size()));
+    if (last_status_ != OHMHIP_OK)
+    {
+      return false;
+    }
+    device_ray_filter_ = ray_filter;
+    ray_filter_ = RayFilterFunction();
+    return true;
+  }
   const RayFilterFunction &rayFilter() const { return ray_filter_; }
   const RayFilterFunction &effectiveRayFilter() const { return ray_filter_; }
-  void clearRayFilter() { ray_filter_ = RayFilterFunction(); }
+  const DeviceRayFilter &deviceRayFilter() const { return device_ray_filter_; }
+  void clearRayFilter()
+  {
+    clearDeviceRayFilter();
+    ray_filter_ = RayFilterFunction();
+  }
+  /// What the device chain does to `rays` without touching the map: every ray as the chain leaves it and its
+  /// RayFilterFlag byte (rejected: kRffInvalid); returns the number of rays kept (ohmhip_map_apply_ray_filter).
+  size_t applyRayFilter(const dvec3 *rays, size_t element_count, std::vector<dvec3> &rays_out,
+                        std::vector<unsigned char> &flags_out)
+  {
+    rays_out.assign(element_count & ~size_t(1), dvec3{ 0, 0, 0 });
+    flags_out.assign(element_count / 2, 0);
+    size_t passed = 0;
+    last_status_ = gpuOk() ? ohmhip_map_apply_ray_filter(handle_, reinterpret_cast<const double *>(rays), element_count,
+                                                         reinterpret_cast<double *>(rays_out.data()), flags_out.data(),
+                                                         &passed) :
+                             OHMHIP_ERR_INVALID_ARG;
+    return (last_status_ == OHMHIP_OK) ? passed : 0;
+  }
 
   using RayMapper::integrateRays;
   /// ohmgpu/GpuMap.cpp:416: returns points integrated, 0 on failure (gpuOk() false, device error).
@@ -1162,7 +1276,16 @@ protected:
   ohmhip_voxel_edit_stats last_edit_stats_{};
   size_t last_partial_ = 0;
   unsigned partition_world_ = 1;
+  void clearDeviceRayFilter()
+  {
+    if (!device_ray_filter_.stages().empty() && gpuOk())
+    {
+      last_status_ = ohmhip_map_set_ray_filter_stages(handle_, nullptr, 0);
+    }
+    device_ray_filter_ = DeviceRayFilter();
+  }
   RayFilterFunction ray_filter_;
+  DeviceRayFilter device_ray_filter_;  ///< the chain set on the device (empty: none)
   bool time_base_checked_ = false;  ///< a stamped call under a host filter has seen to the time base
   ohmhip_map_config cfg_;
   GpuCache cache_view_{ this };

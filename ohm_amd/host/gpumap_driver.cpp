@@ -268,6 +268,52 @@ int modeClipBox(const Args &args)
   return finishIntegration(args, map, *gpu_map, integrateInBatches(*gpu_map, rays, args.batch_rays), rays.size());
 }
 
+/// occchain: GpuMap::setRayFilter(DeviceRayFilter) -- goodRay(6) then clipBounded on the box (-1, -1, -0.5)-(2, 1.5, 1),
+/// evaluated on the device -- on a map with a mean layer and 16^3 regions; the rays in host-pointer calls of batch_rays.
+/// out: u64 points the calls reported, u64 rays applyRayFilter kept, its flag byte per ray, the map dump.  Also checked
+/// here: the chain's host form gives applyRayFilter's verdicts, and clearRayFilter empties the device chain.
+int modeChain(const Args &args)
+{
+  const std::vector<ohm::dvec3> rays = readRays(args.input);
+  ohm::OccupancyMap map = hostMap(args.resolution, true, 16);
+  const std::unique_ptr<ohm::GpuMap> gpu_map = makeGpuMap<ohm::GpuMap>(map, args);
+  const ohm::Aabb box(ohm::dvec3{ -1.0, -1.0, -0.5 }, ohm::dvec3{ 2.0, 1.5, 1.0 });
+  ohm::DeviceRayFilter chain;
+  chain.goodRay(6.0).clipBounded(box);
+  check(gpu_map->setRayFilter(chain) && !gpu_map->rayFilter() && gpu_map->deviceRayFilter().stages().size() == 2u,
+        kFailedCall);
+  std::vector<ohm::dvec3> moved;
+  std::vector<unsigned char> flags;
+  const size_t kept = gpu_map->applyRayFilter(rays.data(), rays.size(), moved, flags);
+  check(gpu_map->lastStatus() == OHMHIP_OK, kFailedCall);
+  size_t host_kept = 0;
+  for (size_t i = 0; i + 1 < rays.size(); i += 2)
+  {
+    ohm::dvec3 start = rays[i], end = rays[i + 1];
+    unsigned host_flags = 0;
+    const bool ok = chain(&start, &end, &host_flags);
+    host_kept += ok ? 1u : 0u;
+    check(host_flags == flags[i / 2] && std::memcmp(&start, &moved[i], sizeof(start)) == 0 &&
+            std::memcmp(&end, &moved[i + 1], sizeof(end)) == 0,
+          kUnexpected);
+  }
+  check(host_kept == kept, kUnexpected);
+  const size_t total = integrateInBatches(*gpu_map, rays, args.batch_rays);
+  gpu_map->syncVoxels();
+  gpu_map->clearRayFilter();
+  unsigned stages_left = 99;
+  check(ohmhip_map_ray_filter_stages(gpu_map->handle(), nullptr, 0, &stages_left) == OHMHIP_OK && stages_left == 0u,
+        kUnexpected);
+  std::printf("integrated %zu of %llu points, %zu kept by the chain, %zu regions\n", total,
+              (unsigned long long)rays.size(), kept, map.regionCount());
+  OutFile out(args.output);
+  out.value(uint64_t(total));
+  out.value(uint64_t(kept));
+  out.array(flags);
+  writeRegionDump(out, map);
+  return (total == 2 * kept) ? kOk : kUnexpected;
+}
+
 /// The rays in calls of `batch_rays` rays (0: one call), each written to the start of `device_rays`, which grows to hold
 /// it; each(points in the call).
 void forEachDeviceBatch(const std::vector<ohm::dvec3> &rays, size_t batch_rays, gputil::Buffer &device_rays,
@@ -1220,6 +1266,7 @@ const Mode kModes[] = {
   { "occcoalesce", &modeCoalesce, true },
   { "occowner", &modeOwner, true },
   { "occclipbox", &modeClipBox, true },
+  { "occchain", &modeChain, true },
   { "occpart", &modePartition, true },
   { "occpartint", &modePartitionedIntegrator, true },
   { "transform", &modeTransform, true },
