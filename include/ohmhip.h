@@ -1409,6 +1409,58 @@ OHMHIP_EXPERIMENTAL int ohmhip_map_integrate_voxels_device(ohmhip_map_t map, con
                                                            const void *d_keys10, const double *d_points_xyz,
                                                            size_t count, ohmhip_voxel_edit_stats *stats);
 
+/* LAYER CHANGES.  OccupancyMap::updateLayout(new_layout, preserve_map) and the add*Layer calls built on it
+ * (ohm/OccupancyMap.cpp:521-682, MapChunk::updateLayout ohm/MapChunk.cpp:93-143) on a live device map: the layer set
+ * given to ohmhip_map_create changes, the voxels of the layers in both sets stay where they are.  `layers` is a mask of
+ * OHMHIP_LAYER_BIT values; the map's mode never changes here.  tests/layout_ref.py restates the chunk and the store
+ * record rules on the CPU.
+ *  U1 order: the map is settled first, as every observer does it: rays collected from earlier calls are launched --
+ *     under the OLD layer set -- and an asynchronous launch is finished.  The call is blocking.  Batches presented
+ *     afterwards see the new set.
+ *  U2 content: every region the map holds -- resident, in the host store (SPILL TO HOST), every tile of a tiled region
+ *     (LARGE REGIONS) -- keeps, byte for byte, its block of every layer in both sets.  Every added layer holds its clear
+ *     value in every region (+inf for occupancy, -1 for clearance, 0 otherwise), and in every unassigned slot, so a
+ *     region created later starts cleared.  A removed layer's memory is released: removing a layer and adding it again
+ *     yields a cleared layer, never the old bytes.  Afterwards the map behaves through every entry point like a map
+ *     created with the new set that received the common layers' blocks through ohmhip_map_write_regions -- the
+ *     ordered-replay mask of an NDT or TSDF map included, which is untouched.
+ *  U3 no copy of what stays: for every retained layer ohmhip_map_device_layer_ptr returns the same pointer and stride
+ *     before and after.  Beyond the added layers and the scratch tied to them (the traversal layer's accumulator) the
+ *     call takes no device memory proportional to the map.  Everything new is allocated before anything old is
+ *     released: a failed allocation leaves the map exactly as it was, OHMHIP_ERR_CAPACITY with all of *stats zero.
+ *  U4 host store: the record layout follows the set.  Every record in use is rewritten into the new layout -- common
+ *     layers and the mask row copied, added layers cleared, the region's dirty bits and use stamp kept; the
+ *     write-back's pre-cleaned copies are void; free records of the old size are not handed out again.
+ *  U5 memory limit: the cost of a region (ohmhip_cache_stats::bytes_per_region) follows the new set.  If the resident
+ *     regions no longer fit the limit and spilling is on, the regions the spill policy would evict next move to the
+ *     store first (counted in regions_evicted); with spilling off: OHMHIP_ERR_CAPACITY, map unchanged.  The pool keeps
+ *     its slots (U3); the batches that follow keep no more regions resident than the limit is worth under the new set,
+ *     until ohmhip_map_set_memory_limit sets a limit anew.
+ *  U6 bookkeeping: dirty bits are unchanged.  Adding the clearance layer leaves every region unwritten: all regions are
+ *     stale for ohmhip_map_clearance_stale_regions; removing it forgets that bookkeeping.  Adding the traversal layer
+ *     allocates its accumulator, zeroed; removing the layer frees it.
+ *  U7 required layers, OHMHIP_ERR_UNSUPPORTED if any would go: OHMHIP_MODE_OCCUPANCY occupancy; OHMHIP_MODE_NDT_OM
+ *     occupancy, mean, covariance; OHMHIP_MODE_NDT_TM those and intensity, hit / miss; OHMHIP_MODE_TSDF TSDF.  Also
+ *     OHMHIP_ERR_UNSUPPORTED: a map with region ownership or a partition, and a map with replica merge enabled.
+ *  U8 OHMHIP_ERR_INVALID_ARG, before any device work, for a null map, a bit at or above OHMHIP_LID_COUNT, layers == 0,
+ *     an unknown flag, and a null `layers` pointer in the getter.  The mask the map has already is OHMHIP_OK and does
+ *     nothing beyond U1: the pointers are unchanged.
+ *  U9 OHMHIP_LAYOUT_DISCARD_MAP: the map is cleared as ohmhip_map_clear does it and takes the new set: the result of
+ *     updateLayout(..., false).
+ *  U10 a failed call of any kind leaves the layers, regions, dirty bits, store and statistics as they were (under U5 a
+ *     call that fails after its evictions leaves those regions in the store: they are still the map's). */
+#define OHMHIP_LAYOUT_DISCARD_MAP 1u /* updateLayout(..., preserve_map = false) */
+typedef struct ohmhip_layer_change_stats
+{
+  unsigned layers_before, layers_after;        /* OHMHIP_LAYER_BIT masks */
+  uint64_t regions_resident, regions_in_store; /* after the call */
+  uint64_t regions_evicted;                    /* moved to the host store to stay inside the memory limit */
+  uint64_t bytes_per_region_before, bytes_per_region_after; /* what a resident region costs against the limit */
+} ohmhip_layer_change_stats;
+OHMHIP_EXPERIMENTAL int ohmhip_map_update_layers(ohmhip_map_t map, unsigned layers, unsigned flags,
+                                                 ohmhip_layer_change_stats *stats /* optional */);
+OHMHIP_EXPERIMENTAL int ohmhip_map_layers(ohmhip_map_t map, unsigned *layers);
+
 /* Multi-GPU merge support (no reference equivalent -- ohm is single device).  The resident layer of a
  * map is one allocation of region_stride_bytes per slot: ohm_amd/distributed.py wraps it as a device tensor and runs
  * the RCCL all-reduce of touched-region occupancy deltas on it.  ensure_regions makes regions resident (cleared)

@@ -158,6 +158,16 @@ class VoxelEditStats(C.Structure):
                 ("regions_touched", C.c_uint64), ("regions_created", C.c_uint64)]
 
 
+LAYOUT_DISCARD_MAP = 1  # OHMHIP_LAYOUT_DISCARD_MAP
+
+
+class LayerChangeStats(C.Structure):
+    """ohmhip_layer_change_stats"""
+    _fields_ = [("layers_before", C.c_uint), ("layers_after", C.c_uint), ("regions_resident", C.c_uint64),
+                ("regions_in_store", C.c_uint64), ("regions_evicted", C.c_uint64),
+                ("bytes_per_region_before", C.c_uint64), ("bytes_per_region_after", C.c_uint64)]
+
+
 class MapConfig(C.Structure):
     _fields_ = [("resolution", C.c_double), ("region_dim", C.c_int * 3), ("origin", C.c_double * 3),
                 ("layers", C.c_uint), ("mode", C.c_int), ("hit_value", C.c_float), ("miss_value", C.c_float),
@@ -344,6 +354,8 @@ _sigs = {
     "ohmhip_map_apply_ray_filter": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t)]),
     "ohmhip_map_apply_ray_filter_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.POINTER(C.c_size_t)]),
     "ohmhip_map_update_config": (C.c_int, [_vp, C.POINTER(MapConfig)]),
+    "ohmhip_map_update_layers": (C.c_int, [_vp, C.c_uint, C.c_uint, C.POINTER(LayerChangeStats)]),
+    "ohmhip_map_layers": (C.c_int, [_vp, C.POINTER(C.c_uint)]),
     "ohmhip_map_set_batch_coalescing": (C.c_int, [_vp, C.c_size_t]),
     "ohmhip_map_set_async_launch": (C.c_int, [_vp, C.c_int]),
     "ohmhip_map_set_region_ownership": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int]),

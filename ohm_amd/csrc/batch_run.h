@@ -68,6 +68,16 @@ struct BatchRun
   /// The batch recorded (or bound to a kernel) event k of its ring entry.
   void mark(int k) { m->tev_mask[ring] = uint8_t(m->tev_mask[ring] | (1u << k)); }
 
+  /// The secondary layers' blocks in the pool as it is now.  They are the only pool addresses a batch keeps across its
+  /// attempts: bound by prepare(), and again whenever an attempt replaced the pool (resolveExhaustion).
+  void bindSecondaryLayers()
+  {
+    const bool tsdf = m->config.mode == OHMHIP_MODE_TSDF;
+    sec.traversal = tsdf ? nullptr : static_cast<float *>(m->pool.layers[OHMHIP_LID_TRAVERSAL].get());
+    sec.touch_time = tsdf ? nullptr : static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_TOUCH_TIME].get());
+    sec.incident = tsdf ? nullptr : static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_INCIDENT].get());
+  }
+
   int prepare()
   {
     // This batch's summary block: the next of the three, zeroed by the previous batch's k_plan if that ran.  (Three: the
@@ -140,9 +150,7 @@ struct BatchRun
       ray_flags = OHMHIP_RF_END_POINT_AS_FREE;
     }
     ray_shift = occupancy_mode ? 0 : kEvRayShift;
-    sec.traversal = tsdf_mode ? nullptr : static_cast<float *>(m->pool.layers[OHMHIP_LID_TRAVERSAL].get());
-    sec.touch_time = tsdf_mode ? nullptr : static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_TOUCH_TIME].get());
-    sec.incident = tsdf_mode ? nullptr : static_cast<uint32_t *>(m->pool.layers[OHMHIP_LID_INCIDENT].get());
+    bindSecondaryLayers();
     sec.timestamps = d_timestamps;
     sec.time_base = m->first_ray_time;
     occ_inline = occupancy_mode && !m->pool.layers[OHMHIP_LID_MEAN] && !sec.traversal && !sec.touch_time && !sec.incident &&
@@ -355,7 +363,10 @@ struct BatchRun
     // its samples per region) the binning and the sample sort are launched right away with the buffers of the previous
     // batch; the summary then only confirms the guess, and a wrong guess costs a repeat of the two passes.
     spec_seg_cap = uint32_t(std::min<size_t>(m->segments.bytes / sizeof(Segment), 0xffffffffu));
-    speculated = occupancy_mode && m->spec_bucket_ok && attempt == 0 && spec_seg_cap > 0;
+    // (not on a map whose layer change left fewer usable slots than the pool has, resident_cap: an attempt that runs
+    // into the cap has handed out slots that EXIST, and what the speculative passes write there -- the sample mask, the
+    // hit ranges -- is not the set-up pass's to roll back; beyond the pool's end those passes find no slot to write)
+    speculated = occupancy_mode && m->spec_bucket_ok && attempt == 0 && spec_seg_cap > 0 && m->resident_cap == 0;
     binned_early = speculated && m->early_bin && m->early_bin_event != nullptr;
     // With the early route the binning pass starts on the front stream, so its start marker goes there too.
     hipStream_t bin_stream = binned_early ? f : s;
@@ -396,7 +407,7 @@ struct BatchRun
   bool exhausted() const
   {
     return (info.error & (kErrSlotsFull | kErrHashFull)) || info.n_slots > m->pool.slot_capacity ||
-           info.n_chunks > m->pool.chunk_capacity;
+           (m->resident_cap && info.n_slots > m->resident_cap) || info.n_chunks > m->pool.chunk_capacity;
   }
 
   /// Pool / chunk list exhausted.  Returns an error when the batch fails (the map is as it was before the call) and
@@ -438,6 +449,7 @@ struct BatchRun
       }
       return err;  // the batch fails, the map stays as it was
     }
+    bindSecondaryLayers();  // (the pool that grew is a new pool: the layers' blocks are new allocations)
     retry = true;
     return OHMHIP_OK;
   }

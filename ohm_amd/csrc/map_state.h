@@ -552,6 +552,10 @@ struct ohmhip_map_s
   uint64_t cache_hits = 0, cache_misses = 0, cache_full = 0;  ///< ohmhip_map_cache_stats
   uint64_t rays_beyond_tiles = 0;  ///< ohmhip_map_rays_beyond_tiles (tiled maps: rays cut for key-range reasons)
   uint64_t memory_limit = 0;                                   ///< ohmhip_map_set_memory_limit
+  /// A layer change under a memory limit (layout_impl.h) keeps the pool's slots -- the layers that stay do not move --
+  /// though the limit may be worth fewer regions of the new set than the pool has slots: the batches then use this many
+  /// (0: all of them; the limit bounds the pool's growth only, as without a layer change).
+  uint32_t resident_cap = 0;
   /// Spill to host (ohmhip_map_set_spill_to_host): regions evicted from the pool when the memory limit is reached, by
   /// packed key.  A spilled region is still part of the map: it is listed, read and synced from here, and moves back
   /// into the pool when a batch (or an upload) touches it.

@@ -848,6 +848,7 @@ try
   }
   OHMHIP_SETTLE(m);
   m->memory_limit = bytes;
+  m->resident_cap = 0;  // (a limit set anew bounds the pool's growth; the pool keeps the slots it has)
   return OHMHIP_OK;
 }
 OHMHIP_ABI_CATCH
@@ -1039,6 +1040,7 @@ OHMHIP_ABI_CATCH
 
 }  // extern "C"
 
+#include "layout_impl.h"
 #include "merge_impl.h"
 #include "partition_impl.h"
 #include "ray_filter_impl.h"

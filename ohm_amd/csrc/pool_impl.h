@@ -51,6 +51,16 @@ uint32_t nextPow2(uint32_t v)
   return p;
 }
 
+/// The scratch that goes with the traversal layer, zeroed (queued on `s`): in a pool being built, or beside the layer
+/// a live pool is about to gain (layout_impl.h).
+int allocTraversalAcc(ohmhip_map_t m, ohmhip_map_s::RegionPool &pool, uint32_t capacity, hipStream_t s)
+{
+  const size_t bytes = std::max<size_t>(sizeof(unsigned long long) * size_t(m->mc.region_voxels) * capacity, 4);
+  OHMHIP_CHECK(pool.d_traversal_acc.alloc(bytes));
+  OHMHIP_CHECK(hipMemsetAsync(pool.d_traversal_acc, 0, bytes, s));
+  return OHMHIP_OK;
+}
+
 /// (Re)allocate the region pool for `capacity` regions, preserving the first `keep` slots' contents.  Everything new is
 /// allocated before anything old is released: a failed allocation leaves the map exactly as it was.  `keep` is the
 /// committed slot count at every caller (or the count it is about to commit: 0, in ohmhip_map_clear), so the table
@@ -106,7 +116,7 @@ int allocPool(ohmhip_map_t m, uint32_t capacity, uint32_t keep)
     OHMHIP_CHECK(zalloc(fresh.d_chunks, sizeof(Chunk) * 2 * fresh.chunk_capacity));
     if (m->config.layers & (1u << OHMHIP_LID_TRAVERSAL))
     {
-      OHMHIP_CHECK(zalloc(fresh.d_traversal_acc, sizeof(unsigned long long) * rv * capacity));
+      OHMHIP_CHECK(allocTraversalAcc(m, fresh, capacity, s));
     }
     OHMHIP_CHECK(hipStreamSynchronize(s));
     return OHMHIP_OK;

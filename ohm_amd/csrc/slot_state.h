@@ -71,17 +71,26 @@ SlotArrays slotArrays(const MapConst &mc, const ohmhip_map_s::RegionPool &pool)
   return list;
 }
 
-/// Allocate the arrays of the list in a pool being built, `capacity` slots each (the list's strides; contents undefined).
-int allocSlotArrays(ohmhip_map_t m, ohmhip_map_s::RegionPool &pool, uint32_t capacity, bool merge_base)
+/// Allocate the blocks of the layers in `layers` (a mask of OHMHIP_LAYER_BIT) in `pool`, `capacity` slots each (contents
+/// undefined): a pool being built, or the layers a live pool is about to gain (layout_impl.h).
+int allocLayerArrays(ohmhip_map_t m, ohmhip_map_s::RegionPool &pool, uint32_t capacity, unsigned layers)
 {
   const size_t rv = size_t(m->mc.region_voxels);
   for (int l = 0; l < OHMHIP_LID_COUNT; ++l)
   {
-    if (m->config.layers & (1u << l))
+    if (layers & (1u << l))
     {
       OHMHIP_CHECK(pool.layers[l].alloc(std::max<size_t>(rv * kLayerBytes[l] * capacity, 4)));
     }
   }
+  return OHMHIP_OK;
+}
+
+/// Allocate the arrays of the list in a pool being built, `capacity` slots each (the list's strides; contents undefined).
+int allocSlotArrays(ohmhip_map_t m, ohmhip_map_s::RegionPool &pool, uint32_t capacity, bool merge_base)
+{
+  const size_t rv = size_t(m->mc.region_voxels);
+  OHMHIP_CHECK(allocLayerArrays(m, pool, capacity, m->config.layers));
   OHMHIP_CHECK(pool.d_hit_mask.alloc(std::max<size_t>(((rv + 31) / 32) * sizeof(uint32_t) * capacity, 4)));
   OHMHIP_CHECK(pool.d_dirty.alloc(std::max<size_t>(sizeof(uint32_t) * capacity, 4)));
   OHMHIP_CHECK(pool.d_last_use.alloc(std::max<size_t>(2 * sizeof(uint32_t) * capacity, 4)));
@@ -132,13 +141,14 @@ int copySlots(ohmhip_map_t m, const ohmhip_map_s::RegionPool &from, const ohmhip
 
 /// Slots [first, first + count) of `pool` go back to the pristine state every unassigned slot is in -- all of it, or
 /// only the arrays whose Travel is in `which`.
+/// `only_base`, where not null: only the array that starts there (a layer a live pool has just gained: layout_impl.h).
 int clearSlots(ohmhip_map_t m, const ohmhip_map_s::RegionPool &pool, uint32_t first, uint32_t count, hipStream_t stream,
-               unsigned which = ~0u)
+               unsigned which = ~0u, const void *only_base = nullptr)
 {
   for (const SlotArray &a : slotArrays(m->mc, pool))
   {
     const size_t bytes = a.stride * count;
-    if (bytes == 0 || !(a.travel & which))
+    if (bytes == 0 || !(a.travel & which) || (only_base && a.base != only_base))
     {
       continue;
     }

@@ -132,6 +132,14 @@ LAYERS = {
 }
 
 
+def layer_clear_block(name, region_voxels):
+    """A region's block of layer `name` as a cleared MapChunk holds it (ohm/DefaultLayer.cpp: occupancy +inf, clearance
+    -1, every other layer zero bytes)."""
+    _, dtype, comps = LAYERS[name]
+    value = {"occupancy": np.inf, "clearance": -1.0}.get(name, 0)
+    return np.full(region_voxels * comps, value, dtype=dtype)
+
+
 _libm = C.CDLL("libm.so.6")
 _libm.logf.restype = C.c_float
 _libm.logf.argtypes = [C.c_float]
@@ -215,6 +223,32 @@ class OccupancyMap:
             raise KeyError(name)
         if name not in self.layers:
             self.layers.append(name)
+
+    def removeLayer(self, name):
+        """The layout without layer `name` (MapLayout::removeLayer + OccupancyMap::updateLayout): the chunks lose its
+        blocks."""
+        if name not in LAYERS:
+            raise KeyError(name)
+        self.updateLayout([n for n in self.layers if n != name])
+
+    def updateLayout(self, layers, preserve_map=True):
+        """OccupancyMap::updateLayout (ohm/OccupancyMap.cpp:670-682) with MapChunk::updateLayout (ohm/MapChunk.cpp:
+        93-143) for every chunk: the blocks of layers in both layouts stay, an added layer gets a block of its clear
+        value (layer_clear_block), a removed layer's blocks go.  preserve_map=False drops the chunks instead."""
+        layers = list(dict.fromkeys(layers))
+        for name in layers:
+            if name not in LAYERS:
+                raise KeyError(name)
+        if not preserve_map:
+            self.chunks.clear()
+        rv = self.regionVoxelVolume()
+        for chunk in self.chunks.values():
+            for name in [n for n in chunk if n not in layers]:
+                del chunk[name]
+            for name in layers:
+                if name not in chunk:
+                    chunk[name] = layer_clear_block(name, rv)
+        self.layers[:] = layers
 
     def regionCount(self):
         return len(self.chunks)
@@ -788,8 +822,69 @@ class GpuMap(RayMapper):
         return out
 
     def hasLayer(self, name):
-        """Whether the device map was created with layer `name` (LAYERS)."""
+        """Whether the device map holds layer `name` (LAYERS)."""
         return bool(self._layer_bits & (1 << LAYERS[name][0]))
+
+    # OccupancyMap::updateLayout and the add*Layer calls (ohm/OccupancyMap.cpp:521-682) on the live map: the device map
+    # and the host map it wraps change together (include/ohmhip.h "LAYER CHANGES": the layers that stay do not move).
+    def updateLayout(self, layers, preserve_map=True):
+        """The map holds exactly `layers` (names of LAYERS) from the next batch on: added layers start cleared, removed
+        ones are released, the others keep their voxels.  preserve_map=False also drops every region.  Raises
+        OhmHipError -- and changes nothing -- for a layer the map's mode needs, a partitioned or merging map, or a
+        memory limit the new set does not fit."""
+        layers = list(dict.fromkeys(layers))
+        bits = 0
+        for name in layers:
+            bits |= 1 << LAYERS[name][0]
+        stats = L.LayerChangeStats()
+        L.check(L.lib.ohmhip_map_update_layers(self._handle, bits, 0 if preserve_map else L.LAYOUT_DISCARD_MAP,
+                                               C.byref(stats)), "GpuMap.updateLayout")
+        self._last_layer_change = {name: getattr(stats, name) for name, _ in L.LayerChangeStats._fields_}
+        self._layer_bits = bits
+        self._cfg.layers = bits
+        self._map.updateLayout(layers, preserve_map)
+        # (the chunks' blocks of the new layers are new arrays, the removed layers' are gone)
+        self._block_addr = {name: cache for name, cache in self._block_addr.items() if name in layers}
+        if not preserve_map:
+            self._block_addr = {}
+
+    def addLayer(self, name):
+        if not self.hasLayer(name):
+            self.updateLayout(list(self._map.layers) + [name])
+
+    def removeLayer(self, name):
+        if self.hasLayer(name):
+            self.updateLayout([n for n in self._map.layers if n != name])
+
+    def addVoxelMeanLayer(self):
+        """OccupancyMap::addVoxelMeanLayer (ohm/OccupancyMap.cpp:521)."""
+        self.addLayer("mean")
+
+    def addTraversalLayer(self):
+        self.addLayer("traversal")
+
+    def addTouchTimeLayer(self):
+        self.addLayer("touch_time")
+
+    def addIncidentNormalLayer(self):
+        self.addLayer("incident_normal")
+
+    def voxelMeanEnabled(self):
+        return self.hasLayer("mean")
+
+    def traversalEnabled(self):
+        return self.hasLayer("traversal")
+
+    def touchTimeEnabled(self):
+        return self.hasLayer("touch_time")
+
+    def incidentNormalEnabled(self):
+        return self.hasLayer("incident_normal")
+
+    def lastLayerChangeStats(self):
+        """ohmhip_layer_change_stats of the last updateLayout / addLayer / removeLayer that changed the map (None before
+        the first)."""
+        return getattr(self, "_last_layer_change", None)
 
     def clearanceStaleRegions(self, search_radius, flags=0, axis_scaling=(1.0, 1.0, 1.0)):
         """The regions whose clearance layer is stale for these parameters, (N, 3) int16 in processing order
@@ -1461,12 +1556,13 @@ class ClearanceProcess:
     @staticmethod
     def ensureClearanceLayer(map_):
         """ClearanceProcess::ensureClearanceLayer (ohm/DefaultLayer.cpp:174-193): add the clearance layer (float,
-        cleared to -1) to an OccupancyMap before its GpuMap is created.  A live GpuMap cannot gain a layer: given one
-        without it, this raises."""
+        cleared to -1) to an OccupancyMap before its GpuMap is created.  Given a live GpuMap without the layer this
+        raises: adding a layer there is the caller's decision -- GpuMap.addLayer("clearance") does it in place."""
         if isinstance(map_, GpuMap):
             if not map_.hasLayer("clearance"):
-                raise RuntimeError("ensureClearanceLayer: the device map was created without the clearance layer; "
-                                   "add it to the OccupancyMap before creating the GpuMap")
+                raise RuntimeError("ensureClearanceLayer: the device map does not hold the clearance layer; "
+                                   "add it with GpuMap.addLayer(\"clearance\"), or to the OccupancyMap before creating "
+                                   "the GpuMap")
             return
         map_.addLayer("clearance")
 

@@ -373,6 +373,43 @@ public:
   unsigned layers() const { return layers_; }
   void addLayer(int layer_id) { layers_ |= OHMHIP_LAYER_BIT(layer_id); }
   bool hasLayer(int layer_id) const { return (layers_ & OHMHIP_LAYER_BIT(layer_id)) != 0; }
+  /// The layout without a layer (MapLayout::removeLayer + updateLayout): the chunks lose its blocks.
+  void removeLayer(int layer_id) { updateLayout(layers_ & ~OHMHIP_LAYER_BIT(layer_id)); }
+  /// OccupancyMap::updateLayout (ohm/OccupancyMap.cpp:670-682) with MapChunk::updateLayout (ohm/MapChunk.cpp:93-143) for
+  /// every chunk: the blocks of the layers in both layouts stay, an added layer gets a block of its clear value
+  /// (ohm/DefaultLayer.cpp: occupancy +inf, clearance -1, zero bytes otherwise), a removed layer's blocks go.
+  /// preserve_map == false drops the chunks instead.
+  void updateLayout(unsigned layers, bool preserve_map = true)
+  {
+    if (!preserve_map)
+    {
+      chunks_.clear();
+    }
+    const size_t voxels = regionVoxelVolume();
+    for (auto &entry : chunks_)
+    {
+      std::vector<std::vector<uint8_t>> &blocks = entry.second.voxel_blocks;
+      blocks.resize(OHMHIP_LID_COUNT);
+      for (int layer = 0; layer < OHMHIP_LID_COUNT; ++layer)
+      {
+        const bool wanted = (layers & OHMHIP_LAYER_BIT(layer)) != 0;
+        if (!wanted)
+        {
+          std::vector<uint8_t>().swap(blocks[layer]);
+        }
+        else if (blocks[layer].empty())
+        {
+          const float clear = (layer == OHMHIP_LID_OCCUPANCY) ? INFINITY : (layer == OHMHIP_LID_CLEARANCE) ? -1.0f : 0.0f;
+          blocks[layer].resize(voxels * ohmhip_layer_voxel_bytes(layer));
+          for (size_t at = 0; at + sizeof(float) <= blocks[layer].size(); at += sizeof(float))
+          {
+            std::memcpy(&blocks[layer][at], &clear, sizeof(float));
+          }
+        }
+      }
+    }
+    layers_ = layers;
+  }
 
   using ChunkMap = std::map<std::array<int16_t, 3>, MapChunk>;
   ChunkMap &chunks() { return chunks_; }
@@ -824,6 +861,32 @@ public:
   /// Large host batches return once staged; the launch sequence runs on a thread of the map (see
   /// ohmhip_map_set_async_launch).  Off by default.
   void setAsyncLaunch(bool enable) { OHMHIP_GPUAPICHECK(ohmhip_map_set_async_launch(handle_, enable ? 1 : 0)); }
+
+  /// OccupancyMap::updateLayout and the add*Layer calls (ohm/OccupancyMap.cpp:521-682) on the live map (include/ohmhip.h
+  /// "LAYER CHANGES"): the map holds exactly @p layers (a mask of OHMHIP_LAYER_BIT) from the next batch on -- added
+  /// layers start cleared, removed ones are released, the others keep their voxels where they are -- and the host map
+  /// follows.  preserve_map == false also drops every region.  Throws, and changes nothing, for a layer the map's mode
+  /// needs, a partitioned or merging map, or a memory limit the new set does not fit.
+  void updateLayout(unsigned layers, bool preserve_map = true)
+  {
+    ohmhip_layer_change_stats stats{};
+    OHMHIP_GPUAPICHECK(ohmhip_map_update_layers(handle_, layers, preserve_map ? 0u : OHMHIP_LAYOUT_DISCARD_MAP, &stats));
+    last_layer_change_ = stats;
+    cfg_.layers = layers;
+    map_->updateLayout(layers, preserve_map);
+  }
+  void addLayer(int layer_id) { updateLayout(map_->layers() | OHMHIP_LAYER_BIT(layer_id)); }
+  void removeLayer(int layer_id) { updateLayout(map_->layers() & ~OHMHIP_LAYER_BIT(layer_id)); }
+  void addVoxelMeanLayer() { addLayer(OHMHIP_LID_MEAN); }
+  void addTraversalLayer() { addLayer(OHMHIP_LID_TRAVERSAL); }
+  void addTouchTimeLayer() { addLayer(OHMHIP_LID_TOUCH_TIME); }
+  void addIncidentNormalLayer() { addLayer(OHMHIP_LID_INCIDENT); }
+  bool voxelMeanEnabled() const { return map_->hasLayer(OHMHIP_LID_MEAN); }
+  bool traversalEnabled() const { return map_->hasLayer(OHMHIP_LID_TRAVERSAL); }
+  bool touchTimeEnabled() const { return map_->hasLayer(OHMHIP_LID_TOUCH_TIME); }
+  bool incidentNormalEnabled() const { return map_->hasLayer(OHMHIP_LID_INCIDENT); }
+  /// ohmhip_layer_change_stats of the last updateLayout that reached the device (zero before the first).
+  const ohmhip_layer_change_stats &lastLayerChangeStats() const { return last_layer_change_; }
 
   /// Not in the reference (single device): owner-computes multi-GPU mode, see ohmhip_map_set_region_ownership.  The
   /// map integrates only what falls in the regions @p rank owns among @p world_size maps fed the same ray stream.
@@ -1288,6 +1351,7 @@ protected:
   DeviceRayFilter device_ray_filter_;  ///< the chain set on the device (empty: none)
   bool time_base_checked_ = false;  ///< a stamped call under a host filter has seen to the time base
   ohmhip_map_config cfg_;
+  ohmhip_layer_change_stats last_layer_change_{};
   GpuCache cache_view_{ this };
 };
 
@@ -2212,7 +2276,7 @@ public:
   void reset() { results_.clear(); }
 
   /// ClearanceProcess::ensureClearanceLayer (ohm/DefaultLayer.cpp:174-193): add the clearance layer to the map before
-  /// its GpuMap is created (a live device map cannot gain a layer).
+  /// its GpuMap is created (a live device map gains it through GpuMap::addLayer(OHMHIP_LID_CLEARANCE)).
   static void ensureClearanceLayer(OccupancyMap &map) { map.addLayer(OHMHIP_LID_CLEARANCE); }
 
   /// ClearanceProcess::update (ohmgpu/ClearanceProcess.cpp:418-470): recompute the clearance layer of stale regions in

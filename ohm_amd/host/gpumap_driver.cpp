@@ -1250,6 +1250,88 @@ int modeQueryApi(const Args &args)
   return kOk;
 }
 
+/// layout toggle <mean pattern>: VoxelMean.LayoutToggle (tests/ohmtestgpu/GpuVoxelMeanTests.cpp:143-244) on a map of
+/// 32^3 regions: integrateHit at (1.1, 1.1, 1.1); addVoxelMeanLayer; the mean voxel written as {pattern, 1};
+/// updateLayout back to the first layout.  out, per stage (created, mean added, mean written, layout restored): u32
+/// host layers, u32 device layers (ohmhip_map_layers), f32 occupancy of the voxel, u64 cloud points, f64[3] position of
+/// the first; then u32[2] the mean voxel as added, i32 the status of reading it once the layer is gone.
+/// layout added: the first <batch_rays> rays, stamped 100 + 0.01 i, into an occupancy map of 16^3 regions; the mean,
+/// traversal, touch-time and incident-normal layers added; the other rays, stamped 200 + 0.01 i; syncVoxels.  out: a
+/// map dump.
+int modeLayout(const Args &args)
+{
+  check(args.has(0), kUsage);
+  const std::string which = args.extra[0];
+  OutFile out(args.output);
+  if (which == "toggle")
+  {
+    ohm::OccupancyMap map(args.resolution, 32, 32, 32);
+    ohm::GpuMap gpu(&map, true);
+    check(gpu.gpuOk(), kMapInvalid);
+    const unsigned cached_layout = map.layers();
+    const ohm::dvec3 sample{ 1.1, 1.1, 1.1 };
+    check(gpu.integrateHit(sample) == OHMHIP_OK, kFailedCall);
+    const std::vector<ohm::CloudKey> key = gpu.voxelKeys(&sample, 1);
+    std::vector<uint8_t> value, present;
+    auto stage = [&]() {
+      unsigned device_layers = 0;
+      check(ohmhip_map_layers(gpu.handle(), &device_layers) == OHMHIP_OK, kFailedCall);
+      check(gpu.readVoxels(OHMHIP_LID_OCCUPANCY, key, value, present) == OHMHIP_OK && present[0] == 1, kFailedCall);
+      const ohm::VoxelCloud cloud = ohm::extractCloud(gpu);
+      check(cloud.status == OHMHIP_OK && !cloud.positions.empty(), kFailedCall);
+      out.value(uint32_t(map.layers()));
+      out.value(uint32_t(device_layers));
+      out.bytes(value.data(), sizeof(float));
+      out.value(uint64_t(cloud.count));
+      out.value(cloud.positions[0]);
+    };
+    stage();
+    gpu.addVoxelMeanLayer();
+    check(gpu.voxelMeanEnabled(), kUnexpected);
+    stage();
+    std::vector<uint8_t> mean_added;
+    check(gpu.readVoxels(OHMHIP_LID_MEAN, key, mean_added, present) == OHMHIP_OK && present[0] == 1, kFailedCall);
+    const uint32_t mean[2] = { uint32_t(args.integer(1, 0)), 1u };
+    check(gpu.writeVoxels(OHMHIP_LID_MEAN, key, mean) == OHMHIP_OK, kFailedCall);
+    stage();
+    gpu.updateLayout(cached_layout);
+    check(!gpu.voxelMeanEnabled(), kUnexpected);
+    stage();
+    out.array(mean_added);
+    std::vector<uint8_t> gone;
+    out.value(int32_t(gpu.readVoxels(OHMHIP_LID_MEAN, key, gone, present)));
+    return kOk;
+  }
+  check(which == "added", kUsage);
+  const std::vector<ohm::dvec3> rays = readRays(args.input);
+  ohm::OccupancyMap map(args.resolution, 16, 16, 16);
+  ohm::GpuMap gpu(&map, true);
+  check(gpu.gpuOk(), kMapInvalid);
+  const size_t points = rays.size() & ~size_t(1);
+  const size_t first = std::min(2 * args.batch_rays, points);
+  auto integrate = [&](size_t begin, size_t end, double start) {
+    std::vector<double> stamps((end - begin) / 2);
+    for (size_t i = 0; i < stamps.size(); ++i)
+    {
+      stamps[i] = start + 0.01 * double(i);
+    }
+    check(end == begin || gpu.integrateRays(rays.data() + begin, end - begin, nullptr, stamps.data(), ohm::kRfDefault) ==
+                            end - begin,
+          kFailedCall);
+  };
+  integrate(0, first, 100.0);
+  gpu.addVoxelMeanLayer();
+  gpu.addTraversalLayer();
+  gpu.addTouchTimeLayer();
+  gpu.addIncidentNormalLayer();
+  check(gpu.voxelMeanEnabled() && gpu.traversalEnabled() && gpu.touchTimeEnabled() && gpu.incidentNormalEnabled(),
+        kUnexpected);
+  integrate(first, points, 200.0);
+  gpu.syncVoxels();
+  writeRegionDump(out, map);
+  return kOk;
+}
+
 struct Mode
 {
   const char *name;
@@ -1288,6 +1370,7 @@ const Mode kModes[] = {
   { "covariance", &modeCovariance, true },
   { "filter", &modeFilterPoints, true },
   { "voxeledit", &modeVoxelEdit, true },
+  { "layout", &modeLayout, true },
   { "filter:clipbounded", &modeRayFilter, false },
   { "filter:cliptobounds", &modeRayFilter, false },
   { "filter:clipray", &modeRayFilter, false },
